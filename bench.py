@@ -99,6 +99,10 @@ def parse_args(argv=None):
                          "walks the multi-rank code path of this script (shards, graph capture beside a process group, pipelined "
                          "gather, max-over-ranks timing); with NO GPU a CPU stand-in step exercises launcher, process group, "
                          "gather and timing protocol only.  Its numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the layer returned in the last timed step as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the large arrays, at most 64 MB in all): two builds run "
+                         "with the same arguments can then be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -511,6 +515,60 @@ def grid_leg(args, dev):
             "points": pts}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SEED = 1234
+
+
+def _row_sample(x, row_len, max_elems, gen):
+    """`x` viewed as (rows, row_len): every row when it fits in `max_elems`, else a seeded sample of whole rows (sorted
+    indices); returns (rows as float32 numpy, row indices as float64 numpy)."""
+    import torch
+    x = x.reshape(-1, row_len)
+    n = x.shape[0]
+    if n * row_len <= max_elems:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randperm(n, generator=gen)[:max(1, max_elems // row_len)].sort().values
+    rows = x.index_select(0, idx.to(x.device)).float().cpu().numpy()
+    return rows, idx.double().numpy()
+
+
+def dump_outputs(dirname, out, context):
+    """What a caller of the timed path receives from its last step, as DIR/<name>.npy: the context layer, the estimated
+    (N,H,T,T_M) probability map, the flat CSR mask (row starts in full, a seeded sample of column ids per sequence) and the
+    key used for the scores.  Large arrays are sampled by whole rows with a fixed seed, so two runs with the same arguments
+    sample the same positions.  Reading the map and the column array computes them if the module left them pending."""
+    import numpy as np
+    import torch
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    arrays = {}
+    arrays["context_layer"], arrays["context_layer_rows"] = _row_sample(context, context.shape[-1], 4 * 2 ** 20, gen)
+    probs = out.estimated_attention_probs_m
+    arrays["estimated_attention_probs_m"], arrays["estimated_attention_probs_m_rows"] = _row_sample(
+        probs, probs.shape[-1], 4 * 2 ** 20, gen)
+    csr = out.partial_attention_mask
+    crow = csr.crow.long().cpu()
+    arrays["csr_crow"] = crow.double().numpy()
+    nnz = crow[:, -1]
+    per_seq = max(1, 2 ** 19 // crow.shape[0])
+    u = torch.rand((crow.shape[0], per_seq), generator=gen, dtype=torch.float64)
+    pos = (u * nnz.double().view(-1, 1)).long().clamp(min=0)
+    pos = torch.minimum(pos, (nnz - 1).clamp(min=0).view(-1, 1))
+    col = csr.col.long()
+    arrays["csr_col_sample"] = col.gather(1, pos.to(col.device)).cpu().double().numpy()
+    arrays["csr_col_sample_pos"] = pos.double().numpy()
+    ks = out.key_for_score
+    if isinstance(ks, torch.Tensor):
+        arrays["key_for_score"], arrays["key_for_score_rows"] = _row_sample(ks, ks.shape[-1], 2 * 2 ** 20, gen)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"output dump of {total} bytes exceeds {DUMP_BUDGET_BYTES}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+    return {"dir": dirname, "files": sorted(f"{n}.npy" for n in arrays), "bytes": int(total)}
+
+
 def reference_fixture_check(dev):
     """The hot path (steps H..K) against the REFERENCE's own outputs, inside the bench process: `tests/golden/*.npz` hold seeded
     inputs and what the reference's Triton / torch operators returned for them (`tests/golden/make_golden.py`, run once in the
@@ -853,6 +911,14 @@ def main(argv=None):
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     tokens_per_s = NB * world * T / (elapsed / args.steps)
+
+    # ---- --dump-outputs: the last timed step's outputs, before anything else runs the layer again (outside the timed region)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            ctx_d = ctx() if callable(ctx) else ctx
+            dumped = dump_outputs(args.dump_outputs, out, ctx_d if world > 1 else out.context_layer)
+        torch.cuda.synchronize()
 
     # ---- the same K steps again, `--repeats` times (outside the timed region that `value` comes from): K x 2 ms is thin against
     # box-to-box and run-to-run variance, so the line also says how stable the number is (min / median / max over all runs)
@@ -1212,6 +1278,8 @@ def main(argv=None):
             "host_enqueue_ms_per_step": round(t_enqueued / args.steps * 1e3, 3),
             "regions_ms": {k_: round(v_ * 1e3, 4) for k_, v_ in sorted(regions.items())},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -5,22 +5,81 @@ aliased to this package as INTEGRATION.md section 1 shows -- on seeded inputs (`
 container only).
 
 CPU: `opt_plumbing.SeaOPTAttention` / `SeaOPTDecoderLayer`, the restated callers, loaded with the same state dict give the
-same outputs EXACTLY (dense mode).  GPU: the sparse mode (`benchmarking=True`, HIP kernels) of the same block lands within the
+same outputs EXACTLY (dense mode) on a host whose fp32 CPU kernels round like those of the host the fixture was made on.  Which
+kernels MKL, oneDNN and ATen pick follows the CPU (AVX-512 or AVX2 code paths, Intel or AMD), and another pick rounds the same
+arithmetic differently in the last bits.  `tests/golden/callers_platform.npz` holds digests of a few seeded fp32 operations of
+the layer's kinds and shapes (`platform_probe`, recorded on a host that reproduces callers.npz bit for bit): a host that
+reproduces them is held to bit equality, any other to a few units in the last place of the output's scale (16 eps x max|ref|;
+every other pick of the three libraries' code paths lands within 8).  GPU: the sparse mode (`benchmarking=True`, HIP kernels) of the same block lands within the
 dense-vs-sparse bar of the reference's consistency test (sum of squared errors <= 1e-5 on the context,
 src/main/tests/test_perlin_opt_consist.py:198-232), stateless and decoded piecewise through `past_key_value = (k, v, state)`;
 so does the benchmark's surgery (src/main/benchmark_bert.py:162-203).
 """
+import functools
+import hashlib
 import os
 
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from sea_attention_amd import opt_plumbing as P
 from sea_attention_amd.perlin_attention import PerlinAttentionConfig, get_default_config, register_default_config
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "callers.npz")
+PROBE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "callers_platform.npz")
 CASES = ["tiny", "opt125m"]
+ULP_BOUND = 16          # off the fixture's platform: max|got - ref| <= ULP_BOUND * eps(fp32) * max|ref|
+
+
+def platform_probe():
+    """Seeded fp32 CPU operations of the kinds and shapes the dense-mode layer runs (GEMMs, LayerNorm, softmax, the predictor's
+    convolutions), name -> tensor.  Their bits tell which code paths this host's MKL / ATen / oneDNN take."""
+    g = torch.Generator().manual_seed(7)
+    r = lambda *s: torch.randn(s, generator=g)
+    out = {}
+    for name, (hidden, heads, T, N) in {"tiny": (64, 4, 48, 2), "opt125m": (768, 12, 128, 1)}.items():
+        x = r(N * T, hidden)
+        w, b = r(hidden, hidden) * 0.05, r(hidden) * 0.05
+        out[f"{name}.linear"] = F.linear(x, w, b)
+        out[f"{name}.linear3d"] = F.linear(x.view(N, T, hidden), w, b)
+        out[f"{name}.layer_norm"] = F.layer_norm(x, (hidden,), r(hidden) * 0.05 + 1, b)
+        d = hidden // heads
+        q, k, v = (r(N, heads, T, d) for _ in range(3))
+        s = torch.matmul(q, k.transpose(-1, -2))
+        out[f"{name}.scores"] = s
+        p = torch.softmax(s, -1)
+        out[f"{name}.softmax"] = p
+        out[f"{name}.pv"] = torch.matmul(p, v)
+        out[f"{name}.relu_linear"] = F.relu(F.linear(x, w, b))
+        c = 4 * heads
+        img = r(N, c, T, 64)
+        cw, cb = r(c, c, 3, 3) * 0.05, r(c) * 0.05
+        out[f"{name}.conv_dil2"] = F.conv2d(img, cw, cb, 1, 2, 2)
+        out[f"{name}.conv_s2"] = F.conv2d(img, cw, cb, (2, 1), 1)
+        out[f"{name}.conv_1x1"] = F.conv2d(img, r(heads, c, 1, 1) * 0.05, cb[:heads], 1, 0)
+    return out
+
+
+def platform_digests():
+    return {k: hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest() for k, v in platform_probe().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def on_fixture_platform():
+    """True when this host reproduces the probe recorded on a host that reproduces callers.npz bit for bit."""
+    z = np.load(PROBE)
+    here = platform_digests()
+    return set(z.files) == set(here) and all(str(z[k]) == h for k, h in here.items())
+
+
+def assert_same_as_reference(got, ref, name):
+    if on_fixture_platform():
+        assert torch.equal(got, ref), name
+    else:
+        err, scale = float((got - ref).abs().max()), float(ref.abs().max())
+        assert err <= ULP_BOUND * torch.finfo(torch.float32).eps * scale, (name, err / (torch.finfo(torch.float32).eps * scale))
 
 
 def state_dict_recipe(keys_shapes, seed):
@@ -70,10 +129,10 @@ def test_restated_callers_equal_the_reference_callers_exactly(case, restore_defa
         y_attn, _, present = layer.self_attn(hidden_states=layer.self_attn_layer_norm(x), attention_mask=mask)
         y_layer = layer(hidden_states=x, attention_mask=mask)[0]
         y_exam = layer.exam_surgery(benchmarking=False)(hidden_states=x, attention_mask=mask)[0]
-    assert torch.equal(y_attn, torch.from_numpy(z[f"{case}.y_attn"]))
-    assert torch.equal(present[0], torch.from_numpy(z[f"{case}.present_k"]))
-    assert torch.equal(y_layer, torch.from_numpy(z[f"{case}.y_layer"]))
-    assert torch.equal(y_exam, torch.from_numpy(z[f"{case}.y_exam"]))
+    assert_same_as_reference(y_attn, torch.from_numpy(z[f"{case}.y_attn"]), "y_attn")
+    assert_same_as_reference(present[0], torch.from_numpy(z[f"{case}.present_k"]), "present_k")
+    assert_same_as_reference(y_layer, torch.from_numpy(z[f"{case}.y_layer"]), "y_layer")
+    assert_same_as_reference(y_exam, torch.from_numpy(z[f"{case}.y_exam"]), "y_exam")
 
 
 @pytest.mark.gpu
