@@ -32,15 +32,17 @@ extern "C" {
 /* ABI version, returned by sea_version(); the Python binding refuses a library of another version (a stale .so next to newer
  * Python, or the other way round, through SEA_HIP_LIB).  History of INCOMPATIBLE changes of existing entry points:
  *   1  rounds 1-2
- *   2  round 3: sea_performer_causal_step / _at read k / v / pos FROM THE LAST CHUNK BOUNDARY (T + t_base % C rows) and take the
- *      state image at that boundary;  round 4: sea_predictor_mlp's w2_packed / vectors pad every decoder half to whole
+ *   2  round 3: sea_performer_causal_step (both forms) reads k / v / pos FROM THE LAST CHUNK BOUNDARY (T + t_base % C rows)
+ *      and takes the state image at that boundary;  round 4: sea_predictor_mlp's w2_packed / vectors pad every decoder half to whole
  *      16-row tiles (identical for Wd % 16 == 0), sea_predictor_tail_select accepts probs = NULL and any T_m % 4 == 0 <= 512
- *   3  round 5: new entry points the binding requires (sea_causal_conv_c8_z, sea_predictor_tail_z, sea_predictor_tail_select_z,
- *      sea_causal_conv_c8_f32, sea_decode_cnn_tail_select, sea_predictor_tail_consts, sea_sparse_attention_fused_at);
- *      sea_predictor_tail_select / _at take a
- *      trailing `consts_tab` argument (NULL = the round-4 behaviour)
+ *   3  round 5: new entry points the binding requires (the z, fp32 and decode forms of the convolution, tail, selection and
+ *      attention, sea_decode_cnn_tail_select, sea_predictor_tail_consts); the tail + selection takes a trailing
+ *      `consts_tab` argument (NULL = the round-4 behaviour)
+ *   4  one entry point per operator: the variants that were separate, suffixed entry points of sea_sparse_attention,
+ *      sea_predictor_tail, sea_predictor_tail_select, sea_csr_emit, sea_causal_conv_c8, sea_performer_causal and
+ *      sea_performer_causal_step are gone; each of these takes the variants' arguments instead (NULL / 0 / 1 = not wanted)
  *      */
-#define SEA_ABI_VERSION 3
+#define SEA_ABI_VERSION 4
 
 enum sea_dtype { SEA_F32 = 0, SEA_F16 = 1, SEA_BF16 = 2 };
 
@@ -97,12 +99,16 @@ int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst,
 /* a7  emit the column indices (replaces nonzero() + __scan_col_4_compute,
  * causal_resize_m_to_t.py:493-572,724-746).  col has room for z_cap entries per batch item
  * (col_stride_n elements apart); entries at or beyond crow[n,T_dst] are left untouched.
- * values_out (optional, fp32, same shape as col) receives 1.0 for every emitted entry. */
+ * values_out (optional, fp32, same shape as col) receives 1.0 for every emitted entry.
+ * DECODE form, t_src_dev != NULL (a step captured as a HIP graph): the row widths follow *t_src_dev (device memory: the
+ * current sequence length) and the column ids are head * T_src + key for a FIXED capacity T_src >= *t_src_dev (the K / V
+ * caches' row count), so sea_sparse_attention is called with that same T_src; values_out must be NULL. */
 int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off,
                  int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
                  int64_t T_src, int is_causal, int max_k,
                  void* col, int idx_bytes, int64_t col_stride_n, int64_t z_cap,
                  float* values_out,
+                 const int32_t* t_src_dev, /* decode form, or NULL */
                  sea_stream_t stream);
 
 /* Per-(row, head) offsets of a foreign flat CSR whose rows are grouped by ascending head
@@ -155,19 +161,6 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * crow/col are int32 (internal format), head_off as produced by sea_topk_select.
  * out has dtype out_dtype and arbitrary [n,h,t] element strides (so it can be written straight
  * into the (N, T, H*D) layout of attention.py:1279-1282).
- */
-int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
-                         int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
-                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                         const int32_t* crow, const int32_t* col, int64_t col_stride_n,
-                         const int32_t* head_off,
-                         const float* row_scale, /* (N,H,T_dst) contiguous or NULL */
-                         const void* avg, const int64_t* avg_strides, /* dtype `dtype`, or NULL */
-                         const float* mix,       /* (N,H,T_dst) contiguous or NULL */
-                         void* out, int out_dtype, const int64_t* out_strides,
-                         sea_stream_t stream);
-
-/* The same operator with two more knobs.
  *
  * flags, low byte = kernel path:
  *   SEA_ATTN_AUTO    with a `block_path` plan (sea_attention_plan): the ONE kernel the plan's statistics favour for this
@@ -192,67 +185,57 @@ int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
  * probs_out (optional): fp32, laid out like `col` (row n at probs_out + n*probs_stride_n): entry e receives
  *   rs * softmax_e -- the values of `partial_attention_probs` after flat_csr_softmax + flat_csr_elmul
  *   (attention.py:1162-1171).  Served by the gather kernels (SEA_ATTN_TILE + probs_out is SEA_EUNSUPPORTED;
- *   SEA_ATTN_AUTO falls back to them). */
-enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2 };
-int sea_sparse_attention_ex(const void* q, const void* k, const void* v, int dtype,
-                            int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
-                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                            const int32_t* crow, const int32_t* col, int64_t col_stride_n,
-                            const int32_t* head_off,
-                            const float* row_scale, const void* avg, const int64_t* avg_strides,
-                            const float* mix,
-                            void* out, int out_dtype, const int64_t* out_strides,
-                            float* probs_out, int64_t probs_stride_n,
-                            const uint8_t* block_path, /* buffer filled by sea_attention_plan, or NULL */
-                            int flags, sea_stream_t stream);
-
-/* Steps I + J of the hot path in ONE launch (round 3): the nearest-neighbour interpolation of the kept pixels
- * (causal_resize_m_to_t.py:493-572,631-762) INSIDE the row-indexed sparse attention (flat_csr_masked_bmm / softmax / elmul /
- * sdbmm).  Each lane group of the gather kernels expands ITS (row, head)'s kept pixels to key columns -- sea_csr_emit's
- * arithmetic bit for bit: fp32 scale = w_t / T_m, bounds round_half_away(b * scale), keys descending inside a pixel, the
- * reference's fp32 stepping for a pixel wider than max_k -- into a group-private list in LDS, writes the list to `col` and
- * walks it from LDS.  No separate sea_csr_emit launch, no column re-read from memory.
+ *   SEA_ATTN_AUTO falls back to them).
+ * block_path (optional): the buffer sea_attention_plan filled.
+ *
+ * FUSED form, bits != NULL (round 3): steps I + J of the hot path in ONE launch -- the nearest-neighbour interpolation of
+ * the kept pixels (causal_resize_m_to_t.py:493-572,631-762) INSIDE the row-indexed sparse attention (flat_csr_masked_bmm /
+ * softmax / elmul / sdbmm).  Each lane group of the gather kernels expands ITS (row, head)'s kept pixels to key columns --
+ * sea_csr_emit's arithmetic bit for bit: fp32 scale = w_t / T_m, bounds round_half_away(b * scale), keys descending inside
+ * a pixel, the reference's fp32 stepping for a pixel wider than max_k -- into a group-private list in LDS, writes the list
+ * to `col` and walks it from LDS.  No separate sea_csr_emit launch, no column re-read from memory.  `flags` is not read
+ * (the gather path), block_path must be NULL, probs_out is allowed.
  *   bits      (N, T_dst, ceil(H*T_m/32)) kept-pixel masks of sea_topk_select / sea_predictor_tail_select (T_m % 32 == 0);
+ *             T_m, is_causal, max_k as for that launch.  With bits = NULL, T_m / is_causal / max_k / write_cols are not read;
  *   crow      from sea_csr_row_scan over that launch's row_nnz; head_off from the same launch;
  *   col       (N, col_stride_n) int32: OUTPUT -- after the launch it holds exactly what sea_csr_emit would have written.
- *   write_columns  0 (round 4): the expanded columns stay in LDS and `col` is NOT written (blocks whose key lists exceed the
+ *   write_cols  0 (round 4): the expanded columns stay in LDS and `col` is NOT written (blocks whose key lists exceed the
  *             kernel's LDS list still pass through their part of it): the column array is an output nobody on the hot path
  *             reads -- 266 MB and ~50 us of the headline launch.  A caller that wants it later runs sea_csr_emit on the same
  *             bits / crow (bit-identical); the Python handle keeps its columns pending and does that on first access.
- * Other arguments as sea_sparse_attention_ex (gather path; probs_out allowed).  Rows of 4 lanes and rows wider than 16
- * lanes are SEA_EUNSUPPORTED: run sea_csr_emit + sea_sparse_attention_ex there.
- * sea_attention_few_rows(): for a launch of at most that many rows (N * H * T_dst: a decoding step) sea_csr_emit +
- * sea_sparse_attention_ex is the faster pair -- with T_dst <= 8 that kernel's idle lane groups first touch every K / V row
- * the step will gather, so the rows' dependent walks find them in cache (same arithmetic, bit for bit). */
+ * Rows of 4 lanes and rows wider than 16 lanes are SEA_EUNSUPPORTED: run sea_csr_emit + the plain form there.
+ * sea_attention_few_rows(): for a launch of at most that many rows (N * H * T_dst: a decoding step) sea_csr_emit + the
+ * plain form is the faster pair -- with T_dst <= 8 that kernel's idle lane groups first touch every K / V row the step
+ * will gather, so the rows' dependent walks find them in cache (same arithmetic, bit for bit).
+ *
+ * DECODE form of the fused launch, bits and t_src_dev != NULL (round 5; SURVEY 8f-3, src/main/opt_generate.py:131,
+ * PA/attention.py:410-426): a position of a graph-replayed decoding session has static kernel arguments, so the sequence
+ * length the row widths follow is read from device memory (*t_src_dev, what the decode form of sea_csr_emit reads) while
+ * T_src is the CAPACITY -- the row count of the K / V caches -- with which the column ids are encoded (head * T_src + key).
+ * T_dst <= 8 new rows per sequence, no probs_out; 16-bit d = 64 / 80 / 128 or fp32 d = 32 / 64 (the fused forms), else
+ * SEA_EUNSUPPORTED (run the decode form of sea_csr_emit + the plain form).  The lane groups of a workgroup that have no row
+ * touch the K / V rows of the expanded lists before the one group per row starts its dependent walk (what the unfused
+ * kernel does from `col`).  Same arithmetic in the same order as sea_csr_emit + the plain form: the step stays bitwise
+ * the stateless forward; the emit launch (or the emit phase of sea_decode_cnn_tail_select: pass col = NULL there) and the
+ * crow -> col -> K / V load chain leave the position's critical path.
+ */
+enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2 };
+int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
+                         int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
+                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                         const int32_t* crow, const int32_t* col, int64_t col_stride_n,
+                         const int32_t* head_off,
+                         const float* row_scale, /* (N,H,T_dst) contiguous or NULL */
+                         const void* avg, const int64_t* avg_strides, /* dtype `dtype`, or NULL */
+                         const float* mix,       /* (N,H,T_dst) contiguous or NULL */
+                         void* out, int out_dtype, const int64_t* out_strides,
+                         float* probs_out, int64_t probs_stride_n,
+                         const uint8_t* block_path, /* buffer filled by sea_attention_plan, or NULL */
+                         int flags,
+                         const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols, /* fused form */
+                         const int32_t* t_src_dev, /* decode form, or NULL */
+                         sea_stream_t stream);
 int64_t sea_attention_few_rows(void);
-int sea_sparse_attention_fused(const void* q, const void* k, const void* v, int dtype,
-                               int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
-                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                               const int32_t* crow, int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                               const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
-                               void* out, int out_dtype, const int64_t* out_strides,
-                               float* probs_out, int64_t probs_stride_n,
-                               const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_columns,
-                               sea_stream_t stream);
-
-/* The DECODE form of the fused launch (round 5; SURVEY 8f-3, src/main/opt_generate.py:131, PA/attention.py:410-426): a position
- * of a graph-replayed decoding session has static kernel arguments, so the sequence length the row widths follow is read
- * from device memory (*t_src_dev, what sea_csr_emit_at reads) while T_cap -- the row count of the K / V caches -- is the
- * stride the column ids are encoded with (head * T_cap + key) and the T_src the operator is called with.  T_dst <= 8 new
- * rows per sequence; 16-bit d = 64 / 80 / 128 or fp32 d = 32 / 64 (the fused forms), else SEA_EUNSUPPORTED (run
- * sea_csr_emit_at + sea_sparse_attention_ex).  The lane groups of a workgroup that have no row touch the K / V rows of the
- * expanded lists before the one group per row starts its dependent walk (what the unfused kernel does from `col`).  Same
- * arithmetic in the same order as sea_csr_emit_at + sea_sparse_attention_ex: the step stays bitwise the stateless forward;
- * the emit launch (or the emit phase of sea_decode_cnn_tail_select: pass col = NULL there) and the crow -> col -> K / V
- * load chain leave the position's critical path.  `col`: scratch / output as in sea_sparse_attention_fused. */
-int sea_sparse_attention_fused_at(const void* q, const void* k, const void* v, int dtype,
-                                  int64_t N, int64_t H, int64_t T_dst, int64_t T_cap, int64_t D,
-                                  const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                  const int32_t* crow, int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                  const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
-                                  void* out, int out_dtype, const int64_t* out_strides,
-                                  const uint32_t* bits, int64_t T_m, const int32_t* t_src_dev, int is_causal, int max_k,
-                                  int write_columns, sea_stream_t stream);
 
 /* Backward of the fused operator WITHOUT its epilogue (o = sum_e softmax_e(q.k_e) v_e; the caller applies row scale and mix
  * in its autograd framework): dQ, dK, dV from dO.  Reference shape: masked_mm.py:169-267 + the dense branch's autograd
@@ -288,7 +271,7 @@ int sea_sparse_attention_bwd_gather(const void* q, const void* k, const void* v,
  * kept-pixel bit masks of sea_topk_select / sea_predictor_tail_select (`bits`, (N,T_dst,ceil(H*T_m/32))): entries the block
  * walks against the 16-key tiles it would stage, favourable when entries >= entries_per_tile * tiles (<= 0: 30) -- followed,
  * 4-byte aligned, by the int32 COUNT of such blocks: `block_path` holds ((N*H*ceil(T_dst/16) + 3) & ~3) + 4 bytes.
- * With a plan, sea_sparse_attention_ex launches BOTH kernels over all rows; each reads the count, and ONE of them runs
+ * With a plan, sea_sparse_attention launches BOTH kernels over all rows; each reads the count, and ONE of them runs
  * the launch while the other's workgroups exit at once: the tile kernel when the favourable blocks' share exceeds 1/2
  * (D <= 80) or 13/20 (D = 128), else the gather kernels.  (Round 2 split a launch per block between the two kernels; since
  * the gather kernels deal their rows by length that mix is slower than the better kernel alone -- scripts/
@@ -319,18 +302,16 @@ int sea_split_layernorm(const void* x, int dtype, int64_t N, int64_t C, int64_t 
  * conv_w16 (optional, may be NULL): (16*ceil(H/16), Cp) row-major copy of the weight in `dtype`, channels zero-padded
  * to Cp (multiple of 32) -- with it, 16-bit NHWC / C8 input takes the MFMA variant of the kernel;
  * probs and optional scores (pre-softmax) are (N,H,T,T_m) contiguous of `dtype`.
- * Requires W4*up == T_m, T_m <= 512, W4 a multiple of the 16-byte vector width. */
-int sea_predictor_tail(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
+ * Requires W4*up == T_m, T_m <= 512, W4 a multiple of the 16-byte vector width.
+ * z form, y = NULL and z != NULL: the same tail from z = the 1x1 convolution's output (N, T, H, W4) fp32, as the epilogue
+ * of sea_causal_conv_c8 writes it (16-bit maps, W4 % 4 == 0; C, y_strides, conv_wT, conv_w16 and Cp are not read;
+ * conv_b (>= H) fp32 is still needed: the zero-padded border pixels of the padded 1x1 convolution are the bias alone).
+ * Exactly one of y and z is non-NULL, else SEA_EINVAL. */
+int sea_predictor_tail(const void* y, const float* z, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
                        int64_t up, int64_t T_m, const int64_t* y_strides,
                        const void* conv_wT, const void* conv_b, const void* conv_w16, int64_t Cp,
                        const void* gamma, const void* beta, float eps,
                        void* probs, void* scores, sea_stream_t stream);
-
-/* The same tail from z = the 1x1 convolution's output (N, T, H, W4) fp32, as sea_causal_conv_c8_z writes it (16-bit maps;
- * conv_b (>= H) fp32 is still needed: the zero-padded border pixels of the padded 1x1 convolution are the bias alone). */
-int sea_predictor_tail_z(const float* z, int dtype, int64_t N, int64_t H, int64_t T, int64_t W4, int64_t up, int64_t T_m,
-                         const float* conv_b, const void* gamma, const void* beta, float eps, void* probs, void* scores,
-                         sea_stream_t stream);
 
 /* Predictor tail + grouped top-k selection in one launch: sea_predictor_tail (MFMA variant, 16-bit
  * channels-last / C8 input) followed by sea_topk_select on the probability map it produces, with the map's values
@@ -347,49 +328,51 @@ int sea_predictor_tail_z(const float* z, int dtype, int64_t N, int64_t H, int64_
  * fp32 data (round 5, the reference's measurement protocol): dtype = SEA_F32 with T_m = 256 (W4 = 64, up = 4), H % 4 == 0,
  * H <= 32; `conv_w16` then carries sea_predictor_tail's conv_wT, the (C, Hpad) FP32 transposed weights (Cp ignored), probs is
  * mandatory (the fp32 map is always written) and the 1x1 convolution runs on the fp32 MFMA -- bit-identical to
- * sea_predictor_tail (fp32, channels-last / C8 input: the same device code) followed by sea_topk_select. */
-int sea_predictor_tail_select(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                              int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
+ * sea_predictor_tail (fp32, channels-last / C8 input: the same device code) followed by sea_topk_select.
+ * z form, y = NULL and z != NULL (round 5): the launch is fed with z (N, T, H, W4) fp32 = the 1x1 convolution's output from
+ * the epilogue of sea_causal_conv_c8: the "z tile" of a row -- loads of y and of the weights, MFMAs, LDS stores: a third of
+ * a row's life in this issue-bound kernel -- becomes a 16-byte-per-lane copy into LDS.  C, y_strides, conv_w16 and Cp are
+ * not read; everything else (and every bit of the result) as with y; a caller that wants the map later runs the z form of
+ * sea_predictor_tail on the same z.  Exactly one of y and z is non-NULL, else SEA_EINVAL.
+ * DECODE form, t_src_dev != NULL (y only; T_m = 256, W4 = 64, up = 4): the T rows are the LAST rows of sequences of
+ * *t_src_dev tokens (device memory, for a step replayed as a HIP graph); `keep` is then the absolute table -- keep[i] = K of
+ * the row that sees i+1 keys, for every position the session can reach (attention.py:849-866) -- and keep_stride_n / T_src
+ * are not read.  crow_out (decode form only, T == 1; else NULL): (N, 2) int32 = [0, row total] per batch item, i.e. the
+ * one-row CSR's crow -- the step then needs no sea_csr_row_scan launch. */
+int sea_predictor_tail_select(const void* y, const float* z, int dtype, int64_t N, int64_t C, int64_t H, int64_t T,
+                              int64_t W4, int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
                               const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
                               void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n,
-                              int64_t T_src, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                              int32_t* head_off, const uint32_t* consts_tab, sea_stream_t stream);
+                              int64_t T_src, const int32_t* t_src_dev, int is_causal, int max_k, uint32_t* bits,
+                              int32_t* row_nnz, int32_t* head_off, int32_t* crow_out, const uint32_t* consts_tab,
+                              sea_stream_t stream);
 
 /* The per-pixel constants of the tail -- for every output pixel the <= 3 taps of the area resize, gamma, beta: (W4, up, T_m,
  * gamma, beta) only, the same for every row -- computed ONCE into tab (3 * 256 uint32, 16-byte aligned) instead of by every
- * row's workgroup (round 5; T_m = 256).  The `consts_tab` argument of sea_predictor_tail_select / _at / _z and
+ * row's workgroup (round 5; T_m = 256).  The `consts_tab` argument of sea_predictor_tail_select (every form) and
  * sea_decode_cnn_tail_select takes it (NULL = each row computes the table itself, as before): -3.5 % of the launch at
  * OPT-1.3B x 8, -8 % at H = 12. */
 int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, const void* gamma, const void* beta,
                               uint32_t* tab, sea_stream_t stream);
 
-/* The same launch fed with z (N, T, H, W4) fp32 = the 1x1 convolution's output from sea_causal_conv_c8_z (round 5): the "z
- * tile" of a row -- loads of y and of the weights, MFMAs, LDS stores: a third of a row's life in this issue-bound kernel --
- * becomes a 16-byte-per-lane copy into LDS.  Everything else (and every bit of the result) as sea_predictor_tail_select;
- * a caller that wants the map later runs sea_predictor_tail_z on the same z. */
-int sea_predictor_tail_select_z(const float* z, int dtype, int64_t N, int64_t H, int64_t T, int64_t W4, int64_t up,
-                                int64_t T_m, const float* conv_b, const void* gamma, const void* beta, float eps,
-                                void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n, int64_t T_src,
-                                int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
-                                const uint32_t* consts_tab, sea_stream_t stream);
-
 /* A decoding step's predictor CNN + tail + selection + state advance in ONE launch (round 5; perlin_attention/decode.py).
- * A graph-replayed position used to run conv1, conv2 (each over the session's whole 25-row window), sea_predictor_tail_select_at
- * and sea_c8_window_shift: four launches for one new row per sequence, each at its fixed cost.  Here one workgroup per sequence
+ * A graph-replayed position used to run conv1, conv2 (each over the session's whole 25-row window), the decode form of
+ * sea_predictor_tail_select and sea_c8_window_shift: four launches for one new row per sequence, each at its fixed cost.
+ * Here one workgroup per sequence
  *   - computes conv1's new row from x rows t - 2 dil, t - dil (ring of the MLP's earlier rows) and t (`x_new`, which the MLP
  *     launch has just written), conv2's new row from the ring of conv1's rows -- bit for bit the rows sea_causal_conv_c8 writes
  *     (same operand placement and k order; weights read straight from the packed images, w1_packed / w2_packed / bias as for
  *     sea_causal_conv_c8 with Cin = Cout = C, 3 x 3, `dilation`, pad_w = dilation);
- *   - runs the tail + selection of sea_predictor_tail_select_at on that row (T_m = 256, W4 = 64, up = 4; keep_table over
+ *   - runs the decode form of sea_predictor_tail_select on that row (T_m = 256, W4 = 64, up = 4; keep_table over
  *     absolute rows; outputs bits (N,1,W), row_nnz (N,1), head_off (N,1,H+1), crow_out (N,2), optional probs (N,H,1,256));
  *   - files x_new and conv1's new row in their rings (slot = position % ring size: nothing is shifted) and, as the last
  *     workgroup to finish, advances counters = {rows seen (the new row's position), T_src of the step, T_src of the step JUST
  *     FINISHED}: counters[2] = counters[1], then counters[0] += 1, counters[1] += 1.  Launches behind this one in the same
- *     step (sea_csr_emit_at) read their T_src from counters + 2.  `ticket` is one zero-initialised int32 the library owns
- *     between calls.
- * `col` (optional, C <= 64): the step's CSR columns (N, col_stride_n) int32, ids = head * T_cap + key as sea_csr_emit_at writes
- *   them, at most z_cap per item -- the emit of the one new row runs inside this launch too (one launch less per position);
- *   NULL = the caller runs sea_csr_emit_at.
+ *     step (the decode form of sea_csr_emit) read their T_src from counters + 2.  `ticket` is one zero-initialised int32
+ *     the library owns between calls.
+ * `col` (optional, C <= 64): the step's CSR columns (N, col_stride_n) int32, ids = head * T_cap + key as the decode form of
+ *   sea_csr_emit writes them, at most z_cap per item -- the emit of the one new row runs inside this launch too (one launch
+ *   less per position); NULL = the caller runs that emit.
  * x_new (N, C/8, 64, 8); x_ring (N, ring_x, C/8, 64, 8); y1_ring (N, ring_y, C/8, 64, 8); y2 (N, C/8, 64, 8) scratch, all `dtype`
  * (16-bit); ring sizes > 2 * dilation.  C = 2 H <= 80, H % 4 == 0. */
 int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
@@ -424,32 +407,27 @@ int sea_cumavg_sliced(const void* v, int dtype, int64_t N, int64_t H, int64_t T,
  *   (attention.py:271-276). */
 int sea_split_layernorm_c8(const void* x, int dtype, int64_t N, int64_t C, int64_t T, int64_t S, int64_t W,
                            const void* gamma, const void* beta, float eps, void* out, sea_stream_t stream);
-int sea_causal_conv_c8(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                       const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w,
-                       int relu, void* y, sea_stream_t stream);
-
-/* fp32 twin of sea_causal_conv_c8 (round 5): exact fp32 products and accumulation on v_mfma_f32_16x16x4_f32, for callers that
+/* fp32 form, dtype = SEA_F32 (round 5): exact fp32 products and accumulation on v_mfma_f32_16x16x4_f32, for callers that
  * keep the reference's fp32 measurement protocol (src/main/benchmark_bert.py:196-239).  x (N,T,Cin/8,W,8), y (N,T,Cout/8,W,8)
  * fp32 in the same channel-blocked layout; w_packed (Cout, ksize*ksize, CinP) fp32 = weight[co, ci, i, j] laid out
  * [co][i*ksize+j][ci], ci zero-padded to CinP = Cin rounded up to 16; bias (Cout) fp32.  ksize 1 or 3, Cout <= 80;
- * SEA_EUNSUPPORTED when the fp32 weight image (16*ceil(Cout/16) x ksize^2 x CinP x 4 B) exceeds the 160 KB LDS. */
-int sea_causal_conv_c8_f32(const float* x, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                           const float* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w,
-                           int relu, float* y, sea_stream_t stream);
-
-/* The LAST (conv, ReLU) pair of the predictor CNN with the tail's 1x1 convolution in its epilogue (round 5).  `KeepRes` adds
- * no residual (modules.py:42-55) and a 1x1 kernel commutes with the nearest x`up` upsample that sits between the two
- * (attention.py:266-281), so  z = W1 . relu(conv(x) + bias) + b1  can be formed while the activation tile is still in the
- * matrix pipe's registers: + ceil(H/16) * ceil(Cout/32) MFMAs per 16 pixels (+5.5 % at 64 -> 64 channels, 32 heads).
- *   arguments up to `y` as sea_causal_conv_c8 (ksize = 3, Cout <= 80); y may be NULL (the activation is then not written);
+ * SEA_EUNSUPPORTED when the fp32 weight image (16*ceil(Cout/16) x ksize^2 x CinP x 4 B) exceeds the 160 KB LDS, and with z.
+ *
+ * 1x1 epilogue, z != NULL (round 5, 16-bit data): the LAST (conv, ReLU) pair of the predictor CNN with the tail's 1x1
+ * convolution in its epilogue.  `KeepRes` adds no residual (modules.py:42-55) and a 1x1 kernel commutes with the nearest
+ * x`up` upsample that sits between the two (attention.py:266-281), so  z = W1 . relu(conv(x) + bias) + b1  can be formed
+ * while the activation tile is still in the matrix pipe's registers: + ceil(H/16) * ceil(Cout/32) MFMAs per 16 pixels
+ * (+5.5 % at 64 -> 64 channels, 32 heads).  ksize = 3, Cout <= 80; y may be NULL (the activation is then not written);
  *   conv1x1_w16 (16*ceil(H/16), Cp1) 16-bit row-major, zero padded, Cp1 = Cout rounded up to 32 (= sea_predictor_tail's
- *   conv_w16); conv1x1_b (>= H) fp32; z (N, T, H, W) fp32 -- what sea_predictor_tail_z / sea_predictor_tail_select_z read.
+ *   conv_w16); conv1x1_b (>= H) fp32; z (N, T, H, W) fp32 -- what the z forms of sea_predictor_tail /
+ *   sea_predictor_tail_select read.
  * The activation enters the product rounded to `dtype` exactly as the y store rounds it, with the operand placement and k
- * order of the tail kernels' own z stage: z is bit for bit what they compute from y. */
-int sea_causal_conv_c8_z(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                         const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w,
-                         int relu, void* y, const void* conv1x1_w16, int64_t Cp1, const float* conv1x1_b, int64_t H,
-                         float* z, sea_stream_t stream);
+ * order of the tail kernels' own z stage: z is bit for bit what they compute from y.  z = NULL: no epilogue (conv1x1_w16,
+ * Cp1, conv1x1_b and H are not read). */
+int sea_causal_conv_c8(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
+                       const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w,
+                       int relu, void* y, const void* conv1x1_w16, int64_t Cp1, const float* conv1x1_b, int64_t H,
+                       float* z, sea_stream_t stream);
 
 /* Predictor MLP of SEA's estimator in one launch, 16-bit data, bf16/f16 MFMA:
  *   enc  = GELU(LayerNorm_D1(x W1^T + b1))                      attention_predictor_enc      (attention.py:190-196)
@@ -487,31 +465,27 @@ int sea_predictor_mlp(const void* x, int dtype, int64_t N, int64_t H, int64_t T,
  * 16-bit data runs on 16-bit MFMA with split (hi+lo) operands (64-row chunks at D = 64, 32-row chunks
  * and two column blocks per wave at D = 80 / 128); those kernels can also emit avg_out (N,H,T,D) = cumsum_t(v)/(t+1),
  * the input of the mix step (attention.py:1220-1222) -- pass NULL otherwise (sea_performer_avg_supported says when it
- * may be non-NULL).  FP32 data: fp32 MFMA throughout. */
-int sea_performer_causal(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                         int64_t pos_stride, void* out, void* avg_out, sea_stream_t stream);
-
-/* Sequence-parallel form of sea_performer_causal.  One workgroup walks one (n, h) pair's rows in order, so N*H pairs
+ * may be non-NULL).  FP32 data: fp32 MFMA throughout.
+ *
+ * Sequence-parallel form, n_segments > 1.  One workgroup walks one (n, h) pair's rows in order, so N*H pairs
  * fill N*H compute units: the reference's configurations that put ONE sequence on a GPU (BASELINE configs 4-5: 32-40
  * pairs on 256 CUs) leave most of the chip idle.  With n_segments > 1 the T rows are cut into segments of whole
  * 64-row chunks; a first launch leaves every segment's state increment (sum phi(k)^T [pos|v], sum phi(k), sum v) in
  * `workspace`, the second starts each segment from the sum of the increments before it (added in segment order:
  * results are reproducible run to run; they differ from the one-segment kernel in fp32 summation order only).
  * sea_performer_plan proposes n_segments for a shape (1 when N*H already fills the chip) and the workspace size;
- * the caller owns the workspace (16-byte aligned, no initialisation needed).  n_segments = 1 is
- * sea_performer_causal (workspace may be NULL).  Same role in the reference as sea_performer_causal. */
+ * the caller owns the workspace (16-byte aligned, no initialisation needed).  n_segments = 1: one pass, workspace may be
+ * NULL. */
+int sea_performer_causal(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                         int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
+                         void* workspace, int64_t workspace_bytes, sea_stream_t stream);
 /* 1 when sea_performer_causal* can also write `avg_out` (the cumulative average of v) for this head size, feature
  * count and dtype, else 0 -- the one predicate both sides of the ABI use (host arithmetic only). */
 int sea_performer_avg_supported(int64_t D, int64_t nb, int dtype);
 int sea_performer_plan(int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb, int dtype,
                        int64_t* n_segments, int64_t* workspace_bytes);
-int sea_performer_causal_segmented(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                   const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                   const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                   int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
-                                   void* workspace, int64_t workspace_bytes, sea_stream_t stream);
 
 /* Stateful, CHUNK-ALIGNED form of the causal Performer for kv-cache decoding (role of the reference's
  * StatefulCausalPerformer, attention_state.py:43-140, called from attention.py:559-566 when pconfig.use_cache; parity
@@ -527,49 +501,29 @@ int sea_performer_causal_segmented(const void* q, const void* k, const void* v, 
  * operand tiles, same summation order): outputs and images are BITWISE those of sea_performer_causal over the whole
  * sequence, however the sequence is cut into calls.  16-bit data, D in {64, 80, 128} (fp32 data: SEA_EUNSUPPORTED -- the
  * torch-side state of attention_state.py serves it).  state_in and state_out may alias when n_segments = 1.
- * n_segments / workspace as in sea_performer_causal_segmented (1 / NULL for the few rows of a decode step; a prefill may
- * cut: its image then sums the segments' increments in segment order). */
+ * n_segments / workspace as in sea_performer_causal (1 / NULL for the few rows of a decode step; a prefill may
+ * cut: its image then sums the segments' increments in segment order).
+ * DEVICE-position form, t_base_dev != NULL (a step replayed as a HIP graph, see below): t_base = *t_base_dev and the `t_base`
+ * argument is not read.  k / v are then the BASES (row 0) of the kv-caches -- they already hold the new rows -- and pos the
+ * BASE of the value embedding: the kernel finds the chunk boundary itself and walks the open chunk from there.  q / out /
+ * avg_out: the T new rows.  state_in and state_out are both required and may be one image (updated in place; it changes
+ * only when a chunk completes).  One segment: n_segments = 1 (else SEA_EUNSUPPORTED), workspace not read. */
 int64_t sea_performer_chunk_rows(int64_t D, int64_t nb, int dtype);
 int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype);
 int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
                               const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                               int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
-                              int64_t state_bytes, int64_t t_base, int64_t n_segments, void* workspace,
-                              int64_t workspace_bytes, sea_stream_t stream);
+                              int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev, int64_t n_segments,
+                              void* workspace, int64_t workspace_bytes, sea_stream_t stream);
 
 /* ---- decode step with the position in DEVICE memory ------------------------------------------------------------------
  * The reference's generation loop (src/main/opt_generate.py:131 -> attention.py use_cache branches + attention_state.py)
  * runs one position per forward.  For a step that is captured ONCE as a HIP graph and replayed per token, nothing that
- * changes with the position may sit in kernel arguments: these three entry points read it from device memory instead
- * (an int32 the captured step itself increments).  Everything else of the step -- predictor MLP, the two convolutions
- * over the cached window, row scan, fused attention over K / V caches of fixed capacity -- has static arguments already.
- *
- * sea_performer_causal_step_at: sea_performer_causal_step with t_base = *t_base_dev.  k_cache / v_cache are the BASES (row 0)
- *   of the kv-caches -- they already hold the new rows -- and pos_table the BASE of the value embedding: the kernel finds
- *   the chunk boundary itself and walks the open chunk from there.  q / out / avg_out: the T new rows.  state_in / state_out
- *   may be one image (updated in place; it changes only when a chunk completes).
- * sea_predictor_tail_select_at: sea_predictor_tail_select for the LAST T rows of sequences of *t_src_dev tokens;
- *   keep_table[i] = K of the row that sees i+1 keys, for every position the session can reach (attention.py:849-866).
- *   crow_out (optional; T == 1 only): (N, 2) int32 = [0, row total] per batch item, i.e. the one-row CSR's crow -- the step then
- *   needs no sea_csr_row_scan launch.
- * sea_csr_emit_at: sea_csr_emit with the row widths following *t_src_dev and column ids = head * T_cap + key for a FIXED
- *   capacity T_cap >= *t_src_dev (the K / V caches' row count), so sea_sparse_attention is called with T_src = T_cap. */
-int sea_performer_causal_step_at(const void* q, const void* k_cache, const void* v_cache, const void* pos_table, int dtype,
-                                 const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                 const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                 int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
-                                 int64_t state_bytes, const int32_t* t_base_dev, sea_stream_t stream);
-int sea_predictor_tail_select_at(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                                 int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
-                                 const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                                 void* probs, void* scores, const int32_t* keep_table, const int32_t* t_src_dev,
-                                 int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
-                                 int32_t* crow_out, const uint32_t* consts_tab,
-                                 sea_stream_t stream);
-int sea_csr_emit_at(const uint32_t* bits, const void* crow, int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
-                    const int32_t* t_src_dev, int64_t T_cap, int is_causal, int max_k, void* col, int idx_bytes,
-                    int64_t col_stride_n, int64_t z_cap, sea_stream_t stream);
+ * changes with the position may sit in kernel arguments: the decode forms of sea_performer_causal_step (t_base_dev),
+ * sea_predictor_tail_select, sea_csr_emit and sea_sparse_attention (t_src_dev) read it from device memory instead (an int32
+ * the captured step itself increments).  Everything else of the step -- predictor MLP, the two convolutions over the
+ * cached window, row scan, fused attention over K / V caches of fixed capacity -- has static arguments already. */
 
 /* Algorithmic bytes of one sea_sparse_attention launch:
  * Z*(2*D*s + 4) + N*H*T_dst*(2*D*s + 4).  Host-side helper, no device work. */

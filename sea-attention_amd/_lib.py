@@ -9,7 +9,7 @@ import torch
 from . import _build
 
 SEA_F32, SEA_F16, SEA_BF16 = 0, 1, 2
-ABI_VERSION = 3            # include/sea_hip.h: SEA_ABI_VERSION
+ABI_VERSION = 4            # include/sea_hip.h: SEA_ABI_VERSION
 _DTYPES = {torch.float32: SEA_F32, torch.float16: SEA_F16, torch.bfloat16: SEA_BF16}
 
 _lib = None
@@ -26,20 +26,15 @@ _SIGNATURES = {
     "sea_mask_to_bits": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, i64, c_int, c_int,
                           ptr, ptr, ptr, ptr], c_int),
     "sea_csr_row_scan": ([ptr, i64, i64, ptr, c_int, ptr], c_int),
-    "sea_csr_emit": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, ptr], c_int),
+    "sea_csr_emit": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, ptr, ptr], c_int),
     "sea_csr_head_offsets": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr], c_int),
     "sea_csr_sddmm": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, ptr, ptr, c_int, i64, ptr, ptr], c_int),
     "sea_csr_softmax": ([ptr, ptr, i64, i64, i64, i64, ptr, ptr, c_int, i64, ptr], c_int),
     "sea_csr_elmul": ([ptr, ptr, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, c_int, i64, ptr], c_int),
     "sea_csr_spmm": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, ptr, ptr, c_int, i64, ptr, ptr, ptr], c_int),
     "sea_sparse_attention": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                              ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr], c_int),
-    "sea_sparse_attention_ex": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                                 ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int, ptr], c_int),
-    "sea_sparse_attention_fused": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                                    ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, i64, c_int, c_int, c_int, ptr], c_int),
-    "sea_sparse_attention_fused_at": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                                       ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int, c_int, c_int, ptr], c_int),
+                              ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int,
+                              ptr, i64, c_int, c_int, c_int, ptr, ptr], c_int),
     "sea_sparse_attention_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
                                   ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_sparse_attention_bwd_workspace_bytes": ([i64, i64, i64, i64], i64),
@@ -48,43 +43,33 @@ _SIGNATURES = {
     "sea_attention_plan": ([ptr, i64, i64, i64, i64, i64, c_int, ctypes.c_float, ptr, ptr], c_int),
     "sea_sparse_attention_bytes": ([i64, i64, i64, i64, i64, c_int], i64),
     "sea_split_layernorm": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr, ctypes.c_float, c_int, ptr, ptr], c_int),
-    "sea_predictor_tail": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, ptr, i64, ptr, ptr,
+    "sea_predictor_tail": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, ptr, i64, ptr, ptr,
                             ctypes.c_float, ptr, ptr, ptr], c_int),
     "sea_cumavg": ([ptr, c_int, i64, i64, i64, i64, _i64p, ptr, ptr], c_int),
     "sea_cumavg_sliced": ([ptr, c_int, i64, i64, i64, i64, _i64p, ptr, i64, ptr, i64, ptr], c_int),
-    "sea_predictor_tail_select": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, i64, ptr, ptr,
-                                   ctypes.c_float, ptr, ptr, ptr, i64, i64, c_int, c_int, ptr, ptr, ptr, ptr, ptr], c_int),
+    "sea_predictor_tail_select": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, i64, ptr, ptr,
+                                   ctypes.c_float, ptr, ptr, ptr, i64, i64, ptr, c_int, c_int, ptr, ptr, ptr, ptr, ptr, ptr],
+                                  c_int),
     "sea_predictor_tail_consts": ([c_int, i64, i64, i64, ptr, ptr, ptr, ptr], c_int),
     "sea_predictor_mlp": ([ptr, c_int, i64, i64, i64, i64, _i64p, i64, i64, ptr, ptr, ptr, ctypes.c_float,
                            ctypes.c_float, ptr, i64, ptr, ptr, ptr, ptr], c_int),
     "sea_split_layernorm_c8": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr, ctypes.c_float, ptr, ptr], c_int),
-    "sea_causal_conv_c8": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, i64, ptr, c_int, c_int, c_int, c_int, ptr, ptr], c_int),
+    "sea_causal_conv_c8": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, i64, ptr, c_int, c_int, c_int, c_int, ptr,
+                            ptr, i64, ptr, i64, ptr, ptr], c_int),
     "sea_decode_cnn_tail_select": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int, c_int,
                                     ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr, ptr, ptr, ptr,
                                     ptr, i64, i64, i64, ptr, ptr], c_int),
-    "sea_causal_conv_c8_f32": ([ptr, i64, i64, i64, i64, i64, ptr, i64, ptr, c_int, c_int, c_int, c_int, ptr, ptr], c_int),
-    "sea_causal_conv_c8_z": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, i64, ptr, c_int, c_int, c_int, c_int, ptr,
-                              ptr, i64, ptr, i64, ptr, ptr], c_int),
-    "sea_predictor_tail_z": ([ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ctypes.c_float, ptr, ptr, ptr], c_int),
-    "sea_predictor_tail_select_z": ([ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ctypes.c_float, ptr, ptr,
-                                     ptr, i64, i64, c_int, c_int, ptr, ptr, ptr, ptr, ptr], c_int),
-    "sea_performer_causal": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr, ptr], c_int),
+    "sea_performer_causal": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
+                              i64, ptr, i64, ptr], c_int),
     "sea_performer_state_bytes": ([i64, i64, i64, i64, c_int], i64),
     "sea_performer_chunk_rows": ([i64, i64, c_int], i64),
     "sea_attention_few_rows": ([], i64),
     "sea_performer_causal_step": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
-                                   ptr, ptr, i64, i64, i64, ptr, i64, ptr], c_int),
-    "sea_performer_causal_step_at": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
-                                      ptr, ptr, i64, ptr, ptr], c_int),
-    "sea_predictor_tail_select_at": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, i64, ptr, ptr,
-                                      ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
+                                   ptr, ptr, i64, i64, ptr, i64, ptr, i64, ptr], c_int),
     "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
-    "sea_csr_emit_at": ([ptr, ptr, i64, i64, i64, i64, ptr, i64, c_int, c_int, ptr, c_int, i64, i64, ptr], c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),
     "sea_performer_plan": ([i64, i64, i64, i64, i64, c_int, _i64p, _i64p], c_int),
-    "sea_performer_causal_segmented": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
-                                        i64, ptr, i64, ptr], c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

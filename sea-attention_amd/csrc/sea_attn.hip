@@ -1081,16 +1081,20 @@ static int check_dtype(const char* name, int dtype) {
   return SEA_OK;
 }
 
-// bits != NULL: the fused form (sea_sparse_attention_fused) -- `col` is written by the launch, not read
-static int attention_entry(const char* nm, const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                           int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                           const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                           const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                           const float* row_scale, const void* avg, const int64_t* avg_strides,
-                           const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                           float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
-                           const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols, const int32_t* t_src_dev,
-                           sea_stream_t stream) {
+extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                    float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
+                                    const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                    const int32_t* t_src_dev, sea_stream_t stream) {
+  const char* nm = "sea_sparse_attention";
+  // bits != NULL: the fused form -- `col` is written by the launch, not read -- which runs on the gather kernels;
+  // t_src_dev != NULL: its decode form (T_src is then the capacity of the K / V caches)
+  SEA_REQUIRE(bits != nullptr || t_src_dev == nullptr, SEA_EINVAL, "%s: the decode form (t_src_dev) needs bits", nm);
+  if (bits) flags = SEA_ATTN_GATHER;
   SEA_REQUIRE(q && k && v && crow && col && head_off && out && q_strides && k_strides && v_strides && out_strides,
               SEA_EINVAL, "%s: null pointer", nm);
   if (int e = check_dtype(nm, dtype)) return e;
@@ -1128,7 +1132,7 @@ static int attention_entry(const char* nm, const void* q, const void* k, const v
   p.bits = bits; p.col_w = const_cast<int32_t*>(col); p.T_m = (int)T_m; p.W = (int)((H * T_m + 31) / 32);
   p.max_k = max_k; p.is_causal = is_causal;
   p.fuse_cap = 8192;                                        // entries of a block's key lists held in LDS (32 KB)
-  p.write_cols = write_cols;
+  p.write_cols = write_cols != 0;
   p.t_src_dev = t_src_dev;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && probs_out == nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
@@ -1168,68 +1172,7 @@ static int attention_entry(const char* nm, const void* q, const void* k, const v
   return SEA_OK;
 }
 
-extern "C" int sea_sparse_attention_ex(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                       int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                       const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                       const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                       const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                       const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                       float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
-                                       sea_stream_t stream) {
-  return attention_entry("sea_sparse_attention", q, k, v, dtype, N, H, T_dst, T_src, D, q_strides, k_strides, v_strides, crow, col,
-                         col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, probs_out,
-                         probs_stride_n, block_path, flags, nullptr, 0, 0, 0, 1, nullptr, stream);
-}
-
-// Steps I + J in ONE launch: the gather kernel expands the selection's kept pixels to key columns itself (the emit's
-// arithmetic), writes them to `col` and walks them from LDS.  crow / head_off as for sea_sparse_attention (from
-// sea_csr_row_scan and the selection launch); `col` (N, col_stride_n) is OUTPUT here.
 extern "C" int64_t sea_attention_few_rows(void) { return SEA_ATTN_FEW_ROWS; }
-
-extern "C" int sea_sparse_attention_fused(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                          int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                          const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                          int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                          const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                          const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                          float* probs_out, int64_t probs_stride_n, const uint32_t* bits, int64_t T_m,
-                                          int is_causal, int max_k, int write_columns, sea_stream_t stream) {
-  SEA_REQUIRE(bits != nullptr, SEA_EINVAL, "sea_sparse_attention_fused: null pointer");
-  return attention_entry("sea_sparse_attention_fused", q, k, v, dtype, N, H, T_dst, T_src, D, q_strides, k_strides, v_strides, crow,
-                         col, col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, probs_out,
-                         probs_stride_n, nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_columns != 0, nullptr, stream);
-}
-
-// The decode form of the fused launch: a graph-replayed step (opt_generate.py:131) has static arguments, so the
-// sequence length the row widths follow is read from device memory and T_src = T_cap is the fixed capacity of the K / V
-// caches, with which the column ids are encoded (sea_csr_emit_at's convention).  T_dst <= 8 rows per sequence; the lane groups
-// that have no row touch the K / V rows of the block's expanded lists before the walk starts.  Same arithmetic, same order
-// as sea_csr_emit_at + sea_sparse_attention: the step stays bitwise the stateless forward.
-extern "C" int sea_sparse_attention_fused_at(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                             int64_t T_dst, int64_t T_cap, int64_t D, const int64_t* q_strides,
-                                             const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                             int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                             const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                             const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                             const uint32_t* bits, int64_t T_m, const int32_t* t_src_dev, int is_causal,
-                                             int max_k, int write_columns, sea_stream_t stream) {
-  SEA_REQUIRE(bits != nullptr && t_src_dev != nullptr, SEA_EINVAL, "sea_sparse_attention_fused_at: null pointer");
-  return attention_entry("sea_sparse_attention_fused_at", q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides,
-                         crow, col, col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr,
-                         0, nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_columns != 0, t_src_dev, stream);
-}
-
-extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                    sea_stream_t stream) {
-  return sea_sparse_attention_ex(q, k, v, dtype, N, H, T_dst, T_src, D, q_strides, k_strides, v_strides, crow, col,
-                                 col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides,
-                                 nullptr, 0, nullptr, SEA_ATTN_AUTO, stream);
-}
 
 extern "C" int sea_attention_plan(const uint32_t* bits, int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t T_m,
                                   int is_causal, float entries_per_tile, uint8_t* block_path, sea_stream_t stream) {

@@ -30,7 +30,7 @@ struct AttnParams {
   const int32_t* sel_count;
   int sel_total, sel_num, sel_den;
   int TB;  // row blocks per (n, h): ceil(T_dst / 4)
-  // fused interpolation (sea_sparse_attention_fused): the gather kernel expands the kept pixels itself -- `col` holds no
+  // fused interpolation (sea_sparse_attention with bits): the gather kernel expands the kept pixels itself -- `col` holds no
   // columns yet, the kernel WRITES them (col_w) while it walks them.  bits (N, T_dst, W) from the selection launch.
   const uint32_t* bits;
   int32_t* col_w;
@@ -39,7 +39,7 @@ struct AttnParams {
   // column array is NOT an output of this launch -- the caller's handle keeps its columns pending and sea_csr_emit writes
   // them if anybody ever reads them (round 4: the copy-out was 266 MB and ~50 us of the headline launch for no reader)
   int write_cols;
-  // decode form of the fused interpolation (sea_sparse_attention_fused_at): the row widths follow *t_src_dev (the sequence
+  // decode form of the fused interpolation (sea_sparse_attention with t_src_dev): the row widths follow *t_src_dev (the sequence
   // length, in device memory: a graph-replayed step has static arguments) while T_src above stays the FIXED capacity the
   // column ids are encoded with (head * T_src + key) and the K / V caches are laid out for.  NULL: widths follow T_src.
   const int32_t* t_src_dev;

@@ -10,7 +10,7 @@
 //
 // Mapping = the forward gather kernel's: one LPR-lane group per query row walks the row's entries, K and V rows are
 // fetched as whole 16-byte lane fragments; p_j comes from the forward's per-entry output (`probs_out` of
-// sea_sparse_attention_ex), so no score is recomputed.  dQ is owned by the row (plain store); dK and dV rows are shared
+// sea_sparse_attention), so no score is recomputed.  dQ is owned by the row (plain store); dK and dV rows are shared
 // by every query that keeps the key: fp32 global atomics (global_atomic_add_f32 executes at the memory side, ~1.3 TB/s of
 // added bytes chip-wide -- MI355X_MICROARCH.md -- which bounds this first backward; a CSC pass that turns the scatter into
 // a gather is the known next step).  All gradients are fp32; the caller casts.

@@ -616,9 +616,23 @@ static int launch_conv(const ConvParams& p, hipStream_t s, bool zepi = false) {
   return SEA_OK;
 }
 
-static int conv_common(const char* nm, const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                       const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w, int relu, void* y,
-                       const void* w1, const float* b1, int64_t H1, int64_t Cp1, float* z, bool zepi, sea_stream_t stream) {
+static int conv_f32(const char* nm, const float* x, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
+                    const float* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w, int relu,
+                    float* y, sea_stream_t stream);
+
+// z != NULL: the last (conv, ReLU) pair of the predictor CNN with the 1x1 convolution of the tail in its epilogue: writes
+// z (N, T, H, W) fp32 = W1 . relu(conv(x) + bias) + b1 and, when y is not null, the activation itself.
+extern "C" int sea_causal_conv_c8(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
+                                  const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation,
+                                  int pad_w, int relu, void* y, const void* conv1x1_w16, int64_t Cp1, const float* conv1x1_b,
+                                  int64_t H, float* z, sea_stream_t stream) {
+  const char* nm = "sea_causal_conv_c8";
+  if (dtype == SEA_F32) {
+    SEA_REQUIRE(z == nullptr, SEA_EUNSUPPORTED, "%s: the 1x1 epilogue takes 16-bit data", nm);
+    return conv_f32(nm, (const float*)x, N, T, W, Cin, Cout, (const float*)w_packed, CinP, bias, ksize, dilation, pad_w, relu,
+                    (float*)y, stream);
+  }
+  const bool zepi = z != nullptr;
   SEA_REQUIRE(x && w_packed && bias && (y || zepi), SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
   SEA_REQUIRE(N > 0 && T > 0 && W > 0 && Cin > 0 && Cout > 0 && ksize > 0 && dilation > 0 && pad_w >= 0, SEA_EINVAL,
@@ -633,34 +647,17 @@ static int conv_common(const char* nm, const void* x, int dtype, int64_t N, int6
   p.KS = ksize; p.dil = dilation; p.pad_w = pad_w; p.relu = relu;
   p.w1 = nullptr; p.b1 = nullptr; p.z = nullptr; p.H1 = 0; p.Cp1 = 0;
   if (zepi) {
-    SEA_REQUIRE(w1 && b1 && z, SEA_EINVAL, "%s: null pointer", nm);
-    SEA_REQUIRE(H1 > 0 && H1 <= 64 && Cp1 == (Cout + 31) / 32 * 32 && W % 4 == 0 && ksize == 3 && Cout <= 80, SEA_EUNSUPPORTED,
+    SEA_REQUIRE(conv1x1_w16 && conv1x1_b, SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(H > 0 && H <= 64 && Cp1 == (Cout + 31) / 32 * 32 && W % 4 == 0 && ksize == 3 && Cout <= 80, SEA_EUNSUPPORTED,
                 "%s: needs H <= 64, Cp1 = Cout rounded up to 32, W %% 4 == 0, a 3 x 3 kernel, Cout <= 80", nm);
-    SEA_REQUIRE((((uintptr_t)w1 | (uintptr_t)z) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
-    p.w1 = w1; p.b1 = b1; p.z = z; p.H1 = (int)H1; p.Cp1 = (int)Cp1;
+    SEA_REQUIRE((((uintptr_t)conv1x1_w16 | (uintptr_t)z) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
+    p.w1 = conv1x1_w16; p.b1 = conv1x1_b; p.z = z; p.H1 = (int)H; p.Cp1 = (int)Cp1;
   }
   hipStream_t s = (hipStream_t)stream;
   const int rc = dtype == SEA_BF16 ? launch_conv<__hip_bfloat16>(p, s, zepi) : launch_conv<__half>(p, s, zepi);
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported channel count / kernel size (1 or 3) / image size for the LDS weight tile", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_causal_conv_c8(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                                    const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation,
-                                    int pad_w, int relu, void* y, sea_stream_t stream) {
-  return conv_common("sea_causal_conv_c8", x, dtype, N, T, W, Cin, Cout, w_packed, CinP, bias, ksize, dilation, pad_w, relu, y,
-                     nullptr, nullptr, 0, 0, nullptr, false, stream);
-}
-
-// The last (conv, ReLU) pair of the predictor CNN with the 1x1 convolution of the tail in its epilogue: writes
-// z (N, T, H, W) fp32 = W1 . relu(conv(x) + bias) + b1 and, when y is not null, the activation itself as sea_causal_conv_c8.
-extern "C" int sea_causal_conv_c8_z(const void* x, int dtype, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                                      const void* w_packed, int64_t CinP, const float* bias, int ksize, int dilation,
-                                      int pad_w, int relu, void* y, const void* conv1x1_w16, int64_t Cp1, const float* conv1x1_b,
-                                      int64_t H, float* z, sea_stream_t stream) {
-  return conv_common("sea_causal_conv_c8_z", x, dtype, N, T, W, Cin, Cout, w_packed, CinP, bias, ksize, dilation, pad_w, relu, y,
-                     conv1x1_w16, conv1x1_b, H, Cp1, z, true, stream);
 }
 
 template <int KS>
@@ -690,12 +687,11 @@ static int launch_conv_f32(const ConvF32Params& p, hipStream_t s) {
   return SEA_OK;
 }
 
-// fp32 twin of sea_causal_conv_c8 (exact fp32 products on the fp32 MFMA): x / y in the same C8 layout with 4-byte elements,
-// w_packed (Cout, ksize*ksize, CinP) fp32 with CinP = Cin rounded up to 16.
-extern "C" int sea_causal_conv_c8_f32(const float* x, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
-                                        const float* w_packed, int64_t CinP, const float* bias, int ksize, int dilation,
-                                        int pad_w, int relu, float* y, sea_stream_t stream) {
-  const char* nm = "sea_causal_conv_c8_f32";
+// the fp32 form (exact fp32 products on the fp32 MFMA): x / y in the same C8 layout with 4-byte elements, w_packed
+// (Cout, ksize*ksize, CinP) fp32 with CinP = Cin rounded up to 16.
+static int conv_f32(const char* nm, const float* x, int64_t N, int64_t T, int64_t W, int64_t Cin, int64_t Cout,
+                    const float* w_packed, int64_t CinP, const float* bias, int ksize, int dilation, int pad_w, int relu,
+                    float* y, sea_stream_t stream) {
   SEA_REQUIRE(x && w_packed && bias && y, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(N > 0 && T > 0 && W > 0 && Cin > 0 && Cout > 0 && ksize > 0 && dilation > 0 && pad_w >= 0, SEA_EINVAL, "%s: bad shape", nm);
   SEA_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0 && CinP % 16 == 0 && CinP >= Cin && CinP - Cin < 16 && Cout <= 80, SEA_EUNSUPPORTED,

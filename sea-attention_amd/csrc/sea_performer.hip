@@ -1992,20 +1992,13 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   return SEA_OK;
 }
 
+// n_segments = 1, workspace = NULL: one pass over the rows; more segments run in parallel (sea_performer_plan picks them)
 extern "C" int sea_performer_causal(const void* q, const void* k, const void* v, const void* pos, int dtype,
                                     const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
                                     const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                    int64_t pos_stride, void* out, void* avg_out, sea_stream_t stream) {
-  return perf_entry("sea_performer_causal", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides,
-                    pos_stride, out, avg_out, 1, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, 0, stream);
-}
-
-extern "C" int sea_performer_causal_segmented(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                              const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                              int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
-                                              void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
-  return perf_entry("sea_performer_causal_segmented", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
+                                    int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
+                                    void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
+  return perf_entry("sea_performer_causal", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
                     v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, 0, stream);
 }
 
@@ -2020,29 +2013,23 @@ extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, in
 //   k, v, pos  point at ROW c0 (the caller's kv-cache / embedding table hold those rows), T + t_base % C rows are read;
 //   q, out, avg_out point at the first NEW row, T rows.
 // state_out = the image at the last chunk boundary at or below t_base + T.  16-bit data, D in {64, 80, 128}.
+// t_base_dev != NULL: the position lives in DEVICE memory (SURVEY 8f-3 / opt_generate.py:131: the decode loop captured once as
+// a HIP graph and replayed per token -- nothing position-dependent may live in kernel arguments).  *t_base_dev = rows the
+// state has seen, `t_base` is not read; k / v are the BASES (row 0) of the kv-caches, which already hold the new rows, pos
+// the BASE of the value-embedding table: the kernel finds the chunk boundary itself.  state_in and state_out may be the
+// same image (updated in place); one segment.
 extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
                                          const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
                                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                                          int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                         void* state_out, int64_t state_bytes, int64_t t_base, int64_t n_segments,
-                                         void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
-  return perf_entry("sea_performer_causal_step", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
-                    v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, state_in, state_out,
-                    state_bytes, t_base, nullptr, 1, stream);
-}
-
-// The same step with the position in DEVICE memory (SURVEY 8f-3 / opt_generate.py:131: the decode loop captured once as
-// a HIP graph and replayed per token -- nothing position-dependent may live in kernel arguments).  *t_base_dev = rows the
-// state has seen; k_cache / v_cache are the BASES (row 0) of the kv-caches, which already hold the new rows, pos_table the
-// BASE of the value-embedding table: the kernel finds the chunk boundary itself.  q / out / avg_out: the T new rows.
-// state_in and state_out may be the same image (updated in place); one segment.
-extern "C" int sea_performer_causal_step_at(const void* q, const void* k_cache, const void* v_cache, const void* pos_table, int dtype,
-                                            const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                            int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                            void* state_out, int64_t state_bytes, const int32_t* t_base_dev,
-                                            sea_stream_t stream) {
-  SEA_REQUIRE(t_base_dev && state_in && state_out, SEA_EINVAL, "sea_performer_causal_step_at: null pointer");
-  return perf_entry("sea_performer_causal_step_at", q, k_cache, v_cache, pos_table, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
-                    v_strides, pos_stride, out, avg_out, 1, nullptr, 0, state_in, state_out, state_bytes, 0, t_base_dev, 1, stream);
+                                         void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
+                                         int64_t n_segments, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
+  const char* nm = "sea_performer_causal_step";
+  if (t_base_dev) {
+    SEA_REQUIRE(state_in && state_out, SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(n_segments == 1, SEA_EUNSUPPORTED, "%s: the device-position step runs one segment", nm);
+    t_base = 0; workspace = nullptr; workspace_bytes = 0;
+  }
+  return perf_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
+                    n_segments, workspace, workspace_bytes, state_in, state_out, state_bytes, t_base, t_base_dev, 1, stream);
 }

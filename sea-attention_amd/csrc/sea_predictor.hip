@@ -521,11 +521,32 @@ extern "C" int sea_debug_tail_stamps(unsigned long long* host8) {
 }
 #endif
 
-extern "C" int sea_predictor_tail(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                                  int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_w,
+// y: the activation (any of the layouts y_strides describes).  z: the 1x1 convolution's output, as sea_causal_conv_c8's
+// epilogue writes it: (N, T, H, W4) fp32.
+extern "C" int sea_predictor_tail(const void* y, const float* z, int dtype, int64_t N, int64_t C, int64_t H, int64_t T,
+                                  int64_t W4, int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_w,
                                   const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
                                   const void* beta, float eps, void* probs, void* scores, sea_stream_t stream) {
   const char* nm = "sea_predictor_tail";
+  SEA_REQUIRE((y == nullptr) != (z == nullptr), SEA_EINVAL, "%s: exactly one of y and z", nm);
+  if (z) {
+    SEA_REQUIRE(conv_b && gamma && beta && probs, SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit maps only (dtype %d)", nm, dtype);
+    SEA_REQUIRE(N > 0 && H > 0 && T > 0 && W4 > 0 && up > 0 && T_m > 0, SEA_EINVAL, "%s: bad shape", nm);
+    SEA_REQUIRE(T_m <= 512 && W4 * up == T_m && T_m % 4 == 0 && W4 % 4 == 0, SEA_EUNSUPPORTED,
+                "%s: needs W4 * up == T_m <= 512, T_m %% 4 == 0, W4 %% 4 == 0", nm);
+    SEA_REQUIRE((((uintptr_t)probs | (uintptr_t)scores | (uintptr_t)z) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
+    TailParams p;
+    p.y = nullptr; p.w4 = nullptr; p.b4 = conv_b; p.gamma = gamma; p.beta = beta; p.probs = probs; p.scores = scores; p.eps = eps;
+    p.N = (int)N; p.C = 0; p.H = (int)H; p.T = (int)T; p.W4 = (int)W4; p.UP = (int)up; p.T_M = (int)T_m;
+    p.ys_n = p.ys_c = p.ys_t = p.ys_w = p.ys_c8 = 0; p.w16 = nullptr; p.Cp = 0; p.z = z; p.tab = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(N * T));
+    const int rc = dtype == SEA_F16 ? launch_tail_mfma<__half>(p, grid, s) : launch_tail_mfma<__hip_bfloat16>(p, grid, s);
+    SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported T_m / H for the tail's LDS plan", nm);
+    SEA_CHECK_LAUNCH(nm);
+    return SEA_OK;
+  }
   SEA_REQUIRE(y && y_strides && conv_w && conv_b && gamma && beta && probs, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_F16 || dtype == SEA_BF16, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
   SEA_REQUIRE(N > 0 && C > 0 && H > 0 && T > 0 && W4 > 0 && up > 0 && T_m > 0, SEA_EINVAL, "%s: bad shape", nm);
@@ -581,28 +602,6 @@ extern "C" int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int6
   if (dtype == SEA_F16) hipLaunchKernelGGL((tail_consts_kernel<__half>), dim3(1), dim3(256), 0, s, p, tab, 256);
   else if (dtype == SEA_F32) hipLaunchKernelGGL((tail_consts_kernel<float>), dim3(1), dim3(256), 0, s, p, tab, 256);
   else hipLaunchKernelGGL((tail_consts_kernel<__hip_bfloat16>), dim3(1), dim3(256), 0, s, p, tab, 256);
-  SEA_CHECK_LAUNCH(nm);
-  return SEA_OK;
-}
-
-// The tail from z = the 1x1 convolution's output, as sea_causal_conv_c8_z's epilogue writes it: (N, T, H, W4) fp32.
-extern "C" int sea_predictor_tail_z(const float* z, int dtype, int64_t N, int64_t H, int64_t T, int64_t W4, int64_t up, int64_t T_m,
-                                    const float* conv_b, const void* gamma, const void* beta, float eps, void* probs, void* scores,
-                                    sea_stream_t stream) {
-  const char* nm = "sea_predictor_tail_z";
-  SEA_REQUIRE(z && conv_b && gamma && beta && probs, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit maps only (dtype %d)", nm, dtype);
-  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && W4 > 0 && up > 0 && T_m > 0, SEA_EINVAL, "%s: bad shape", nm);
-  SEA_REQUIRE(T_m <= 512 && W4 * up == T_m && T_m % 4 == 0 && W4 % 4 == 0, SEA_EUNSUPPORTED,
-              "%s: needs W4 * up == T_m <= 512, T_m %% 4 == 0, W4 %% 4 == 0", nm);
-  SEA_REQUIRE((((uintptr_t)probs | (uintptr_t)scores | (uintptr_t)z) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
-  TailParams p;
-  p.y = nullptr; p.w4 = nullptr; p.b4 = conv_b; p.gamma = gamma; p.beta = beta; p.probs = probs; p.scores = scores; p.eps = eps;
-  p.N = (int)N; p.C = 0; p.H = (int)H; p.T = (int)T; p.W4 = (int)W4; p.UP = (int)up; p.T_M = (int)T_m;
-  p.ys_n = p.ys_c = p.ys_t = p.ys_w = p.ys_c8 = 0; p.w16 = nullptr; p.Cp = 0; p.z = z; p.tab = nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == SEA_F16 ? launch_tail_mfma<__half>(p, dim3((unsigned)(N * T)), s) : launch_tail_mfma<__hip_bfloat16>(p, dim3((unsigned)(N * T)), s);
-  SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported T_m / H for the tail's LDS plan", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

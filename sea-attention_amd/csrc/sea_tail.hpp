@@ -21,7 +21,7 @@ struct TailParams {
   const void* w16;   // MFMA variant: (HP16, Cp) 16-bit row-major copy of the conv weight, zero padded
   int Cp;            // channels padded to a multiple of 32
   const uint32_t* tab;  // optional [3][64 E] words in global memory: tail_consts_fill's table, computed once (not per row)
-  const float* z;    // optional (N, T, H, W4) fp32: the 1x1 conv's output, already computed (sea_causal_conv_c8_z's epilogue);
+  const float* z;    // optional (N, T, H, W4) fp32: the 1x1 conv's output, already computed (sea_causal_conv_c8's 1x1 epilogue);
                      // y / w16 are then unused and the z tile is a copy into LDS
 };
 

@@ -1039,7 +1039,7 @@ struct DecodeCnnParams {
   int C, W, RX, RY, dil, pad_w;
 };
 
-// EMIT: the selection's one CSR row is expanded into its column ids here too (csr_emit_row: the sea_csr_emit_at launch that
+// EMIT: the selection's one CSR row is expanded into its column ids here too (csr_emit_row: the decode-form sea_csr_emit launch that
 // followed); instantiated wherever the emit's 20 KB of LDS fit beside the weight image (all but the 80-channel form).
 template <typename T, int EPT, int NT, int KCH, bool EMIT>
 __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(DecodeCnnParams dp, TailParams tp, TopkParams p, EmitParams ep) {
@@ -1306,13 +1306,23 @@ static int launch_tail_select_gen(const TailParams& tp, const TopkParams& p, int
   return SEA_OK;
 }
 
-static int tail_select_common(const char* nm, const float* z, const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                              int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
-                              const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                              void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n,
-                              int64_t T_src, const int32_t* t_src_dev, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                              int32_t* head_off, int32_t* crow1, const uint32_t* consts_tab, sea_stream_t stream) {
-  SEA_REQUIRE(crow1 == nullptr || T == 1, SEA_EINVAL, "%s: crow_out goes with one row per batch item (T = %lld)", nm, (long long)T);
+// y (the activation, C8 / channels-last) or z (the 1x1 convolution's output (N, T, H, W4) fp32, as sea_causal_conv_c8's
+// epilogue writes it: the z tile of a row is then a copy into LDS instead of loads + MFMAs).  t_src_dev != NULL: the decode
+// form (see include/sea_hip.h): keep is the absolute table, keep_stride_n and T_src are not read.
+extern "C" int sea_predictor_tail_select(const void* y, const float* z, int dtype, int64_t N, int64_t C, int64_t H, int64_t T,
+                                         int64_t W4, int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
+                                         const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
+                                         void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n,
+                                         int64_t T_src, const int32_t* t_src_dev, int is_causal, int max_k, uint32_t* bits,
+                                         int32_t* row_nnz, int32_t* head_off, int32_t* crow_out, const uint32_t* consts_tab,
+                                         sea_stream_t stream) {
+  const char* nm = "sea_predictor_tail_select";
+  SEA_REQUIRE((y == nullptr) != (z == nullptr), SEA_EINVAL, "%s: exactly one of y and z", nm);
+  SEA_REQUIRE(!(z && t_src_dev), SEA_EINVAL, "%s: the decode form takes y", nm);
+  SEA_REQUIRE(crow_out == nullptr || t_src_dev, SEA_EINVAL, "%s: crow_out goes with the decode form", nm);
+  if (z) { C = 0; y_strides = nullptr; conv_w16 = nullptr; Cp = 0; }
+  if (t_src_dev) { keep_stride_n = 0; T_src = T; }
+  SEA_REQUIRE(crow_out == nullptr || T == 1, SEA_EINVAL, "%s: crow_out goes with one row per batch item (T = %lld)", nm, (long long)T);
   SEA_REQUIRE((z || (y && y_strides && conv_w16)) && conv_b && gamma && beta && keep && bits && row_nnz && head_off, SEA_EINVAL,
               "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16 || dtype == SEA_F32, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
@@ -1347,7 +1357,7 @@ static int tail_select_common(const char* nm, const float* z, const void* y, int
   p.is_causal = is_causal; p.max_k = max_k;
   p.M = (int)(H * T_m); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes((int)T_m);
   p.keep = keep; p.keep_stride_n = keep_stride_n;
-  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = t_src_dev; p.crow1 = crow1;
+  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = t_src_dev; p.crow1 = crow_out;
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if (dtype == SEA_F32) rc = launch_tail_select_f32(tp, p, N * T, s);
@@ -1356,44 +1366,6 @@ static int tail_select_common(const char* nm, const float* z, const void* y, int
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: this (H, T_m) does not fit the fused kernel's LDS plan (run sea_predictor_tail + sea_topk_select)", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_predictor_tail_select(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                                         int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
-                                         const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                                         void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n,
-                                         int64_t T_src, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                         int32_t* head_off, const uint32_t* consts_tab, sea_stream_t stream) {
-  return tail_select_common("sea_predictor_tail_select", nullptr, y, dtype, N, C, H, T, W4, up, T_m, y_strides, conv_b, conv_w16, Cp, gamma,
-                            beta, eps, probs, scores, keep, keep_stride_n, T_src, nullptr, is_causal, max_k, bits, row_nnz,
-                            head_off, nullptr, consts_tab, stream);
-}
-
-// The same launch fed with z = the 1x1 convolution's output (N, T, H, W4) fp32 as sea_causal_conv_c8_z's epilogue writes it:
-// the z tile of a row is then a copy into LDS instead of loads + MFMAs (a third of a row's life in this issue-bound kernel).
-extern "C" int sea_predictor_tail_select_z(const float* z, int dtype, int64_t N, int64_t H, int64_t T, int64_t W4, int64_t up,
-                                           int64_t T_m, const float* conv_b, const void* gamma, const void* beta, float eps,
-                                           void* probs, void* scores, const int32_t* keep, int64_t keep_stride_n, int64_t T_src,
-                                           int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
-                                           const uint32_t* consts_tab, sea_stream_t stream) {
-  SEA_REQUIRE(z, SEA_EINVAL, "sea_predictor_tail_select_z: null pointer");
-  return tail_select_common("sea_predictor_tail_select_z", z, nullptr, dtype, N, 0, H, T, W4, up, T_m, nullptr, conv_b, nullptr, 0,
-                            gamma, beta, eps, probs, scores, keep, keep_stride_n, T_src, nullptr, is_causal, max_k, bits, row_nnz,
-                            head_off, nullptr, consts_tab, stream);
-}
-
-// Decode form (a step captured as a HIP graph): the T new rows are the LAST rows of sequences of *t_src_dev tokens (device
-// memory); keep_table[i] = K of the row with i+1 visible keys, for every position the session can reach.
-extern "C" int sea_predictor_tail_select_at(const void* y, int dtype, int64_t N, int64_t C, int64_t H, int64_t T, int64_t W4,
-                                            int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
-                                            const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                                            void* probs, void* scores, const int32_t* keep_table, const int32_t* t_src_dev,
-                                            int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
-                                            int32_t* crow_out, const uint32_t* consts_tab, sea_stream_t stream) {
-  SEA_REQUIRE(t_src_dev, SEA_EINVAL, "sea_predictor_tail_select_at: null pointer");
-  return tail_select_common("sea_predictor_tail_select_at", nullptr, y, dtype, N, C, H, T, W4, up, T_m, y_strides, conv_b, conv_w16, Cp,
-                            gamma, beta, eps, probs, scores, keep_table, 0, T, t_src_dev, is_causal, max_k, bits, row_nnz,
-                            head_off, crow_out, consts_tab, stream);
 }
 
 // One launch for a decoding step's predictor CNN + tail + selection + state advance (DecodeCnnParams above; round 5).
@@ -1435,7 +1407,7 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
   const char* nm = "sea_decode_cnn_tail_select";
   SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31)), SEA_EUNSUPPORTED,
               "%s: the in-launch emit serves C <= 64 channels (beyond that the weight image leaves no LDS for it: pass col = NULL "
-              "and call sea_csr_emit_at with t_src_dev = counters + 2)", nm);
+              "and call sea_csr_emit with t_src_dev = counters + 2)", nm);
   SEA_REQUIRE(x_new && x_ring && y1_ring && y2 && w1_packed && bias1 && w2_packed && bias2 && conv_b && conv_w16 && gamma && beta &&
                   keep_table && counters && ticket && bits && row_nnz && head_off && crow_out, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
@@ -1489,9 +1461,18 @@ extern "C" int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst
   return SEA_OK;
 }
 
-static int emit_common(const char* nm, const uint32_t* bits, const void* crow, int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
-                       int64_t T_src, const int32_t* t_src_dev, int64_t T_enc, int is_causal, int max_k, void* col, int idx_bytes,
-                       int64_t col_stride_n, int64_t z_cap, float* values_out, sea_stream_t stream) {
+// t_src_dev != NULL: the decode form (a step captured as a HIP graph): the rows' widths follow *t_src_dev (device memory:
+// the current sequence length), the column ids are head * T_src + key with T_src the FIXED capacity T_cap >= *t_src_dev,
+// so the attention launch that consumes them (K / V caches of T_cap rows) needs nothing position-dependent in its arguments.
+extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
+                            int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
+                            int64_t col_stride_n, int64_t z_cap, float* values_out, const int32_t* t_src_dev,
+                            sea_stream_t stream) {
+  (void)head_off;  // offsets follow from the flat (head-major) emission order; kept in the ABI for symmetry
+  const char* nm = "sea_csr_emit";
+  SEA_REQUIRE(!(t_src_dev && values_out), SEA_EUNSUPPORTED, "%s: the decode form writes no values", nm);
+  const int64_t T_enc = T_src;
+  if (t_src_dev) T_src = T_dst;
   SEA_REQUIRE(bits && crow && col, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(idx_bytes == 4 || idx_bytes == 8, SEA_EINVAL, "%s: idx_bytes must be 4 or 8", nm);
   SEA_REQUIRE(N > 0 && H > 0 && T_dst > 0 && T_m > 0 && max_k > 0, SEA_EINVAL, "%s: bad shape", nm);
@@ -1508,25 +1489,6 @@ static int emit_common(const char* nm, const uint32_t* bits, const void* crow, i
   else hipLaunchKernelGGL((csr_emit_kernel<int64_t>), grid, block, 0, s, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
-                            int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
-                            int64_t col_stride_n, int64_t z_cap, float* values_out, sea_stream_t stream) {
-  (void)head_off;  // offsets follow from the flat (head-major) emission order; kept in the ABI for symmetry
-  return emit_common("sea_csr_emit", bits, crow, N, H, T_dst, T_m, T_src, nullptr, T_src, is_causal, max_k, col, idx_bytes,
-                     col_stride_n, z_cap, values_out, stream);
-}
-
-// Decode form (a step captured as a HIP graph): the rows' widths follow *t_src_dev (device memory: the current sequence
-// length), the column ids are head * T_cap + key with a FIXED capacity T_cap >= *t_src_dev, so the attention launch that
-// consumes them (K / V caches of T_cap rows) needs nothing position-dependent in its arguments.
-extern "C" int sea_csr_emit_at(const uint32_t* bits, const void* crow, int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
-                               const int32_t* t_src_dev, int64_t T_cap, int is_causal, int max_k, void* col, int idx_bytes,
-                               int64_t col_stride_n, int64_t z_cap, sea_stream_t stream) {
-  SEA_REQUIRE(t_src_dev, SEA_EINVAL, "sea_csr_emit_at: null pointer");
-  return emit_common("sea_csr_emit_at", bits, crow, N, H, T_dst, T_m, T_dst, t_src_dev, T_cap, is_causal, max_k, col, idx_bytes,
-                     col_stride_n, z_cap, nullptr, stream);
 }
 
 extern "C" int sea_csr_head_offsets(const void* crow, const void* col, int idx_bytes, int64_t N, int64_t H,

@@ -277,7 +277,7 @@ def all_gather_rows(local: torch.Tensor, bounds: List[Tuple[int, int]], group=No
 #   * the causal Performer's running sums up to row lo_r.  They are linear in the rows, so every rank first runs the
 #     Performer over its own rows FROM ZERO (phase A: only the state image matters), the images are all-gathered
 #     (N*H x ~30 KB each) and rank r starts from inc_0 + ... + inc_{r-1}, added in rank order -- the same sum, in the same
-#     order, the one-GPU sequence-parallel Performer forms (sea_performer_causal_segmented);
+#     order, the one-GPU sequence-parallel Performer forms (sea_performer_causal with n_segments > 1);
 #   * the last 8 rows of the predictor CNN's input (two dilated causal 3-tap convolutions reach back 2*2*(3-1) rows):
 #     one point-to-point hand-off r -> r+1 of the channel-blocked rows the one-launch MLP has just produced (64 KB);
 #   * K and V of rows < hi_r: replicated (2*H*T*d elements).

@@ -145,7 +145,7 @@ class PerlinAttention(nn.Module):
         # format runs the emit launch then (bit-identical).  False = written by the step
         self.lazy_csr_columns = True
         # C8 predictor CNN: True = the last (conv, ReLU) launch also evaluates the tail's 1x1 convolution on the tile it holds
-        # and hands z (N, T, H, T_M/4) fp32 to the tail instead of its activation (`sea_causal_conv_c8_z`; bit-identical, the
+        # and hands z (N, T, H, T_M/4) fp32 to the tail instead of its activation (`sea_causal_conv_c8` with z; bit-identical, the
         # activation of the last pair is then not written).  Built in round 5 and MEASURED SLOWER (conv2 +27 us, tail
         # +-0 at OPT-1.3B x 8 -- the tail's z stage is latency its other resident waves already hide): off by default
         self.conv_z_epilogue = False
@@ -259,7 +259,7 @@ class PerlinAttention(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def _fuses_interpolation(self, q, T_M) -> bool:
-        """Steps I + J in one launch (`sea_sparse_attention_fused`): with `sparse_kernel` "gather" or "auto" and a head shape
+        """Steps I + J in one launch (the fused form of `sea_sparse_attention`): with `sparse_kernel` "gather" or "auto" and a head shape
         the fused gather kernels cover, the CSR's column array is left to the attention launch.  "auto" takes it wherever
         it exists: fused gather beats emit + the better of {gather, tile} on every map measured (OPT-1.3B x 8: layer's own
         0.99 + 0.03 vs 0.96 + 0.18 ms, structured 0.98 vs tile 0.90 + 0.18; LLaMA-13B: gather wins anyway); the plan-based
@@ -354,7 +354,7 @@ class PerlinAttention(nn.Module):
         """Steps F-G (+ H) on the C8 kernels: the (conv, ReLU) pairs of `cnn.keepres`, then upsample + 1x1 conv + area resize +
         `cnn.lnorm2` + softmax -- with the top-k selection in the same launch when `allow_select` (sparse mode, unpadded
         batch, nobody probing).  `conv_z_epilogue`: the LAST pair's launch also evaluates the 1x1 convolution on the tile it
-        holds (`sea_causal_conv_c8_z`) and hands z to the tail instead of the activation (bit-identical; the activation of the
+        holds (`sea_causal_conv_c8` with z) and hands z to the tail instead of the activation (bit-identical; the activation of the
         last pair is then never written).  Returns (probs, scores); `self._fused_selection` is set when the selection ran."""
         conv4 = body[-1].module
         T_M_, Hh = self.pconfig.attention_predictor_length, self.num_attention_heads
@@ -912,7 +912,7 @@ class PerlinAttention(nn.Module):
             if fs is not None and fs[0] is probs and not_padded and not probing:
                 # the selection already ran inside the predictor-tail launch on this very map: scan + emit only
                 # `sparse_kernel = "gather"`: the column array is left to the attention launch, whose gather kernels do the
-                # interpolation of their own (row, head) themselves and write `col` (sea_sparse_attention_fused: steps I + J
+                # interpolation of their own (row, head) themselves and write `col` (sea_sparse_attention with bits: steps I + J
                 # in one launch); with any other consumer the handle runs the emit launch on first use of `.col`
                 csr, mask_m = ops.csr_from_selection(*fs[1], H, T_M, T_SRC, int(self.pconfig.k), True, z_cap,
                                                      defer_emit=self._fuses_interpolation(q, T_M)), None

@@ -10,7 +10,7 @@ tensor shapes that grow), so the step is bound by the host enqueueing them.
   * K / V caches of a fixed capacity; the new row is written at a device-resident index,
   * the Performer state image and the predictor CNN's window are updated in place,
   * the three kernels that need the position read it from a device int32
-    (`sea_performer_causal_step_at`, `sea_predictor_tail_select_at`, `sea_csr_emit_at`, include/sea_hip.h),
+    (the decode forms of `sea_performer_causal_step`, `sea_predictor_tail_select`, `sea_csr_emit`, include/sea_hip.h),
   * column ids are encoded against the cache capacity, so the fused attention launch has static arguments.
 
 The whole step is then captured ONCE with `torch.cuda.graph` and replayed per token.  Round 4: the framework glue around
@@ -28,7 +28,7 @@ earlier rows it needs, t - 2 and t - 4, live in two small rings: the MLP's previ
 runs the unchanged tail + selection on it and advances the device counters.  Nothing is shifted any more: a ring slot is
 position % ring size.  Still bitwise (`csrc/sea_convfrag.hpp: conv_row_c8` reproduces the convolution kernel's operand
 placement and k order).  Shapes outside that kernel (three-convolution bodies, H > 40) keep the round-4 launches.
-Round 5, later: the attention launch of a position is `sea_sparse_attention_fused_at` -- the gather kernel expands the one
+Round 5, later: the attention launch of a position is the decode form of `sea_sparse_attention` -- the gather kernel expands the one
 row's kept pixels itself (row widths from the device counter), its idle lane groups warm the K / V rows of the expanded lists
 -- so the CSR row's column ids are not on the critical path any more (no emit phase / launch; `session.csr.col` emits on
 first read).  `fused_attention=False` keeps the emit + unfused launch pair (bitwise the same context).
@@ -161,7 +161,7 @@ class DecodeSession:
         conv4 = body[-1].module
         if self.fused_cnn:
             # conv1 + conv2 (one new row each) + tail + selection + the counters' advance: one launch
-            # The attention launch expands the kept pixels itself (sea_sparse_attention_fused_at: the emit phase / launch and the
+            # The attention launch expands the kept pixels itself (decode form of sea_sparse_attention: the emit phase / launch and the
             # crow -> col -> K / V chain leave the position's critical path); where that form does not exist the CSR row's
             # column ids come out of this launch (LDS allowing) or an emit launch behind it, as in the first round-5 version.
             fused_attn = self.fused_attention and ops.fused_interp_supported(self.q_in.dtype, D, T_M)

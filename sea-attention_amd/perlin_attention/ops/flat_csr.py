@@ -210,8 +210,8 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
                        t_src_dev: Optional[torch.Tensor] = None, defer_emit: bool = False, crow: Optional[torch.Tensor] = None):
     """Row scan + emit: the (bits, row_nnz, head_off) of a selection launch (sea_topk_select or the fused
     sea_predictor_tail_select) -> FlatCSR.  Two launches, no host sync.
-    Decode form (`sea_csr_emit_at`): `t_src_dev` (one int32 on the device) is the sequence length the row widths follow,
-    `T_src` the FIXED capacity the column ids are encoded with (the FlatCSR says T_src = capacity)."""
+    Decode form (`sea_csr_emit` with `t_src_dev`): `t_src_dev` (one int32 on the device) is the sequence length the row widths
+    follow, `T_src` the FIXED capacity the column ids are encoded with (the FlatCSR says T_src = capacity)."""
     lib = _lib.load()
     N, T_dst = row_nnz.shape
     dev = bits.device
@@ -219,31 +219,20 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
     if crow is None:
         crow = torch.empty((N, T_dst + 1), dtype=torch.int32, device=dev)
         _lib.check(lib.sea_csr_row_scan(_p(row_nnz), N, T_dst, _p(crow), 4, st), "sea_csr_row_scan")
-    else:                     # the selection launch already wrote it (one row per item: sea_predictor_tail_select_at's crow_out)
+    else:                     # the selection launch already wrote it (one row per item: the decode form's crow_out)
         assert crow.dtype == torch.int32 and tuple(crow.shape) == (N, T_dst + 1) and crow.is_contiguous()
     if z_cap is None:
         z_cap = z_capacity(keep.cpu(), H, T_dst, T_src, T_m, int(k), is_causal)
     col = torch.empty((N, z_cap), dtype=torch.int32, device=dev)
     if t_src_dev is not None:
         assert t_src_dev.dtype == torch.int32 and t_src_dev.numel() == 1 and t_src_dev.is_cuda
-        def emit_at():
-            with torch.cuda.device(dev):
-                _lib.check(lib.sea_csr_emit_at(
-                    _p(bits), _p(crow), N, H, T_dst, T_m, _p(t_src_dev), T_src, int(is_causal), int(k),
-                    _p(col), 4, col.stride(0), z_cap, _lib.stream_ptr()), "sea_csr_emit_at")
-        csr = FlatCSR(crow, col, head_off, H, T_src, bits=bits, row_nnz=row_nnz)
-        csr.t_src_dev = t_src_dev
-        if defer_emit:      # sparse_attention's decode form (sea_sparse_attention_fused_at) expands the kept pixels itself
-            csr._pending = (int(T_m), int(k), bool(is_causal), emit_at)
-        else:
-            emit_at()
-        return csr
     def emit():
         with torch.cuda.device(dev):
             _lib.check(lib.sea_csr_emit(
                 _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
-                _p(col), 4, col.stride(0), z_cap, None, _lib.stream_ptr()), "sea_csr_emit")
+                _p(col), 4, col.stride(0), z_cap, None, _p(t_src_dev), _lib.stream_ptr()), "sea_csr_emit")
     csr = FlatCSR(crow, col, head_off, H, T_src, bits=bits, row_nnz=row_nnz)
+    csr.t_src_dev = t_src_dev
     if defer_emit:          # the fused attention launch (sparse_attention(..., fuse_emit=True)) will write `col`; any other
         csr._pending = (int(T_m), int(k), bool(is_causal), emit)    # reader of `.col` triggers this emit launch itself
     else:
@@ -289,7 +278,7 @@ def attention_few_rows() -> int:
 
 
 def fused_interp_supported(dtype, D: int, T_m: int, rows: int = None) -> bool:
-    """Shapes `sea_sparse_attention_fused` covers (steps I + J in one launch): rows of 8 or 16 lanes (16-bit d = 64 / 80 / 128,
+    """Shapes the fused form of `sea_sparse_attention` covers (steps I + J in one launch): rows of 8 or 16 lanes (16-bit d = 64 / 80 / 128,
     fp32 d = 32 / 64), T_m a multiple of 32 -- and, when the caller says how many (n, h, t) rows the launch has, more than
     `attention_few_rows()` of them (a decoding step runs emit + the wave-per-row kernel instead)."""
     if rows is not None and rows <= attention_few_rows():
@@ -418,7 +407,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
                      plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False):
-    """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention_ex`).
+    """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
     row_scale, mix: fp32 (N,H,T_dst) contiguous (already passed through sigmoid); avg like v.
@@ -444,7 +433,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         return sparse_attention_autograd(q, k, v, csr, row_scale, avg, mix)
     N, H, T_dst, D = q.shape
     # a handle whose columns are still pending (csr_from_selection(..., defer_emit=True)): the gather kernels expand the
-    # kept pixels themselves and WRITE `col` (sea_sparse_attention_fused) where their fused form exists; anything else
+    # kept pixels themselves and WRITE `col` (the fused form of sea_sparse_attention) where it exists; anything else
     # (the tile kernel, a plan that may choose it, rows of 4 lanes / d = 80 / wider than 16 lanes) reads `.col`, which
     # runs the emit launch first
     decode_form = csr.t_src_dev is not None                   # a decoding step: the sequence length lives in device memory
@@ -466,43 +455,37 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     if plan is not None:
         nb_ = N * H * ((T_dst + 15) // 16)
         assert plan.dtype == torch.uint8 and plan.numel() == ((nb_ + 3) & ~3) + 4 and plan.is_contiguous()
+
+    def launch(col, probs, block_path, flags, bits=None, T_m=0, is_causal=0, max_k=0, write_cols=1, t_src_dev=None):
+        return lib.sea_sparse_attention(
+            _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
+            _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
+            _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
+            _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
+            _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
+            _p(probs), probs.stride(0) if probs is not None else 0, _p(block_path), flags,
+            _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), _lib.stream_ptr())
+
     if fused:
         T_m_, max_k_, causal_, _emit = csr._pending
         raw_col = csr._col
         probs = torch.zeros(raw_col.shape, dtype=torch.float32, device=q.device) if want_probs else None
-        common = (_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
-                  _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
-                  _p(csr.crow), _p(raw_col), raw_col.stride(0), _p(csr.head_off),
-                  _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
-                  _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out))
-        write_cols = 0 if keep_columns_pending else 1
-        if decode_form:
-            rc = lib.sea_sparse_attention_fused_at(*common, _p(csr.bits), T_m_, _p(csr.t_src_dev), int(causal_), max_k_, write_cols,
-                                                   _lib.stream_ptr())
-        else:
-            rc = lib.sea_sparse_attention_fused(*common, _p(probs), probs.stride(0) if probs is not None else 0,
-                                                _p(csr.bits), T_m_, int(causal_), max_k_, write_cols, _lib.stream_ptr())
+        rc = launch(raw_col, probs, None, _lib.SEA_ATTN_GATHER, csr.bits, T_m_, int(causal_), max_k_,
+                    0 if keep_columns_pending else 1, csr.t_src_dev)
         if rc == 0:
             if not keep_columns_pending:
                 csr._pending = None                         # the launch has written the columns
             return (out, probs) if want_probs else out
         if rc != _lib.SEA_EUNSUPPORTED:
-            _lib.check(rc, "sea_sparse_attention_fused")
+            _lib.check(rc, "sea_sparse_attention")
         # a shape the fused form does not cover (nothing was launched): emit, then the plain operator below
     probs = torch.zeros(csr.col.shape, dtype=torch.float32, device=q.device) if want_probs else None
     flags = _PATHS[path] | ((int(row_tiles) & 0xf) << 8)
     if key_window:
         assert key_window & (key_window - 1) == 0, "key_window is a power of two"
         flags |= (int(key_window).bit_length() - 1) << 12
-    _lib.check(lib.sea_sparse_attention_ex(
-        _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
-        _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
-        _p(csr.crow), _p(csr.col), csr.col.stride(0), _p(csr.head_off),
-        _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
-        _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
-        _p(probs), probs.stride(0) if probs is not None else 0,
-        _p(plan) if (plan is not None and path == "auto" and not want_probs) else c_void_p(0), flags,
-        _lib.stream_ptr()), "sea_sparse_attention")
+    block_path = plan if (plan is not None and path == "auto" and not want_probs) else None
+    _lib.check(launch(csr.col, probs, block_path, flags), "sea_sparse_attention")
     return (out, probs) if want_probs else out
 
 
@@ -569,7 +552,7 @@ def resize_from_m_to_t_csr(x, masked_fill_value, k, target_width=None, training=
     if Z > 0:
         _lib.check(lib.sea_csr_emit(
             _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
-            _p(col), 8, col.stride(0), Z, None, st), "sea_csr_emit")
+            _p(col), 8, col.stride(0), Z, None, None, st), "sea_csr_emit")
     return torch.sparse_csr_tensor(crow, col, values, size=(N, T_dst, H * T_src))
 
 

@@ -180,7 +180,7 @@ def predictor_tail(y: torch.Tensor, conv_w: torch.Tensor, conv_b: torch.Tensor, 
     cw, cb, g, b, w16, Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, y.device)
     probs = torch.empty((N, H, T, T_m), dtype=dt, device=y.device)
     scores = torch.empty_like(probs) if want_scores else None
-    _lib.check(lib.sea_predictor_tail(_p(y), _lib.dtype_code(dt), N, C, H, T, W4, up, T_m, _lib.strides5_blocked(y),
+    _lib.check(lib.sea_predictor_tail(_p(y), None, _lib.dtype_code(dt), N, C, H, T, W4, up, T_m, _lib.strides5_blocked(y),
                                       _p(cw), _p(cb), _p(w16), Cp, _p(g), _p(b), float(eps), _p(probs), _p(scores),
                                       _lib.stream_ptr()), "sea_predictor_tail")
     return probs, scores
@@ -225,7 +225,7 @@ def _tail_consts(ln_w: torch.Tensor, ln_b: torch.Tensor, up: int, T_m: int, dt, 
 def predictor_tail_z(z: torch.Tensor, conv_w: torch.Tensor, conv_b: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor,
                      up: int, T_m: int, dtype: torch.dtype, eps: float = 1e-5, want_scores: bool = False):
     """predictor_tail from z (N, T, H, W4) fp32 = the 1x1 convolution's output as `causal_conv_c8_z` writes it
-    (`sea_predictor_tail_z`): area resize -> LayerNorm -> softmax; probs (N,H,T,T_m) of `dtype` [, scores]."""
+    (the z form of `sea_predictor_tail`): area resize -> LayerNorm -> softmax; probs (N,H,T,T_m) of `dtype` [, scores]."""
     lib = _lib.load()
     _lib.require_gpu(z, conv_w, conv_b, ln_w, ln_b)
     N, T, H, W4 = z.shape
@@ -234,14 +234,14 @@ def predictor_tail_z(z: torch.Tensor, conv_w: torch.Tensor, conv_b: torch.Tensor
     _cw, cb, g, b, _w16, _Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dtype, z.device)
     probs = torch.empty((N, H, T, T_m), dtype=dtype, device=z.device)
     scores = torch.empty_like(probs) if want_scores else None
-    _lib.check(lib.sea_predictor_tail_z(_p(z), _lib.dtype_code(dtype), N, H, T, W4, up, T_m, _p(cb), _p(g), _p(b), float(eps),
-                                        _p(probs), _p(scores), _lib.stream_ptr()), "sea_predictor_tail_z")
+    _lib.check(lib.sea_predictor_tail(None, _p(z), _lib.dtype_code(dtype), N, 0, H, T, W4, up, T_m, None, None, _p(cb), None, 0,
+                                      _p(g), _p(b), float(eps), _p(probs), _p(scores), _lib.stream_ptr()), "sea_predictor_tail")
     return probs, scores
 
 
 def predictor_tail_select_supported(y: torch.Tensor, H: int, T_m: int, decode: bool = False) -> bool:
     """Shapes csrc/sea_topk.hip: predictor_tail_select(_gen)_kernel take (see sea_predictor_tail_select in sea_hip.h):
-    any predictor length T_m % 4 == 0 up to 512 whose row fits the kernel's LDS plan; the decode form (`_at`) and the
+    any predictor length T_m % 4 == 0 up to 512 whose row fits the kernel's LDS plan; the decode form (`t_src_dev`) and the
     register-resident kernel take T_m = 256 with H % 4 == 0."""
     if y.dtype == torch.float32:      # fp32 data (round 5): the T_m = 256 form on the fp32 MFMA, H <= 32, no decode form
         return (y.dim() == 5 or y.stride(1) == 1) and T_m == 256 and H % 4 == 0 and H <= 32 and not decode
@@ -269,8 +269,8 @@ def predictor_tail_select(y: Optional[torch.Tensor], conv_w: torch.Tensor, conv_
     `LazyTensor` that runs `predictor_tail` on the kept `y` (or `predictor_tail_z` on the kept `z`) the first time anything
     touches its values -- with the weights as they are AT THAT MOMENT: realize it (`ops.realize`) before editing them.
     `z` (with `y = None`, `map_dtype`): the 1x1 convolution's output (N, T, H, W4) fp32 from `causal_conv_c8_z`
-    (`sea_predictor_tail_select_z`: the row's z tile is a copy instead of loads + MFMAs).
-    Decode form (`sea_predictor_tail_select_at`, a step replayed as a HIP graph): `t_src_dev` is a one-element int32
+    (the z form of `sea_predictor_tail_select`: the row's z tile is a copy instead of loads + MFMAs).
+    Decode form (`sea_predictor_tail_select` with `t_src_dev`, a step replayed as a HIP graph): `t_src_dev` is a one-element int32
     device tensor holding the sequence length (T_src is ignored) and `keep` a table over absolute row indices."""
     lib = _lib.load()
     H = conv_w.shape[0]
@@ -280,7 +280,7 @@ def predictor_tail_select(y: Optional[torch.Tensor], conv_w: torch.Tensor, conv_
         N, T, Hz, W4 = z.shape
         assert Hz == H and z.dtype == torch.float32 and z.is_contiguous() and W4 * up == T_m
         assert predictor_tail_select_supported(torch.empty((0, 0, 1, 1, 8), dtype=map_dtype), H, T_m)
-        dt, dev = map_dtype, z.device
+        C, dt, dev = 0, map_dtype, z.device
     else:
         _lib.require_gpu(y, conv_w, conv_b, ln_w, ln_b, keep)
         if y.dim() == 5:
@@ -314,21 +314,11 @@ def predictor_tail_select(y: Optional[torch.Tensor], conv_w: torch.Tensor, conv_
                                 and crow_out.is_contiguous()), "crow_out: the decode form with one row per batch item"
     if t_src_dev is not None:
         assert t_src_dev.dtype == torch.int32 and t_src_dev.numel() == 1 and t_src_dev.is_cuda and keep.ndim == 1
-        _lib.check(lib.sea_predictor_tail_select_at(
-            _p(y), _lib.dtype_code(dt), N, C, H, T, W4, up, T_m, _lib.strides5_blocked(y), _p(cb), _p(w16), Cp, _p(g), _p(b),
-            float(eps), _p(probs), _p(scores), _p(keep), _p(t_src_dev), int(is_causal), int(k),
-            _p(bits), _p(row_nnz), _p(head_off), _p(crow_out), _p(tab), _lib.stream_ptr()), "sea_predictor_tail_select_at")
-        return probs, scores, (bits, row_nnz, head_off)
-    if z is not None:
-        _lib.check(lib.sea_predictor_tail_select_z(
-            _p(z), _lib.dtype_code(dt), N, H, T, W4, up, T_m, _p(cb), _p(g), _p(b), float(eps),
-            _p(None if lazy_probs else probs), _p(scores), _p(keep), T if keep.ndim == 2 else 0, T_src, int(is_causal), int(k),
-            _p(bits), _p(row_nnz), _p(head_off), _p(tab), _lib.stream_ptr()), "sea_predictor_tail_select_z")
-        return probs, scores, (bits, row_nnz, head_off)
     _lib.check(lib.sea_predictor_tail_select(
-        _p(y), _lib.dtype_code(dt), N, C, H, T, W4, up, T_m, _lib.strides5_blocked(y), _p(cb), _p(w16), Cp, _p(g), _p(b),
-        float(eps), _p(None if lazy_probs else probs), _p(scores), _p(keep), T if keep.ndim == 2 else 0, T_src, int(is_causal), int(k),
-        _p(bits), _p(row_nnz), _p(head_off), _p(tab), _lib.stream_ptr()), "sea_predictor_tail_select")
+        _p(y), _p(z), _lib.dtype_code(dt), N, C, H, T, W4, up, T_m, _lib.strides5_blocked(y) if y is not None else None,
+        _p(cb), _p(w16), Cp, _p(g), _p(b), float(eps), _p(None if lazy_probs else probs), _p(scores),
+        _p(keep), T if keep.ndim == 2 else 0, T_src, _p(t_src_dev), int(is_causal), int(k),
+        _p(bits), _p(row_nnz), _p(head_off), _p(crow_out), _p(tab), _lib.stream_ptr()), "sea_predictor_tail_select")
     return probs, scores, (bits, row_nnz, head_off)
 
 
@@ -418,10 +408,9 @@ def performer_value(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
         one_pair = performer_plan(1, 1, 4096, D, nb, q.dtype)         # a shape the plan always cuts: bytes per (pair, segment)
         ws_bytes = N * H * (nseg - 1) * (one_pair[1] // (one_pair[0] - 1))
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device) if nseg > 1 else None
-    _lib.check(lib.sea_performer_causal_segmented(
+    _lib.check(lib.sea_performer_causal(
         _p(q), _p(k), _p(v), _p(pos), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(k),
-        _lib.strides3(v), pos.stride(0), _p(out), _p(avg), nseg, _p(ws), ws_bytes, _lib.stream_ptr()),
-        "sea_performer_causal_segmented")
+        _lib.strides3(v), pos.stride(0), _p(out), _p(avg), nseg, _p(ws), ws_bytes, _lib.stream_ptr()), "sea_performer_causal")
     return (out, avg) if want_avg else out
 
 
@@ -440,7 +429,7 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     pass's); `pos` is the value-embedding table from row 0; `state_in` the image a previous call returned (the state at c0;
     None while no chunk has completed).  Returns (performer_value (N,H,T_new,3D), cumulative average of v for the new rows
     or None, state_out = the image at the last chunk boundary <= t_base + T_new; a new tensor, the input is kept).
-    Decode form (`sea_performer_causal_step_at`, a step replayed as a HIP graph): `t_base_dev` is a one-element int32
+    Decode form (`sea_performer_causal_step` with `t_base_dev`, a step replayed as a HIP graph): `t_base_dev` is a one-element int32
     device tensor holding the rows seen so far, k / v the fixed-capacity caches (already holding the new row), and
     `state_in` is updated in place."""
     lib = _lib.load()
@@ -484,16 +473,10 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
         one_pair = performer_plan(1, 1, 4096, D, nb, q.dtype)
         ws_bytes = N * H * (n_segments - 1) * (one_pair[1] // (one_pair[0] - 1))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
-    if t_base_dev is not None:
-        _lib.check(lib.sea_performer_causal_step_at(
-            _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
-            _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, _p(t_base_dev),
-            _lib.stream_ptr()), "sea_performer_causal_step_at")
-        return out, avg, state_out
     _lib.check(lib.sea_performer_causal_step(
         _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
-        _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, int(t_base), int(n_segments),
-        _p(ws), ws_bytes, _lib.stream_ptr()), "sea_performer_causal_step")
+        _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, int(t_base), _p(t_base_dev),
+        int(n_segments), _p(ws), ws_bytes, _lib.stream_ptr()), "sea_performer_causal_step")
     return out, avg, state_out
 
 
@@ -620,7 +603,7 @@ def causal_conv_c8(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ks
                    relu: bool = True) -> torch.Tensor:
     """Causal (along T) dilated conv + bias (+ReLU) on a C8 activation (N, T, Cin/8, W, 8).
     `weight` is the module's (Cout, Cin, 2k-1, k) parameter.  Returns (N, T, Cout/8, W, 8).  16-bit data: bf16 / f16 MFMA
-    (`sea_causal_conv_c8`); fp32 data: the fp32 MFMA, exact products (`sea_causal_conv_c8_f32`, `conv_c8_f32_supported`)."""
+    (`sea_causal_conv_c8`); fp32 data: the fp32 MFMA, exact products (its fp32 form, `conv_c8_f32_supported`)."""
     lib = _lib.load()
     _lib.require_gpu(x, weight, bias)
     N, T, C8, W, _e = x.shape
@@ -630,19 +613,15 @@ def causal_conv_c8(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ks
     (wp, CinP), bf = _cached("conv", (weight, bias), x.dtype,
                              lambda: (pack_conv_weight(weight, ksize, x.dtype), bias.to(x.dtype).float().contiguous()))
     y = torch.empty((N, T, Cout // 8, W, 8), dtype=x.dtype, device=x.device)
-    if x.dtype == torch.float32:
-        assert conv_c8_f32_supported(Cin, Cout, ksize)
-        _lib.check(lib.sea_causal_conv_c8_f32(_p(x), N, T, W, Cin, Cout, _p(wp), CinP, _p(bf), int(ksize), int(dilation),
-                                              int(pad_w), int(relu), _p(y), _lib.stream_ptr()), "sea_causal_conv_c8_f32")
-        return y
+    assert x.dtype != torch.float32 or conv_c8_f32_supported(Cin, Cout, ksize)
     _lib.check(lib.sea_causal_conv_c8(_p(x), _lib.dtype_code(x.dtype), N, T, W, Cin, Cout, _p(wp), CinP, _p(bf),
-                                      int(ksize), int(dilation), int(pad_w), int(relu), _p(y), _lib.stream_ptr()),
-               "sea_causal_conv_c8")
+                                      int(ksize), int(dilation), int(pad_w), int(relu), _p(y), None, 0, None, 0, None,
+                                      _lib.stream_ptr()), "sea_causal_conv_c8")
     return y
 
 
 def conv_c8_f32_supported(Cin: int, Cout: int, ksize: int) -> bool:
-    """Shapes `sea_causal_conv_c8_f32` takes: the fp32 weight image must fit the 160 KB LDS (24 -> 24 channels: 37 KB,
+    """Shapes the fp32 form of `sea_causal_conv_c8` takes: the fp32 weight image must fit the 160 KB LDS (24 -> 24 channels: 37 KB,
     64 -> 64: 148 KB; 80 -> 80 does not)."""
     nt, cinp = (Cout + 15) // 16, (Cin + 15) // 16 * 16
     return (ksize in (1, 3) and Cin % 8 == 0 and Cout % 8 == 0 and Cout <= 80
@@ -650,7 +629,7 @@ def conv_c8_f32_supported(Cin: int, Cout: int, ksize: int) -> bool:
 
 
 def conv_z_supported(Cout: int, H: int, ksize: int, W: int) -> bool:
-    """Shapes `sea_causal_conv_c8_z` takes: a 3 x 3 layer of at most 80 output channels (5 MFMA tiles), H <= 64."""
+    """Shapes the 1x1 epilogue of `sea_causal_conv_c8` takes: a 3 x 3 layer of at most 80 output channels (5 MFMA tiles), H <= 64."""
     return ksize == 3 and Cout % 8 == 0 and Cout <= 80 and 0 < H <= 64 and W % 4 == 0
 
 
@@ -659,7 +638,7 @@ def causal_conv_c8_z(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
                      conv1x1_w: torch.Tensor, conv1x1_b: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor,
                      relu: bool = True, want_y: bool = False):
     """`causal_conv_c8` of the LAST (conv, ReLU) pair of the predictor CNN with the tail's 1x1 convolution in its epilogue
-    (`sea_causal_conv_c8_z`).  conv1x1_w (H, Cout) = the live row of the 1x1 kernel, conv1x1_b (H); ln_w / ln_b are only the
+    (`sea_causal_conv_c8` with `z`).  conv1x1_w (H, Cout) = the live row of the 1x1 kernel, conv1x1_b (H); ln_w / ln_b are only the
     rest of the tail's cache key (one pack serves the conv epilogue and the tail launches).
     Returns (y or None, z): z (N, T, H, W) fp32 = W1 . relu(conv(x) + bias) + b1 -- bit for bit what the tail kernels compute
     from y; y (N, T, Cout/8, W, 8) only with `want_y`."""
@@ -674,9 +653,9 @@ def causal_conv_c8_z(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     _cw, cb, _g, _b, w16, Cp = _tail_pack(conv1x1_w, conv1x1_b, ln_w, ln_b, x.dtype, x.device)
     y = torch.empty((N, T, Cout // 8, W, 8), dtype=x.dtype, device=x.device) if want_y else None
     z = torch.empty((N, T, H, W), dtype=torch.float32, device=x.device)
-    _lib.check(lib.sea_causal_conv_c8_z(_p(x), _lib.dtype_code(x.dtype), N, T, W, Cin, Cout, _p(wp), CinP, _p(bf),
-                                        int(ksize), int(dilation), int(pad_w), int(relu), _p(y), _p(w16), Cp, _p(cb), H, _p(z),
-                                        _lib.stream_ptr()), "sea_causal_conv_c8_z")
+    _lib.check(lib.sea_causal_conv_c8(_p(x), _lib.dtype_code(x.dtype), N, T, W, Cin, Cout, _p(wp), CinP, _p(bf),
+                                      int(ksize), int(dilation), int(pad_w), int(relu), _p(y), _p(w16), Cp, _p(cb), H, _p(z),
+                                      _lib.stream_ptr()), "sea_causal_conv_c8")
     return y, z
 
 

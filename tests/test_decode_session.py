@@ -85,7 +85,7 @@ def test_session_steps_equal_cached_forward(dtype, N, H, d, T0, steps, use_graph
 @pytest.mark.parametrize("dtype,N,H,d,T0", [(torch.bfloat16, 2, 8, 64, 250), (torch.bfloat16, 1, 4, 80, 90), (torch.float16, 1, 8, 128, 300),
                                             (torch.bfloat16, 1, 40, 64, 70)])
 def test_session_attention_forms_agree(dtype, N, H, d, T0, use_graph):
-    """Round 5: the attention launch of a position expands the kept pixels itself (sea_sparse_attention_fused_at) instead of
+    """Round 5: the attention launch of a position expands the kept pixels itself (the decode form of sea_sparse_attention) instead of
     reading the columns an emit phase / launch wrote.  Both forms give the same bits, and the pending handle's columns -- emitted
     on first read -- are the ones the unfused form walked."""
     T_M, k, steps = 256, 16, 5
@@ -121,8 +121,8 @@ def test_session_attention_forms_agree(dtype, N, H, d, T0, use_graph):
                                                      (torch.bfloat16, 4, 80, 3000, 64, True),    # d = 80: 8 lanes x (8 + 2) elements per row
                                                      (torch.bfloat16, 4, 64, 1, 64, False)])     # the very first position: one key
 def test_decode_attention_operator_forms_agree(dtype, H, d, T_src, k, heavy):
-    """`sea_sparse_attention_fused_at` (one new row per sequence: sparse_attn_decode1_kernel -- the whole workgroup serves the
-    row) against `sea_csr_emit_at` + the unfused launch on one selection: bitwise, for rows far longer than a chunk, thinned
+    """The decode form of `sea_sparse_attention` (one new row per sequence: sparse_attn_decode1_kernel -- the whole workgroup serves the
+    row) against the decode form of `sea_csr_emit` + the unfused launch on one selection: bitwise, for rows far longer than a chunk, thinned
     pixels, ragged ends and empty heads."""
     from sea_attention_amd.perlin_attention import ops
     N, T_m, T_cap = 2, 256, T_src + 40
@@ -173,9 +173,9 @@ def test_decode_attention_operator_forms_agree(dtype, H, d, T_src, k, heavy):
 
 @pytest.mark.parametrize("dtype,H,d,T_dst", [(torch.bfloat16, 4, 64, 3), (torch.float16, 4, 128, 8), (torch.bfloat16, 4, 80, 2)])
 def test_decode_attention_operator_few_rows(dtype, H, d, T_dst):
-    """T_dst = 2 .. 8 new rows per sequence through `sea_sparse_attention_fused_at`: the lane-group decode form (`DEC`
+    """T_dst = 2 .. 8 new rows per sequence through the decode form of `sea_sparse_attention`: the lane-group decode form (`DEC`
     instantiations: expansion inside the launch, row widths from the device counter, lists warmed by the whole block) against
-    `sea_csr_emit_at` + the unfused launch -- bitwise."""
+    the decode form of `sea_csr_emit` + the unfused launch -- bitwise."""
     from sea_attention_amd.perlin_attention import ops
     N, T_m, T_src, k = 2, 256, 1500, 16
     T_cap = T_src + 24

@@ -1,4 +1,4 @@
-"""-m gpu: steps I + J in one launch (`sea_sparse_attention_fused`, round 3): the gather attention kernels do the
+"""-m gpu: steps I + J in one launch (the fused form of `sea_sparse_attention`, round 3): the gather attention kernels do the
 nearest-neighbour interpolation of their own (row, head) themselves -- expand the kept pixels to key columns, WRITE the
 CSR's column array and walk it from LDS -- instead of reading what a separate emit launch wrote.
 

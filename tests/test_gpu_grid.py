@@ -83,7 +83,7 @@ def test_reference_grid_runs_on_the_fused_kernels(monkeypatch, T, K, T_M, dtype)
     for h_ in hooks:
         h_.remove()
     assert ran == [], f"torch predictor modules ran: {ran}"
-    # two (conv, ReLU) launches (the second one through sea_causal_conv_c8_z when the module's `conv_z_epilogue` is on)
+    # two (conv, ReLU) launches (the second one through the 1x1 epilogue of sea_causal_conv_c8 when the module's `conv_z_epilogue` is on)
     assert calls.get("performer_value") == 1 and calls.get("predictor_mlp") == 1
     assert calls.get("causal_conv_c8", 0) + calls.get("causal_conv_c8_z", 0) == 2
     assert calls.get("predictor_tail_select") == 1 and calls.get("sparse_attention") == 1

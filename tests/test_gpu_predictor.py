@@ -235,7 +235,7 @@ def test_causal_conv_c8_launch_geometries_agree(ops):
 @pytest.mark.parametrize("N,Cin,Cout,T,W", [(2, 24, 24, 40, 64), (1, 64, 64, 21, 64), (1, 24, 24, 33, 16), (1, 32, 48, 17, 128),
                                             (1, 16, 32, 12, 40), (1, 24, 24, 9, 96), (1, 8, 8, 7, 24), (1, 40, 40, 13, 64)])
 def test_causal_conv_c8_fp32(ops, N, Cin, Cout, T, W, dil):
-    """`sea_causal_conv_c8_f32` (round 5): fp32 data on the fp32 MFMA -- exact fp32 products, so the bar is fp32 rounding noise
+    """The fp32 form of `sea_causal_conv_c8` (round 5): fp32 data on the fp32 MFMA -- exact fp32 products, so the bar is fp32 rounding noise
     (the 16-bit kernels' 2e-2 becomes 1e-5), tap positions and causality as for the 16-bit kernel."""
     assert ops.conv_c8_f32_supported(Cin, Cout, 3) and not ops.conv_c8_f32_supported(80, 80, 3)
     g = torch.Generator().manual_seed(3)
@@ -490,7 +490,7 @@ def test_predictor_tail_select_fp32_bit_identical(ops, N, H, T, k):
                                          (1, 20, 50, 16, 256), (1, 12, 90, 32, 96), (1, 12, 70, 32, 384), (1, 32, 40, 64, 128),
                                          (1, 36, 30, 32, 256)])
 def test_conv_z_epilogue_bit_identical(ops, dtype, N, H, T, k, T_M):
-    """`sea_causal_conv_c8_z` (round 5): the last (conv, ReLU) launch with the tail's 1x1 convolution in its epilogue.  Its
+    """`sea_causal_conv_c8` with its 1x1 epilogue (round 5): the last (conv, ReLU) launch with the tail's 1x1 convolution in its epilogue.  Its
     activation is bitwise `causal_conv_c8`'s, z is what the tail's own z stage computes from that activation (checked through
     the maps: tail(z) == tail(y) bit for bit, tail + selection likewise) and equals the fp32 product of the rounded operands."""
     C, W4 = 2 * H, T_M // 4
@@ -560,7 +560,7 @@ def test_performer_emits_cumulative_average(ops, N, H, T, D):
     (torch.float32, 1, 2, 900, 64, 8),
 ])
 def test_performer_sequence_parallel_equals_sequential(ops, dtype, N, H, T, D, nbf):
-    """`sea_performer_causal_segmented`: cutting the rows into segments (two launches, carried state) gives the rows of
+    """`sea_performer_causal` with n_segments > 1: cutting the rows into segments (two launches, carried state) gives the rows of
     the one-pass kernel up to fp32 summation order -- i.e. at most one rounding step of the output dtype apart on a
     small fraction of the elements -- for the plan's choice and for forced 2 / 4 segments; the copy of v stays exact."""
     import math

@@ -1,5 +1,5 @@
 """-m gpu: the MFMA tile path of the fused sparse attention (csrc/sea_attn_tile.hip) and the per-entry probabilities
-output of the gather path, through the C ABI (`sea_sparse_attention_ex`), against the CPU oracle and the reference's
+output of the gather path, through the C ABI (`sea_sparse_attention`), against the CPU oracle and the reference's
 golden fixtures.
 
 Tolerances: 16-bit inputs are compared with the oracle evaluated in fp32 on the SAME rounded inputs.  bf16: P enters
