@@ -100,9 +100,14 @@ int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst,
  * causal_resize_m_to_t.py:493-572,724-746).  col has room for z_cap entries per batch item
  * (col_stride_n elements apart); entries at or beyond crow[n,T_dst] are left untouched.
  * values_out (optional, fp32, same shape as col) receives 1.0 for every emitted entry.
+ * Ids are head * T_src + key; a pixel wider than max_k is thinned with the reference's fp32 stepping of those ids, exact
+ * while H * T_src < 2^24 (else SEA_EUNSUPPORTED).
  * DECODE form, t_src_dev != NULL (a step captured as a HIP graph): the row widths follow *t_src_dev (device memory: the
  * current sequence length) and the column ids are head * T_src + key for a FIXED capacity T_src >= *t_src_dev (the K / V
- * caches' row count), so sea_sparse_attention is called with that same T_src; values_out must be NULL. */
+ * caches' row count), so sea_sparse_attention is called with that same T_src; values_out must be NULL.  A thinned pixel is
+ * stepped in fp32 on the KEY alone and the head offset is added as an integer, so the capacity changes no id: needs
+ * H * T_src < 2^31 (int32 ids) and T_src < 2^24 (fp32-exact keys).  Where H * T_src < 2^24 the ids are the stateless
+ * form's bit for bit. */
 int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off,
                  int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
                  int64_t T_src, int is_causal, int max_k,
@@ -212,6 +217,9 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * PA/attention.py:410-426): a position of a graph-replayed decoding session has static kernel arguments, so the sequence
  * length the row widths follow is read from device memory (*t_src_dev, what the decode form of sea_csr_emit reads) while
  * T_src is the CAPACITY -- the row count of the K / V caches -- with which the column ids are encoded (head * T_src + key).
+ * Thinned pixels are stepped as the decode form of sea_csr_emit steps them (the key alone: the capacity changes no id;
+ * H * T_src < 2^31).  The stateless fused form steps head * T_src + key like the reference and, like sea_csr_emit, refuses
+ * H * T_src >= 2^24 (SEA_EUNSUPPORTED).
  * T_dst <= 8 new rows per sequence, no probs_out; 16-bit d = 64 / 80 / 128 or fp32 d = 32 / 64 (the fused forms), else
  * SEA_EUNSUPPORTED (run the decode form of sea_csr_emit + the plain form).  The lane groups of a workgroup that have no row
  * touch the K / V rows of the expanded lists before the one group per row starts its dependent walk (what the unfused

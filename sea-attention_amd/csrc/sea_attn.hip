@@ -197,7 +197,7 @@ __device__ inline int slot_length(const AttnParams& p, int n, int h, int tn) {
 // execute in order: no workgroup barrier after the one that sizes the lists.  Blocks whose lists would not fit the LDS
 // budget expand straight into `col` and read it back past the L1 (rare: a head that takes most of a row).
 // Every thread of the block calls (one workgroup barrier inside).
-template <int LPR, int RPB>
+template <int LPR, int RPB, bool DEC = false>
 __device__ inline void fused_expand(const AttnParams& p, int n, int h, int tt, bool rowok, int gi, int sub, int beg, int end,
                                     int hcol, int t_src, int* s_keys, int* lbase_out, bool* fits_out, int* total_out) {
   __shared__ int s_glen[RPB];
@@ -249,10 +249,14 @@ __device__ inline void fused_expand(const AttnParams& p, int n, int h, int tt, b
         else { for (int j = 0; j < wd; ++j) gcol[beg + off + j] = c0 - j; }
         off += wd;
       } else {                                             // thinned pixel: the reference's fp32 stepping (csr_emit_kernel)
-        const float rs = (float)lo + (float)hcol, re = (float)hi + (float)hcol;
+        // DEC: hcol = h * T_cap (the cache capacity) -- stepped on the key alone, the head offset added as an integer, so that
+        // the capacity cannot round a key; where h * T_cap + hi < 2^24 both forms are exact integers: the same bits
+        const float fb = DEC ? 0.0f : (float)hcol;
+        const int ib = DEC ? hcol : 0;
+        const float rs = (float)lo + fb, re = (float)hi + fb;
         const float step = __fdiv_rn(re - rs, (float)p.max_k);
         for (int j = 0; j < p.max_k; ++j) {
-          const int c = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f);
+          const int c = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f) + ib;
           if (fits) s_keys[lbase + off + j] = c; else gcol[beg + off + j] = c;
         }
         off += p.max_k;
@@ -354,7 +358,7 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, lane_off);
 
   // ---- a decoding step: T_dst of one or a few rows, so all but a few of the block's lane groups have no row -- and the one
@@ -546,7 +550,7 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
   // (the 16-byte fragments of the lists' K / V rows: 128 of a row's 160 bytes, i.e. both of its cache lines)
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, off_m);
 
@@ -705,10 +709,12 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
       const int j0 = max(0, c0 - off), j1 = min(cnt, c0 + CH - off);
       if (wd <= p.max_k) {
         for (int j = j0; j < j1; ++j) s_keys[off + j - c0] = hi - 1 - j;
-      } else {                                             // thinned pixel: the reference's fp32 stepping (csr_emit_kernel)
-        const float rs = (float)lo + (float)hcol, re = (float)hi + (float)hcol;
+      } else {                                             // thinned pixel: the reference's fp32 stepping (csr_emit_kernel) on
+        // the key alone (fused_expand's decode form: the capacity's head offset never enters the fp32 values; where
+        // h * T_cap + hi < 2^24 this is bit for bit the stepping of h * T_cap + key)
+        const float rs = (float)lo, re = (float)hi;
         const float step = __fdiv_rn(re - rs, (float)p.max_k);
-        for (int j = j0; j < j1; ++j) s_keys[off + j - c0] = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f) - hcol;
+        for (int j = j0; j < j1; ++j) s_keys[off + j - c0] = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f);
       }
       if (owns_last && j1 == cnt) {                        // the last entry's key again in the slots up to the step boundary
         const int lastkey = s_keys[total - 1 - c0];
@@ -1141,6 +1147,10 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   if (bits) {
     SEA_REQUIRE(path != SEA_ATTN_TILE && block_path == nullptr, SEA_EUNSUPPORTED, "%s: the fused interpolation runs on the gather kernels", nm);
     SEA_REQUIRE(T_m > 0 && T_m % 32 == 0 && max_k > 0, SEA_EUNSUPPORTED, "%s: fused interpolation needs T_m %% 32 == 0", nm);
+    // the stateless form steps thinned pixels on head * T_src + key in fp32 (the reference's arithmetic): sea_csr_emit's guard;
+    // the decode form steps the key alone (fused_expand) and needs int32 ids and fp32-exact keys only (`small` below: T_src < 2^24)
+    if (t_src_dev) SEA_REQUIRE(H * T_src < (1ll << 31), SEA_EUNSUPPORTED, "%s: the decode form needs int32 ids (H*T_cap < 2^31)", nm);
+    else SEA_REQUIRE(H * T_src < (1ll << 24), SEA_EUNSUPPORTED, "%s: H*T_src must stay below 2^24 (fp32-exact ids)", nm);
   }
   p.TB = (int)((T_dst + 3) / 4);
   hipStream_t s = (hipStream_t)stream;

@@ -862,7 +862,8 @@ struct EmitParams {
 //   4. the threads write their runs (keys descending inside a pixel, causal_resize_m_to_t.py:569) into an LDS
 //      window of the row, which is flushed with fully coalesced stores.
 // A pixel whose width exceeds max_k is thinned with the reference's fp32 step arithmetic; every other pixel is
-// plain integer work (ids stay below 2^24, so the reference's fp32 ids are exact integers there).
+// plain integer work (ids stay below 2^24, so the reference's fp32 ids are exact integers there; the decode form steps
+// the key alone and adds the head offset h * T_cap as an integer, so its ids need only int32 and keys below 2^24).
 constexpr int EM_TABLE = 1024;                        // pixel-bound table (T_m <= 1024; else bounds on the fly)
 constexpr int EM_WIN = 4096;                          // entries staged per flush
 
@@ -985,11 +986,15 @@ __device__ __forceinline__ void csr_emit_row(const EmitParams& p, const int row)
             }
             off += wd;
           } else {                                                  // thinned pixel: the reference's fp32 stepping
-            const float rs = (float)lo + (float)hb, re = (float)hi + (float)hb;
+            // decode form (hb = h * T_cap, the cache capacity): stepped on the key alone, the head offset added as an integer,
+            // so that the capacity cannot round a key; where h * T_cap + hi < 2^24 both forms are exact integers: the same bits
+            const float fb = p.t_src_dev ? 0.0f : (float)hb;
+            const int ib = p.t_src_dev ? hb : 0;
+            const float rs = (float)lo + fb, re = (float)hi + fb;
             const float step = __fdiv_rn(re - rs, (float)p.max_k);
             for (int j = 0; j < p.max_k; ++j) {
               const int o = off + j - win;
-              if ((unsigned)o < (unsigned)EM_WIN) s_out[o] = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f);
+              if ((unsigned)o < (unsigned)EM_WIN) s_out[o] = (int)((re - (float)(int)__fmul_rn((float)j, step)) - 1.0f) + ib;
             }
             off += p.max_k;
           }
@@ -1405,7 +1410,8 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
                                           int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
                                           int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream) {
   const char* nm = "sea_decode_cnn_tail_select";
-  SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31)), SEA_EUNSUPPORTED,
+  SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31) && T_cap < (1ll << 24)),
+              SEA_EUNSUPPORTED,
               "%s: the in-launch emit serves C <= 64 channels (beyond that the weight image leaves no LDS for it: pass col = NULL "
               "and call sea_csr_emit with t_src_dev = counters + 2)", nm);
   SEA_REQUIRE(x_new && x_ring && y1_ring && y2 && w1_packed && bias1 && w2_packed && bias2 && conv_b && conv_w16 && gamma && beta &&
@@ -1476,7 +1482,12 @@ extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_
   SEA_REQUIRE(bits && crow && col, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(idx_bytes == 4 || idx_bytes == 8, SEA_EINVAL, "%s: idx_bytes must be 4 or 8", nm);
   SEA_REQUIRE(N > 0 && H > 0 && T_dst > 0 && T_m > 0 && max_k > 0, SEA_EINVAL, "%s: bad shape", nm);
-  SEA_REQUIRE(H * T_enc < (1ll << 24) && T_enc >= T_src, SEA_EUNSUPPORTED, "%s: H*T_src must stay below 2^24 (fp32-exact ids)", nm);
+  if (t_src_dev) {                                   // keys (< *t_src_dev <= T_enc) stepped in fp32, the head offset as an integer
+    SEA_REQUIRE(H * T_enc < (1ll << 31) && T_enc < (1ll << 24) && T_enc >= T_src, SEA_EUNSUPPORTED,
+                "%s: the decode form needs int32 ids (H*T_cap < 2^31) and fp32-exact keys (T_cap < 2^24)", nm);
+  } else {
+    SEA_REQUIRE(H * T_enc < (1ll << 24) && T_enc >= T_src, SEA_EUNSUPPORTED, "%s: H*T_src must stay below 2^24 (fp32-exact ids)", nm);
+  }
   if (z_cap == 0) return SEA_OK;
   EmitParams p;
   p.bits = bits; p.crow = crow; p.T_enc = (int)T_enc; p.t_src_dev = t_src_dev;

@@ -31,7 +31,9 @@ placement and k order).  Shapes outside that kernel (three-convolution bodies, H
 Round 5, later: the attention launch of a position is the decode form of `sea_sparse_attention` -- the gather kernel expands the one
 row's kept pixels itself (row widths from the device counter), its idle lane groups warm the K / V rows of the expanded lists
 -- so the CSR row's column ids are not on the critical path any more (no emit phase / launch; `session.csr.col` emits on
-first read).  `fused_attention=False` keeps the emit + unfused launch pair (bitwise the same context).
+its first read after each step: a replayed step re-arms the handle).  `fused_attention=False` keeps the emit + unfused launch
+pair (bitwise the same context).  Column ids are head * capacity + key, and the capacity never changes a bit: a thinned
+pixel's keys are stepped in fp32 on the key alone, the head offset is added as an integer (include/sea_hip.h, sea_csr_emit).
 """
 from typing import Optional
 
@@ -124,7 +126,8 @@ class DecodeSession:
         self.q_in = torch.zeros((N, H, 1, D), dtype=dt, device=dev)
         self.ctx = torch.zeros((N, 1, H * D), dtype=at.context_layer_dtype or torch.float32, device=dev)
         self.fused_attention = bool(fused_attention)   # the attention launch's decode form (False: emit + the unfused launch)
-        self.csr = None
+        self.csr = None                                                      # the CSR row of the last step
+        self._col_emit = None                                                # its pending-column state (graph replay re-arms it)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.probs = None                                                    # estimated attention probabilities of the last step
         self._pinned, self._prep_generation = None, ops.prep_generation()
@@ -181,6 +184,7 @@ class DecodeSession:
                                  avg=avg_rows, mix=avg_scale, out=self.ctx.view(self.N, 1, H, D).permute(0, 2, 1, 3),
                                  path="gather", keep_columns_pending=True)
             self.csr = csr                                                    # (the step's selection: columns on first read of .col)
+            self._col_emit = csr._pending                                     # (None: a launch of the step writes the columns)
             return
         y = self.xs                                                           # (N, LB + 1, C/8, W, 8)
         for i in range(0, len(body) - 2, 2):
@@ -195,6 +199,7 @@ class DecodeSession:
                              row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
                              avg=avg_rows, mix=avg_scale, out=self.ctx.view(self.N, 1, H, D).permute(0, 2, 1, 3),
                              path="gather")
+        self.csr, self._col_emit = csr, None                                  # (the emit launch above wrote the columns)
         ops.c8_window_shift(self.xs, counters=self.ctr32[:2])                 # the window of the next position; counters += 1
 
     def _capture(self):
@@ -252,6 +257,11 @@ class DecodeSession:
         self._stage(q, k, v)
         if self.graph is not None:
             self.graph.replay()
+            # the handle of the capture is every replay's: its cached wire format is the first step's, and columns that no
+            # replayed launch writes are pending again (the emit launcher reads this step's bits / crow / counter)
+            self.csr._wire = None
+            if self._col_emit is not None:
+                self.csr._pending = self._col_emit
         else:
             self._launch()
         self.length += 1
