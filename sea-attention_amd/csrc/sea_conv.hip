@@ -368,6 +368,176 @@ __global__ __launch_bounds__(NW * 64, (NT <= 4 ? 3 : 2)) void causal_conv_c8_ker
   }
 }
 
+// ---- the weight-stationary form of the 16-bit 3 x 3, 64 -> 64 channel, W = 64 layer (the predictor's own shape) -------------
+// causal_conv_c8_kernel holds the 74 KB weight image in LDS, which caps it at 2 x 6 waves per CU with every pixel fragment a
+// buffer load into registers: its loads and stores share one in-order vmcnt with nothing to stage them, and ~55 us of a
+// 180 us launch waited on memory the matrix pipe could have hidden.  Here the weights leave LDS:
+//  * one 4-wave workgroup per CU, one wave per SIMD; each wave keeps its A fragments for a whole row in registers -- 18 k-steps
+//    x 4 M-tiles x 4 VGPRs = 288 -- in the same (tap row, 32-channel chunk, tap column) order and lane placement;
+//  * a workgroup walks a contiguous run of rows, 4 at a time (wave w: row r + w).  The input rows sit in an LDS ring of
+//    8 + 2 dil slots (rows r - 2 dil .. r + 3 of this step, r + 4 .. r + 7 of the next one in flight), filled by LDS-DMA:
+//    one global_load_lds_dwordx4 wave-instruction = one 1 KB C8 channel block of a row.  Each channel block carries dil zero
+//    pixels either side, so a column tap that leaves the row reads zeros and no fragment needs a mask;
+//  * B fragments come from the ring by ds_read_b128 (a 16-pixel run of one block is 256 contiguous bytes: conflict-free); the
+//    MFMA waves issue no global loads.  Per step: wait for this wave's fills (a counted vmcnt that skips the previous row's
+//    8 stores), one barrier, the fills of the next step (into the slots the previous step read), 288 MFMAs, the epilogue.
+// Same MFMA, same operand placement, same k order (tap rows wholly in the causal padding skipped), same epilogue arithmetic:
+// every output is bit for bit the one causal_conv_c8_kernel<T, 4, 3, true> writes.
+#ifndef SEA_CONV_NO_RING
+#define SEA_CONV_RING 1
+#else
+#define SEA_CONV_RING 0
+#endif
+#if SEA_CONV_RING
+constexpr int RING_WAVES = 4;
+constexpr int RING_MAX_DIL = 4;                  // 8 + 2 dil slots of 8 (64 + 2 dil) x 16 bytes: 147 KB at dil = 4
+
+// one 1 KB LDS-DMA piece: lane l's 16 bytes from gsrc land at lds_dst + 16 l (M0 = the wave-uniform LDS base).  hipcc does
+// not count it in its waits: the kernel waits for it itself (ring_wait_barrier).
+__device__ __forceinline__ void ring_glds16(const void* gsrc, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// this wave's fills retired (vmcnt(N): the N stores issued after them may stay in flight), its LDS reads and writes
+// retired, then the workgroup barrier
+template <int N> __device__ __forceinline__ void ring_wait_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory");
+}
+
+template <typename T>
+__global__ __launch_bounds__(RING_WAVES * 64, 1) void causal_conv_ring_kernel(ConvParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NT = 4, KCH = 2, NSTEPS = 18, C8 = 8;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  const int dil = p.dil;
+  const int R = 8 + 2 * dil;                                 // ring slots
+  const int BS = (64 + 2 * dil) * 16;                        // bytes per channel block (dil zero pixels either side)
+  const int SLOT = C8 * BS;
+  float* sBias = reinterpret_cast<float*>(smem + (size_t)R * SLOT);
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const int nrows = p.N * p.T;
+  const int per = (nrows + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int g0 = (int)blockIdx.x * per, g1 = min(nrows, g0 + per);
+  if (g0 >= g1) return;                                      // (workgroup-uniform)
+
+  // ---- weights -> registers: wreg[st][nt] = the fragment causal_conv_c8_kernel reads from its LDS image at (st, nt) ----------
+  uint4 wreg[NSTEPS][NT];
+  {
+    const T* wg = reinterpret_cast<const T*>(p.w);
+#pragma unroll
+    for (int st = 0; st < NSTEPS; ++st) {
+      const int tj = st % 3, tc = st / 3, cci = tc % KCH, ti = tc / KCH;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const int co = conv_chan<NT>(nt, li >> 2) + (li & 3);
+        wreg[st][nt] = *reinterpret_cast<const uint4*>(wg + (int64_t)co * (9 * 64) + (ti * 3 + tj) * 64 + cci * 32 + lg * 8);
+      }
+    }
+  }
+  // ---- zero pads of every slot's channel blocks, biases -------------------------------------------------------------------
+  for (int i = threadIdx.x; i < R * C8 * 2 * dil; i += RING_WAVES * 64) {
+    const int px = i % (2 * dil), blk = i / (2 * dil);       // blk = slot * 8 + channel block
+    const int off = blk * BS + (px < dil ? px : 64 + px) * 16;
+    *reinterpret_cast<uint4*>(smem + off) = make_uint4(0, 0, 0, 0);
+  }
+  if (threadIdx.x < 64) sBias[threadIdx.x] = p.b[threadIdx.x];
+
+  const int row_bytes = 64 * 64 * (int)sizeof(T);
+  const char* xg = reinterpret_cast<const char*>(p.x);
+  auto slot_of = [&](int g) { return g % R; };               // g >= 0
+  auto fill = [&](int g) {                                   // the whole row g: 8 channel blocks
+#ifndef SEA_CONV_RING_EXP_NOLOAD
+    const char* src = xg + (int64_t)g * row_bytes + lane * 16;
+    const unsigned dst = lds0 + (unsigned)(slot_of(g) * SLOT + dil * 16);
+#pragma unroll
+    for (int b = 0; b < C8; ++b) ring_glds16(src + b * (64 * 16), __builtin_amdgcn_readfirstlane(dst + b * BS));
+#endif
+  };
+  // prologue: the 2 dil halo rows before the run (those that exist) and the run's first 4 rows, dealt round the waves
+  {
+    const int h0 = max(0, g0 - 2 * dil), h1 = min(g1, g0 + RING_WAVES);
+    for (int g = h0 + wv; g < h1; g += RING_WAVES) fill(g);
+  }
+
+  cf4 acc[NT][4];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) acc[nt][mt] = cf4{0.f, 0.f, 0.f, 0.f};
+  const unsigned lane_rd = (unsigned)((lg * BS) + li * 16);  // + slot * SLOT + cci * 4 BS + (mt * 16 + dil * tj) * 16
+  bool stored = false;                                       // this wave issued a row's 8 stores after its last fills
+
+#pragma unroll 1
+  for (int r = g0; r < g1; r += RING_WAVES) {
+    if (stored) ring_wait_barrier<8>(); else ring_wait_barrier<0>();
+    if (r + RING_WAVES + wv < g1) fill(r + RING_WAVES + wv);   // the next step's row of this wave
+    const int g = r + wv;
+    stored = false;
+    if (g < g1) {                                            // (wave-uniform)
+      const int t = g % p.T;
+      int sl[3];
+#pragma unroll
+      for (int ti = 0; ti < 3; ++ti) sl[ti] = slot_of(max(0, g - dil * (2 - ti))) * SLOT;
+      const int ti0 = t >= 2 * dil ? 0 : t >= dil ? 1 : 2;   // tap rows entirely in the causal padding: skipped
+      // B fragments one k-step ahead in two register sets: step st + 1's reads leave before step st's 16 MFMAs (read
+      // just in front of its MFMAs, every step exposed an LDS round trip).  The reads do not depend on ti0 (a skipped
+      // tap row reads a valid slot it does not use); the MFMAs of a skipped row are a wave-uniform branch.
+      auto rd = [&](int st, cu4 (&b)[4]) {
+        const int tj = st % 3, cci = (st / 3) % KCH, ti = st / (3 * KCH);
+        const char* a = smem + lane_rd + sl[ti] + cci * 4 * BS + dil * tj * 16;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) b[mt] = *reinterpret_cast<const cu4*>(a + mt * 256);
+      };
+      auto mm = [&](int st, const cu4 (&b)[4]) {
+        if (st / (3 * KCH) < ti0) return;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt) acc[nt][mt] = Mfma16<T>::run(wreg[st][nt], b[mt], acc[nt][mt]);
+      };
+      cu4 b0[4], b1[4];
+      rd(0, b0);
+#pragma unroll
+      for (int st = 0; st < NSTEPS; st += 2) {
+        rd(st + 1, b1);  __builtin_amdgcn_sched_barrier(0);
+        mm(st, b0);      __builtin_amdgcn_sched_barrier(0);
+        if (st + 2 < NSTEPS) { rd(st + 2, b0);  __builtin_amdgcn_sched_barrier(0); }
+        mm(st + 1, b1);  __builtin_amdgcn_sched_barrier(0);
+      }
+      // epilogue: causal_conv_c8_kernel's, at W = 64 and 64 output channels
+      T* yn = reinterpret_cast<T*>(p.y) + (int64_t)g * (64 * 64);
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        const int wpix = mt * 16 + li;
+        unsigned pk[2 * NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const float4 b4 = *reinterpret_cast<const float4*>(sBias + conv_chan<NT>(nt, lg));
+          float v0 = acc[nt][mt][0] + b4.x, v1 = acc[nt][mt][1] + b4.y, v2 = acc[nt][mt][2] + b4.z, v3 = acc[nt][mt][3] + b4.w;
+          if (p.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+          pk[2 * nt] = pack2<T>(v0, v1);
+          pk[2 * nt + 1] = pack2<T>(v2, v3);
+          acc[nt][mt] = cf4{0.f, 0.f, 0.f, 0.f};
+        }
+#ifndef SEA_CONV_RING_EXP_NOSTORE
+#pragma unroll
+        for (int q = 0; q < NT / 2; ++q)
+          *reinterpret_cast<uint4*>(yn + ((int64_t)(q * 4 + lg) * 64 + wpix) * 8) = make_uint4(pk[4 * q], pk[4 * q + 1], pk[4 * q + 2], pk[4 * q + 3]);
+#else
+        if (pk[0] == 0x12345678u) *reinterpret_cast<uint4*>(yn + wpix * 8) = make_uint4(pk[1], pk[2], pk[3], pk[4]);   // (timing only)
+#endif
+      }
+#ifndef SEA_CONV_RING_EXP_NOSTORE
+      stored = true;
+#endif
+    }
+  }
+}
+#endif  // SEA_CONV_RING
+
 // ---- fp32 DATA (round 5): the same implicit GEMM on v_mfma_f32_16x16x4_f32 -------------------------------------------------
 // The reference's measurement protocol is fp32 (src/main/benchmark_bert.py:196-239) and until now fp32 tensors took the
 // framework's dilated convolutions (MIOpen: 2 x 0.63 ms at BASELINE config 2, a quarter of that step each).  Same layout idea
@@ -560,8 +730,49 @@ __global__ __launch_bounds__(256) void split_layernorm_c8_kernel(const T* x, T* 
 
 using namespace sea;
 
+// compute units of the current device, asked once per device (the persistent grids are sized by it)
+static int device_cus() {
+  static int cus[64];
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess) return 256;
+  int c = __atomic_load_n(&cus[d & 63], __ATOMIC_RELAXED);
+  if (c <= 0) {
+    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c <= 0) c = 256;
+    __atomic_store_n(&cus[d & 63], c, __ATOMIC_RELAXED);
+  }
+  return c;
+}
+
+#if SEA_CONV_RING
+// the weight-stationary form takes a 16-bit 3 x 3, 64 -> 64 channel layer on 64-pixel rows when there are at least
+// RING_MIN_ROWS_PER_CU rows per compute unit.  Measured (scripts/ab_conv_ring.py, same box): 128 rows per CU (OPT-1.3B x 8)
+// 157 - 163 us against 175 - 182; 32 (OPT-2.7B x 1) 49 - 51 against 47 - 47.5 and 16 (OPT-1.3B x 1) 31 - 32 against 30.5 - 31:
+// with few rows per workgroup the 2 dil halo rows, the weight load and the single-wave pipeline's ramp do not pay.
+constexpr int RING_MIN_ROWS_PER_CU = 128;
+static bool ring_takes(const ConvParams& p, bool zepi, int cus) {
+  return !zepi && p.KS == 3 && p.Cin == 64 && p.Cout == 64 && p.CinP == 64 && p.W == 64 && p.pad_w == p.dil &&
+         p.dil <= RING_MAX_DIL && (int64_t)p.N * p.T >= (int64_t)RING_MIN_ROWS_PER_CU * cus;
+}
+template <typename T>
+static int launch_conv_ring(const ConvParams& p, hipStream_t s, int cus) {
+  const int64_t nrows = (int64_t)p.N * p.T;
+  if (nrows >= (int64_t)1 << 30) return SEA_EUNSUPPORTED;
+  const size_t lds = (size_t)(8 + 2 * p.dil) * 8 * (64 + 2 * p.dil) * 16 + 64 * sizeof(float);
+  int64_t blocks = (nrows + RING_WAVES - 1) / RING_WAVES;
+  if (blocks > cus) blocks = cus;                            // persistent: one workgroup per CU, weights loaded once each
+  static DevOnce once;
+  if (once.first()) SEA_MAX_LDS((causal_conv_ring_kernel<T>), 160 * 1024);
+  hipLaunchKernelGGL((causal_conv_ring_kernel<T>), dim3((unsigned)blocks), dim3(RING_WAVES * 64), lds, s, p);
+  return SEA_OK;
+}
+#endif
+
 template <typename T>
 static int launch_conv(const ConvParams& p, hipStream_t s, bool zepi = false) {
+  const int cus = device_cus();
+#if SEA_CONV_RING
+  if (ring_takes(p, zepi, cus)) return launch_conv_ring<T>(p, s, cus);
+#endif
   const int nt = (p.Cout + 15) / 16;
   size_t lds = (size_t)(p.KS * p.KS * (p.CinP / 32)) * 4 * (16 * nt) * 8 * sizeof(T) + (size_t)(16 * nt) * sizeof(float);
   if (zepi) lds += (size_t)((nt + 1) / 2) * ((p.H1 + 15) / 16) * 64 * 16 + (size_t)((p.H1 + 15) / 16) * 16 * sizeof(float);   // the 1x1 weights' operand fragments + biases
@@ -573,8 +784,8 @@ static int launch_conv(const ConvParams& p, hipStream_t s, bool zepi = false) {
   const bool w8 = nt <= 3 || nt == 5 || nwork <= 16384;
   const int nw = w8 ? 8 : CONV_WAVES;
   int64_t blocks = (nwork + nw - 1) / nw;
-  if (blocks > 256 * 2) blocks = 256 * 2;      // persistent: two resident workgroups per CU, weights staged once each
-  if (lds > 80 * 1024 && blocks > 256) blocks = 256;     // an image this large leaves room for ONE workgroup per CU: one staging round
+  if (blocks > cus * 2) blocks = cus * 2;      // persistent: two resident workgroups per CU, weights staged once each
+  if (lds > 80 * 1024 && blocks > cus) blocks = cus;     // an image this large leaves room for ONE workgroup per CU: one staging round
   dim3 grid((unsigned)blocks), block(nw * 64);
 #define SEA_CONV_L(NTV, KSV, ZV, NWV)                                                                               \
   do {                                                                                                              \
@@ -670,7 +881,8 @@ static int launch_conv_f32(const ConvF32Params& p, hipStream_t s) {
   if (nwork >= (int64_t)1 << 30) return SEA_EUNSUPPORTED;
   const int per_cu = lds > 80 * 1024 ? 1 : lds > 40 * 1024 ? 2 : 4;                    // resident workgroups per CU (by LDS)
   int64_t blocks = (nwork + CONVF_WAVES - 1) / CONVF_WAVES;
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;                                     // persistent: weights staged once each
+  const int cus = device_cus();
+  if (blocks > cus * per_cu) blocks = cus * per_cu;                                     // persistent: weights staged once each
   dim3 grid((unsigned)blocks), block(CONVF_WAVES * 64);
 #define SEA_CONVF(NTV)                                                                                  \
   do {                                                                                                  \
