@@ -1,4 +1,6 @@
-// Causal Performer (generalized ReLU feature map + causal linear attention) as ONE fp32-MFMA kernel, gfx950.
+// Causal Performer (generalized ReLU feature map + causal linear attention) as ONE fused kernel, gfx950.  Three forms:
+// performer_kernel (fp32 data, described here), performer_bf16_kernel and performer_bf16w_kernel (16-bit data, D = 64 and
+// D = 80 / 128); perf_form at the end of the file picks one per (dtype, D, nb).
 //
 // Replaces step B of SEA's estimator (reference: src/models/perlin_attention/attention.py:497-514,556-590 ->
 // performer_pytorch.FastAttention, causal=True, generalized_attention=True; not vendored, see
@@ -18,7 +20,6 @@
 // permuted accordingly on the A side.  All products run on v_mfma_f32_16x16x4_f32 (exact fp32).
 #include "sea_common.hpp"
 #include <cstdlib>
-#include <type_traits>
 
 #ifdef SEA_STAMP
 __device__ unsigned long long sea_dbg_perf[16];
@@ -95,29 +96,23 @@ template <> struct S16<__half> {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph8, a), __builtin_bit_cast(ph8, b), c, 0, 0, 0);
   }
 };
-template <> struct S16<float> {};     // (fp32 data never takes the 16-bit feature-map product)
 
-// NW = waves per workgroup (8: two per SIMD, so one wave's LDS/MFMA latency hides behind the other's issue)
-template <typename T, int D, int NBT, int C, int NW, bool STATE_ONLY>
-__global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
-  constexpr int NTH = NW * 64;
-  constexpr int VEC = Elem<T>::VEC;
+// fp32 data.  NW = 8 waves per workgroup: two per SIMD, so one wave's LDS/MFMA latency hides behind the other's issue
+template <int D, int NBT, int C, bool STATE_ONLY>
+__global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
+  constexpr int NW = 8, NTH = NW * 64;
+  constexpr int VEC = Elem<float>::VEC;
   constexpr int E = 2 * D, NBP = NBT * 16;
   constexpr int RB = C / 16;                  // row blocks per chunk
   constexpr int EB = E / 16;                  // column blocks of V / S / O
   constexpr int JB = (EB + NW - 1) / NW;      // column blocks owned by one wave
   constexpr int LDQ = D + 2, LDV = E + 16, LDP = NBP + 2, LDA = C + 2, LDW = D + 2;
   static_assert(LDA <= LDQ, "the A tile is overlaid on the Q tile");
-  // 16-bit data: q, k and the projection ARE 16-bit values, so the feature-map product runs exactly on the 16x16x32
-  // 16-bit MFMA (8x the fp32 MFMA rate) from raw 16-bit LDS images [k-chunk of 8][row][8]; everything downstream stays fp32
-  constexpr bool IS16 = !std::is_same<T, float>::value;
-  constexpr int DK = (D + 31) / 32 * 32;      // feature-map contraction length, zero padded to whole 32-wide k-steps
-  constexpr int F0 = IS16 ? 0 : NBP * LDW, F1 = IS16 ? C * LDA : C * LDQ, F2 = IS16 ? 0 : C * LDQ;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sW = smem;               // NBP x LDW   W (rows >= nb are zero)                      [fp32 data only]
-  float* sQ = sW + F0;            // C x LDQ     Q chunk, later the masked A tile (C x LDA)   [16-bit data: the A tile only]
-  float* sK = sQ + F1;            // C x LDQ                                                  [fp32 data only]
-  float* sV = sK + F2;            // C x LDV     [pos | v]
+  float* sW = smem;               // NBP x LDW   W (rows >= nb are zero)
+  float* sQ = sW + NBP * LDW;     // C x LDQ     Q chunk, later the masked A tile (C x LDA)
+  float* sK = sQ + C * LDQ;       // C x LDQ
+  float* sV = sK + C * LDQ;       // C x LDV     [pos | v]
   float* sQp = sV + C * LDV;      // C x LDP     phi(Q)
   float* sKp = sQp + C * LDP;     // C x LDP     phi(K)
   float* sKsum = sKp + C * LDP;   // NBP         running sum of phi(k)
@@ -125,10 +120,6 @@ __global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
   constexpr int DSL = RB + NW * 64 / C;       // partial-denominator slots per row: RB key blocks + carry parts
   float* sDenP = sDen + C;        // C x DSL     partials, summed in a fixed order (bitwise reproducible)
   float* sA = sQ;
-  static_assert((F0 + F1 + F2 + C * LDV + 2 * C * LDP + NBP + C + C * DSL) % 4 == 0, "16-bit images start 16-byte aligned");
-  unsigned short* sW16 = reinterpret_cast<unsigned short*>(sDenP + C * DSL);   // [DK/8][NBP][8]
-  unsigned short* sQ16 = sW16 + (DK / 8) * NBP * 8;                             // [DK/8][C][8]
-  unsigned short* sK16 = sQ16 + (DK / 8) * C * 8;                               // [DK/8][C][8]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -138,31 +129,17 @@ __global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
   const int n = nh / p.H, h = nh - n * p.H;
   const int seg = blockIdx.y;
   const int t_begin = seg * p.seg_len, t_end = min(p.T, t_begin + p.seg_len);
-  const T* qb = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1];
-  const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1];
-  const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1];
+  const float* qb = reinterpret_cast<const float*>(p.q) + n * p.qs[0] + h * p.qs[1];
+  const float* kb = reinterpret_cast<const float*>(p.k) + n * p.ks[0] + h * p.ks[1];
+  const float* vb = reinterpret_cast<const float*>(p.v) + n * p.vs[0] + h * p.vs[1];
   const int tb = p.t_base_dev ? *p.t_base_dev : p.t_base;       // rows the state has already seen (block-uniform)
-  const T* pb = reinterpret_cast<const T*>(p.pos) + (p.t_base_dev ? (int64_t)tb * p.pos_stride : 0);
-  T* ob = reinterpret_cast<T*>(p.out) + (int64_t)nh * p.T * (3 * D);
+  const float* pb = reinterpret_cast<const float*>(p.pos) + (p.t_base_dev ? (int64_t)tb * p.pos_stride : 0);
+  float* ob = reinterpret_cast<float*>(p.out) + (int64_t)nh * p.T * (3 * D);
   const float cnorm = powf((float)D, -0.25f);
 
-  if constexpr (IS16) {
-    for (int i = tid; i < (DK / 8) * NBP * 8; i += NTH) {
-      const int j = i & 7, f = (i >> 3) % NBP, dd = ((i >> 3) / NBP) * 8 + j;
-      sW16[i] = (f < p.nb && dd < D) ? S16<T>::bits(p.W[f * D + dd]) : (unsigned short)0;
-    }
-    // padding k-chunks (D = 80: chunks 10, 11 of 12) are zeroed once; the staging below never writes them -- and must
-    // not race with this loop, so the live chunks are left alone here
-    if constexpr (DK > D)
-      for (int i = tid; i < 2 * ((DK - D) / 8) * C * 8; i += NTH) {
-        const int m = i / (((DK - D) / 8) * C * 8), rest = i - m * (((DK - D) / 8) * C * 8);
-        sQ16[(m * (DK / 8) + D / 8) * C * 8 + rest] = 0;
-      }
-  } else {
-    for (int i = tid; i < NBP * LDW; i += NTH) {
-      const int r = i / LDW, c = i - r * LDW;
-      sW[i] = (r < p.nb && c < D) ? p.W[r * D + c] : 0.f;
-    }
+  for (int i = tid; i < NBP * LDW; i += NTH) {
+    const int r = i / LDW, c = i - r * LDW;
+    sW[i] = (r < p.nb && c < D) ? p.W[r * D + c] : 0.f;
   }
 
   // state = sum of the increments of the segments before this one (fixed order); raw per-thread register images
@@ -233,19 +210,12 @@ __global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
         const int r = ch / (D / VEC), c = (ch - r * (D / VEC)) * VEC;
         float fq[VEC], fk[VEC], fv[VEC], fp[VEC];
         if (!STATE_ONLY && r < rows) *reinterpret_cast<uint4*>(ob + (int64_t)(t0 + r) * (3 * D) + 2 * D + c) = pv[i];
-        unpack16<T>(pv[i], fv); unpack16<T>(pp[i], fp);
-        if constexpr (IS16) {                                // raw 16-byte pieces: k-chunk c/8, row r
-          *reinterpret_cast<uint4*>(sQ16 + ((c / 8) * C + r) * 8) = pq[i];
-          *reinterpret_cast<uint4*>(sK16 + ((c / 8) * C + r) * 8) = pk[i];
-        } else {
-          unpack16<T>(pq[i], fq); unpack16<T>(pk[i], fk);
-        }
+        unpack16<float>(pv[i], fv); unpack16<float>(pp[i], fp);
+        unpack16<float>(pq[i], fq); unpack16<float>(pk[i], fk);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-          if constexpr (!IS16) {
-            sQ[r * LDQ + c + j] = fq[j];
-            sK[r * LDQ + c + j] = fk[j];
-          }
+          sQ[r * LDQ + c + j] = fq[j];
+          sK[r * LDQ + c + j] = fk[j];
           sV[r * LDV + c + j] = fp[j];
           sV[r * LDV + D + c + j] = fv[j];
         }
@@ -260,34 +230,6 @@ __global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
     // a wave takes (matrix, row block) pairs: one A fragment feeds NBT independent accumulators
     for (int grp = (STATE_ONLY ? RB : 0) + wv; grp < 2 * RB; grp += NW) {   // the state-only pass needs phi(K) alone
       const int which = grp / RB, ib = grp - which * RB;        // 0: Q, 1: K
-      if constexpr (IS16) {
-        // transposed product X^T[f][t] = sum_d W[f][d] x[t][d]: a lane ends up with 4 consecutive features of one row
-        const unsigned short* src16 = which ? sK16 : sQ16;
-        f4 acc[NBT];
-#pragma unroll
-        for (int fb = 0; fb < NBT; ++fb) acc[fb] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) {
-          const uint4 bx = *reinterpret_cast<const uint4*>(src16 + ((4 * ks + lg) * C + ib * 16 + li) * 8);
-#pragma unroll
-          for (int fb = 0; fb < NBT; ++fb) {
-            const uint4 aw = *reinterpret_cast<const uint4*>(sW16 + ((4 * ks + lg) * NBP + fb * 16 + li) * 8);
-            acc[fb] = S16<T>::mfma(aw, bx, acc[fb]);
-          }
-        }
-        float* dst = which ? sKp : sQp;
-        const int row = ib * 16 + li;
-#pragma unroll
-        for (int fb = 0; fb < NBT; ++fb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int col = fb * 16 + lg * 4 + r;
-            float val = fmaxf(cnorm * acc[fb][r], 0.f) + 1e-3f;
-            if (col >= p.nb || row >= rows) val = 0.f;       // padded features / rows beyond T contribute nothing
-            dst[row * LDP + col] = val;
-          }
-        continue;
-      }
       const float* src = which ? sK : sQ;
       f4 acc[NBT];
 #pragma unroll
@@ -406,7 +348,7 @@ __global__ __launch_bounds__(NW * 64) void performer_kernel(PerfParams p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = ib * 16 + lg * 4 + r;
-            if (row < rows) ob[(int64_t)(t0 + row) * (3 * D) + col] = from_f<T>(o[ib][r] / sDen[row]);
+            if (row < rows) ob[(int64_t)(t0 + row) * (3 * D) + col] = o[ib][r] / sDen[row];
           }
         }
         }
@@ -1759,96 +1701,104 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
 
 using namespace sea;
 
-template <typename T, int D, int NBT, int C, int NW = 8>
+// Both passes of one kernel form: pass 1 (STATE_ONLY) on the first nseg-1 segments, pass 2 on all nseg (see PerfParams).
+// Every form runs 512-thread workgroups.
+template <void (*STATE_PASS)(PerfParams), void (*OUT_PASS)(PerfParams), int C, size_t LDS>
 static int launch_perf(const PerfParams& p, hipStream_t s) {
-  constexpr int E = 2 * D, NBP = NBT * 16;
-  constexpr bool IS16 = !std::is_same<T, float>::value;
-  constexpr int DK = (D + 31) / 32 * 32;
-  constexpr size_t lds = IS16
-      ? sizeof(float) * (C * (C + 2) + C * (E + 16) + 2 * C * (NBP + 2) + NBP + C + C * (C / 16 + NW * 64 / C)) +
-            2 * ((DK / 8) * NBP * 8 + 2 * (DK / 8) * C * 8)
-      : sizeof(float) * (NBP * (D + 2) + 2 * C * (D + 2) + C * (E + 16) + 2 * C * (NBP + 2) + NBP + C +
-                         C * (C / 16 + NW * 64 / C));
-  static_assert(lds <= 160 * 1024, "LDS budget");
+  static_assert(LDS <= 160 * 1024, "LDS budget");
   static DevOnce once;              // one per template instantiation and device; the attribute call is a slow driver round trip
-  if (lds > 64 * 1024 && once.first()) {
-    SEA_MAX_LDS((performer_kernel<T, D, NBT, C, NW, false>), lds);
-    SEA_MAX_LDS((performer_kernel<T, D, NBT, C, NW, true>), lds);
+  if (LDS > 64 * 1024 && once.first()) {
+    SEA_MAX_LDS(STATE_PASS, LDS);
+    SEA_MAX_LDS(OUT_PASS, LDS);
   }
   if (p.seg_len % C != 0) return SEA_EINVAL;
   if (p.nseg > 1)
-    hipLaunchKernelGGL((performer_kernel<T, D, NBT, C, NW, true>), dim3((unsigned)(p.N * p.H), (unsigned)(p.nseg - 1)), dim3(NW * 64), lds, s, p);
-  hipLaunchKernelGGL((performer_kernel<T, D, NBT, C, NW, false>), dim3((unsigned)(p.N * p.H), (unsigned)p.nseg), dim3(NW * 64), lds, s, p);
+    hipLaunchKernelGGL(STATE_PASS, dim3((unsigned)(p.N * p.H), (unsigned)(p.nseg - 1)), dim3(512), LDS, s, p);
+  hipLaunchKernelGGL(OUT_PASS, dim3((unsigned)(p.N * p.H), (unsigned)p.nseg), dim3(512), LDS, s, p);
   return SEA_OK;
 }
 
-// floats of carry per (n, h, segment) of the fp32 kernel: the per-thread state registers + the k-sum
-template <int D, int NBT, int NW = 8>
-constexpr int64_t perf_carry_floats() { return (int64_t)(((2 * D / 16) + NW - 1) / NW) * NBT * 4 * NW * 64 + NBT * 16; }
+// A kernel form: the launch, its chunk rows, the size of its carry / state image, and whether it is one of the 16-bit
+// MFMA kernels, which alone have the chunk-aligned step and the cumulative average (avg_out).
+struct PerfForm {
+  int (*launch)(const PerfParams&, hipStream_t) = nullptr;   // null: no form for this shape
+  int C = 0;
+  int64_t carry_floats = 0;       // per (n, h, segment)
+  bool mfma16 = false;
+};
 
-template <typename T, int NBT>
-static int launch_perf_bf16(const PerfParams& p, hipStream_t s) {
+// fp32 kernel: LDS images and carry floats (the per-thread state registers + the k-sum)
+template <int D, int NBT, int C>
+constexpr size_t perf_lds() {
+  constexpr int E = 2 * D, NBP = NBT * 16;
+  return sizeof(float) * (NBP * (D + 2) + 2 * C * (D + 2) + C * (E + 16) + 2 * C * (NBP + 2) + NBP + C + C * (C / 16 + 512 / C));
+}
+template <int D, int NBT>
+constexpr int64_t perf_carry_floats() { return (int64_t)(((2 * D / 16) + 7) / 8) * NBT * 4 * 512 + NBT * 16; }
+template <int D, int NBT, int C>
+static PerfForm perf_f32_form() {
+  return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, C, perf_lds<D, NBT, C>()>, C,
+          perf_carry_floats<D, NBT>(), false};
+}
+
+// 16-bit kernel, D = 64
+template <int NBT>
+constexpr size_t perf_bf16_lds() {
   constexpr int D = 64, C = 64, NTH = 512, E = 2 * D, NBP = NBT * 16, FP = ((NBT + 1) / 2) * 32, LDQ2 = FP + 16, LDK2 = (FP == 64) ? 96 : FP + 8, LDA = C + 16;
   constexpr int NSET = (FP == 64) ? 2 : 1;                   // phi image sets (performer_bf16_kernel)
-  constexpr size_t lds = 2 * ((D / 8) * NBP * 8 + 2 * (D / 8) * C * 8 + C * E + NSET * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
-                         sizeof(float) * (FP + C * (C / 16 + NTH / C) + 8 * FP);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static DevOnce once;
-  if (once.first()) {
-    SEA_MAX_LDS((performer_bf16_kernel<T, NBT, false>), lds);
-    SEA_MAX_LDS((performer_bf16_kernel<T, NBT, true>), lds);
-  }
-  if (p.seg_len % C != 0) return SEA_EINVAL;
-  if (p.nseg > 1)
-    hipLaunchKernelGGL((performer_bf16_kernel<T, NBT, true>), dim3((unsigned)(p.N * p.H), (unsigned)(p.nseg - 1)), dim3(NTH), lds, s, p);
-  hipLaunchKernelGGL((performer_bf16_kernel<T, NBT, false>), dim3((unsigned)(p.N * p.H), (unsigned)p.nseg), dim3(NTH), lds, s, p);
-  return SEA_OK;
+  return 2 * ((D / 8) * NBP * 8 + 2 * (D / 8) * C * 8 + C * E + NSET * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
+         sizeof(float) * (FP + C * (C / 16 + NTH / C) + 8 * FP);
 }
-
 template <int NBT>
 constexpr int64_t perf_bf16_carry_floats() { return (int64_t)NBT * 4 * 512 + ((NBT + 1) / 2) * 32 + 512; }
-
-// the wide-head form of the 16-bit kernel (d = 128: 32-row chunks, two column blocks per wave)
-template <typename T, int D, int C, int NBT>
-static int launch_perf_bf16w(const PerfParams& p, hipStream_t s) {
-  constexpr int NTH = 512, NBP = NBT * 16, FP = ((NBT + 1) / 2) * 32, LDQ2 = FP + 16, LDK2 = (FP == 64) ? 96 : FP + 8, LDA = C + 16;
-  constexpr int KC = (D + 31) / 32 * 4, EL = 256;
-  constexpr size_t lds = 2 * (KC * NBP * 8 + 2 * KC * C * 8 + C * EL + 2 * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
-                         sizeof(float) * (FP + C * (C / 16 + 8) + 8 * FP) +
-                         sizeof(float) * 8 * FP + 2 * C * EL;     // the state pass's second k-sum partials and second [pos | v] image
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static DevOnce once;
-  if (once.first()) {
-    SEA_MAX_LDS((performer_bf16w_kernel<T, D, C, NBT, false>), lds);
-    SEA_MAX_LDS((performer_bf16w_kernel<T, D, C, NBT, true>), lds);
-  }
-  if (p.seg_len % C != 0) return SEA_EINVAL;
-  if (p.nseg > 1)
-    hipLaunchKernelGGL((performer_bf16w_kernel<T, D, C, NBT, true>), dim3((unsigned)(p.N * p.H), (unsigned)(p.nseg - 1)), dim3(NTH), lds, s, p);
-  hipLaunchKernelGGL((performer_bf16w_kernel<T, D, C, NBT, false>), dim3((unsigned)(p.N * p.H), (unsigned)p.nseg), dim3(NTH), lds, s, p);
-  return SEA_OK;
+template <typename T, int NBT>
+static PerfForm perf_bf16_form() {
+  static_assert(perf_bf16_lds<NBT>() > 64 * 1024, "the attribute is set above 64 KB");
+  return {launch_perf<performer_bf16_kernel<T, NBT, true>, performer_bf16_kernel<T, NBT, false>, 64, perf_bf16_lds<NBT>()>, 64,
+          perf_bf16_carry_floats<NBT>(), true};
 }
 
+// the wide-head form of the 16-bit kernel (d = 80 / 128: 32-row chunks, up to two column blocks per wave)
+template <int D, int C, int NBT>
+constexpr size_t perf_bf16w_lds() {
+  constexpr int NBP = NBT * 16, FP = ((NBT + 1) / 2) * 32, LDQ2 = FP + 16, LDK2 = (FP == 64) ? 96 : FP + 8, LDA = C + 16;
+  constexpr int KC = (D + 31) / 32 * 4, EL = 256;
+  return 2 * (KC * NBP * 8 + 2 * KC * C * 8 + C * EL + 2 * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
+         sizeof(float) * (FP + C * (C / 16 + 8) + 8 * FP) +
+         sizeof(float) * 8 * FP + 2 * C * EL;     // the state pass's second k-sum partials and second [pos | v] image
+}
 template <int D, int NBT>
 constexpr int64_t perf_bf16w_carry_floats() { return (int64_t)((2 * D / 16 + 7) / 8) * NBT * 4 * 512 + ((NBT + 1) / 2) * 32 + ((2 * D / 16 + 7) / 8) * 512; }
+template <typename T, int D, int NBT>
+static PerfForm perf_bf16w_form() {
+  static_assert(perf_bf16w_lds<D, 32, NBT>() > 64 * 1024, "the attribute is set above 64 KB");
+  return {launch_perf<performer_bf16w_kernel<T, D, 32, NBT, true>, performer_bf16w_kernel<T, D, 32, NBT, false>, 32,
+                      perf_bf16w_lds<D, 32, NBT>()>, 32, perf_bf16w_carry_floats<D, NBT>(), true};
+}
 
 template <typename T>
-static int dispatch_perf(const PerfParams& p, int D, int nbt, hipStream_t s) {
-  if constexpr (!std::is_same<T, float>::value) {           // 16-bit data, d = 64 / 128: split-operand 16-bit MFMA kernels
-    if (D == 64) {
-      if (nbt <= 3) return launch_perf_bf16<T, 3>(p, s);
-      if (nbt <= 5) return launch_perf_bf16<T, 5>(p, s);
-    }
-    if (D == 80 && nbt <= 3) return launch_perf_bf16w<T, 80, 32, 3>(p, s);
-    if (D == 80 && nbt <= 5) return launch_perf_bf16w<T, 80, 32, 5>(p, s);
-    if (D == 128 && nbt <= 5) return launch_perf_bf16w<T, 128, 32, 5>(p, s);
-  }
-  if (D == 64 && nbt <= 3) return launch_perf<T, 64, 3, 64>(p, s);
-  if (D == 64 && nbt <= 5) return launch_perf<T, 64, 5, 64>(p, s);
-  if (D == 80 && nbt <= 3) return launch_perf<T, 80, 3, 64>(p, s);
-  if (D == 80 && nbt <= 5) return launch_perf<T, 80, 5, 32>(p, s);
-  if (D == 128 && nbt <= 5) return launch_perf<T, 128, 5, 32>(p, s);
-  return SEA_EUNSUPPORTED;
+static PerfForm perf_form16(int64_t D, int64_t nbt) {
+  if (D == 64 && nbt <= 3) return perf_bf16_form<T, 3>();
+  if (D == 64 && nbt <= 5) return perf_bf16_form<T, 5>();
+  if (D == 80 && nbt <= 3) return perf_bf16w_form<T, 80, 3>();
+  if (D == 80 && nbt <= 5) return perf_bf16w_form<T, 80, 5>();
+  if (D == 128 && nbt <= 5) return perf_bf16w_form<T, 128, 5>();
+  return {};
+}
+
+// The one table of kernel forms: 16-bit data takes the split-operand 16-bit MFMA kernels, fp32 data the fp32-MFMA kernel.
+static PerfForm perf_form(int dtype, int64_t D, int64_t nb) {
+  if (D <= 0 || nb <= 0) return {};
+  const int64_t nbt = (nb + 15) / 16;
+  if (dtype == SEA_F16) return perf_form16<__half>(D, nbt);
+  if (dtype == SEA_BF16) return perf_form16<__hip_bfloat16>(D, nbt);
+  if (dtype != SEA_F32) return {};
+  if (D == 64 && nbt <= 3) return perf_f32_form<64, 3, 64>();
+  if (D == 64 && nbt <= 5) return perf_f32_form<64, 5, 64>();
+  if (D == 80 && nbt <= 3) return perf_f32_form<80, 3, 64>();
+  if (D == 80 && nbt <= 5) return perf_f32_form<80, 5, 32>();
+  if (D == 128 && nbt <= 5) return perf_f32_form<128, 5, 32>();
+  return {};
 }
 
 #ifdef SEA_STAMP
@@ -1864,34 +1814,9 @@ extern "C" int sea_debug_perf_stamps(unsigned long long* host8) {
 }
 #endif
 
-// carry floats per (n, h, segment) of the kernel dispatch_perf picks (0: unsupported shape)
-static int64_t perf_carry_floats_for(int dtype, int D, int nbt) {
-  if (dtype != SEA_F32 && D == 64) {
-    if (nbt <= 3) return perf_bf16_carry_floats<3>();
-    if (nbt <= 5) return perf_bf16_carry_floats<5>();
-  }
-  if (dtype != SEA_F32 && D == 80 && nbt <= 3) return perf_bf16w_carry_floats<80, 3>();
-  if (dtype != SEA_F32 && D == 80 && nbt <= 5) return perf_bf16w_carry_floats<80, 5>();
-  if (dtype != SEA_F32 && D == 128 && nbt <= 5) return perf_bf16w_carry_floats<128, 5>();
-  if (D == 64 && nbt <= 3) return perf_carry_floats<64, 3>();
-  if (D == 64 && nbt <= 5) return perf_carry_floats<64, 5>();
-  if (D == 80 && nbt <= 3) return perf_carry_floats<80, 3>();
-  if (D == 80 && nbt <= 5) return perf_carry_floats<80, 5>();
-  if (D == 128 && nbt <= 5) return perf_carry_floats<128, 5>();
-  return 0;
-}
-
-// rows per chunk of the 16-bit MFMA kernel dispatch_perf picks (0: no chunk-aligned step for this shape / dtype)
-static int perf_chunk_rows_for(int dtype, int D, int nbt) {
-  if (dtype == SEA_F32) return 0;
-  if (D == 64 && nbt <= 5) return 64;
-  if ((D == 80 || D == 128) && nbt <= 5) return 32;
-  return 0;
-}
-
 extern "C" int64_t sea_performer_chunk_rows(int64_t D, int64_t nb, int dtype) {
-  if (D <= 0 || nb <= 0) return 0;
-  return perf_chunk_rows_for(dtype, (int)D, (int)((nb + 15) / 16));
+  const PerfForm f = perf_form(dtype, D, nb);
+  return f.mfma16 ? f.C : 0;
 }
 
 // rows per segment: whole 64-row chunks (a multiple of every kernel's chunk size), segments as even as possible
@@ -1901,16 +1826,14 @@ static int64_t perf_seg_len(int64_t T, int64_t nseg) {
 }
 
 // avg_out comes from the 16-bit MFMA kernels only (16-bit data, d = 64, 80 or 128, up to 80 features)
-extern "C" int sea_performer_avg_supported(int64_t D, int64_t nb, int dtype) {
-  return (dtype == SEA_BF16 || dtype == SEA_F16) && (D == 64 || D == 80 || D == 128) && nb > 0 && nb <= 80;
-}
+extern "C" int sea_performer_avg_supported(int64_t D, int64_t nb, int dtype) { return perf_form(dtype, D, nb).mfma16; }
 
 extern "C" int sea_performer_plan(int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb, int dtype,
                                   int64_t* n_segments, int64_t* workspace_bytes) {
   const char* nm = "sea_performer_plan";
   SEA_REQUIRE(n_segments && workspace_bytes, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0 && nb > 0, SEA_EINVAL, "%s: bad shape", nm);
-  const int64_t cf = perf_carry_floats_for(dtype, (int)D, (int)((nb + 15) / 16));
+  const int64_t cf = perf_form(dtype, D, nb).carry_floats;
   SEA_REQUIRE(cf > 0, SEA_EUNSUPPORTED, "%s: unsupported head size D=%lld / feature count nb=%lld", nm, (long long)D, (long long)nb);
   // One workgroup walks one (n, h) pair's rows in order; with fewer pairs than compute units the rows are cut into
   // segments (pass 1 re-does the phi(K) / state part of all but the last: ~1/3 extra work for nseg x the parallelism).
@@ -1945,12 +1868,12 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
               SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
   PerfParams p;
   p.q = q; p.k = k; p.v = v; p.pos = pos; p.W = proj; p.out = out; p.avg = avg_out;
-  SEA_REQUIRE(avg_out == nullptr || (sea_performer_avg_supported(D, nb, dtype) && ((uintptr_t)avg_out & 15) == 0),
-              SEA_EUNSUPPORTED, "%s: avg_out needs the 16-bit MFMA kernel (bf16 / fp16 data, D = 64)", nm);
+  const PerfForm form = perf_form(dtype, D, nb);
+  SEA_REQUIRE(avg_out == nullptr || (form.mfma16 && ((uintptr_t)avg_out & 15) == 0),
+              SEA_EUNSUPPORTED, "%s: avg_out needs the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
   for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
   p.pos_stride = pos_stride;
   p.N = (int)N; p.H = (int)H; p.T = (int)T; p.nb = (int)nb;
-  const int nbt = (int)((nb + 15) / 16);
   SEA_REQUIRE(n_segments >= 1 && n_segments <= 64, SEA_EINVAL, "%s: n_segments %lld outside 1..64", nm, (long long)n_segments);
   p.nseg = (int)n_segments;
   // local rows of the call: the new rows plus, for a chunk-aligned step, the open chunk's old rows in front of them (with the
@@ -1958,9 +1881,8 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   int64_t TL = T;
   p.aligned = aligned;
   if (aligned) {
-    const int C = perf_chunk_rows_for(dtype, (int)D, nbt);
-    SEA_REQUIRE(C > 0, SEA_EUNSUPPORTED, "%s: the chunk-aligned step runs on the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
-    TL = T + (t_base_dev ? C - 1 : t_base % C);
+    SEA_REQUIRE(form.mfma16, SEA_EUNSUPPORTED, "%s: the chunk-aligned step runs on the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
+    TL = T + (t_base_dev ? form.C - 1 : t_base % form.C);
   }
   p.seg_len = (int)perf_seg_len(TL, n_segments);
   p.carry = reinterpret_cast<float*>(workspace);
@@ -1969,7 +1891,7 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   p.t_base = (int)t_base;
   p.t_base_dev = t_base_dev;
   if (state_in || state_out) {
-    const int64_t need = N * H * perf_carry_floats_for(dtype, (int)D, nbt) * (int64_t)sizeof(float);
+    const int64_t need = N * H * form.carry_floats * (int64_t)sizeof(float);
     SEA_REQUIRE(need > 0 && state_bytes >= need && ((((uintptr_t)state_in) | ((uintptr_t)state_out)) & 15) == 0 && t_base >= 0,
                 SEA_EINVAL, "%s: state images of %lld bytes needed (16-byte aligned), got %lld", nm, (long long)need, (long long)state_bytes);
     SEA_REQUIRE(state_in != nullptr || t_base == 0, SEA_EINVAL, "%s: t_base %lld without state_in", nm, (long long)t_base);
@@ -1978,15 +1900,11 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   if (n_segments > 1) {
     SEA_REQUIRE((n_segments - 1) * (int64_t)p.seg_len < TL, SEA_EINVAL, "%s: %lld segments leave one empty at T=%lld (use sea_performer_plan)",
                 nm, (long long)n_segments, (long long)TL);
-    const int64_t need = N * H * (n_segments - 1) * perf_carry_floats_for(dtype, (int)D, nbt) * (int64_t)sizeof(float);
+    const int64_t need = N * H * (n_segments - 1) * form.carry_floats * (int64_t)sizeof(float);
     SEA_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need, SEA_EINVAL,
                 "%s: workspace of %lld bytes needed (16-byte aligned), got %lld", nm, (long long)need, (long long)workspace_bytes);
   }
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (dtype == SEA_F32) rc = dispatch_perf<float>(p, (int)D, nbt, s);
-  else if (dtype == SEA_F16) rc = dispatch_perf<__half>(p, (int)D, nbt, s);
-  else rc = dispatch_perf<__hip_bfloat16>(p, (int)D, nbt, s);
+  const int rc = form.launch ? form.launch(p, (hipStream_t)stream) : SEA_EUNSUPPORTED;
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported head size D=%lld / feature count nb=%lld", nm, (long long)D, (long long)nb);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
@@ -2004,7 +1922,7 @@ extern "C" int sea_performer_causal(const void* q, const void* k, const void* v,
 
 extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype) {
   if (N <= 0 || H <= 0 || D <= 0 || nb <= 0) return 0;
-  return N * H * perf_carry_floats_for(dtype, (int)D, (int)((nb + 15) / 16)) * (int64_t)sizeof(float);
+  return N * H * perf_form(dtype, D, nb).carry_floats * (int64_t)sizeof(float);
 }
 
 // Stateful step, CHUNK ALIGNED (kv-cache decoding that reproduces the stateless pass bit for bit, attention_state.py:43-140 /

@@ -396,10 +396,11 @@ class PerlinAttention(nn.Module):
         bench = get_bench()
         self._avg_ahead = None
         hip_perf = (self._hip_estimator_ok(q) and not_padded and q_for_atten.shape == v_for_atten.shape
-                    and ops.performer_supported(q.shape[-1], self.performer_nb_features)
+                    and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
                     and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype)
         if hip_perf:
-            # value augmentation + Performer + concat with v: one fp32-MFMA kernel (csrc/sea_performer.hip)
+            # value augmentation + Performer + concat with v: one launch (two with segments) of the kernel form
+            # csrc/sea_performer.hip picks for the dtype and shape
             with timer("performer"):
                 pos = self.v_eye_learned_causal[0, 0, :T_SRC, :]
                 # sparse mode: the same launch also emits the cumulative average of v that step K mixes in

@@ -348,10 +348,11 @@ def cumavg(v: torch.Tensor, out: Optional[torch.Tensor] = None, n_slices: int = 
     return out
 
 
-def performer_supported(D: int, nb: int) -> bool:
-    """Shapes the fused Performer kernel is instantiated for (csrc/sea_performer.hip: dispatch_perf)."""
-    nbt = (nb + 15) // 16
-    return D in (64, 80, 128) and nbt <= 5
+def performer_supported(D: int, nb: int, dtype=None) -> bool:
+    """Does the fused Performer have a kernel form for this shape and dtype (None: for any of fp32 / fp16 / bf16)?  Asked
+    of the library (csrc/sea_performer.hip: perf_form)."""
+    dtypes = (dtype,) if dtype is not None else (torch.float32, torch.float16, torch.bfloat16)
+    return any(_lib.load().sea_performer_state_bytes(1, 1, int(D), int(nb), _lib.dtype_code(dt)) > 0 for dt in dtypes)
 
 
 def performer_avg_supported(q: torch.Tensor, nb: int) -> bool:
@@ -405,8 +406,7 @@ def performer_value(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torc
     nseg, ws_bytes = performer_plan(N, H, T, D, nb, q.dtype)
     if n_segments is not None and n_segments != nseg:                 # caller's choice (tests, A/B timing)
         nseg = int(n_segments)
-        one_pair = performer_plan(1, 1, 4096, D, nb, q.dtype)         # a shape the plan always cuts: bytes per (pair, segment)
-        ws_bytes = N * H * (nseg - 1) * (one_pair[1] // (one_pair[0] - 1))
+        ws_bytes = N * H * (nseg - 1) * lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(q.dtype))
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device) if nseg > 1 else None
     _lib.check(lib.sea_performer_causal(
         _p(q), _p(k), _p(v), _p(pos), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(k),
@@ -470,8 +470,7 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
         avg = torch.empty((N, H, T, D), dtype=q.dtype, device=q.device)
     ws, ws_bytes = None, 0
     if n_segments > 1:
-        one_pair = performer_plan(1, 1, 4096, D, nb, q.dtype)
-        ws_bytes = N * H * (n_segments - 1) * (one_pair[1] // (one_pair[0] - 1))
+        ws_bytes = N * H * (n_segments - 1) * lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(q.dtype))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
     _lib.check(lib.sea_performer_causal_step(
         _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),

@@ -127,5 +127,21 @@ def test_host_side_planning_entries():
     assert b"D=96" in lib.sea_last_error()
     sb = lib.sea_performer_state_bytes(2, 4, 64, 33, BF16)
     assert sb > 0 and sb % (2 * 4) == 0 and lib.sea_performer_state_bytes(2, 4, 96, 33, BF16) == 0
+    # every Performer query answers from one table of kernel forms: across each form's edges they agree with each other
+    from sea_attention_amd.perlin_attention import ops
+    for dtype in (torch.float32, torch.float16, torch.bfloat16):
+        code = _lib.dtype_code(dtype)
+        for D in (63, 64, 80, 96, 128):
+            for nb in (1, 48, 49, 80, 81):
+                a, b = (ctypes.c_int64 * 1)(), (ctypes.c_int64 * 1)()
+                planned = lib.sea_performer_plan(1, 2, 4096, D, nb, code, a, b) == 0
+                one = lib.sea_performer_state_bytes(1, 1, D, nb, code)
+                supported = D in (64, 80, 128) and nb <= 80
+                assert planned == (one > 0) == ops.performer_supported(D, nb, dtype) == supported, (dtype, D, nb)
+                assert ops.performer_supported(D, nb) == supported
+                mfma16 = supported and dtype != torch.float32
+                assert (lib.sea_performer_chunk_rows(D, nb, code) > 0) == bool(lib.sea_performer_avg_supported(D, nb, code)) == mfma16
+                if planned:
+                    assert a[0] > 1 and b[0] == 2 * (a[0] - 1) * one, (dtype, D, nb)
     # algorithmic bytes of the graded kernel: Z (2 d s + 4) + N H T (2 d s + 4)   
     assert lib.sea_sparse_attention_bytes(1000, 2, 3, 10, 64, 2) == 1000 * (2 * 64 * 2 + 4) + 2 * 3 * 10 * (2 * 64 * 2 + 4)
