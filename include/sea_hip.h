@@ -41,6 +41,8 @@ extern "C" {
  *   4  one entry point per operator: the variants that were separate, suffixed entry points of sea_sparse_attention,
  *      sea_predictor_tail, sea_predictor_tail_select, sea_csr_emit, sea_causal_conv_c8, sea_performer_causal and
  *      sea_performer_causal_step are gone; each of these takes the variants' arguments instead (NULL / 0 / 1 = not wanted)
+ *      Later, additive (no bump): the *_ragged entries of the decode step (per-sequence positions: sea_decode_stage,
+ *      sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention, sea_csr_emit)
  *      */
 #define SEA_ABI_VERSION 4
 
@@ -115,6 +117,15 @@ int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off
                  float* values_out,
                  const int32_t* t_src_dev, /* decode form, or NULL */
                  sea_stream_t stream);
+/* The decode form with a length PER SEQUENCE (a batch whose sequences sit at different positions): batch item n's rows
+ * follow t_src_dev[n * t_src_stride] (t_src_stride >= 1), ids are head * T_cap + key.  No values output.  NULL t_src_dev or
+ * a stride < 1: SEA_EINVAL; shapes as for sea_csr_emit's decode form. */
+int sea_csr_emit_ragged(const uint32_t* bits, const void* crow, const int32_t* head_off,
+                        int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
+                        int64_t T_cap, int is_causal, int max_k,
+                        void* col, int idx_bytes, int64_t col_stride_n, int64_t z_cap,
+                        const int32_t* t_src_dev, int64_t t_src_stride,
+                        sea_stream_t stream);
 
 /* Per-(row, head) offsets of a foreign flat CSR whose rows are grouped by ascending head
  * (replaces __flat_csr_sdbmm_tch_compute, flat_csr_sdbmm.py:48-127). */
@@ -243,6 +254,20 @@ int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
                          const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols, /* fused form */
                          const int32_t* t_src_dev, /* decode form, or NULL */
                          sea_stream_t stream);
+/* The decode form with a length PER SEQUENCE: sequence n's row widths follow t_src_dev[n * t_src_stride] (t_src_stride >= 1);
+ * T_cap is the caches' capacity the ids are encoded with.  The gather path, no probs_out, no plan; bits and t_src_dev are
+ * required (NULL: SEA_EINVAL).  Per workgroup the length is one scalar load: the same kernels, the same bits per sequence
+ * as the shared-length form at that sequence's length. */
+int sea_sparse_attention_ragged(const void* q, const void* k, const void* v, int dtype,
+                                int64_t N, int64_t H, int64_t T_dst, int64_t T_cap, int64_t D,
+                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                const int32_t* crow, const int32_t* col, int64_t col_stride_n,
+                                const int32_t* head_off,
+                                const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
+                                void* out, int out_dtype, const int64_t* out_strides,
+                                const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                const int32_t* t_src_dev, int64_t t_src_stride,
+                                sea_stream_t stream);
 int64_t sea_attention_few_rows(void);
 
 /* Backward of the fused operator WITHOUT its epilogue (o = sum_e softmax_e(q.k_e) v_e; the caller applies row scale and mix
@@ -391,6 +416,17 @@ int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, v
                                int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
                                int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
                                int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream);
+/* The same with a counter triple PER SEQUENCE: sequence n's {seen, T_src, T_src just finished} at counters + n * counter_stride
+ * (counter_stride >= 3, else SEA_EINVAL).  Workgroup n reads its own triple (ring slots, row widths, the in-launch emit); the
+ * last workgroup advances all N triples as above. */
+int sea_decode_cnn_tail_select_ragged(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
+                                      int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
+                                      const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
+                                      int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
+                                      const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
+                                      int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
+                                      int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
+                                      int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
 
 /* Causal cumulative average out[n,h,t,:] = sum_{s<=t} v[n,h,s,:] / (t+1), fp32 accumulation.
  * Replaces `avg_v.cumsum(-2) / arange(1..T)` (attention.py:1220-1222).  out (N,H,T,D) contiguous. */
@@ -524,6 +560,15 @@ int sea_performer_causal_step(const void* q, const void* k, const void* v, const
                               int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
                               int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev, int64_t n_segments,
                               void* workspace, int64_t workspace_bytes, sea_stream_t stream);
+/* The device-position form with a position PER SEQUENCE: sequence n has seen t_base_dev[n * t_base_stride] rows
+ * (t_base_stride >= 1).  Its chunk boundary, cache rows, embedding rows and state image (the n-th contiguous H images of
+ * state_in / state_out) follow from that.  t_base_dev NULL or a stride < 1: SEA_EINVAL.  One segment. */
+int sea_performer_causal_step_ragged(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                     const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                     const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                     int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
+                                     int64_t state_bytes, const int32_t* t_base_dev, int64_t t_base_stride,
+                                     sea_stream_t stream);
 
 /* ---- decode step with the position in DEVICE memory ------------------------------------------------------------------
  * The reference's generation loop (src/main/opt_generate.py:131 -> attention.py use_cache branches + attention_state.py)
@@ -548,6 +593,12 @@ int64_t sea_sparse_attention_bytes(int64_t Z, int64_t N, int64_t H, int64_t T_ds
 int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
                      const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                      void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, sea_stream_t stream);
+/* sea_decode_stage with a counter PER SEQUENCE: sequence n's k / v rows go to cache row counters[n * counter_stride]
+ * (counter_stride >= 1, else SEA_EINVAL); a sequence whose row lies outside the capacity writes nothing. */
+int sea_decode_stage_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                            void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                            sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
 
 #ifdef __cplusplus

@@ -27,6 +27,7 @@ _SIGNATURES = {
                           ptr, ptr, ptr, ptr], c_int),
     "sea_csr_row_scan": ([ptr, i64, i64, ptr, c_int, ptr], c_int),
     "sea_csr_emit": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, ptr, ptr], c_int),
+    "sea_csr_emit_ragged": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, i64, ptr], c_int),
     "sea_csr_head_offsets": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr], c_int),
     "sea_csr_sddmm": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, ptr, ptr, c_int, i64, ptr, ptr], c_int),
     "sea_csr_softmax": ([ptr, ptr, i64, i64, i64, i64, ptr, ptr, c_int, i64, ptr], c_int),
@@ -35,6 +36,9 @@ _SIGNATURES = {
     "sea_sparse_attention": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
                               ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int,
                               ptr, i64, c_int, c_int, c_int, ptr, ptr], c_int),
+    "sea_sparse_attention_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
+                                     ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p,
+                                     ptr, i64, c_int, c_int, c_int, ptr, i64, ptr], c_int),
     "sea_sparse_attention_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
                                   ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_sparse_attention_bwd_workspace_bytes": ([i64, i64, i64, i64], i64),
@@ -59,6 +63,9 @@ _SIGNATURES = {
     "sea_decode_cnn_tail_select": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int, c_int,
                                     ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr, ptr, ptr, ptr,
                                     ptr, i64, i64, i64, ptr, ptr], c_int),
+    "sea_decode_cnn_tail_select_ragged": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int,
+                                           c_int, ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr,
+                                           ptr, ptr, ptr, ptr, i64, i64, i64, ptr, i64, ptr], c_int),
     "sea_performer_causal": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
                               i64, ptr, i64, ptr], c_int),
     "sea_performer_state_bytes": ([i64, i64, i64, i64, c_int], i64),
@@ -66,7 +73,10 @@ _SIGNATURES = {
     "sea_attention_few_rows": ([], i64),
     "sea_performer_causal_step": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
                                    ptr, ptr, i64, i64, ptr, i64, ptr, i64, ptr], c_int),
+    "sea_performer_causal_step_ragged": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
+                                          ptr, ptr, ptr, ptr, i64, ptr, i64, ptr], c_int),
     "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, ptr], c_int),
+    "sea_decode_stage_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),
     "sea_performer_plan": ([i64, i64, i64, i64, i64, c_int, _i64p, _i64p], c_int),
@@ -124,6 +134,18 @@ def strides3(t):
     """element strides [n, h, t] of a (N,H,T,D) tensor whose last stride is 1, as a C int64[3]."""
     assert t.stride(-1) == 1, "innermost stride must be 1"
     return (c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))
+
+
+def counter_stride(counter, N):
+    """Row stride of a decode step's device counter: a 1-D int32 tensor is ONE counter shared by the batch (0: the
+    shared-position entry points); a 2-D (N, k) view holds one row per sequence (its row stride: the *_ragged entries)."""
+    assert counter.dtype == torch.int32 and counter.is_cuda
+    if counter.dim() == 2:
+        assert counter.shape[0] == N and counter.stride(1) == 1 and counter.stride(0) >= counter.shape[1], \
+            "per-sequence counters: an (N, k) view with a row per sequence"
+        return counter.stride(0)
+    assert counter.dim() == 1
+    return 0
 
 
 def strides4(t):

@@ -358,7 +358,7 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? p.t_src_dev[n * p.t_src_stride] : p.T_src, s_keys, &lbase, &fits, &ltotal);
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, lane_off);
 
   // ---- a decoding step: T_dst of one or a few rows, so all but a few of the block's lane groups have no row -- and the one
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? *p.t_src_dev : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? p.t_src_dev[n * p.t_src_stride] : p.T_src, s_keys, &lbase, &fits, &ltotal);
   // (the 16-byte fragments of the lists' K / V rows: 128 of a row's 160 bytes, i.e. both of its cache lines)
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, off_m);
 
@@ -680,7 +680,7 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
   const int hcol = h * p.T_src;
 
   // ---- B: one thread per pixel of the head --------------------------------------------------------------------------
-  const int w_t = row_width(0, 1, *p.t_src_dev, p.is_causal);
+  const int w_t = row_width(0, 1, p.t_src_dev[n * p.t_src_stride], p.is_causal);
   const float scale = interp_scale(w_t, p.T_m);
   const uint32_t* brow = p.bits + (int64_t)n * p.W + h * (p.T_m >> 5);
   const bool kept = tid < p.T_m && ((brow[tid >> 5] >> (tid & 31)) & 1u);
@@ -1087,16 +1087,15 @@ static int check_dtype(const char* name, int dtype) {
   return SEA_OK;
 }
 
-extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                    float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
-                                    const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                    const int32_t* t_src_dev, sea_stream_t stream) {
-  const char* nm = "sea_sparse_attention";
+static int sparse_attention_entry(const char* nm, const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                  int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
+                                  const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                  const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                  const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                  const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                  float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
+                                  const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                  const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream) {
   // bits != NULL: the fused form -- `col` is written by the launch, not read -- which runs on the gather kernels;
   // t_src_dev != NULL: its decode form (T_src is then the capacity of the K / V caches)
   SEA_REQUIRE(bits != nullptr || t_src_dev == nullptr, SEA_EINVAL, "%s: the decode form (t_src_dev) needs bits", nm);
@@ -1140,6 +1139,9 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   p.fuse_cap = 8192;                                        // entries of a block's key lists held in LDS (32 KB)
   p.write_cols = write_cols != 0;
   p.t_src_dev = t_src_dev;
+  SEA_REQUIRE(t_src_stride >= 0 && t_src_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad T_src stride %lld", nm,
+              (long long)t_src_stride);
+  p.t_src_stride = (int)t_src_stride;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && probs_out == nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
                 "%s: the decode form takes T_dst <= %d rows per sequence, no probs_out", nm, SEA_ATTN_WARM_ROWS);
@@ -1180,6 +1182,38 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported head size %lld", nm, (long long)D);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
+}
+
+extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                    float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
+                                    const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                    const int32_t* t_src_dev, sea_stream_t stream) {
+  return sparse_attention_entry("sea_sparse_attention", q, k, v, dtype, N, H, T_dst, T_src, D, q_strides, k_strides, v_strides,
+                                crow, col, col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides,
+                                probs_out, probs_stride_n, block_path, flags, bits, T_m, is_causal, max_k, write_cols, t_src_dev,
+                                0, stream);
+}
+
+// per-sequence lengths (the decode form only: bits and t_src_dev required): sequence n's rows follow t_src_dev[n * t_src_stride]
+extern "C" int sea_sparse_attention_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                           int64_t T_dst, int64_t T_cap, int64_t D, const int64_t* q_strides,
+                                           const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                           const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                           const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                           const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                           const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                           const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream) {
+  const char* nm = "sea_sparse_attention_ragged";
+  SEA_REQUIRE(bits && t_src_dev, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
+  return sparse_attention_entry(nm, q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides, crow, col,
+                                col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr, 0,
+                                nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_cols, t_src_dev, t_src_stride, stream);
 }
 
 extern "C" int64_t sea_attention_few_rows(void) { return SEA_ATTN_FEW_ROWS; }

@@ -43,6 +43,7 @@ struct AttnParams {
   // length, in device memory: a graph-replayed step has static arguments) while T_src above stays the FIXED capacity the
   // column ids are encoded with (head * T_src + key) and the K / V caches are laid out for.  NULL: widths follow T_src.
   const int32_t* t_src_dev;
+  int t_src_stride;   // 0: one length for the batch; else sequence n's at t_src_dev[n * t_src_stride] (per-sequence positions)
 };
 
 template <typename TO, int VEC> __device__ inline void store_frag(TO* dst, const float* f);

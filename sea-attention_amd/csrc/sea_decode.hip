@@ -25,10 +25,12 @@ struct StageParams {
   int N, H, D, cap;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void decode_stage_kernel(StageParams p) {
-  const int pos = p.ctr[0];
-  if (pos < 0 || pos >= p.cap) return;                       // (the host mirrors the length and refuses before this can happen)
+// RAGGED: a counter pair per sequence, sequence n's at ctr + n * ctr_stride (read per item: the items of a workgroup span
+// sequences); a sequence whose row lies outside the caches writes nothing
+template <typename T, bool RAGGED>
+__global__ __launch_bounds__(256) void decode_stage_kernel(StageParams p, int ctr_stride) {
+  const int pos0 = p.ctr[0];
+  if (!RAGGED && (pos0 < 0 || pos0 >= p.cap)) return;       // (the host mirrors the length and refuses before this can happen)
   const int rows = p.N * p.H;
   const int per = p.D / 8;                                   // 16-byte chunks per row (launcher: D % 8 == 0)
   const T* srcs[3] = {reinterpret_cast<const T*>(p.q), reinterpret_cast<const T*>(p.k), reinterpret_cast<const T*>(p.v)};
@@ -37,6 +39,8 @@ __global__ __launch_bounds__(256) void decode_stage_kernel(StageParams p) {
     const int which = c / (rows * per);
     const int r = (c - which * rows * per) / per, j = c % per;
     const int n = r / p.H, h = r - n * p.H;
+    const int pos = RAGGED ? p.ctr[n * ctr_stride] : pos0;
+    if (RAGGED && which != 0 && (pos < 0 || pos >= p.cap)) continue;
     const uint4 val = *reinterpret_cast<const uint4*>(srcs[which] + n * strs[which][0] + h * strs[which][1] + j * 8);
     T* dst;
     if (which == 0) dst = reinterpret_cast<T*>(p.q_in) + (int64_t)r * p.D;
@@ -66,13 +70,15 @@ __global__ __launch_bounds__(256) void c8_window_shift_kernel(uint4* xs, int row
 
 using namespace sea;
 
-extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, sea_stream_t stream) {
-  const char* nm = "sea_decode_stage";
+static int decode_stage_entry(const char* nm, const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                              int64_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                              void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                              sea_stream_t stream) {
   SEA_REQUIRE(q && k && v && q_strides && k_strides && v_strides && q_in && kv_cache && counters, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
   SEA_REQUIRE(N > 0 && H > 0 && D > 0 && capacity > 0 && N * H * D < (1ll << 24), SEA_EINVAL, "%s: bad shape", nm);
+  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
+              (long long)counter_stride);
   SEA_REQUIRE(D % 8 == 0, SEA_EUNSUPPORTED, "%s: D must be a multiple of 8 (16-byte rows)", nm);
   bool al = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_in | (uintptr_t)kv_cache) & 15) == 0;
   for (int i = 0; i < 2; ++i) al = al && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
@@ -84,10 +90,34 @@ extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int
   hipStream_t s = (hipStream_t)stream;
   const int64_t chunks = 3 * N * H * (D / 8);
   const unsigned blocks = (unsigned)((chunks + 255) / 256 > 1024 ? 1024 : (chunks + 255) / 256);
-  if (dtype == SEA_F16) hipLaunchKernelGGL((decode_stage_kernel<__half>), dim3(blocks), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16>), dim3(blocks), dim3(256), 0, s, p);
+  const int cs = (int)counter_stride;
+  if (dtype == SEA_F16) {
+    if (cs) hipLaunchKernelGGL((decode_stage_kernel<__half, true>), dim3(blocks), dim3(256), 0, s, p, cs);
+    else hipLaunchKernelGGL((decode_stage_kernel<__half, false>), dim3(blocks), dim3(256), 0, s, p, 0);
+  } else {
+    if (cs) hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true>), dim3(blocks), dim3(256), 0, s, p, cs);
+    else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, false>), dim3(blocks), dim3(256), 0, s, p, 0);
+  }
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
+}
+
+extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, sea_stream_t stream) {
+  return decode_stage_entry("sea_decode_stage", q, k, v, dtype, N, H, D, q_strides, k_strides, v_strides, q_in, kv_cache, capacity,
+                            counters, 0, stream);
+}
+
+// per-sequence positions: sequence n's new row goes to cache row counters[n * counter_stride] (counter_stride >= 1)
+extern "C" int sea_decode_stage_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+                                       const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                       void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters,
+                                       int64_t counter_stride, sea_stream_t stream) {
+  const char* nm = "sea_decode_stage_ragged";
+  SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: counter_stride must be >= 1 (got %lld)", nm, (long long)counter_stride);
+  return decode_stage_entry(nm, q, k, v, dtype, N, H, D, q_strides, k_strides, v_strides, q_in, kv_cache, capacity, counters,
+                            counter_stride, stream);
 }
 
 extern "C" int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream) {

@@ -65,6 +65,9 @@ struct PerfParams {
   // device-resident form of t_base (a captured decode step replayed as a HIP graph: the position lives in memory).  When
   // set, `pos` is the BASE of the embedding table and the kernel reads its rows from row *t_base_dev on.
   const int32_t* t_base_dev;
+  // per-sequence positions (sea_performer_causal_step_ragged, the SEQ instantiations of the 16-bit kernels): sequence n has
+  // seen t_base_dev[n * t_base_stride] rows.  0: the one position above
+  int t_base_stride;
   // chunk-aligned step (the 16-bit MFMA kernels): the state image is the state at the last CHUNK BOUNDARY c0 =
   // floor(t_base / C) * C, and the open chunk's rows c0 .. t_base-1 are walked again (k, v, pos from the caller's kv-cache,
   // no q, no output), so that every new row is computed by the very instruction sequence the stateless pass runs for it --
@@ -432,7 +435,7 @@ __device__ inline uint2 lds_tr(const unsigned short* p) {      // ds_read_b64_tr
   return __builtin_bit_cast(uint2, v);
 }
 
-template <typename T, int NBT, bool STATE_ONLY>
+template <typename T, int NBT, bool STATE_ONLY, bool SEQ = false>
 __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   constexpr int D = 64, C = 64, NW = 8, NTH = 512, E = 2 * D;
   constexpr int NBP = NBT * 16;
@@ -472,7 +475,8 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   const int nh = blockIdx.x;
   const int n = nh / p.H, h = nh - n * p.H;
   const int seg = blockIdx.y;                              // sequence-parallel form, see PerfParams
-  const int tb = p.t_base_dev ? *p.t_base_dev : p.t_base;       // rows the state has already seen (block-uniform)
+  const int tb = SEQ ? p.t_base_dev[n * p.t_base_stride] : p.t_base_dev ? *p.t_base_dev : p.t_base;   // rows seen (block-uniform)
+  // (SEQ: per-sequence positions; a form of its own, so that the shared-position step's counter load does not wait for n)
   // chunk-aligned step: local row 0 is the chunk boundary at or below tb; the `lead` rows up to tb are the open chunk's old
   // rows (k, v, pos only).  Otherwise lead = 0 and local row 0 is row tb.
   const int lead = p.aligned ? tb % C : 0;
@@ -954,7 +958,7 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
 // reads, the cumulative average on the matrix cores, segments, state images, and (round 4) the chunk walk pipelined over
 // three barriers with two sets of phi images and results stored straight from the accumulators -- is the D = 64 kernel's.
 // The 25 KB of result tiles the first version flushed one chunk later paid for the second image set (d = 128: 120 KB).
-template <typename T, int D, int C, int NBT, bool STATE_ONLY>
+template <typename T, int D, int C, int NBT, bool STATE_ONLY, bool SEQ = false>
 __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   constexpr int NW = 8, NTH = 512, E = 2 * D, CPR = D / 8;
   constexpr int DP = (D + 31) / 32 * 32, KC = DP / 8;    // head dimension padded to whole k-steps, its 8-element chunks
@@ -995,7 +999,8 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   const int nh = blockIdx.x;
   const int n = nh / p.H, h = nh - n * p.H;
   const int seg = blockIdx.y;                              // sequence-parallel form, see PerfParams
-  const int tb = p.t_base_dev ? *p.t_base_dev : p.t_base;       // rows the state has already seen (block-uniform)
+  const int tb = SEQ ? p.t_base_dev[n * p.t_base_stride] : p.t_base_dev ? *p.t_base_dev : p.t_base;   // rows seen (block-uniform)
+  // (SEQ: per-sequence positions; a form of its own, so that the shared-position step's counter load does not wait for n)
   // chunk-aligned step: local row 0 is the chunk boundary at or below tb; the `lead` rows up to tb are the open chunk's old
   // rows (k, v, pos only).  Otherwise lead = 0 and local row 0 is row tb.
   const int lead = p.aligned ? tb % C : 0;
@@ -1702,16 +1707,22 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
 using namespace sea;
 
 // Both passes of one kernel form: pass 1 (STATE_ONLY) on the first nseg-1 segments, pass 2 on all nseg (see PerfParams).
-// Every form runs 512-thread workgroups.
-template <void (*STATE_PASS)(PerfParams), void (*OUT_PASS)(PerfParams), int C, size_t LDS>
+// Every form runs 512-thread workgroups.  SEQ_PASS: OUT_PASS with a position per sequence (t_base_stride > 0, one segment).
+template <void (*STATE_PASS)(PerfParams), void (*OUT_PASS)(PerfParams), void (*SEQ_PASS)(PerfParams), int C, size_t LDS>
 static int launch_perf(const PerfParams& p, hipStream_t s) {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static DevOnce once;              // one per template instantiation and device; the attribute call is a slow driver round trip
   if (LDS > 64 * 1024 && once.first()) {
     SEA_MAX_LDS(STATE_PASS, LDS);
     SEA_MAX_LDS(OUT_PASS, LDS);
+    SEA_MAX_LDS(SEQ_PASS, LDS);
   }
   if (p.seg_len % C != 0) return SEA_EINVAL;
+  if (p.t_base_stride > 0) {
+    if (p.nseg != 1) return SEA_EINVAL;
+    hipLaunchKernelGGL(SEQ_PASS, dim3((unsigned)(p.N * p.H)), dim3(512), LDS, s, p);
+    return SEA_OK;
+  }
   if (p.nseg > 1)
     hipLaunchKernelGGL(STATE_PASS, dim3((unsigned)(p.N * p.H), (unsigned)(p.nseg - 1)), dim3(512), LDS, s, p);
   hipLaunchKernelGGL(OUT_PASS, dim3((unsigned)(p.N * p.H), (unsigned)p.nseg), dim3(512), LDS, s, p);
@@ -1737,7 +1748,8 @@ template <int D, int NBT>
 constexpr int64_t perf_carry_floats() { return (int64_t)(((2 * D / 16) + 7) / 8) * NBT * 4 * 512 + NBT * 16; }
 template <int D, int NBT, int C>
 static PerfForm perf_f32_form() {
-  return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, C, perf_lds<D, NBT, C>()>, C,
+  return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, performer_kernel<D, NBT, C, false>, C,
+                      perf_lds<D, NBT, C>()>, C,
           perf_carry_floats<D, NBT>(), false};
 }
 
@@ -1754,7 +1766,8 @@ constexpr int64_t perf_bf16_carry_floats() { return (int64_t)NBT * 4 * 512 + ((N
 template <typename T, int NBT>
 static PerfForm perf_bf16_form() {
   static_assert(perf_bf16_lds<NBT>() > 64 * 1024, "the attribute is set above 64 KB");
-  return {launch_perf<performer_bf16_kernel<T, NBT, true>, performer_bf16_kernel<T, NBT, false>, 64, perf_bf16_lds<NBT>()>, 64,
+  return {launch_perf<performer_bf16_kernel<T, NBT, true>, performer_bf16_kernel<T, NBT, false>,
+                      performer_bf16_kernel<T, NBT, false, true>, 64, perf_bf16_lds<NBT>()>, 64,
           perf_bf16_carry_floats<NBT>(), true};
 }
 
@@ -1772,7 +1785,8 @@ constexpr int64_t perf_bf16w_carry_floats() { return (int64_t)((2 * D / 16 + 7) 
 template <typename T, int D, int NBT>
 static PerfForm perf_bf16w_form() {
   static_assert(perf_bf16w_lds<D, 32, NBT>() > 64 * 1024, "the attribute is set above 64 KB");
-  return {launch_perf<performer_bf16w_kernel<T, D, 32, NBT, true>, performer_bf16w_kernel<T, D, 32, NBT, false>, 32,
+  return {launch_perf<performer_bf16w_kernel<T, D, 32, NBT, true>, performer_bf16w_kernel<T, D, 32, NBT, false>,
+                      performer_bf16w_kernel<T, D, 32, NBT, false, true>, 32,
                       perf_bf16w_lds<D, 32, NBT>()>, 32, perf_bf16w_carry_floats<D, NBT>(), true};
 }
 
@@ -1856,7 +1870,7 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
                       const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                       int64_t pos_stride, void* out, void* avg_out, int64_t n_segments, void* workspace,
                       int64_t workspace_bytes, const void* state_in, void* state_out, int64_t state_bytes, int64_t t_base,
-                      const int32_t* t_base_dev, int aligned,
+                      const int32_t* t_base_dev, int64_t t_base_stride, int aligned,
                       sea_stream_t stream) {
   SEA_REQUIRE(q && k && v && pos && proj && out && q_strides && k_strides && v_strides, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_F16 || dtype == SEA_BF16, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
@@ -1890,6 +1904,9 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   p.state_out = reinterpret_cast<float*>(state_out);
   p.t_base = (int)t_base;
   p.t_base_dev = t_base_dev;
+  SEA_REQUIRE(t_base_stride >= 0 && t_base_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad position stride %lld", nm,
+              (long long)t_base_stride);
+  p.t_base_stride = (int)t_base_stride;
   if (state_in || state_out) {
     const int64_t need = N * H * form.carry_floats * (int64_t)sizeof(float);
     SEA_REQUIRE(need > 0 && state_bytes >= need && ((((uintptr_t)state_in) | ((uintptr_t)state_out)) & 15) == 0 && t_base >= 0,
@@ -1917,7 +1934,7 @@ extern "C" int sea_performer_causal(const void* q, const void* k, const void* v,
                                     int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
                                     void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
   return perf_entry("sea_performer_causal", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
-                    v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, 0, stream);
+                    v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, 0, 0, stream);
 }
 
 extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype) {
@@ -1936,18 +1953,44 @@ extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, in
 // state has seen, `t_base` is not read; k / v are the BASES (row 0) of the kv-caches, which already hold the new rows, pos
 // the BASE of the value-embedding table: the kernel finds the chunk boundary itself.  state_in and state_out may be the
 // same image (updated in place); one segment.
-extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                         int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                         void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
-                                         int64_t n_segments, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
-  const char* nm = "sea_performer_causal_step";
+static int perf_step_entry(const char* nm, const void* q, const void* k, const void* v, const void* pos, int dtype,
+                           const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                           int64_t pos_stride, void* out, void* avg_out, const void* state_in,
+                           void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
+                           int64_t t_base_stride, int64_t n_segments, void* workspace, int64_t workspace_bytes,
+                           sea_stream_t stream) {
   if (t_base_dev) {
     SEA_REQUIRE(state_in && state_out, SEA_EINVAL, "%s: null pointer", nm);
     SEA_REQUIRE(n_segments == 1, SEA_EUNSUPPORTED, "%s: the device-position step runs one segment", nm);
     t_base = 0; workspace = nullptr; workspace_bytes = 0;
   }
   return perf_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
-                    n_segments, workspace, workspace_bytes, state_in, state_out, state_bytes, t_base, t_base_dev, 1, stream);
+                    n_segments, workspace, workspace_bytes, state_in, state_out, state_bytes, t_base, t_base_dev, t_base_stride, 1,
+                    stream);
+}
+
+extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                         int64_t pos_stride, void* out, void* avg_out, const void* state_in,
+                                         void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
+                                         int64_t n_segments, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
+  return perf_step_entry("sea_performer_causal_step", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides,
+                         pos_stride, out, avg_out, state_in, state_out, state_bytes, t_base, t_base_dev, 0, n_segments, workspace,
+                         workspace_bytes, stream);
+}
+
+// per-sequence positions: sequence n has seen t_base_dev[n * t_base_stride] rows (t_base_stride >= 1; device-position form only)
+extern "C" int sea_performer_causal_step_ragged(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                                const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                                int64_t pos_stride, void* out, void* avg_out, const void* state_in,
+                                                void* state_out, int64_t state_bytes, const int32_t* t_base_dev,
+                                                int64_t t_base_stride, sea_stream_t stream) {
+  const char* nm = "sea_performer_causal_step_ragged";
+  SEA_REQUIRE(t_base_dev, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
+  return perf_step_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
+                         state_in, state_out, state_bytes, 0, t_base_dev, t_base_stride, 1, nullptr, 0, stream);
 }

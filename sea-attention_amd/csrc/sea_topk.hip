@@ -58,6 +58,7 @@ struct TopkParams {
   // decode step replayed as a HIP graph: T_src (the rows' absolute widths) read from device memory; `keep` is then a
   // table over ABSOLUTE row indices (entry i = K of the row with i+1 visible keys), not over the T_dst rows of the call
   const int32_t* t_src_dev;
+  int t_src_stride;       // 0: one T_src for the batch; else batch item n's at t_src_dev[n * t_src_stride]
   // decode step, ONE row per batch item: the row scan is trivial -- crow = [0, row total] -- and is written here (N, 2),
   // which saves the step a launch; nullptr everywhere else
   int32_t* crow1;
@@ -263,7 +264,7 @@ __device__ __forceinline__ void select_body(const TopkParams& p, uint32_t (&key)
   if (tid == 0) s_ncand = 0;
 
   if (!FROM_MASK) {
-    const int K = p.keep[n * p.keep_stride_n + t + (p.t_src_dev ? *p.t_src_dev - p.T_dst : 0)];
+    const int K = p.keep[n * p.keep_stride_n + t + (p.t_src_dev ? p.t_src_dev[n * p.t_src_stride] - p.T_dst : 0)];
     if (K >= p.M) {
 #pragma unroll
       for (int j = 0; j < R; ++j)
@@ -449,7 +450,7 @@ __device__ __forceinline__ void select_body(const TopkParams& p, uint32_t (&key)
 
   STAMP(3);   // selection flags
   // ---- outputs ----------------------------------------------------------------------------------
-  const int w_t = row_width(t, p.T_dst, p.t_src_dev ? *p.t_src_dev : p.T_src, p.is_causal);
+  const int w_t = row_width(t, p.T_dst, p.t_src_dev ? p.t_src_dev[n * p.t_src_stride] : p.T_src, p.is_causal);
   const float scale = interp_scale(w_t, p.T_m);
   const bool tm_pow2 = (p.T_m & (p.T_m - 1)) == 0;      // block-uniform
   const int tm_sh = __ffs(p.T_m) - 1;
@@ -853,6 +854,7 @@ struct EmitParams {
   float* values_out;
   int T_enc;                       // column = head * T_enc + key (T_src, or a fixed cache capacity in the decode form)
   const int32_t* t_src_dev;        // decode step replayed as a HIP graph: T_src (row widths) read from device memory
+  int t_src_stride;                // 0: one T_src for the batch; else batch item n's at t_src_dev[n * t_src_stride]
 };
 
 // One workgroup per row.
@@ -881,7 +883,7 @@ __device__ __forceinline__ void csr_emit_row(const EmitParams& p, const int row)
   I* col = reinterpret_cast<I*>(p.col) + n * p.col_stride_n;
   float* vals = p.values_out ? p.values_out + n * p.col_stride_n : nullptr;
   const uint32_t* bits = p.bits + (int64_t)row * p.W;
-  const int w_t = row_width(t, p.T_dst, p.t_src_dev ? *p.t_src_dev : p.T_src, p.is_causal);
+  const int w_t = row_width(t, p.T_dst, p.t_src_dev ? p.t_src_dev[n * p.t_src_stride] : p.T_src, p.is_causal);
   const float scale = interp_scale(w_t, p.T_m);
   const bool table = p.T_m <= EM_TABLE;
   if (table)
@@ -1040,6 +1042,7 @@ struct DecodeCnnParams {
   const void *w1, *w2;    // packed (C, 9 * CinP)
   const float *b1, *b2;   // (C)
   int32_t* counters;      // [seen, tsrc, tsrc of the step just finished]
+  int ctr_stride;         // 0: one counter triple for the batch; else sequence n's at counters + n * ctr_stride
   int32_t* ticket;
   int C, W, RX, RY, dil, pad_w;
 };
@@ -1050,7 +1053,7 @@ template <typename T, int EPT, int NT, int KCH, bool EMIT>
 __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(DecodeCnnParams dp, TailParams tp, TopkParams p, EmitParams ep) {
   extern __shared__ __attribute__((aligned(16))) float s_z[];
   const int n = (int)blockIdx.x;
-  const int pos = dp.counters[0];                                  // rows the session has seen = index of the new position
+  const int pos = dp.counters[n * dp.ctr_stride];                 // rows the sequence has seen = index of the new position
   const int64_t row = (int64_t)dp.C * dp.W;                        // elements per C8 row
   const T* xn = reinterpret_cast<const T*>(dp.x_new) + n * row;
   T* xr = reinterpret_cast<T*>(dp.x_ring) + (int64_t)n * dp.RX * row;
@@ -1105,10 +1108,14 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
     __threadfence();
     const int done = atomicAdd(dp.ticket, 1);
     if (done == (int)gridDim.x - 1) {                              // every workgroup has read the counters and finished
-      const int ts = dp.counters[1];
-      dp.counters[2] = ts;                                         // (the emit launch behind this one reads the step's T_src here)
-      dp.counters[0] = pos + 1;
-      dp.counters[1] = ts + 1;
+      const int rows = dp.ctr_stride ? (int)gridDim.x : 1;         // (per-sequence counters: every sequence's triple)
+      for (int m = 0; m < rows; ++m) {
+        int32_t* c = dp.counters + m * dp.ctr_stride;
+        const int ts = c[1];
+        c[2] = ts;                                                 // (the emit launch behind this one reads the step's T_src here)
+        c[0] = c[0] + 1;
+        c[1] = ts + 1;
+      }
       *dp.ticket = 0;
       __threadfence();
     }
@@ -1206,7 +1213,7 @@ static int select_common(const char* name, const void* src, int dtype, int64_t N
   p.is_causal = is_causal; p.max_k = max_k;
   p.M = (int)(H * T_m); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes((int)T_m);
   p.keep = keep; p.keep_stride_n = keep_stride_n;
-  p.bits = bits; p.mask_out = mask_out; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = nullptr; p.crow1 = nullptr;
+  p.bits = bits; p.mask_out = mask_out; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = nullptr; p.t_src_stride = 0; p.crow1 = nullptr;
   const int64_t rows = N * T_dst;
   if (dtype == SEA_F32) launch_select<float, FROM_MASK>(p, rows, s);
   else if (dtype == SEA_F16) launch_select<__half, FROM_MASK>(p, rows, s);
@@ -1362,7 +1369,7 @@ extern "C" int sea_predictor_tail_select(const void* y, const float* z, int dtyp
   p.is_causal = is_causal; p.max_k = max_k;
   p.M = (int)(H * T_m); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes((int)T_m);
   p.keep = keep; p.keep_stride_n = keep_stride_n;
-  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = t_src_dev; p.crow1 = crow_out;
+  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = t_src_dev; p.t_src_stride = 0; p.crow1 = crow_out;
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if (dtype == SEA_F32) rc = launch_tail_select_f32(tp, p, N * T, s);
@@ -1401,15 +1408,14 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
   return SEA_OK;
 }
 
-extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
-                                          int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                                          const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
-                                          int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
-                                          const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                                          int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                          int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                                          int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream) {
-  const char* nm = "sea_decode_cnn_tail_select";
+static int decode_cnn_entry(const char* nm, const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N,
+                            int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
+                            const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation, int pad_w,
+                            const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
+                            void* probs, const int32_t* keep_table, int32_t* counters, int32_t* ticket, int is_causal, int max_k,
+                            uint32_t* bits, int32_t* row_nnz, int32_t* head_off, int32_t* crow_out, int32_t* col,
+                            int64_t col_stride_n, int64_t z_cap, int64_t T_cap, const uint32_t* consts_tab,
+                            int64_t counter_stride, sea_stream_t stream) {
   SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31) && T_cap < (1ll << 24)),
               SEA_EUNSUPPORTED,
               "%s: the in-launch emit serves C <= 64 channels (beyond that the weight image leaves no LDS for it: pass col = NULL "
@@ -1425,9 +1431,11 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
               "%s: a ring must hold the rows t - 2 dil .. t in distinct slots (more than 2 * dilation of them)", nm);
   SEA_REQUIRE((((uintptr_t)x_new | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)y2 | (uintptr_t)w1_packed | (uintptr_t)w2_packed |
                 (uintptr_t)conv_w16 | (uintptr_t)probs) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
+  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
+              (long long)counter_stride);
   DecodeCnnParams dp;
   dp.x_new = x_new; dp.x_ring = x_ring; dp.y1_ring = y1_ring; dp.y2 = y2; dp.w1 = w1_packed; dp.w2 = w2_packed; dp.b1 = bias1; dp.b2 = bias2;
-  dp.counters = counters; dp.ticket = ticket;
+  dp.counters = counters; dp.ctr_stride = (int)counter_stride; dp.ticket = ticket;
   dp.C = (int)C; dp.W = (int)W4; dp.RX = (int)ring_x; dp.RY = (int)ring_y; dp.dil = dilation; dp.pad_w = pad_w;
   TailParams tp;
   tp.y = y2; tp.w4 = nullptr; tp.b4 = conv_b; tp.gamma = gamma; tp.beta = beta; tp.probs = probs; tp.scores = nullptr; tp.eps = eps;
@@ -1441,16 +1449,50 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
   p.is_causal = is_causal; p.max_k = max_k;
   p.M = (int)(H * 256); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes(256);
   p.keep = keep_table; p.keep_stride_n = 0;
-  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = counters + 1; p.crow1 = crow_out;
+  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = counters + 1; p.t_src_stride = (int)counter_stride; p.crow1 = crow_out;
   EmitParams ep;
   ep.bits = bits; ep.crow = crow_out; ep.H = (int)H; ep.T_dst = 1; ep.T_m = 256; ep.T_src = 1; ep.is_causal = is_causal; ep.max_k = max_k;
   ep.W = p.W; ep.col = col; ep.col_stride_n = col_stride_n; ep.z_cap = z_cap; ep.values_out = nullptr; ep.T_enc = (int)T_cap;
-  ep.t_src_dev = counters + 1;
+  ep.t_src_dev = counters + 1; ep.t_src_stride = (int)counter_stride;
   hipStream_t s = (hipStream_t)stream;
   const int rc = dtype == SEA_F16 ? launch_decode_cnn<__half>(dp, tp, p, ep, s) : launch_decode_cnn<__hip_bfloat16>(dp, tp, p, ep, s);
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
+}
+
+extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
+                                          int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
+                                          const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
+                                          int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
+                                          const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
+                                          int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
+                                          int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
+                                          int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream) {
+  return decode_cnn_entry("sea_decode_cnn_tail_select", x_new, x_ring, y1_ring, y2, dtype, N, C, H, W4, ring_x, ring_y,
+                          w1_packed, bias1, w2_packed, bias2, CinP, dilation, pad_w, conv_b, conv_w16, Cp, gamma, beta, eps,
+                          probs, keep_table, counters, ticket, is_causal, max_k, bits, row_nnz, head_off, crow_out, col,
+                          col_stride_n, z_cap, T_cap, consts_tab, 0, stream);
+}
+
+// per-sequence counters: sequence n's triple at counters + n * counter_stride (counter_stride >= 3); the last workgroup advances all N
+extern "C" int sea_decode_cnn_tail_select_ragged(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N,
+                                                 int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
+                                                 const void* w1_packed, const float* bias1, const void* w2_packed,
+                                                 const float* bias2, int64_t CinP, int dilation, int pad_w, const void* conv_b,
+                                                 const void* conv_w16, int64_t Cp, const void* gamma, const void* beta,
+                                                 float eps, void* probs, const int32_t* keep_table, int32_t* counters,
+                                                 int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
+                                                 int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n,
+                                                 int64_t z_cap, int64_t T_cap, const uint32_t* consts_tab,
+                                                 int64_t counter_stride, sea_stream_t stream) {
+  const char* nm = "sea_decode_cnn_tail_select_ragged";
+  SEA_REQUIRE(counter_stride >= 3, SEA_EINVAL, "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm,
+              (long long)counter_stride);
+  return decode_cnn_entry(nm, x_new, x_ring, y1_ring, y2, dtype, N, C, H, W4, ring_x, ring_y, w1_packed, bias1, w2_packed,
+                          bias2, CinP, dilation, pad_w, conv_b, conv_w16, Cp, gamma, beta, eps, probs, keep_table, counters,
+                          ticket, is_causal, max_k, bits, row_nnz, head_off, crow_out, col, col_stride_n, z_cap, T_cap,
+                          consts_tab, counter_stride, stream);
 }
 
 extern "C" int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst, void* crow, int idx_bytes,
@@ -1470,12 +1512,11 @@ extern "C" int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst
 // t_src_dev != NULL: the decode form (a step captured as a HIP graph): the rows' widths follow *t_src_dev (device memory:
 // the current sequence length), the column ids are head * T_src + key with T_src the FIXED capacity T_cap >= *t_src_dev,
 // so the attention launch that consumes them (K / V caches of T_cap rows) needs nothing position-dependent in its arguments.
-extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
+static int csr_emit_entry(const char* nm, const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
                             int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
                             int64_t col_stride_n, int64_t z_cap, float* values_out, const int32_t* t_src_dev,
-                            sea_stream_t stream) {
+                            int64_t t_src_stride, sea_stream_t stream) {
   (void)head_off;  // offsets follow from the flat (head-major) emission order; kept in the ABI for symmetry
-  const char* nm = "sea_csr_emit";
   SEA_REQUIRE(!(t_src_dev && values_out), SEA_EUNSUPPORTED, "%s: the decode form writes no values", nm);
   const int64_t T_enc = T_src;
   if (t_src_dev) T_src = T_dst;
@@ -1488,9 +1529,11 @@ extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_
   } else {
     SEA_REQUIRE(H * T_enc < (1ll << 24) && T_enc >= T_src, SEA_EUNSUPPORTED, "%s: H*T_src must stay below 2^24 (fp32-exact ids)", nm);
   }
+  SEA_REQUIRE(t_src_stride >= 0 && t_src_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad T_src stride %lld", nm,
+              (long long)t_src_stride);
   if (z_cap == 0) return SEA_OK;
   EmitParams p;
-  p.bits = bits; p.crow = crow; p.T_enc = (int)T_enc; p.t_src_dev = t_src_dev;
+  p.bits = bits; p.crow = crow; p.T_enc = (int)T_enc; p.t_src_dev = t_src_dev; p.t_src_stride = (int)t_src_stride;
   p.H = (int)H; p.T_dst = (int)T_dst; p.T_m = (int)T_m; p.T_src = (int)T_src;
   p.is_causal = is_causal; p.max_k = max_k; p.W = (int)((H * T_m + 31) / 32);
   p.col = col; p.col_stride_n = col_stride_n; p.z_cap = z_cap; p.values_out = values_out;
@@ -1500,6 +1543,26 @@ extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_
   else hipLaunchKernelGGL((csr_emit_kernel<int64_t>), grid, block, 0, s, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
+}
+
+extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
+                            int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
+                            int64_t col_stride_n, int64_t z_cap, float* values_out, const int32_t* t_src_dev,
+                            sea_stream_t stream) {
+  return csr_emit_entry("sea_csr_emit", bits, crow, head_off, N, H, T_dst, T_m, T_src, is_causal, max_k, col, idx_bytes,
+                        col_stride_n, z_cap, values_out, t_src_dev, 0, stream);
+}
+
+// per-sequence lengths (decode form only): batch item n's rows follow t_src_dev[n * t_src_stride] (t_src_stride >= 1)
+extern "C" int sea_csr_emit_ragged(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
+                                   int64_t T_dst, int64_t T_m, int64_t T_cap, int is_causal, int max_k, void* col, int idx_bytes,
+                                   int64_t col_stride_n, int64_t z_cap, const int32_t* t_src_dev, int64_t t_src_stride,
+                                   sea_stream_t stream) {
+  const char* nm = "sea_csr_emit_ragged";
+  SEA_REQUIRE(t_src_dev, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
+  return csr_emit_entry(nm, bits, crow, head_off, N, H, T_dst, T_m, T_cap, is_causal, max_k, col, idx_bytes, col_stride_n, z_cap,
+                        nullptr, t_src_dev, t_src_stride, stream);
 }
 
 extern "C" int sea_csr_head_offsets(const void* crow, const void* col, int idx_bytes, int64_t N, int64_t H,

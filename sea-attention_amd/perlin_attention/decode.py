@@ -34,19 +34,44 @@ row's kept pixels itself (row widths from the device counter), its idle lane gro
 its first read after each step: a replayed step re-arms the handle).  `fused_attention=False` keeps the emit + unfused launch
 pair (bitwise the same context).  Column ids are head * capacity + key, and the capacity never changes a bit: a thinned
 pixel's keys are stepped in fp32 on the key alone, the head offset is added as an integer (include/sea_hip.h, sea_csr_emit).
+
+Sequences at different positions (`DecodeSession.from_sequences`): the counters are an (N, 3) block, a row per sequence, and
+every launch of the step takes the *_ragged entry of its operator (include/sea_hip.h).  Each of those kernels serves one
+sequence per workgroup, so a sequence's position is one scalar load from its row; the step is bitwise N sessions of N = 1.
+`admit` puts a new prompt into one slot between steps (continuous batching) without a new capture: the graph holds pointers
+to the session's buffers only.
 """
 from typing import Optional
 
 import torch
 
+from .. import _lib
 from . import ops
 from .attention_state import PerlinAttentionState, cnn_lookback
+
+
+def _cnn_convs(at):
+    """The predictor CNN body's convolutions (CausalConv2d modules)."""
+    body = list(at.attention_predictor_cnn[1].module.net.children())
+    return [body[i].module for i in range(0, len(body) - 2, 2)]
+
+
+def _fused_cnn_ok(convs, C, H, T_M, dt, LB) -> bool:
+    """Does `sea_decode_cnn_tail_select` serve this predictor (two 3 x 3 width-preserving convolutions of one dilation)?"""
+    return (len(convs) == 2 and all(c.kernel_size == 3 and c.in_channels == C and c.out_channels == C
+                                    and isinstance(c.dilation, int) and c.dilation == convs[0].dilation
+                                    and c.padding[1] == c.dilation for c in convs)
+            and ops.decode_cnn_supported(C, H, T_M, dt) and LB > 2 * convs[0].dilation)
 
 
 class DecodeSession:
     """Built from the state of a cached forward (`PerlinAttentionOutput.state`, HIP estimator: 16-bit inference) and the
     K / V prefix that forward saw.  `step(q, k, v)` takes the NEW row of each tensor, (N, H, 1, D), and returns the
-    context row (N, 1, H*D) -- a static buffer, overwritten by the next step."""
+    context row (N, 1, H*D) -- a static buffer, overwritten by the next step.
+    `from_sequences` builds a session whose sequences sit at different positions (`ragged`; host mirror `lengths`)."""
+
+    ragged = False               # (class defaults: a uniform session's instance attributes are what they always were)
+    lengths = None
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -76,13 +101,9 @@ class DecodeSession:
         # round 5: the fused CNN + tail + selection launch (module docstring).  x ring: the MLP's rows of the last LB positions,
         # row of position p in slot p % LB (what `win` holds, by position instead of by age); y1 ring: conv1's rows of the last
         # positions (8 slots: t - 2 dil and t - 4 dil... t must sit in distinct slots for dilation 2)
-        body = list(at.attention_predictor_cnn[1].module.net.children())
-        convs = [body[i].module for i in range(0, len(body) - 2, 2)]
+        convs = _cnn_convs(at)
         C = cs.rows_c8.shape[2] * 8
-        self.fused_cnn = (len(convs) == 2 and all(c.kernel_size == 3 and c.in_channels == C and c.out_channels == C
-                                                  and isinstance(c.dilation, int) and c.dilation == convs[0].dilation
-                                                  and c.padding[1] == c.dilation for c in convs)
-                          and ops.decode_cnn_supported(C, H, self.T_M, dt) and LB > 2 * convs[0].dilation)
+        self.fused_cnn = _fused_cnn_ok(convs, C, H, self.T_M, dt, LB)
         if self.fused_cnn:
             dil, RY = convs[0].dilation, 2 * 2 * convs[0].dilation + 1      # t, t - dil, t - 2 dil in distinct slots: 9 for dil 2
             row_shape = tuple(cs.rows_c8.shape[2:])
@@ -115,6 +136,13 @@ class DecodeSession:
         self.tsrc_done32 = self.ctr32[2:3]
         self.crow = torch.zeros((N, 2), dtype=torch.int32, device=dev)        # one-row CSR: [0, row total], written by the selection
         self.length = L                                                      # host mirror (bounds check only)
+        self._static_buffers(dev, dt, fused_attention)
+        if use_graph:
+            self._capture()
+
+    def _static_buffers(self, dev, dt, fused_attention):
+        """What does not depend on the prefixes: the K_t table, the column bound, the step's input / output buffers."""
+        at, N, H, D, capacity = self.attention, self.N, self.H, self.D, self.capacity
         # K_t of every reachable position (attention.py:849-866, the same fp32 expression as the stateless path) and
         # the largest CSR row any of them can emit
         keep_cpu, _ = at._decode_keep(H, capacity, capacity, self.T_M)
@@ -131,13 +159,137 @@ class DecodeSession:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.probs = None                                                    # estimated attention probabilities of the last step
         self._pinned, self._prep_generation = None, ops.prep_generation()
+
+    @classmethod
+    def from_sequences(cls, attention, sequences, capacity: int, use_graph: bool = True, fused_attention: bool = True):
+        """A session over sequences of DIFFERENT lengths.  `sequences`: [(state, key_prefix, value_prefix), ...], each the
+        output of an N = 1 cached forward, (1, H, L_i, D) with its own L_i.  Slot n of the batch is sequence n; `step` takes
+        and returns (N, ...) rows as for a uniform session, and every row equals that sequence's own N = 1 session bit for
+        bit.  Defined where the fused CNN launch runs (`ops.decode_cnn_supported`: two-convolution body, T_M = 256, H <= 40,
+        16-bit data); anything else raises ValueError, as do mismatched H / D / dtype, a prefix shorter than the CNN's reach
+        and L_i >= capacity."""
+        self = cls.__new__(cls)
+        at = self.attention = attention
+        pc = at.pconfig
+        seqs = list(sequences)
+        if not (pc.causal and not at.training):
+            raise ValueError("decoding is the causal inference path")
+        if not seqs:
+            raise ValueError("from_sequences needs at least one (state, key_prefix, value_prefix)")
+        kp0 = seqs[0][1]
+        if kp0.dim() != 4:
+            raise ValueError("key / value prefixes are (1, H, L, D)")
+        self.N, self.H, self.D, self.capacity = len(seqs), int(kp0.shape[1]), int(kp0.shape[3]), int(capacity)
+        self.dtype = kp0.dtype
+        if self.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"a ragged session runs on 16-bit data (got {self.dtype})")
+        self.T_M, self.k = int(pc.attention_predictor_length), int(pc.k)
+        self.LB = cnn_lookback(at.attention_predictor_cnn)
+        convs = _cnn_convs(at)
+        C = 2 * self.H                                                       # (the predictor's channel count: two per head)
+        self.fused_cnn = _fused_cnn_ok(convs, C, self.H, self.T_M, self.dtype, self.LB)
+        if not self.fused_cnn:
+            raise ValueError("a ragged session needs the fused CNN launch: a two-convolution predictor body, T_M = 256, "
+                             f"H <= 40 with H % 4 == 0, 16-bit data (got {len(convs)} convolutions, T_M = {self.T_M}, H = {self.H})")
+        if not self.capacity <= at.v_eye_learned_causal.shape[2]:
+            raise ValueError(f"capacity {self.capacity} beyond the value embedding ({at.v_eye_learned_causal.shape[2]} rows)")
+        lengths = [self._check_sequence(*sq) for sq in seqs]
+        N, H, D, dt, dev = self.N, self.H, self.D, self.dtype, kp0.device
+        self.ragged = True
+        dil = convs[0].dilation
+        row_shape = (C // 8, self.T_M // 4, 8)
+        per = seqs[0][0].states[PerlinAttentionState.PERFORMER].image.numel()
+        self.image = torch.empty((N * per,), dtype=torch.float32, device=dev)          # sequence n's H images: the n-th slice
+        self.x_ring = torch.zeros((N, self.LB) + row_shape, dtype=dt, device=dev)
+        self.y1_ring = torch.zeros((N, 2 * 2 * dil + 1) + row_shape, dtype=dt, device=dev)
+        self.x_new = torch.zeros((N, 1) + row_shape, dtype=dt, device=dev)
+        self.y2 = torch.zeros((N,) + row_shape, dtype=dt, device=dev)
+        self.ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.xs = None
+        self.kv_cache = torch.zeros((2, N, H, self.capacity, D), dtype=dt, device=dev)
+        self.k_cache, self.v_cache = self.kv_cache[0], self.kv_cache[1]
+        # per-sequence counters: row n = [seen, tsrc, tsrc of the step just closed] of sequence n (the uniform session's
+        # three, once per sequence); the launches take (N, k) views of it -- a counter per sequence
+        self.ctr32 = torch.zeros((N, 3), dtype=torch.int32, device=dev)
+        self.seen32, self.tsrc32, self.tsrc_done32 = self.ctr32[:, 0:1], self.ctr32[:, 1:2], self.ctr32[:, 2:3]
+        self.crow = torch.zeros((N, 2), dtype=torch.int32, device=dev)
+        self.lengths = list(lengths)                                         # host mirror (bounds checks only)
+        for n, (st, kp, vp) in enumerate(seqs):
+            self._seed_slot(n, st, kp, vp)
+        self._static_buffers(dev, dt, fused_attention)
         if use_graph:
             self._capture()
+        return self
+
+    def _check_sequence(self, state, key_prefix, value_prefix) -> int:
+        """One sequence of a ragged session, validated against the session's shape; returns its length."""
+        if key_prefix.dim() != 4 or key_prefix.shape[0] != 1 or value_prefix.shape != key_prefix.shape:
+            raise ValueError("each sequence is the output of an N = 1 cached forward: key / value prefixes (1, H, L, D)")
+        if not key_prefix.is_cuda:
+            raise ValueError("the prefixes live on the GPU")
+        _, H, L, D = key_prefix.shape
+        if (H, D, key_prefix.dtype, value_prefix.dtype) != (self.H, self.D, self.dtype, self.dtype):
+            raise ValueError(f"every sequence has H = {self.H}, D = {self.D}, {self.dtype} "
+                             f"(got H = {H}, D = {D}, {key_prefix.dtype} / {value_prefix.dtype})")
+        if state is None or state.seq_len != L:
+            raise ValueError("the state must have seen exactly its prefix")
+        ps = state.states.get(PerlinAttentionState.PERFORMER)
+        cs = state.states.get(PerlinAttentionState.CNN)
+        if ps is None or ps.image is None or cs is None or not torch.is_tensor(cs.rows_c8):
+            raise ValueError("the session continues a state written by the HIP estimator (16-bit inference, supported head size)")
+        if cs.rows_c8.shape[0] != 1 or cs.rows_c8.shape[1] != self.LB or cs.rows_c8.shape[2] * 8 != 2 * H:
+            raise ValueError(f"the prefix must be at least the predictor CNN's reach ({self.LB} rows)")
+        nb = self.attention.performer.projection_matrix.shape[0]
+        if ps.image.numel() * 4 != _lib.load().sea_performer_state_bytes(1, H, D, nb, _lib.dtype_code(self.dtype)):
+            raise ValueError("the Performer state image is not one sequence's")
+        if not L < self.capacity:
+            raise ValueError(f"a prefix of {L} rows leaves no room in a capacity of {self.capacity}")
+        return int(L)
+
+    def _seed_slot(self, n, state, key_prefix, value_prefix):
+        """Slot n of a ragged session := the sequence (state, prefixes): its Performer image, rings (slot = position % ring,
+        seeded as a uniform session seeds them), cache rows and counters."""
+        L, LB, at = int(key_prefix.shape[2]), self.LB, self.attention
+        ps = state.states[PerlinAttentionState.PERFORMER]
+        rows = state.states[PerlinAttentionState.CNN].rows_c8
+        conv1 = _cnn_convs(at)[0]
+        dil, RY = conv1.dilation, self.y1_ring.shape[1]
+        self.image.view(self.N, -1)[n].copy_(ps.image.view(-1))
+        pos = torch.arange(L - LB, L, device=rows.device)
+        self.x_ring[n, pos % LB] = rows[0]
+        y1 = ops.causal_conv_c8(rows.contiguous(), conv1.weight, conv1.bias, 3, dil, dil, relu=True)
+        keep_rows = min(RY - 1, LB - 2 * dil)
+        p1 = torch.arange(L - keep_rows, L, device=rows.device)
+        self.y1_ring[n].zero_()
+        self.y1_ring[n, p1 % RY] = y1[0, LB - keep_rows:]
+        self.kv_cache[:, n].zero_()
+        self.k_cache[n, :, :L] = key_prefix[0]
+        self.v_cache[n, :, :L] = value_prefix[0]
+        self.ctr32[n] = torch.tensor([L, L + 1, L + 1], dtype=torch.int32)
+        self.lengths[n] = L
+
+    @torch.no_grad()
+    def admit(self, slot: int, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor):
+        """Continuous batching: slot `slot` of a ragged session starts over on a new sequence (an N = 1 cached forward's
+        state and prefixes), between two steps.  The other slots go on where they were; the captured graph stays (it holds
+        pointers to the session's buffers, whose contents change here), so `captures` does not move."""
+        if not self.ragged:
+            raise ValueError("admit: only a ragged session (DecodeSession.from_sequences) takes new sequences")
+        if not 0 <= slot < self.N:
+            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        self._check_sequence(state, key_prefix, value_prefix)
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        self._seed_slot(slot, state, key_prefix, value_prefix)
 
     @property
     def win(self) -> torch.Tensor:
         """The predictor CNN's input rows of the last LB positions, oldest first, (N, LB, C/8, W, 8): a view of the shifted
         window (round-4 launches) or the ring read out by age (fused CNN launch; a copy)."""
+        if self.ragged:                                            # (each sequence's ring by its own age)
+            dev = self.x_ring.device
+            pos = torch.tensor(self.lengths, device=dev).view(-1, 1) + torch.arange(-self.LB, 0, device=dev).view(1, -1)
+            return self.x_ring[torch.arange(self.N, device=dev).view(-1, 1), pos % self.LB]
         if self.fused_cnn:
             pos = torch.arange(self.length - self.LB, self.length, device=self.x_ring.device)
             return self.x_ring[:, pos % self.LB]
@@ -145,7 +297,7 @@ class DecodeSession:
 
     # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new row
     def _stage(self, q, k, v):
-        ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:2])
+        ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2])
 
     # the (captured) launches of one position; everything position-dependent is read from device memory
     def _launch(self):
@@ -234,23 +386,37 @@ class DecodeSession:
         self._pinned = pins
         self._prep_generation = ops.prep_generation()
 
-    def export_state(self) -> PerlinAttentionState:
+    def export_state(self, slot: Optional[int] = None) -> PerlinAttentionState:
         """The session's state as the `PerlinAttentionState` a cached forward continues from (copies: the session keeps
-        running on its own buffers)."""
+        running on its own buffers).  `slot`: that sequence alone, as an N = 1 state (a ragged session exports one
+        sequence at a time)."""
         from .attention_state import PerformerState, CnnWindowState, CumAvgState
+        if slot is None and self.ragged and self.N > 1:
+            raise ValueError("a ragged session exports one sequence at a time: export_state(slot)")
+        if slot is not None and not 0 <= slot < self.N:
+            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        length = self.lengths[slot or 0] if self.ragged else self.length
+        image, win = self.image, self.win
+        if slot is not None:
+            image, win = image.view(self.N, -1)[slot], win[slot:slot + 1]
         st = PerlinAttentionState(self.attention)
         ps = PerformerState()
-        ps.image, ps.seq_index = self.image.clone(), self.length
+        ps.image, ps.seq_index = image.clone(), length
         cs = CnnWindowState(self.LB)
-        cs.rows_c8 = self.win.clone()
+        cs.rows_c8 = win.clone()
         cav = CumAvgState()
-        cav.prev_len, cav.in_image = self.length, True
+        cav.prev_len, cav.in_image = length, True
         st.states = {PerlinAttentionState.PERFORMER: ps, PerlinAttentionState.CNN: cs, PerlinAttentionState.CUMAVG: cav}
         return st
 
     @torch.no_grad()
     def step(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
-        assert self.length < self.capacity, "cache capacity reached"
+        if self.ragged:
+            full = [n for n, L in enumerate(self.lengths) if L >= self.capacity]
+            if full:
+                raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full}")
+        else:
+            assert self.length < self.capacity, "cache capacity reached"
         if self.graph is not None and ops.prep_generation() != self._prep_generation:
             self.graph = None                                      # (re-captured below, BEFORE this step's stage launch: the capture
             self._capture()                                        #  runs a warm-up step on saved copies of the state)
@@ -264,7 +430,10 @@ class DecodeSession:
                 self.csr._pending = self._col_emit
         else:
             self._launch()
-        self.length += 1
+        if self.ragged:
+            self.lengths = [L + 1 for L in self.lengths]
+        else:
+            self.length += 1
         return self.ctx
 
 

@@ -51,9 +51,15 @@ class FlatCSR:
         # defer_emit=True)` hands such a handle to the fused attention launch, which writes `col` itself; whoever reads
         # `.col` first otherwise runs the emit launch then (same stream: ordered behind the selection)
         self._pending = None
-        # decode handles (csr_from_selection(..., t_src_dev=...)): the device counter the row widths follow; T_src is then the
-        # fixed capacity the column ids are encoded with
+        # decode handles (csr_from_selection(..., t_src_dev=...)): the device counter the row widths follow -- one int32, or an
+        # (N, 1) view with a row per sequence (per-sequence positions: `t_src_stride` > 0); T_src is then the fixed capacity
+        # the column ids are encoded with
         self.t_src_dev = None
+
+    @property
+    def t_src_stride(self) -> int:
+        """0: one sequence length for the batch; else the row stride of the per-sequence counters (`t_src_dev`)."""
+        return self.t_src_dev.stride(0) if self.t_src_dev is not None and self.t_src_dev.dim() == 2 else 0
 
     @property
     def col(self):
@@ -91,7 +97,7 @@ class FlatCSR:
         cut = lambda t: t[n0:n1] if t is not None else None
         sub = FlatCSR(self.crow[n0:n1], self._col[n0:n1], self.head_off[n0:n1], self.H, self.T_src, cut(self.bits), cut(self.row_nnz),
                       cut(self.vals))
-        sub.t_src_dev = self.t_src_dev
+        sub.t_src_dev = self.t_src_dev[n0:n1] if self.t_src_stride else self.t_src_dev
         if self._pending is not None:
             T_m, k, causal, _emit = self._pending
             sub._pending = (T_m, k, causal, lambda: self.col)
@@ -211,7 +217,9 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
     """Row scan + emit: the (bits, row_nnz, head_off) of a selection launch (sea_topk_select or the fused
     sea_predictor_tail_select) -> FlatCSR.  Two launches, no host sync.
     Decode form (`sea_csr_emit` with `t_src_dev`): `t_src_dev` (one int32 on the device) is the sequence length the row widths
-    follow, `T_src` the FIXED capacity the column ids are encoded with (the FlatCSR says T_src = capacity)."""
+    follow, `T_src` the FIXED capacity the column ids are encoded with (the FlatCSR says T_src = capacity).  An (N, 1) view of
+    per-sequence counters gives each batch item its own length (`sea_csr_emit_ragged`); the handle keeps it for a deferred
+    emit."""
     lib = _lib.load()
     N, T_dst = row_nnz.shape
     dev = bits.device
@@ -224,10 +232,17 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
     if z_cap is None:
         z_cap = z_capacity(keep.cpu(), H, T_dst, T_src, T_m, int(k), is_causal)
     col = torch.empty((N, z_cap), dtype=torch.int32, device=dev)
+    t_stride = 0
     if t_src_dev is not None:
-        assert t_src_dev.dtype == torch.int32 and t_src_dev.numel() == 1 and t_src_dev.is_cuda
+        t_stride = _lib.counter_stride(t_src_dev, N)
+        assert t_stride > 0 or t_src_dev.numel() == 1
     def emit():
         with torch.cuda.device(dev):
+            if t_stride > 0:
+                _lib.check(lib.sea_csr_emit_ragged(
+                    _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
+                    _p(col), 4, col.stride(0), z_cap, _p(t_src_dev), t_stride, _lib.stream_ptr()), "sea_csr_emit_ragged")
+                return
             _lib.check(lib.sea_csr_emit(
                 _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
                 _p(col), 4, col.stride(0), z_cap, None, _p(t_src_dev), _lib.stream_ptr()), "sea_csr_emit")
@@ -457,6 +472,14 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         assert plan.dtype == torch.uint8 and plan.numel() == ((nb_ + 3) & ~3) + 4 and plan.is_contiguous()
 
     def launch(col, probs, block_path, flags, bits=None, T_m=0, is_causal=0, max_k=0, write_cols=1, t_src_dev=None):
+        if t_src_dev is not None and csr.t_src_stride:      # per-sequence lengths (the decode form only)
+            return lib.sea_sparse_attention_ragged(
+                _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
+                _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
+                _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
+                _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
+                _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
+                _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), csr.t_src_stride, _lib.stream_ptr())
         return lib.sea_sparse_attention(
             _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
             _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),

@@ -431,7 +431,8 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     or None, state_out = the image at the last chunk boundary <= t_base + T_new; a new tensor, the input is kept).
     Decode form (`sea_performer_causal_step` with `t_base_dev`, a step replayed as a HIP graph): `t_base_dev` is a one-element int32
     device tensor holding the rows seen so far, k / v the fixed-capacity caches (already holding the new row), and
-    `state_in` is updated in place."""
+    `state_in` is updated in place.  An (N, 1) view of a per-sequence counter block gives each sequence its own position
+    (`sea_performer_causal_step_ragged`; sequence n's state image is the n-th contiguous slice of `state_in`)."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, pos, projection)
     N, H, T, D = q.shape
@@ -447,7 +448,8 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     sb = int(lib.sea_performer_state_bytes(N, H, D, nb, _lib.dtype_code(q.dtype)))
     assert sb > 0, "unsupported head size / feature count"
     if t_base_dev is not None:
-        assert t_base_dev.dtype == torch.int32 and t_base_dev.numel() == 1 and t_base_dev.is_cuda
+        t_stride = _lib.counter_stride(t_base_dev, N)
+        assert t_stride > 0 or t_base_dev.numel() == 1
         assert state_in is not None and t_base == 0 and n_segments == 1
         kc, vc, pc = k, v, pos                                   # cache / table bases: the kernel finds the boundary
         assert pos.shape[0] >= k.shape[2]
@@ -472,6 +474,12 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     if n_segments > 1:
         ws_bytes = N * H * (n_segments - 1) * lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(q.dtype))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
+    if t_base_dev is not None and t_stride > 0:
+        _lib.check(lib.sea_performer_causal_step_ragged(
+            _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
+            _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, _p(t_base_dev), t_stride,
+            _lib.stream_ptr()), "sea_performer_causal_step_ragged")
+        return out, avg, state_out
     _lib.check(lib.sea_performer_causal_step(
         _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
         _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, int(t_base), _p(t_base_dev),
@@ -663,19 +671,26 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
                  counters: torch.Tensor) -> None:
     """`sea_decode_stage`: the new rows of a decoding step, (N,H,1,D) each (any [n,h] strides), into the session's static
     buffers -- q into q_in (N,H,1,D), k / v into kv_cache (2,N,H,capacity,D) at the row the device counters name
-    (int32 [seen, tsrc]: row = counters[0])."""
+    (int32 [seen, tsrc]: row = counters[0]).  An (N, >= 1) view of a per-sequence counter block writes sequence n's rows at
+    counters[n, 0] (`sea_decode_stage_ragged`)."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, q_in, kv_cache, counters)
     N, H, one, D = q.shape
     assert one == 1 and k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
     assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, 1, D) and kv_cache.is_contiguous() and kv_cache.shape[:3] == (2, N, H)
-    assert counters.dtype == torch.int32 and counters.numel() == 2 and counters.is_contiguous()
+    stride = _lib.counter_stride(counters, N) if counters.dim() == 2 else 0      # (an (N, k) view: a counter per sequence)
+    assert stride > 0 or (counters.dtype == torch.int32 and counters.numel() == 2 and counters.is_contiguous())
     # the kernel moves whole 16-byte vectors: rows contiguous along D, [n, h] strides in multiples of 8 elements, 16-byte aligned
     # base.  Anything else (e.g. rows sliced out of a fused qkv buffer at an odd offset) is repacked here -- the session used
     # to take any layout through `.copy_` (ADVICE r4)
     ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
     q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
     st = lambda t: (ctypes_i64 * 2)(t.stride(0), t.stride(1))
+    if stride > 0:
+        _lib.check(lib.sea_decode_stage_ragged(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v),
+                                               _p(q_in), _p(kv_cache), kv_cache.shape[3], _p(counters), stride, _lib.stream_ptr()),
+                   "sea_decode_stage_ragged")
+        return
     _lib.check(lib.sea_decode_stage(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v), _p(q_in),
                                     _p(kv_cache), kv_cache.shape[3], _p(counters), _lib.stream_ptr()), "sea_decode_stage")
 
@@ -699,8 +714,9 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     """One launch for a decoding step's predictor CNN (two 3 x 3 dilated causal convolutions, one new row each), tail,
     selection and the advance of the session's device counters (`sea_decode_cnn_tail_select`).  `conv1` / `conv2` are the
     `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  `col_out` (N, z_cap) int32 with `T_cap` (C <=
-    64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.  Returns (probs or None, (bits,
-    row_nnz, head_off))."""
+    64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.  `counters` (3,) is the batch's
+    one triple; an (N, 3) block holds one per sequence (`sea_decode_cnn_tail_select_ragged`: each workgroup reads its own
+    sequence's, the launch advances all of them).  Returns (probs or None, (bits, row_nnz, head_off))."""
     lib = _lib.load()
     _lib.require_gpu(x_new, x_ring, y1_ring, y2, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket, crow_out)
     N, C8, W4, _e = x_new.shape[0], x_new.shape[-3], x_new.shape[-2], x_new.shape[-1]
@@ -710,7 +726,9 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     assert decode_cnn_supported(C, H, T_m, dt) and W4 * 4 == T_m
     for cv in (conv1, conv2):
         assert cv.kernel_size == 3 and cv.in_channels == C and cv.out_channels == C and cv.padding[1] == cv.dilation == conv1.dilation
-    assert counters.dtype == torch.int32 and counters.numel() == 3 and ticket.dtype == torch.int32 and ticket.numel() == 1
+    stride = _lib.counter_stride(counters, N)
+    assert (counters.numel() == 3 or stride > 0) and counters.shape[-1] == 3 and counters.is_contiguous()
+    assert ticket.dtype == torch.int32 and ticket.numel() == 1
     assert keep.dtype == torch.int32 and keep.ndim == 1 and crow_out.dtype == torch.int32 and tuple(crow_out.shape) == (N, 2)
     packs = []
     for cv in (conv1, conv2):
@@ -725,12 +743,15 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     bits = torch.empty((N, 1, Wb), dtype=torch.int32, device=dev)
     row_nnz = torch.empty((N, 1), dtype=torch.int32, device=dev)
     head_off = torch.empty((N, 1, H + 1), dtype=torch.int32, device=dev)
-    _lib.check(lib.sea_decode_cnn_tail_select(
-        _p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _lib.dtype_code(dt), N, C, H, W4, x_ring.shape[1], y1_ring.shape[1],
-        _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp, _p(g), _p(b),
-        float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
-        _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
-        int(T_cap), _p(tab), _lib.stream_ptr()), "sea_decode_cnn_tail_select")
+    args = (_p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _lib.dtype_code(dt), N, C, H, W4, x_ring.shape[1], y1_ring.shape[1],
+            _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp, _p(g), _p(b),
+            float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
+            _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
+            int(T_cap), _p(tab))
+    if stride > 0:
+        _lib.check(lib.sea_decode_cnn_tail_select_ragged(*args, stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select_ragged")
+    else:
+        _lib.check(lib.sea_decode_cnn_tail_select(*args, _lib.stream_ptr()), "sea_decode_cnn_tail_select")
     return probs, (bits, row_nnz, head_off)
 
 
