@@ -42,7 +42,9 @@ extern "C" {
  *      sea_predictor_tail, sea_predictor_tail_select, sea_csr_emit, sea_causal_conv_c8, sea_performer_causal and
  *      sea_performer_causal_step are gone; each of these takes the variants' arguments instead (NULL / 0 / 1 = not wanted)
  *      Later, additive (no bump): the *_ragged entries of the decode step (per-sequence positions: sea_decode_stage,
- *      sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention, sea_csr_emit)
+ *      sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention, sea_csr_emit); then the *_paged
+ *      entries (K / V in a pool of pages with a block table per sequence: sea_decode_stage, sea_performer_causal_step,
+ *      sea_sparse_attention)
  *      */
 #define SEA_ABI_VERSION 4
 
@@ -268,6 +270,25 @@ int sea_sparse_attention_ragged(const void* q, const void* k, const void* v, int
                                 const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
                                 const int32_t* t_src_dev, int64_t t_src_stride,
                                 sea_stream_t stream);
+/* Paged K / V, the one-row decode form of sea_sparse_attention_ragged (T_dst = 1, 16-bit data, D in {64, 80, 128},
+ * T_m <= 256; bits and t_src_dev required).  k / v are the K / V halves of a page pool (P, H, page_rows, D) with element
+ * strides [page, head, row]; sequence n's key r lives in page block_table[n * table_stride + r / page_rows] (int32, on the
+ * device) at row r % page_rows.  Keys and column ids stay logical: ids are head * T_cap + key as in the contiguous form, and the
+ * context rows are bitwise that form's.  page_rows: a power of two and a multiple of the Performer chunk of D
+ * (sea_performer_chunk_rows); table_stride >= ceil(T_cap / page_rows), at most 4096 pages per table row; the page stride must
+ * stay below 4 GB and a page below 2 GB.  Null pointers, a bad page size or table stride: SEA_EINVAL; other dtypes / D /
+ * shapes: SEA_EUNSUPPORTED. */
+int sea_sparse_attention_paged(const void* q, const void* k, const void* v, int dtype,
+                               int64_t N, int64_t H, int64_t T_dst, int64_t T_cap, int64_t D,
+                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                               const int32_t* crow, const int32_t* col, int64_t col_stride_n,
+                               const int32_t* head_off,
+                               const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
+                               void* out, int out_dtype, const int64_t* out_strides,
+                               const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                               const int32_t* t_src_dev, int64_t t_src_stride,
+                               const int32_t* block_table, int64_t table_stride, int64_t page_rows,
+                               sea_stream_t stream);
 int64_t sea_attention_few_rows(void);
 
 /* Backward of the fused operator WITHOUT its epilogue (o = sum_e softmax_e(q.k_e) v_e; the caller applies row scale and mix
@@ -569,6 +590,18 @@ int sea_performer_causal_step_ragged(const void* q, const void* k, const void* v
                                      int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
                                      int64_t state_bytes, const int32_t* t_base_dev, int64_t t_base_stride,
                                      sea_stream_t stream);
+/* Paged K / V, one new row per sequence (T = 1): k / v are the K / V halves of a page pool (P, H, page_rows, D), strides
+ * [page, head, row].  Sequence n's open chunk c0 .. seen (c0 = floor(seen / C) * C) lies in page
+ * block_table[n * table_stride + c0 / page_rows] from row c0 % page_rows on: page_rows is a power of two and a multiple of C,
+ * so one table lookup per workgroup serves the step.  capacity: the logical rows a table row covers (table_stride >=
+ * ceil(capacity / page_rows)).  Everything else as in sea_performer_causal_step_ragged, bitwise. */
+int sea_performer_causal_step_paged(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                    const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                    const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                    int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
+                                    int64_t state_bytes, const int32_t* t_base_dev, int64_t t_base_stride,
+                                    const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t capacity,
+                                    sea_stream_t stream);
 
 /* ---- decode step with the position in DEVICE memory ------------------------------------------------------------------
  * The reference's generation loop (src/main/opt_generate.py:131 -> attention.py use_cache branches + attention_state.py)
@@ -599,6 +632,15 @@ int sea_decode_stage_ragged(const void* q, const void* k, const void* v, int dty
                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                             void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
                             sea_stream_t stream);
+/* sea_decode_stage_ragged into a page pool kv_pool (2, pool_pages, H, page_rows, D) dense (K pages, then V pages: one page
+ * index for both): sequence n's k / v rows go to page block_table[n * table_stride + ctr / page_rows], row ctr % page_rows
+ * (ctr = counters[n * counter_stride]).  A row at or beyond `capacity`, or whose table entry is outside 0 .. pool_pages-1,
+ * writes nothing.  Page rule and refusals as for sea_sparse_attention_paged. */
+int sea_decode_stage_paged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                           void* q_in, void* kv_pool, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                           const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                           sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
 
 #ifdef __cplusplus

@@ -39,6 +39,9 @@ _SIGNATURES = {
     "sea_sparse_attention_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
                                      ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p,
                                      ptr, i64, c_int, c_int, c_int, ptr, i64, ptr], c_int),
+    "sea_sparse_attention_paged": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
+                                    ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p,
+                                    ptr, i64, c_int, c_int, c_int, ptr, i64, ptr, i64, i64, ptr], c_int),
     "sea_sparse_attention_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
                                   ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_sparse_attention_bwd_workspace_bytes": ([i64, i64, i64, i64], i64),
@@ -75,8 +78,12 @@ _SIGNATURES = {
                                    ptr, ptr, i64, i64, ptr, i64, ptr, i64, ptr], c_int),
     "sea_performer_causal_step_ragged": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
                                           ptr, ptr, ptr, ptr, i64, ptr, i64, ptr], c_int),
+    "sea_performer_causal_step_paged": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
+                                         ptr, ptr, ptr, ptr, i64, ptr, i64, ptr, i64, i64, i64, ptr], c_int),
     "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, ptr], c_int),
     "sea_decode_stage_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr], c_int),
+    "sea_decode_stage_paged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64,
+                                i64, ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),
     "sea_performer_plan": ([i64, i64, i64, i64, i64, c_int, _i64p, _i64p], c_int),

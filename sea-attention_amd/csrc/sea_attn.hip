@@ -647,7 +647,10 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
 }
 
 // X80: d = 80 on 8 lanes per row -- lane j holds elements 8j .. 8j+7 plus the pair 64+2j, 65+2j (sparse_attn_rows80_kernel's map)
-template <typename T, typename TO, int LPR, bool X80 = false>
+// PAGED: K / V in a page pool (AttnParams::table).  The sequence's block-table row is staged in LDS behind the V rows at kernel
+// start (its first ceil(T_src / page_rows) entries; dynamic LDS sized for the capacity's), and phase C translates each key to
+// (page, row) from there: the page term is a 64-bit product (page x page bytes overflows 32 bits), the row term stays 32-bit
+template <typename T, typename TO, int LPR, bool X80 = false, bool PAGED = false>
 __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) {
   constexpr int VEC = Elem<T>::VEC, NT = 256, NG = NT / LPR, XT = X80 ? 2 : 0, DL = LPR * (VEC + XT);
   static_assert(!X80 || LPR == 8, "d = 80: eight lanes per row");
@@ -666,9 +669,15 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
   const int n = (int)blockIdx.x / p.H, h = (int)blockIdx.x - n * p.H;
   const bool dact = X80 || sub * VEC < p.D;
   const int sube = dact ? sub : 0;
-  const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1]);
-  const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1]);
+  const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + (PAGED ? 0 : n * p.ks[0]) + h * p.ks[1]);
+  const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + (PAGED ? 0 : n * p.vs[0]) + h * p.vs[1]);
   const uint32_t kst = (uint32_t)p.ks[2] * (uint32_t)sizeof(T), vst = (uint32_t)p.vs[2] * (uint32_t)sizeof(T);
+  int* s_tab = reinterpret_cast<int*>(s_v + (size_t)CH * DL);          // PAGED: [ceil(T_src / page_rows)] the table row
+  if constexpr (PAGED) {
+    const int npg = (p.t_src_dev[n * p.t_src_stride] + (1 << p.page_shift) - 1) >> p.page_shift;   // pages holding keys
+    const int32_t* trow = p.table + (int64_t)n * p.table_stride;
+    for (int i = tid; i < npg; i += NT) s_tab[i] = trow[i];            // (read after phase B's barrier)
+  }
   const uint32_t lane_off = (uint32_t)(sube * VEC) * (uint32_t)sizeof(T);
   uint4 qraw = make_uint4(0, 0, 0, 0);
   if (dact) qraw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + sub * VEC);
@@ -734,12 +743,22 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
       for (int i = 0; i < EPG; ++i) {
         const int e = grp + i * NG;
         const uint32_t key_c = (uint32_t)s_keys[e < nent ? e : 0];
-        const uint32_t ko = __umul24(key_c, kst), vo = __umul24(key_c, vst);
-        kr[i] = *reinterpret_cast<const uint4*>(kbase + (ko + lane_off));
-        vr[i] = *reinterpret_cast<const uint4*>(vbase + (vo + lane_off));
+        const char* kb = kbase;
+        const char* vb = vbase;
+        uint32_t ko, vo;
+        if constexpr (PAGED) {
+          const uint32_t pg = (uint32_t)s_tab[key_c >> p.page_shift], row = key_c & ((1u << p.page_shift) - 1u);
+          kb += (uint64_t)pg * (uint32_t)p.ks[0] * sizeof(T);
+          vb += (uint64_t)pg * (uint32_t)p.vs[0] * sizeof(T);
+          ko = __umul24(row, kst); vo = __umul24(row, vst);
+        } else {
+          ko = __umul24(key_c, kst); vo = __umul24(key_c, vst);
+        }
+        kr[i] = *reinterpret_cast<const uint4*>(kb + (ko + lane_off));
+        vr[i] = *reinterpret_cast<const uint4*>(vb + (vo + lane_off));
         if constexpr (X80) {
-          kx[i] = *reinterpret_cast<const uint32_t*>(kbase + (ko + off_x));
-          vx[i] = *reinterpret_cast<const uint32_t*>(vbase + (vo + off_x));
+          kx[i] = *reinterpret_cast<const uint32_t*>(kb + (ko + off_x));
+          vx[i] = *reinterpret_cast<const uint32_t*>(vb + (vo + off_x));
         }
       }
 #pragma unroll
@@ -968,6 +987,20 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
   if constexpr (sizeof(T) == 2 && !WP) {
     // one new row per sequence (a DecodeSession position): the whole workgroup serves the row (sparse_attn_decode1_kernel)
     if (p.bits && p.t_src_dev && p.T_dst == 1 && p.T_m <= 256 && small && (lpr == 8 || lpr == 16 || p.D == 80)) {
+      if (p.table) {                                       // paged K / V: the PAGED forms, the table row behind the V rows
+        const int tab = (int)((p.T_src + (1 << p.page_shift) - 1) >> p.page_shift) * (int)sizeof(int);
+        if (p.D == 80) {
+          constexpr int CH = 256, DL = 80;
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+        } else if (lpr == 8) {
+          constexpr int CH = 256, DL = 64;
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+        } else {
+          constexpr int CH = 128, DL = 128;
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+        }
+        return SEA_OK;
+      }
       if (p.D == 80) {
         constexpr int CH = 256, DL = 80;
         hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
@@ -981,6 +1014,7 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
       return SEA_OK;
     }
   }
+  if (p.table) return SEA_EUNSUPPORTED;                    // (only the one-row decode kernel reads a page pool)
   if constexpr (sizeof(T) == 2) {
     if (p.D == 80 && small) {                          // d = 80: 8 lanes x (8 + 2) elements per row
       const int rpb = 8 * 8;                               // 8 waves x 8 rows, sorted by length
@@ -1095,7 +1129,8 @@ static int sparse_attention_entry(const char* nm, const void* q, const void* k, 
                                   const float* mix, void* out, int out_dtype, const int64_t* out_strides,
                                   float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
                                   const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                  const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream) {
+                                  const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream,
+                                  const int32_t* table = nullptr, int64_t table_stride = 0, int page_shift = 0) {
   // bits != NULL: the fused form -- `col` is written by the launch, not read -- which runs on the gather kernels;
   // t_src_dev != NULL: its decode form (T_src is then the capacity of the K / V caches)
   SEA_REQUIRE(bits != nullptr || t_src_dev == nullptr, SEA_EINVAL, "%s: the decode form (t_src_dev) needs bits", nm);
@@ -1142,6 +1177,7 @@ static int sparse_attention_entry(const char* nm, const void* q, const void* k, 
   SEA_REQUIRE(t_src_stride >= 0 && t_src_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad T_src stride %lld", nm,
               (long long)t_src_stride);
   p.t_src_stride = (int)t_src_stride;
+  p.table = table; p.table_stride = (int)table_stride; p.page_shift = page_shift;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && probs_out == nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
                 "%s: the decode form takes T_dst <= %d rows per sequence, no probs_out", nm, SEA_ATTN_WARM_ROWS);
@@ -1214,6 +1250,38 @@ extern "C" int sea_sparse_attention_ragged(const void* q, const void* k, const v
   return sparse_attention_entry(nm, q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides, crow, col,
                                 col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr, 0,
                                 nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_cols, t_src_dev, t_src_stride, stream);
+}
+
+// paged K / V (the one-row decode form only): k / v are the K / V halves of a page pool, strides [page, head, row]; sequence n's
+// key r lives in page block_table[n * table_stride + r / page_rows] at row r % page_rows.  Column ids stay head * T_cap + key.
+extern "C" int sea_sparse_attention_paged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                          int64_t T_dst, int64_t T_cap, int64_t D, const int64_t* q_strides,
+                                          const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                          const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                          const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                          const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                          const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                          const int32_t* t_src_dev, int64_t t_src_stride, const int32_t* block_table,
+                                          int64_t table_stride, int64_t page_rows, sea_stream_t stream) {
+  const char* nm = "sea_sparse_attention_paged";
+  SEA_REQUIRE(bits && t_src_dev && block_table && k_strides && v_strides, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  if (int e = paged_layout_check(nm, dtype, D, T_cap, page_rows, table_stride, N)) return e;
+  SEA_REQUIRE(T_dst == 1 && T_m > 0 && T_m <= 256, SEA_EUNSUPPORTED, "%s: the one-row decode form (T_dst = 1, T_m <= 256)", nm);
+  SEA_REQUIRE((T_cap + page_rows - 1) / page_rows <= 4096, SEA_EUNSUPPORTED,
+              "%s: a table row of %lld pages does not fit the kernel's LDS (4096 at most)", nm, (long long)((T_cap + page_rows - 1) / page_rows));
+  // byte offsets: the page term is 64-bit (a page index times the page stride, which must fit 32 bits), the row term 32-bit
+  // (24-bit factors: __umul24 of the row and the row stride)
+  const int64_t esz = 2;
+  SEA_REQUIRE(k_strides[0] > 0 && v_strides[0] > 0 && k_strides[0] * esz < (1ll << 32) && v_strides[0] * esz < (1ll << 32) &&
+                  k_strides[2] * esz < (1ll << 24) && v_strides[2] * esz < (1ll << 24) &&
+                  page_rows * k_strides[2] * esz < (1ll << 31) && page_rows * v_strides[2] * esz < (1ll << 31),
+              SEA_EUNSUPPORTED, "%s: page / row strides whose byte offsets do not fit (page stride < 4 GB, page < 2 GB)", nm);
+  return sparse_attention_entry(nm, q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides, crow, col,
+                                col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr, 0,
+                                nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_cols, t_src_dev, t_src_stride, stream,
+                                block_table, table_stride, __builtin_ctzll(page_rows));
 }
 
 extern "C" int64_t sea_attention_few_rows(void) { return SEA_ATTN_FEW_ROWS; }

@@ -53,6 +53,25 @@ struct DevOnce {
     }                                                                                                                \
   } while (0)
 
+// ---- paged K / V (the *_paged decode entries) ------------------------------------------------
+// page_rows is a power of two and a multiple of the Performer chunk C of the head size (sea_performer_chunk_rows: 64 at
+// d = 64, 32 at d = 80 / 128), so the rows a chunk-aligned step reads -- the open chunk and the new row -- lie in one page.
+// A sequence's table row covers its capacity: table_stride >= ceil(capacity / page_rows).
+inline int paged_layout_check(const char* nm, int dtype, int64_t D, int64_t capacity, int64_t page_rows, int64_t table_stride,
+                              int64_t N) {
+  const int64_t C = sea_performer_chunk_rows(D, 1, dtype);
+  SEA_REQUIRE(C > 0, SEA_EUNSUPPORTED, "%s: paged K / V needs 16-bit data with D in {64, 80, 128} (dtype %d, D=%lld)", nm, dtype,
+              (long long)D);
+  SEA_REQUIRE(page_rows > 0 && (page_rows & (page_rows - 1)) == 0 && page_rows % C == 0 && page_rows < (1ll << 24), SEA_EINVAL,
+              "%s: page_rows %lld must be a power of two and a multiple of the Performer chunk (%lld rows)", nm,
+              (long long)page_rows, (long long)C);
+  SEA_REQUIRE(capacity > 0 && capacity < (1ll << 24), SEA_EINVAL, "%s: bad capacity %lld", nm, (long long)capacity);
+  SEA_REQUIRE(table_stride >= (capacity + page_rows - 1) / page_rows && table_stride * N < (1ll << 31), SEA_EINVAL,
+              "%s: table_stride %lld is below the %lld pages of a capacity of %lld rows", nm, (long long)table_stride,
+              (long long)((capacity + page_rows - 1) / page_rows), (long long)capacity);
+  return SEA_OK;
+}
+
 // ---- element access ------------------------------------------------------------------------
 template <typename T> struct Elem;
 template <> struct Elem<float> {

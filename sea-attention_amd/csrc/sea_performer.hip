@@ -74,6 +74,11 @@ struct PerfParams {
   // bitwise the stateless result for any split of the sequence into calls.  k / v / pos then point at row c0 (with
   // t_base_dev: at row 0 of the caches / the table, the kernel adds c0); q / out / avg at the first new row.
   int aligned;
+  // paged K / V (sea_performer_causal_step_paged, the PAGED instantiations of the SEQ forms): k / v are the K / V halves of a
+  // page pool, strides [page, head, row]; sequence n's chunk c0 lives in page table[n * table_stride + c0 / page_rows] at row
+  // c0 % page_rows (page_rows = 1 << page_shift, a multiple of C: the open chunk and the new row lie in that one page)
+  const int32_t* table;
+  int table_stride, page_shift;
 };
 
 typedef __attribute__((ext_vector_type(8))) __bf16 pbf8;
@@ -435,7 +440,7 @@ __device__ inline uint2 lds_tr(const unsigned short* p) {      // ds_read_b64_tr
   return __builtin_bit_cast(uint2, v);
 }
 
-template <typename T, int NBT, bool STATE_ONLY, bool SEQ = false>
+template <typename T, int NBT, bool STATE_ONLY, bool SEQ = false, bool PAGED = false>
 __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   constexpr int D = 64, C = 64, NW = 8, NTH = 512, E = 2 * D;
   constexpr int NBP = NBT * 16;
@@ -484,9 +489,15 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   const int TL = p.T + lead;                               // local rows of this call
   const int t_begin = seg * p.seg_len, t_end = min(TL, t_begin + p.seg_len);
   const T* qb = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] - (int64_t)lead * p.qs[2];   // rows < lead are never read
-  const int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;      // k / v given as cache bases: start at the boundary
-  const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
-  const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
+  int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;            // k / v given as cache bases: start at the boundary
+  int64_t kv_n = n;
+  if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
+    static_assert(SEQ, "the paged step has a position per sequence");
+    kv_n = p.table[(int64_t)n * p.table_stride + (row_base >> p.page_shift)];
+    cache_row = row_base & ((1 << p.page_shift) - 1);
+  }
+  const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
+  const T* vb = reinterpret_cast<const T*>(p.v) + kv_n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
   const T* pb = reinterpret_cast<const T*>(p.pos) + (p.t_base_dev ? (int64_t)row_base * p.pos_stride : 0);
   T* ob = reinterpret_cast<T*>(p.out) + (int64_t)nh * p.T * (3 * D) - (int64_t)lead * (3 * D);           // rows < lead are never stored
   const float cnorm = powf((float)D, -0.25f);
@@ -958,7 +969,7 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
 // reads, the cumulative average on the matrix cores, segments, state images, and (round 4) the chunk walk pipelined over
 // three barriers with two sets of phi images and results stored straight from the accumulators -- is the D = 64 kernel's.
 // The 25 KB of result tiles the first version flushed one chunk later paid for the second image set (d = 128: 120 KB).
-template <typename T, int D, int C, int NBT, bool STATE_ONLY, bool SEQ = false>
+template <typename T, int D, int C, int NBT, bool STATE_ONLY, bool SEQ = false, bool PAGED = false>
 __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   constexpr int NW = 8, NTH = 512, E = 2 * D, CPR = D / 8;
   constexpr int DP = (D + 31) / 32 * 32, KC = DP / 8;    // head dimension padded to whole k-steps, its 8-element chunks
@@ -1008,9 +1019,15 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   const int TL = p.T + lead;                               // local rows of this call
   const int t_begin = seg * p.seg_len, t_end = min(TL, t_begin + p.seg_len);
   const T* qb = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] - (int64_t)lead * p.qs[2];   // rows < lead are never read
-  const int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;      // k / v given as cache bases: start at the boundary
-  const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
-  const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
+  int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;            // k / v given as cache bases: start at the boundary
+  int64_t kv_n = n;
+  if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
+    static_assert(SEQ, "the paged step has a position per sequence");
+    kv_n = p.table[(int64_t)n * p.table_stride + (row_base >> p.page_shift)];
+    cache_row = row_base & ((1 << p.page_shift) - 1);
+  }
+  const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
+  const T* vb = reinterpret_cast<const T*>(p.v) + kv_n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
   const T* pb = reinterpret_cast<const T*>(p.pos) + (p.t_base_dev ? (int64_t)row_base * p.pos_stride : 0);
   T* ob = reinterpret_cast<T*>(p.out) + (int64_t)nh * p.T * (3 * D) - (int64_t)lead * (3 * D);           // rows < lead are never stored
   const float cnorm = powf((float)D, -0.25f);
@@ -1707,8 +1724,10 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
 using namespace sea;
 
 // Both passes of one kernel form: pass 1 (STATE_ONLY) on the first nseg-1 segments, pass 2 on all nseg (see PerfParams).
-// Every form runs 512-thread workgroups.  SEQ_PASS: OUT_PASS with a position per sequence (t_base_stride > 0, one segment).
-template <void (*STATE_PASS)(PerfParams), void (*OUT_PASS)(PerfParams), void (*SEQ_PASS)(PerfParams), int C, size_t LDS>
+// Every form runs 512-thread workgroups.  SEQ_PASS: OUT_PASS with a position per sequence (t_base_stride > 0, one segment);
+// PAGED_PASS: SEQ_PASS over a page pool (p.table; null: the form has none).
+template <void (*STATE_PASS)(PerfParams), void (*OUT_PASS)(PerfParams), void (*SEQ_PASS)(PerfParams),
+          void (*PAGED_PASS)(PerfParams), int C, size_t LDS>
 static int launch_perf(const PerfParams& p, hipStream_t s) {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static DevOnce once;              // one per template instantiation and device; the attribute call is a slow driver round trip
@@ -1716,8 +1735,17 @@ static int launch_perf(const PerfParams& p, hipStream_t s) {
     SEA_MAX_LDS(STATE_PASS, LDS);
     SEA_MAX_LDS(OUT_PASS, LDS);
     SEA_MAX_LDS(SEQ_PASS, LDS);
+    if constexpr (PAGED_PASS != nullptr) SEA_MAX_LDS(PAGED_PASS, LDS);
   }
   if (p.seg_len % C != 0) return SEA_EINVAL;
+  if (p.table) {
+    if constexpr (PAGED_PASS == nullptr) return SEA_EUNSUPPORTED;
+    else {
+      if (p.nseg != 1 || p.t_base_stride <= 0) return SEA_EINVAL;
+      hipLaunchKernelGGL(PAGED_PASS, dim3((unsigned)(p.N * p.H)), dim3(512), LDS, s, p);
+      return SEA_OK;
+    }
+  }
   if (p.t_base_stride > 0) {
     if (p.nseg != 1) return SEA_EINVAL;
     hipLaunchKernelGGL(SEQ_PASS, dim3((unsigned)(p.N * p.H)), dim3(512), LDS, s, p);
@@ -1748,8 +1776,8 @@ template <int D, int NBT>
 constexpr int64_t perf_carry_floats() { return (int64_t)(((2 * D / 16) + 7) / 8) * NBT * 4 * 512 + NBT * 16; }
 template <int D, int NBT, int C>
 static PerfForm perf_f32_form() {
-  return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, performer_kernel<D, NBT, C, false>, C,
-                      perf_lds<D, NBT, C>()>, C,
+  return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, performer_kernel<D, NBT, C, false>,
+                      nullptr, C, perf_lds<D, NBT, C>()>, C,
           perf_carry_floats<D, NBT>(), false};
 }
 
@@ -1767,7 +1795,8 @@ template <typename T, int NBT>
 static PerfForm perf_bf16_form() {
   static_assert(perf_bf16_lds<NBT>() > 64 * 1024, "the attribute is set above 64 KB");
   return {launch_perf<performer_bf16_kernel<T, NBT, true>, performer_bf16_kernel<T, NBT, false>,
-                      performer_bf16_kernel<T, NBT, false, true>, 64, perf_bf16_lds<NBT>()>, 64,
+                      performer_bf16_kernel<T, NBT, false, true>, performer_bf16_kernel<T, NBT, false, true, true>, 64,
+                      perf_bf16_lds<NBT>()>, 64,
           perf_bf16_carry_floats<NBT>(), true};
 }
 
@@ -1786,8 +1815,8 @@ template <typename T, int D, int NBT>
 static PerfForm perf_bf16w_form() {
   static_assert(perf_bf16w_lds<D, 32, NBT>() > 64 * 1024, "the attribute is set above 64 KB");
   return {launch_perf<performer_bf16w_kernel<T, D, 32, NBT, true>, performer_bf16w_kernel<T, D, 32, NBT, false>,
-                      performer_bf16w_kernel<T, D, 32, NBT, false, true>, 32,
-                      perf_bf16w_lds<D, 32, NBT>()>, 32, perf_bf16w_carry_floats<D, NBT>(), true};
+                      performer_bf16w_kernel<T, D, 32, NBT, false, true>, performer_bf16w_kernel<T, D, 32, NBT, false, true, true>,
+                      32, perf_bf16w_lds<D, 32, NBT>()>, 32, perf_bf16w_carry_floats<D, NBT>(), true};
 }
 
 template <typename T>
@@ -1871,7 +1900,7 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
                       int64_t pos_stride, void* out, void* avg_out, int64_t n_segments, void* workspace,
                       int64_t workspace_bytes, const void* state_in, void* state_out, int64_t state_bytes, int64_t t_base,
                       const int32_t* t_base_dev, int64_t t_base_stride, int aligned,
-                      sea_stream_t stream) {
+                      const int32_t* table, int64_t table_stride, int page_shift, sea_stream_t stream) {
   SEA_REQUIRE(q && k && v && pos && proj && out && q_strides && k_strides && v_strides, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_F16 || dtype == SEA_BF16, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
   SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0 && nb > 0, SEA_EINVAL, "%s: bad shape", nm);
@@ -1907,6 +1936,7 @@ static int perf_entry(const char* nm, const void* q, const void* k, const void* 
   SEA_REQUIRE(t_base_stride >= 0 && t_base_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad position stride %lld", nm,
               (long long)t_base_stride);
   p.t_base_stride = (int)t_base_stride;
+  p.table = table; p.table_stride = (int)table_stride; p.page_shift = page_shift;
   if (state_in || state_out) {
     const int64_t need = N * H * form.carry_floats * (int64_t)sizeof(float);
     SEA_REQUIRE(need > 0 && state_bytes >= need && ((((uintptr_t)state_in) | ((uintptr_t)state_out)) & 15) == 0 && t_base >= 0,
@@ -1934,7 +1964,8 @@ extern "C" int sea_performer_causal(const void* q, const void* k, const void* v,
                                     int64_t pos_stride, void* out, void* avg_out, int64_t n_segments,
                                     void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
   return perf_entry("sea_performer_causal", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides,
-                    v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, 0, 0, stream);
+                    v_strides, pos_stride, out, avg_out, n_segments, workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, 0, 0,
+                    nullptr, 0, 0, stream);
 }
 
 extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype) {
@@ -1959,7 +1990,7 @@ static int perf_step_entry(const char* nm, const void* q, const void* k, const v
                            int64_t pos_stride, void* out, void* avg_out, const void* state_in,
                            void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
                            int64_t t_base_stride, int64_t n_segments, void* workspace, int64_t workspace_bytes,
-                           sea_stream_t stream) {
+                           sea_stream_t stream, const int32_t* table = nullptr, int64_t table_stride = 0, int page_shift = 0) {
   if (t_base_dev) {
     SEA_REQUIRE(state_in && state_out, SEA_EINVAL, "%s: null pointer", nm);
     SEA_REQUIRE(n_segments == 1, SEA_EUNSUPPORTED, "%s: the device-position step runs one segment", nm);
@@ -1967,7 +1998,7 @@ static int perf_step_entry(const char* nm, const void* q, const void* k, const v
   }
   return perf_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
                     n_segments, workspace, workspace_bytes, state_in, state_out, state_bytes, t_base, t_base_dev, t_base_stride, 1,
-                    stream);
+                    table, table_stride, page_shift, stream);
 }
 
 extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
@@ -1993,4 +2024,27 @@ extern "C" int sea_performer_causal_step_ragged(const void* q, const void* k, co
   SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
   return perf_step_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
                          state_in, state_out, state_bytes, 0, t_base_dev, t_base_stride, 1, nullptr, 0, stream);
+}
+
+// paged K / V: k / v are the K / V halves of a page pool (strides [page, head, row]); sequence n's open chunk c0 .. seen and its
+// new row lie in page block_table[n * table_stride + c0 / page_rows], from row c0 % page_rows on.  One new row per sequence.
+extern "C" int sea_performer_causal_step_paged(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                               const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                               int64_t pos_stride, void* out, void* avg_out, const void* state_in,
+                                               void* state_out, int64_t state_bytes, const int32_t* t_base_dev,
+                                               int64_t t_base_stride, const int32_t* block_table, int64_t table_stride,
+                                               int64_t page_rows, int64_t capacity, sea_stream_t stream) {
+  const char* nm = "sea_performer_causal_step_paged";
+  SEA_REQUIRE(t_base_dev && block_table, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
+  SEA_REQUIRE(T == 1, SEA_EINVAL, "%s: one new row per sequence (T=%lld)", nm, (long long)T);
+  const PerfForm form = perf_form(dtype, D, nb);
+  SEA_REQUIRE(form.mfma16, SEA_EUNSUPPORTED, "%s: the chunk-aligned step runs on the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
+  if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+  SEA_REQUIRE(page_rows % form.C == 0, SEA_EINVAL, "%s: page_rows %lld is not a multiple of the chunk (%d rows)", nm,
+              (long long)page_rows, form.C);
+  return perf_step_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
+                         state_in, state_out, state_bytes, 0, t_base_dev, t_base_stride, 1, nullptr, 0, stream, block_table,
+                         table_stride, __builtin_ctzll(page_rows));
 }

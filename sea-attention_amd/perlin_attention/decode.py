@@ -40,8 +40,17 @@ every launch of the step takes the *_ragged entry of its operator (include/sea_h
 sequence per workgroup, so a sequence's position is one scalar load from its row; the step is bitwise N sessions of N = 1.
 `admit` puts a new prompt into one slot between steps (continuous batching) without a new capture: the graph holds pointers
 to the session's buffers only.
+
+Paged K / V (`from_sequences(..., page_rows=...)`): one pool of fixed-size pages, (2, P, H, page_rows, D), shared by all
+slots, and a device block table (N, ceil(capacity / page_rows)) int32 naming each sequence's pages in order.  A `PageAllocator`
+on the host hands pages out: seeding or `admit` gives a slot the pages of its prefix plus the next row, `step` a new page to
+every slot whose next row starts one (written into the device table in stream order, no host synchronise).  The three
+launches that touch K / V take their *_paged entries; keys and column ids stay logical (head * capacity + key), so every
+result is bitwise the contiguous ragged session's.  page_rows is a power of two and a multiple of the Performer chunk: the
+rows a chunk-aligned step walks again lie in one page.
 """
-from typing import Optional
+from collections import deque
+from typing import List, Optional
 
 import torch
 
@@ -64,6 +73,42 @@ def _fused_cnn_ok(convs, C, H, T_M, dt, LB) -> bool:
             and ops.decode_cnn_supported(C, H, T_M, dt) and LB > 2 * convs[0].dilation)
 
 
+class PageAllocator:
+    """Free list of a paged K / V pool's pages (host only; the device block table is the session's business).  Pages go out
+    lowest index first at the start; pages given back are handed out again before any never-used one (most recently
+    returned first), so a slot that is re-admitted reuses the pages it gave back."""
+
+    def __init__(self, pool_pages: int):
+        if pool_pages < 1:
+            raise ValueError(f"a pool of {pool_pages} pages")
+        self.pool_pages = int(pool_pages)
+        self._free = deque(range(self.pool_pages))
+        self._used = set()
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def take(self, count: int) -> List[int]:
+        """`count` pages, or RuntimeError (and nothing taken) when fewer are free."""
+        if count > len(self._free):
+            raise RuntimeError(f"page pool exhausted: {count} page(s) wanted, {len(self._free)} of {self.pool_pages} free")
+        pages = [self._free.popleft() for _ in range(count)]
+        self._used.update(pages)
+        return pages
+
+    def give_back(self, pages) -> None:
+        """Return pages taken before; a page that is not out (a double free, a foreign index) is refused with ValueError
+        before any of them goes back."""
+        pages = list(pages)
+        bad = [pg for pg in pages if pg not in self._used]
+        if bad or len(set(pages)) != len(pages):
+            raise ValueError(f"pages {bad or pages} are not out of this pool (double free?)")
+        for pg in reversed(pages):
+            self._used.discard(pg)
+            self._free.appendleft(pg)
+
+
 class DecodeSession:
     """Built from the state of a cached forward (`PerlinAttentionOutput.state`, HIP estimator: 16-bit inference) and the
     K / V prefix that forward saw.  `step(q, k, v)` takes the NEW row of each tensor, (N, H, 1, D), and returns the
@@ -72,6 +117,9 @@ class DecodeSession:
 
     ragged = False               # (class defaults: a uniform session's instance attributes are what they always were)
     lengths = None
+    paged = False                # (from_sequences(..., page_rows=...): K / V in a page pool, see the module docstring)
+    page_rows = None
+    block_table = None
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -161,13 +209,18 @@ class DecodeSession:
         self._pinned, self._prep_generation = None, ops.prep_generation()
 
     @classmethod
-    def from_sequences(cls, attention, sequences, capacity: int, use_graph: bool = True, fused_attention: bool = True):
+    def from_sequences(cls, attention, sequences, capacity: int, use_graph: bool = True, fused_attention: bool = True,
+                       page_rows: Optional[int] = None, pool_pages: Optional[int] = None):
         """A session over sequences of DIFFERENT lengths.  `sequences`: [(state, key_prefix, value_prefix), ...], each the
         output of an N = 1 cached forward, (1, H, L_i, D) with its own L_i.  Slot n of the batch is sequence n; `step` takes
         and returns (N, ...) rows as for a uniform session, and every row equals that sequence's own N = 1 session bit for
         bit.  Defined where the fused CNN launch runs (`ops.decode_cnn_supported`: two-convolution body, T_M = 256, H <= 40,
         16-bit data); anything else raises ValueError, as do mismatched H / D / dtype, a prefix shorter than the CNN's reach
-        and L_i >= capacity."""
+        and L_i >= capacity.
+        `page_rows`: K / V in a pool of `pool_pages` pages of that many rows (default: enough for every slot at capacity; it
+        may be far fewer), bitwise the contiguous session.  page_rows is a power of two and a multiple of the Performer chunk
+        (`ops.performer_chunk_rows`: 64 at d = 64, 32 at d = 80 / 128); paging needs the fused decode attention
+        (`fused_attention=True`, d in {64, 80, 128}).  ValueError otherwise, or when the prefixes do not fit the pool."""
         self = cls.__new__(cls)
         at = self.attention = attention
         pc = at.pconfig
@@ -195,6 +248,25 @@ class DecodeSession:
             raise ValueError(f"capacity {self.capacity} beyond the value embedding ({at.v_eye_learned_causal.shape[2]} rows)")
         lengths = [self._check_sequence(*sq) for sq in seqs]
         N, H, D, dt, dev = self.N, self.H, self.D, self.dtype, kp0.device
+        n_tab = None
+        if page_rows is not None:
+            page_rows = int(page_rows)
+            nb = at.performer.projection_matrix.shape[0]
+            chunk = ops.performer_chunk_rows(D, nb, dt)
+            if not fused_attention:
+                raise ValueError("paged K / V runs on the fused decode attention (fused_attention=True): the unfused launches "
+                                 "read contiguous caches only")
+            if D not in (64, 80, 128) or chunk <= 0 or not ops.fused_interp_supported(dt, D, self.T_M):
+                raise ValueError(f"paged K / V needs the one-row decode attention form (16-bit d = 64 / 80 / 128; got d = {D})")
+            if page_rows < 1 or page_rows & (page_rows - 1) or page_rows % chunk:
+                raise ValueError(f"page_rows {page_rows}: a power of two and a multiple of the Performer chunk ({chunk} rows)")
+            n_tab = -(-self.capacity // page_rows)
+            need = sum(-(-(L + 1) // page_rows) for L in lengths)
+            pool_pages = N * n_tab if pool_pages is None else int(pool_pages)
+            if pool_pages < need:
+                raise ValueError(f"a pool of {pool_pages} pages of {page_rows} rows cannot hold the prefixes ({need} pages)")
+        elif pool_pages is not None:
+            raise ValueError("pool_pages goes with page_rows")
         self.ragged = True
         dil = convs[0].dilation
         row_shape = (C // 8, self.T_M // 4, 8)
@@ -206,7 +278,16 @@ class DecodeSession:
         self.y2 = torch.zeros((N,) + row_shape, dtype=dt, device=dev)
         self.ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.xs = None
-        self.kv_cache = torch.zeros((2, N, H, self.capacity, D), dtype=dt, device=dev)
+        if n_tab is not None:
+            # the pool (2, P, H, page_rows, D): K pages and V pages share one page index; kv_cache names the pool (what the
+            # stage writes and the capture saves), k_cache / v_cache its two halves (P, H, page_rows, D)
+            self.paged, self.page_rows = True, page_rows
+            self.allocator = PageAllocator(pool_pages)
+            self.pages = [[] for _ in range(N)]                             # host mirror of the table: slot n's pages in order
+            self.block_table = torch.full((N, n_tab), -1, dtype=torch.int32, device=dev)
+            self.kv_cache = torch.zeros((2, pool_pages, H, page_rows, D), dtype=dt, device=dev)
+        else:
+            self.kv_cache = torch.zeros((2, N, H, self.capacity, D), dtype=dt, device=dev)
         self.k_cache, self.v_cache = self.kv_cache[0], self.kv_cache[1]
         # per-sequence counters: row n = [seen, tsrc, tsrc of the step just closed] of sequence n (the uniform session's
         # three, once per sequence); the launches take (N, k) views of it -- a counter per sequence
@@ -262,22 +343,82 @@ class DecodeSession:
         p1 = torch.arange(L - keep_rows, L, device=rows.device)
         self.y1_ring[n].zero_()
         self.y1_ring[n, p1 % RY] = y1[0, LB - keep_rows:]
-        self.kv_cache[:, n].zero_()
-        self.k_cache[n, :, :L] = key_prefix[0]
-        self.v_cache[n, :, :L] = value_prefix[0]
+        if self.paged:
+            self._seed_pages(n, key_prefix, value_prefix)
+        else:
+            self.kv_cache[:, n].zero_()
+            self.k_cache[n, :, :L] = key_prefix[0]
+            self.v_cache[n, :, :L] = value_prefix[0]
         self.ctr32[n] = torch.tensor([L, L + 1, L + 1], dtype=torch.int32)
         self.lengths[n] = L
+
+    def _seed_pages(self, n, key_prefix, value_prefix):
+        """Slot n of a paged session := the prefix: its old pages go back first, then ceil((L + 1) / page_rows) pages (the
+        prefix and the row of the next step) take the prefix rows, zero behind them, and the device table row names them."""
+        L, H, D, pr = int(key_prefix.shape[2]), self.H, self.D, self.page_rows
+        count = -(-(L + 1) // pr)
+        if count > self.allocator.free_pages + len(self.pages[n]):
+            raise RuntimeError(f"page pool exhausted: slot {n} needs {count} pages, {self.allocator.free_pages} free "
+                               f"+ {len(self.pages[n])} of its own")
+        self.allocator.give_back(self.pages[n])
+        self.pages[n] = pages = self.allocator.take(count)
+        dev = self.kv_cache.device
+        rows = torch.zeros((2, H, count * pr, D), dtype=self.dtype, device=dev)
+        rows[0, :, :L] = key_prefix[0]
+        rows[1, :, :L] = value_prefix[0]
+        idx = torch.tensor(pages, dtype=torch.long, device=dev)
+        self.kv_cache[:, idx] = rows.view(2, H, count, pr, D).transpose(1, 2)
+        self.block_table[n].fill_(-1)
+        self.block_table[n, :count] = idx.to(torch.int32)
+
+    @property
+    def free_pages(self) -> Optional[int]:
+        """Pages of the pool no slot holds (a paged session; None otherwise): what a scheduler may still admit or grow into."""
+        return self.allocator.free_pages if self.paged else None
+
+    def sequence_kv(self, slot: int):
+        """Sequence `slot`'s logical K and V rows, (1, H, L, D) each (copies; a paged session gathers them from its pages):
+        what a cached forward continues from, with `export_state(slot)`."""
+        if not self.ragged:
+            raise ValueError("sequence_kv: a ragged session (DecodeSession.from_sequences)")
+        if not 0 <= slot < self.N:
+            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        L = self.lengths[slot]
+        if self.paged:
+            idx = torch.tensor(self.pages[slot], dtype=torch.long, device=self.kv_cache.device)
+            kv = self.kv_cache[:, idx].transpose(1, 2).reshape(2, self.H, -1, self.D)[:, :, :L]
+        else:
+            kv = self.kv_cache[:, slot, :, :L]
+        return kv[0:1].clone(), kv[1:2].clone()
+
+    def _grow_pages(self):
+        """Before a step's first launch: a page for every slot whose next row starts one.  Refused (RuntimeError naming the
+        slots, nothing changed) when the pool has too few; the table entries are written in stream order behind the host's
+        decision (small fills, no synchronise)."""
+        want = [n for n, L in enumerate(self.lengths) if L >= len(self.pages[n]) * self.page_rows]
+        if not want:
+            return
+        if len(want) > self.allocator.free_pages:
+            raise RuntimeError(f"page pool exhausted: slot(s) {want} need a new page, {self.allocator.free_pages} free")
+        for n, pg in zip(want, self.allocator.take(len(want))):
+            self.block_table[n, len(self.pages[n])].fill_(pg)
+            self.pages[n].append(pg)
 
     @torch.no_grad()
     def admit(self, slot: int, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor):
         """Continuous batching: slot `slot` of a ragged session starts over on a new sequence (an N = 1 cached forward's
         state and prefixes), between two steps.  The other slots go on where they were; the captured graph stays (it holds
-        pointers to the session's buffers, whose contents change here), so `captures` does not move."""
+        pointers to the session's buffers, whose contents change here), so `captures` does not move.  A paged session
+        gives the slot's pages back first; when the pool still cannot hold the new prefix it raises RuntimeError and leaves
+        the slot as it was."""
         if not self.ragged:
             raise ValueError("admit: only a ragged session (DecodeSession.from_sequences) takes new sequences")
         if not 0 <= slot < self.N:
             raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
-        self._check_sequence(state, key_prefix, value_prefix)
+        L = self._check_sequence(state, key_prefix, value_prefix)
+        if self.paged and -(-(L + 1) // self.page_rows) > self.allocator.free_pages + len(self.pages[slot]):
+            raise RuntimeError(f"page pool exhausted: slot {slot} needs {-(-(L + 1) // self.page_rows)} pages for a prefix of {L} "
+                               f"rows, {self.allocator.free_pages} free + {len(self.pages[slot])} of its own")
         if self.csr is not None and self.csr.col_is_pending:
             self.csr.col                              # the last step's pending columns follow the counters: emit before they move
         self._seed_slot(slot, state, key_prefix, value_prefix)
@@ -297,15 +438,20 @@ class DecodeSession:
 
     # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new row
     def _stage(self, q, k, v):
+        if self.paged:
+            ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2], block_table=self.block_table,
+                             capacity=self.capacity)
+            return
         ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2])
 
     # the (captured) launches of one position; everything position-dependent is read from device memory
     def _launch(self):
         at, H, D, T_M = self.attention, self.H, self.D, self.T_M
+        paged = dict(block_table=self.block_table, capacity=self.capacity) if self.paged else {}
         # chunk-aligned step: the kernel walks the open Performer chunk again from the caches (which hold the new row already)
         performer_value, avg_rows, _ = ops.performer_step(
             self.q_in, self.k_cache, self.v_cache, at.v_eye_learned_causal[0, 0], at.performer.projection_matrix,
-            state_in=self.image, t_base_dev=self.seen32)
+            state_in=self.image, t_base_dev=self.seen32, **paged)
         _x, _t, row_scale, avg_scale = ops.predictor_mlp(
             performer_value, at.attention_predictor_enc[0], at.attention_predictor_enc[1],
             at.attention_predictor_dec_row[0], at.attention_predictor_cnn[0].module,
@@ -334,7 +480,7 @@ class DecodeSession:
             ops.sparse_attention(self.q_in, self.k_cache, self.v_cache, csr,
                                  row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
                                  avg=avg_rows, mix=avg_scale, out=self.ctx.view(self.N, 1, H, D).permute(0, 2, 1, 3),
-                                 path="gather", keep_columns_pending=True)
+                                 path="gather", keep_columns_pending=True, block_table=self.block_table)
             self.csr = csr                                                    # (the step's selection: columns on first read of .col)
             self._col_emit = csr._pending                                     # (None: a launch of the step writes the columns)
             return
@@ -415,6 +561,8 @@ class DecodeSession:
             full = [n for n, L in enumerate(self.lengths) if L >= self.capacity]
             if full:
                 raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full}")
+            if self.paged:
+                self._grow_pages()
         else:
             assert self.length < self.capacity, "cache capacity reached"
         if self.graph is not None and ops.prep_generation() != self._prep_generation:

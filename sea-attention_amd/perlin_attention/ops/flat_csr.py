@@ -421,7 +421,8 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      avg: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None,
                      out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
-                     plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False):
+                     plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False,
+                     block_table: Optional[torch.Tensor] = None):
     """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
@@ -440,7 +441,10 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     hands out as `partial_attention_probs` (attention.py:1162-1171); returns (out, probs).
     keep_columns_pending: with a handle whose columns are pending and the fused launch serving it, do NOT write the column
     array (the launch keeps the expanded columns in LDS): the handle stays pending and whoever reads `.col` later runs the
-    emit launch -- for callers that return the CSR without anybody reading it (the layer's hot path)."""
+    emit launch -- for callers that return the CSR without anybody reading it (the layer's hot path).
+    block_table: paged K / V (`sea_sparse_attention_paged`): k / v are the K / V halves of a page pool (P, H, page_rows, D),
+    sequence n's key r in page block_table[n, r // page_rows] (int32, (N, >= ceil(csr.T_src / page_rows))).  Only the one-row
+    decode form reads pages: a pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, csr.crow)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, row_scale, avg, mix)):
@@ -455,6 +459,8 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     fused = (csr.col_is_pending and fuse_emit and path != "tile" and not (path == "auto" and plan is not None)
              and fused_interp_supported(q.dtype, D, csr._pending[0], None if decode_form else N * H * T_dst)
              and not (decode_form and (want_probs or T_dst > 8)))
+    if block_table is not None:
+        return _sparse_attention_paged(q, k, v, csr, block_table, row_scale, avg, mix, out, out_dtype, keep_columns_pending)
     T_src = k.shape[2]
     assert k.shape == (N, H, T_src, D) and v.shape == (N, H, T_src, D)
     assert q.dtype == k.dtype == v.dtype
@@ -510,6 +516,42 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     block_path = plan if (plan is not None and path == "auto" and not want_probs) else None
     _lib.check(launch(csr.col, probs, block_path, flags), "sea_sparse_attention")
     return (out, probs) if want_probs else out
+
+
+def _sparse_attention_paged(q, k, v, csr: FlatCSR, block_table, row_scale, avg, mix, out, out_dtype, keep_columns_pending):
+    """`sparse_attention(..., block_table=...)`: the one-row decode form over a page pool (no other kernel reads pages)."""
+    lib = _lib.load()
+    _lib.require_gpu(k, v, block_table)
+    N, H, T_dst, D = q.shape
+    if not (csr.col_is_pending and csr.t_src_stride and T_dst == 1 and q.dtype in (torch.float16, torch.bfloat16)
+            and D in (64, 80, 128)):
+        raise ValueError("paged K / V: the one-row decode form only (a pending per-sequence decode CSR, T_dst = 1, "
+                         f"16-bit d = 64 / 80 / 128; got T_dst = {T_dst}, {q.dtype}, d = {D})")
+    P, Hk, page_rows, Dk = k.shape
+    assert (Hk, Dk) == (H, D) and v.shape == k.shape and q.dtype == k.dtype == v.dtype and k.stride(-1) == 1 and v.stride(-1) == 1
+    assert (csr.N, csr.T_dst, csr.H) == (N, T_dst, H)
+    assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
+    if out is None:
+        out = torch.empty((N, H, T_dst, D), dtype=out_dtype or torch.float32, device=q.device)
+    assert out.shape == (N, H, T_dst, D) and out.stride(-1) == 1
+    if row_scale is not None:
+        assert row_scale.dtype == torch.float32 and row_scale.shape == (N, H, T_dst) and row_scale.is_contiguous()
+    if mix is not None:
+        assert avg is not None and avg.shape == (N, H, T_dst, D) and avg.dtype == q.dtype
+        assert mix.dtype == torch.float32 and mix.shape == (N, H, T_dst) and mix.is_contiguous()
+    T_m, max_k, causal, _emit = csr._pending
+    col = csr._col
+    _lib.check(lib.sea_sparse_attention_paged(
+        _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, csr.T_src, D,
+        _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
+        _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
+        _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
+        _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
+        _p(csr.bits), T_m, int(causal), max_k, 0 if keep_columns_pending else 1, _p(csr.t_src_dev), csr.t_src_stride,
+        _p(block_table), block_table.stride(0), page_rows, _lib.stream_ptr()), "sea_sparse_attention_paged")
+    if not keep_columns_pending:
+        csr._pending = None                                 # the launch has written the columns
+    return out
 
 
 def plan_blocks(plan: torch.Tensor, N: int, H: int, T_dst: int) -> torch.Tensor:

@@ -422,7 +422,8 @@ def performer_chunk_rows(D: int, nb: int, dtype) -> int:
 @_lib.device_guarded
 def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor, projection: torch.Tensor,
                    state_in: torch.Tensor = None, t_base: int = 0, want_avg: bool = True, n_segments: int = 1,
-                   t_base_dev: Optional[torch.Tensor] = None):
+                   t_base_dev: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None,
+                   capacity: Optional[int] = None):
     """Stateful, chunk-aligned causal Performer (`sea_performer_causal_step`).  q (N,H,T_new,D) are the NEW rows of sequences
     that have seen `t_base` rows; k, v (N,H,>=t_base+T_new,D) are the kv-cache FROM ROW 0 (the call reads them from the last
     chunk boundary c0 <= t_base on: the open chunk is walked again, which is what makes the rows bitwise the stateless
@@ -432,12 +433,16 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     Decode form (`sea_performer_causal_step` with `t_base_dev`, a step replayed as a HIP graph): `t_base_dev` is a one-element int32
     device tensor holding the rows seen so far, k / v the fixed-capacity caches (already holding the new row), and
     `state_in` is updated in place.  An (N, 1) view of a per-sequence counter block gives each sequence its own position
-    (`sea_performer_causal_step_ragged`; sequence n's state image is the n-th contiguous slice of `state_in`)."""
+    (`sea_performer_causal_step_ragged`; sequence n's state image is the n-th contiguous slice of `state_in`).
+    Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32 with per-sequence `t_base_dev`, one new row each): k / v
+    are the K / V halves of a page pool, (P, H, page_rows, D); sequence n's row r lives in page block_table[n, r // page_rows]
+    (`sea_performer_causal_step_paged`).  `capacity`: the logical rows per sequence the table covers."""
     lib = _lib.load()
-    _lib.require_gpu(q, k, v, pos, projection)
+    _lib.require_gpu(q, k, v, pos, projection, block_table)
     N, H, T, D = q.shape
     nb = projection.shape[0]
-    assert k.shape[:2] == (N, H) and k.shape[-1] == D and v.shape == k.shape and pos.shape[-1] == D
+    paged = block_table is not None
+    assert k.shape[1] == H and (paged or k.shape[0] == N) and k.shape[-1] == D and v.shape == k.shape and pos.shape[-1] == D
     C = performer_chunk_rows(D, nb, q.dtype)
     assert C > 0, "the stateful Performer runs on the 16-bit MFMA kernels (bf16 / fp16 data, D in {64, 80, 128})"
     q = q if q.stride(-1) == 1 else q.contiguous()
@@ -452,7 +457,7 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
         assert t_stride > 0 or t_base_dev.numel() == 1
         assert state_in is not None and t_base == 0 and n_segments == 1
         kc, vc, pc = k, v, pos                                   # cache / table bases: the kernel finds the boundary
-        assert pos.shape[0] >= k.shape[2]
+        assert pos.shape[0] >= (int(capacity) if paged else k.shape[2])
     else:
         c0 = (int(t_base) // C) * C
         assert k.shape[2] >= t_base + T and pos.shape[0] >= t_base + T, "k / v / pos must cover the rows seen plus the new ones"
@@ -474,6 +479,14 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     if n_segments > 1:
         ws_bytes = N * H * (n_segments - 1) * lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(q.dtype))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
+    if paged:
+        assert t_base_dev is not None and t_stride > 0 and capacity is not None, "the paged step: per-sequence positions, a capacity"
+        assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
+        _lib.check(lib.sea_performer_causal_step_paged(
+            _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
+            _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, _p(t_base_dev), t_stride,
+            _p(block_table), block_table.stride(0), k.shape[2], int(capacity), _lib.stream_ptr()), "sea_performer_causal_step_paged")
+        return out, avg, state_out
     if t_base_dev is not None and t_stride > 0:
         _lib.check(lib.sea_performer_causal_step_ragged(
             _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
@@ -668,16 +681,20 @@ def causal_conv_c8_z(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
 
 @_lib.device_guarded
 def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.Tensor, kv_cache: torch.Tensor,
-                 counters: torch.Tensor) -> None:
+                 counters: torch.Tensor, block_table: Optional[torch.Tensor] = None, capacity: Optional[int] = None) -> None:
     """`sea_decode_stage`: the new rows of a decoding step, (N,H,1,D) each (any [n,h] strides), into the session's static
     buffers -- q into q_in (N,H,1,D), k / v into kv_cache (2,N,H,capacity,D) at the row the device counters name
     (int32 [seen, tsrc]: row = counters[0]).  An (N, >= 1) view of a per-sequence counter block writes sequence n's rows at
-    counters[n, 0] (`sea_decode_stage_ragged`)."""
+    counters[n, 0] (`sea_decode_stage_ragged`).  Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32, per-sequence
+    counters): kv_cache is a page pool (2, P, H, page_rows, D) and sequence n's rows go to page block_table[n, row // page_rows]
+    (`sea_decode_stage_paged`); `capacity` is the logical rows per sequence."""
     lib = _lib.load()
-    _lib.require_gpu(q, k, v, q_in, kv_cache, counters)
+    _lib.require_gpu(q, k, v, q_in, kv_cache, counters, block_table)
     N, H, one, D = q.shape
+    paged = block_table is not None
     assert one == 1 and k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
-    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, 1, D) and kv_cache.is_contiguous() and kv_cache.shape[:3] == (2, N, H)
+    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, 1, D) and kv_cache.is_contiguous()
+    assert kv_cache.shape[0] == 2 and kv_cache.shape[2] == H and (paged or kv_cache.shape[1] == N)
     stride = _lib.counter_stride(counters, N) if counters.dim() == 2 else 0      # (an (N, k) view: a counter per sequence)
     assert stride > 0 or (counters.dtype == torch.int32 and counters.numel() == 2 and counters.is_contiguous())
     # the kernel moves whole 16-byte vectors: rows contiguous along D, [n, h] strides in multiples of 8 elements, 16-byte aligned
@@ -686,6 +703,14 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
     ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
     q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
     st = lambda t: (ctypes_i64 * 2)(t.stride(0), t.stride(1))
+    if paged:
+        assert stride > 0 and capacity is not None, "the paged stage: per-sequence counters and a capacity"
+        assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
+        _lib.check(lib.sea_decode_stage_paged(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v),
+                                              _p(q_in), _p(kv_cache), int(capacity), _p(counters), stride, _p(block_table),
+                                              block_table.stride(0), kv_cache.shape[3], kv_cache.shape[1], _lib.stream_ptr()),
+                   "sea_decode_stage_paged")
+        return
     if stride > 0:
         _lib.check(lib.sea_decode_stage_ragged(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v),
                                                _p(q_in), _p(kv_cache), kv_cache.shape[3], _p(counters), stride, _lib.stream_ptr()),
