@@ -44,7 +44,7 @@ extern "C" {
  *      Later, additive (no bump): the *_ragged entries of the decode step (per-sequence positions: sea_decode_stage,
  *      sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention, sea_csr_emit); then the *_paged
  *      entries (K / V in a pool of pages with a block table per sequence: sea_decode_stage, sea_performer_causal_step,
- *      sea_sparse_attention)
+ *      sea_sparse_attention); then sea_decode_fork (fork / beam reorder of a paged session's slots)
  *      */
 #define SEA_ABI_VERSION 4
 
@@ -642,6 +642,37 @@ int sea_decode_stage_paged(const void* q, const void* k, const void* v, int dtyp
                            const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
                            sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
+
+/* Fork / beam reorder of a paged ragged session's slots, between two steps (perlin_attention/decode.py: DecodeSession.fork and
+ * reorder).  `moves`: DEVICE int32 (M, 5), one row per destination slot: {src, dst, src_open, dst_open, stage}.  Destination
+ * dst continues as a copy of slot src; it receives
+ *   - src's Performer image slice (sea_performer_state_bytes(1, H, D, nb, dtype) bytes at slot * that in `image`),
+ *   - src's x_ring and y1_ring slices (x_ring_bytes / y1_ring_bytes per slot, each a multiple of 16),
+ *   - src's counter row (three int32 at slot * counter_stride, counter_stride >= 3),
+ *   - a block-table row: src's entries below its open index o = seen >> log2(page_rows) (seen = src's first counter), then
+ *     dst_open at o, then -1 up to ceil(capacity / page_rows) entries,
+ *   - when src_open >= 0 and dst_open >= 0: pool page dst_open := pool page src_open, K and V, all page_rows rows
+ *     (kv_pool (2, pool_pages, H, page_rows, D) dense; src_open is src's page at index o, -1 when src has none).
+ * SNAPSHOT semantics: every destination gets its source's state as it was before the call, also when that source is the
+ * destination of another move (a beam swap, a cycle).  Such a move names a staging slot, stage in 0 .. n_staged-1 (else -1):
+ * a first launch copies those sources' image, rings, counters and table rows into `staging` (n_staged slots of
+ * img_bytes + x_ring_bytes + y1_ring_bytes + 16 + 16 * ceil(ceil(capacity / page_rows) / 4) bytes each), a second writes
+ * every destination.  The first launch is skipped when n_staged = 0.  No host synchronisation.
+ * The device contents of `moves` cannot be checked here; the caller guarantees:
+ *   - destinations are distinct, and no move has src == dst,
+ *   - a move whose source is the destination of another move has a staging slot of its own,
+ *   - destination open pages are distinct, and held by no slot before the call (so no source page is written),
+ *   - the block table, pool and counters describe the host's view of the session (the table rows name pool pages).
+ * Out-of-range slots, stage indices and pages in `moves` skip the item instead of writing out of bounds.
+ * This is the only entry that writes one slot's state from another's; it must not run concurrently with a step of the same
+ * session (call it in the step's stream, between steps).  Null pointers (staging: when n_staged > 0), M outside 1 .. N,
+ * n_staged outside 0 .. M, a counter_stride below 3, a bad page size / table stride / pool, a staging buffer too small:
+ * SEA_EINVAL; other dtypes / D, ring bytes that are not whole 16-byte chunks, unaligned buffers: SEA_EUNSUPPORTED. */
+int sea_decode_fork(const int32_t* moves, int64_t M, int64_t n_staged, int dtype, int64_t N, int64_t H, int64_t D, int64_t nb,
+                    void* image, void* x_ring, int64_t x_ring_bytes, void* y1_ring, int64_t y1_ring_bytes,
+                    int32_t* counters, int64_t counter_stride, int32_t* block_table, int64_t table_stride, int64_t capacity,
+                    void* kv_pool, int64_t page_rows, int64_t pool_pages, void* staging, int64_t staging_bytes,
+                    sea_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "sea_decode_stage_paged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64,
                                 i64, ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
+    "sea_decode_fork": ([ptr, i64, i64, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr, i64, ptr, i64, ptr, i64, i64, ptr, i64, i64,
+                         ptr, i64, ptr], c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),
     "sea_performer_plan": ([i64, i64, i64, i64, i64, c_int, _i64p, _i64p], c_int),
 }

@@ -12,6 +12,8 @@
 //                         all rows and walks them top to bottom, so no thread reads what another one writes.  It is the
 //                         LAST launch of a step and also advances the two counters (rows the state has seen, keys the next
 //                         row sees): every reader of this step has finished (stream order), the next step's have not begun.
+//   decode_fork_kernel    between two steps, slots of a paged session continue as copies of other slots (fork / beam
+//                         reorder): a slot's small state and its open page are copied, its closed pages are shared.
 #include "sea_common.hpp"
 
 namespace sea {
@@ -78,6 +80,73 @@ __global__ __launch_bounds__(256) void c8_window_shift_kernel(uint4* xs, int row
     const uint4 cur = nxt;
     if (r + 2 < rows) nxt = base[(int64_t)(r + 2) * chunks_per_row];
     base[(int64_t)r * chunks_per_row] = cur;
+  }
+}
+
+// sea_decode_fork: M moves (src, dst, src_open, dst_open, stage) between slots of a paged session.  A move's work is a row of
+// items: the slot's 16-byte chunks of the Performer image, x ring and y1 ring, then its three counters and its block-table
+// entries (int32 items), then -- second launch only -- both halves of the open page in 16-byte chunks.  One grid-stride loop
+// walks (move, item): the open-page copy (the bulk of the bytes) is spread over the whole grid.
+// STAGE (first launch): the small state of every move with a staging slot (stage >= 0: its source is also a destination)
+// goes to that slot.  Second launch: every destination is written, from the staging slot when the move has one, else from
+// the source's own rows -- which no move of the call writes (host precondition) -- so each destination gets its source's
+// state as it was before the call.  The pages copied from are no destination's open page (they are the sources' open pages,
+// held by their slots), and the destination pages are held by no other slot: no item reads what another item writes.
+struct ForkParams {
+  const int32_t* moves;                 // (M, 5)
+  uint4 *image, *x_ring, *y1_ring;      // slot n's slices at n * img16 / x16 / y16 chunks
+  int32_t *ctr, *table;                 // slot n's counters at n * ctr_stride, table row at n * table_stride
+  uint4* pool;                          // (2, pool_pages, page16) chunks: K pages, then V pages
+  uint4* staging;                       // n_staged slots of slot16 chunks: image | x | y1 | counters (1 chunk) | table entries
+  int M, n_staged, N, img16, x16, y16, ctr_stride, table_stride, n_entries, page_shift, pool_pages, page16, slot16;
+};
+
+template <bool STAGE>
+__global__ __launch_bounds__(256) void decode_fork_kernel(ForkParams p) {
+  const int vec = p.img16 + p.x16 + p.y16;
+  const int small = vec + 3 + p.n_entries;
+  const int per = small + (STAGE ? 0 : 2 * p.page16);
+  const int total = per * p.M;                               // (host: < 2^31)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int m = i / per, c = i - m * per;
+    const int32_t* mv = p.moves + 5 * m;
+    const int src = mv[0], dst = mv[1], stage = mv[4];
+    if (src < 0 || src >= p.N || dst < 0 || dst >= p.N) continue;
+    const bool staged = stage >= 0 && stage < p.n_staged;
+    if (STAGE && !staged) continue;
+    uint4* slot = staged ? p.staging + (int64_t)stage * p.slot16 : nullptr;
+    int32_t* slot_ctr = staged ? reinterpret_cast<int32_t*>(slot + vec) : nullptr;
+    int32_t* slot_tab = staged ? slot_ctr + 4 : nullptr;
+    if (c < vec) {                                           // image / rings: 16-byte chunks
+      uint4* base;
+      int per_slot, j;
+      if (c < p.img16) { base = p.image; per_slot = p.img16; j = c; }
+      else if (c < p.img16 + p.x16) { base = p.x_ring; per_slot = p.x16; j = c - p.img16; }
+      else { base = p.y1_ring; per_slot = p.y16; j = c - p.img16 - p.x16; }
+      if (STAGE) slot[c] = base[(int64_t)src * per_slot + j];
+      else base[(int64_t)dst * per_slot + j] = staged ? slot[c] : base[(int64_t)src * per_slot + j];
+    } else if (c < vec + 3) {                                // counters [seen, tsrc, tsrc of the step just closed]
+      const int k = c - vec;
+      if (STAGE) slot_ctr[k] = p.ctr[(int64_t)src * p.ctr_stride + k];
+      else p.ctr[(int64_t)dst * p.ctr_stride + k] = staged ? slot_ctr[k] : p.ctr[(int64_t)src * p.ctr_stride + k];
+    } else if (c < small) {                                  // block-table entry j
+      const int j = c - vec - 3;
+      if (STAGE) { slot_tab[j] = p.table[(int64_t)src * p.table_stride + j]; continue; }
+      // below the source's open page index (the page row `seen` lies in): the shared closed pages; at it: the destination's
+      // own open page (or -1: the source has none); behind it: no page
+      const int seen = staged ? slot_ctr[0] : p.ctr[(int64_t)src * p.ctr_stride];
+      const int open = seen >> p.page_shift;
+      int32_t e = -1;
+      if (j < open) e = staged ? slot_tab[j] : p.table[(int64_t)src * p.table_stride + j];
+      else if (j == open) e = mv[3];
+      p.table[(int64_t)dst * p.table_stride + j] = e;
+    } else if (!STAGE) {                                     // the open page: K half, then V half
+      const int src_pg = mv[2], dst_pg = mv[3];
+      if (src_pg < 0 || src_pg >= p.pool_pages || dst_pg < 0 || dst_pg >= p.pool_pages) continue;
+      const int k = c - small, half = k >= p.page16 ? 1 : 0, j = k - half * p.page16;
+      const int64_t h0 = (int64_t)half * p.pool_pages;
+      p.pool[(h0 + dst_pg) * p.page16 + j] = p.pool[(h0 + src_pg) * p.page16 + j];
+    }
   }
 }
 
@@ -168,6 +237,60 @@ extern "C" int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t ro
   SEA_REQUIRE(total < (1ll << 31), SEA_EUNSUPPORTED, "%s: window too large", nm);
   hipLaunchKernelGGL(c8_window_shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<uint4*>(xs), (int)rows, cpr, total, counters);
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+
+// fork / reorder of a paged session's slots (decode.py: DecodeSession.fork / reorder); include/sea_hip.h states the layout
+// and the preconditions the caller guarantees
+extern "C" int sea_decode_fork(const int32_t* moves, int64_t M, int64_t n_staged, int dtype, int64_t N, int64_t H, int64_t D,
+                               int64_t nb, void* image, void* x_ring, int64_t x_ring_bytes, void* y1_ring, int64_t y1_ring_bytes,
+                               int32_t* counters, int64_t counter_stride, int32_t* block_table, int64_t table_stride,
+                               int64_t capacity, void* kv_pool, int64_t page_rows, int64_t pool_pages, void* staging,
+                               int64_t staging_bytes, sea_stream_t stream) {
+  const char* nm = "sea_decode_fork";
+  SEA_REQUIRE(moves && image && x_ring && y1_ring && counters && block_table && kv_pool, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && D > 0 && nb > 0 && N < (1ll << 24), SEA_EINVAL, "%s: bad shape", nm);
+  SEA_REQUIRE(M >= 1 && M <= N, SEA_EINVAL, "%s: %lld moves for %lld slots (1 .. N, distinct destinations)", nm, (long long)M,
+              (long long)N);
+  SEA_REQUIRE(n_staged >= 0 && n_staged <= M, SEA_EINVAL, "%s: n_staged %lld outside 0 .. M = %lld", nm, (long long)n_staged,
+              (long long)M);
+  SEA_REQUIRE(counter_stride >= 3 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: counter_stride %lld (3 counters per slot)",
+              nm, (long long)counter_stride);
+  if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+  SEA_REQUIRE(pool_pages > 0 && pool_pages < (1ll << 31), SEA_EINVAL, "%s: bad pool of %lld pages", nm, (long long)pool_pages);
+  const int64_t img_bytes = sea_performer_state_bytes(1, H, D, nb, dtype);
+  SEA_REQUIRE(img_bytes > 0 && img_bytes % 16 == 0 && x_ring_bytes > 0 && x_ring_bytes % 16 == 0 && y1_ring_bytes > 0 &&
+              y1_ring_bytes % 16 == 0, SEA_EUNSUPPORTED, "%s: per-slot image / ring bytes (%lld, %lld, %lld) must be whole 16-byte chunks",
+              nm, (long long)img_bytes, (long long)x_ring_bytes, (long long)y1_ring_bytes);
+  const int64_t page_bytes = H * page_rows * D * 2;          // one half (K or V) of a page
+  const int64_t n_entries = (capacity + page_rows - 1) / page_rows;
+  const int64_t vec = (img_bytes + x_ring_bytes + y1_ring_bytes) / 16;
+  const int64_t slot16 = vec + 1 + (n_entries + 3) / 4;
+  const int64_t per = vec + 3 + n_entries + 2 * page_bytes / 16;
+  SEA_REQUIRE(per * M < (1ll << 31) && pool_pages * page_bytes * 2 < (1ll << 62) && N * vec < (1ll << 31), SEA_EUNSUPPORTED,
+              "%s: slot state or pages too large", nm);
+  SEA_REQUIRE(n_staged == 0 || (staging && staging_bytes >= n_staged * slot16 * 16), SEA_EINVAL,
+              "%s: staging buffer of %lld bytes, %lld needed (%lld slots of %lld)", nm, (long long)(staging ? staging_bytes : 0),
+              (long long)(n_staged * slot16 * 16), (long long)n_staged, (long long)(slot16 * 16));
+  const uintptr_t al = (uintptr_t)image | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)kv_pool | (uintptr_t)staging;
+  SEA_REQUIRE((al & 15) == 0, SEA_EUNSUPPORTED, "%s: image, rings, pool and staging must be 16-byte aligned", nm);
+  ForkParams p;
+  p.moves = moves; p.image = (uint4*)image; p.x_ring = (uint4*)x_ring; p.y1_ring = (uint4*)y1_ring;
+  p.ctr = counters; p.table = block_table; p.pool = (uint4*)kv_pool; p.staging = (uint4*)staging;
+  p.M = (int)M; p.n_staged = (int)n_staged; p.N = (int)N;
+  p.img16 = (int)(img_bytes / 16); p.x16 = (int)(x_ring_bytes / 16); p.y16 = (int)(y1_ring_bytes / 16);
+  p.ctr_stride = (int)counter_stride; p.table_stride = (int)table_stride; p.n_entries = (int)n_entries;
+  p.page_shift = __builtin_ctzll(page_rows); p.pool_pages = (int)pool_pages; p.page16 = (int)(page_bytes / 16);
+  p.slot16 = (int)slot16;
+  hipStream_t s = (hipStream_t)stream;
+  auto grid = [](int64_t items) { return (unsigned)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048); };
+  if (n_staged > 0) {
+    hipLaunchKernelGGL(decode_fork_kernel<true>, dim3(grid((vec + 3 + n_entries) * M)), dim3(256), 0, s, p);
+    SEA_CHECK_LAUNCH(nm);
+  }
+  hipLaunchKernelGGL(decode_fork_kernel<false>, dim3(grid(per * M)), dim3(256), 0, s, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

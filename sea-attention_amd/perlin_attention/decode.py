@@ -48,6 +48,12 @@ every slot whose next row starts one (written into the device table in stream or
 launches that touch K / V take their *_paged entries; keys and column ids stay logical (head * capacity + key), so every
 result is bitwise the contiguous ragged session's.  page_rows is a power of two and a multiple of the Performer chunk: the
 rows a chunk-aligned step walks again lie in one page.
+
+Fork and beam reorder (`fork`, `reorder`; paged ragged sessions, between steps): during a step only the stage writes K / V, row
+`seen` of each slot, in the slot's last ("open") page; every page below it is immutable while the sequence lives.  So a slot
+may continue as a copy of another by sharing that slot's closed pages (the allocator counts holders) and copying only its
+small state -- Performer image slice, rings, counter row, block-table row -- and its open page: one `sea_decode_fork` call
+(include/sea_hip.h), snapshot semantics for swaps, cycles and many-to-one parent maps.
 """
 from collections import deque
 from typing import List, Optional
@@ -76,37 +82,59 @@ def _fused_cnn_ok(convs, C, H, T_M, dt, LB) -> bool:
 class PageAllocator:
     """Free list of a paged K / V pool's pages (host only; the device block table is the session's business).  Pages go out
     lowest index first at the start; pages given back are handed out again before any never-used one (most recently
-    returned first), so a slot that is re-admitted reuses the pages it gave back."""
+    returned first), so a slot that is re-admitted reuses the pages it gave back.
+    A page that is out has one or more holders (`share` adds one: a closed page named by several block tables after a fork);
+    `give_back` drops one holder per page, and the page returns to the free list when its last holder gives it back."""
 
     def __init__(self, pool_pages: int):
         if pool_pages < 1:
             raise ValueError(f"a pool of {pool_pages} pages")
         self.pool_pages = int(pool_pages)
         self._free = deque(range(self.pool_pages))
-        self._used = set()
+        self._holders = {}                                                   # page -> holders (pages that are out)
 
     @property
     def free_pages(self) -> int:
         return len(self._free)
+
+    def holders(self, page: int) -> int:
+        """How many holders page `page` has (0: it is free)."""
+        return self._holders.get(page, 0)
 
     def take(self, count: int) -> List[int]:
         """`count` pages, or RuntimeError (and nothing taken) when fewer are free."""
         if count > len(self._free):
             raise RuntimeError(f"page pool exhausted: {count} page(s) wanted, {len(self._free)} of {self.pool_pages} free")
         pages = [self._free.popleft() for _ in range(count)]
-        self._used.update(pages)
+        for pg in pages:
+            self._holders[pg] = 1
         return pages
 
-    def give_back(self, pages) -> None:
-        """Return pages taken before; a page that is not out (a double free, a foreign index) is refused with ValueError
-        before any of them goes back."""
+    def share(self, pages) -> None:
+        """One more holder for each of `pages` (a page may be named more than once); a page that is not out is refused
+        with ValueError before any of them changes."""
         pages = list(pages)
-        bad = [pg for pg in pages if pg not in self._used]
-        if bad or len(set(pages)) != len(pages):
-            raise ValueError(f"pages {bad or pages} are not out of this pool (double free?)")
+        bad = [pg for pg in pages if pg not in self._holders]
+        if bad:
+            raise ValueError(f"pages {bad} are not out of this pool: only a page that is out can be shared")
+        for pg in pages:
+            self._holders[pg] += 1
+
+    def give_back(self, pages) -> None:
+        """Drop one holder of each page taken or shared before; a page named more often than it has holders (a double free,
+        a foreign index) is refused with ValueError before any of them changes."""
+        pages = list(pages)
+        count = {}
+        for pg in pages:
+            count[pg] = count.get(pg, 0) + 1
+        bad = [pg for pg, c in count.items() if c > self._holders.get(pg, 0)]
+        if bad:
+            raise ValueError(f"pages {bad} are not out of this pool (double free?)")
         for pg in reversed(pages):
-            self._used.discard(pg)
-            self._free.appendleft(pg)
+            self._holders[pg] -= 1
+            if self._holders[pg] == 0:
+                del self._holders[pg]
+                self._free.appendleft(pg)
 
 
 class DecodeSession:
@@ -357,9 +385,10 @@ class DecodeSession:
         prefix and the row of the next step) take the prefix rows, zero behind them, and the device table row names them."""
         L, H, D, pr = int(key_prefix.shape[2]), self.H, self.D, self.page_rows
         count = -(-(L + 1) // pr)
-        if count > self.allocator.free_pages + len(self.pages[n]):
+        own = self._reclaimable(n)
+        if count > self.allocator.free_pages + own:
             raise RuntimeError(f"page pool exhausted: slot {n} needs {count} pages, {self.allocator.free_pages} free "
-                               f"+ {len(self.pages[n])} of its own")
+                               f"+ {own} of its own")
         self.allocator.give_back(self.pages[n])
         self.pages[n] = pages = self.allocator.take(count)
         dev = self.kv_cache.device
@@ -371,10 +400,23 @@ class DecodeSession:
         self.block_table[n].fill_(-1)
         self.block_table[n, :count] = idx.to(torch.int32)
 
+    def _reclaimable(self, n) -> int:
+        """Pages slot n gives back to the free list when it lets go of them: those it is the last holder of."""
+        return sum(1 for pg in self.pages[n] if self.allocator.holders(pg) == 1)
+
     @property
     def free_pages(self) -> Optional[int]:
-        """Pages of the pool no slot holds (a paged session; None otherwise): what a scheduler may still admit or grow into."""
+        """Pages of the pool no slot holds (a paged session; None otherwise): what a scheduler may still admit or grow into.
+        free_pages + the distinct pages the slots hold = the pool (a shared page counts once)."""
         return self.allocator.free_pages if self.paged else None
+
+    @property
+    def shared_pages(self) -> Optional[List[int]]:
+        """The pages more than one slot holds (after `fork` / `reorder`: closed pages, never written again while they are
+        shared), ascending; None when the session is not paged."""
+        if not self.paged:
+            return None
+        return sorted({pg for row in self.pages for pg in row if self.allocator.holders(pg) > 1})
 
     def sequence_kv(self, slot: int):
         """Sequence `slot`'s logical K and V rows, (1, H, L, D) each (copies; a paged session gathers them from its pages):
@@ -416,12 +458,104 @@ class DecodeSession:
         if not 0 <= slot < self.N:
             raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
         L = self._check_sequence(state, key_prefix, value_prefix)
-        if self.paged and -(-(L + 1) // self.page_rows) > self.allocator.free_pages + len(self.pages[slot]):
+        if self.paged and -(-(L + 1) // self.page_rows) > self.allocator.free_pages + self._reclaimable(slot):
             raise RuntimeError(f"page pool exhausted: slot {slot} needs {-(-(L + 1) // self.page_rows)} pages for a prefix of {L} "
-                               f"rows, {self.allocator.free_pages} free + {len(self.pages[slot])} of its own")
+                               f"rows, {self.allocator.free_pages} free + {self._reclaimable(slot)} of its own")
         if self.csr is not None and self.csr.col_is_pending:
             self.csr.col                              # the last step's pending columns follow the counters: emit before they move
         self._seed_slot(slot, state, key_prefix, value_prefix)
+
+    @torch.no_grad()
+    def fork(self, src: int, dsts) -> None:
+        """Parallel sampling: every slot in `dsts` drops what it held (as in `admit`) and continues as a copy of slot `src`:
+        the same length, Performer image, CNN rings and counters.  Its block table names `src`'s closed pages -- shared,
+        never copied -- and a private copy of `src`'s open page (the page the next row goes to; none when `src`'s last step
+        filled a page: the next step gives every slot a page of its own).  Paged ragged sessions only, between steps, one
+        `sea_decode_fork` call; the captured graph stays.  Refused, with nothing changed: a slot out of range (IndexError),
+        `src` in `dsts` or a repeated slot (ValueError), too few free pages (RuntimeError naming the slots)."""
+        self._require_paged("fork")
+        dsts = [int(d) for d in dsts]
+        for n in [src] + dsts:
+            if not 0 <= n < self.N:
+                raise IndexError(f"slot {n} outside 0..{self.N - 1}")
+        if src in dsts or len(set(dsts)) != len(dsts):
+            raise ValueError(f"fork({src}, {dsts}): the destinations are distinct slots other than the source")
+        parents = list(range(self.N))
+        for d in dsts:
+            parents[d] = src
+        self._move(parents)
+
+    @torch.no_grad()
+    def reorder(self, parents) -> None:
+        """Beam search (HF `_reorder_cache`): slot i continues as what slot `parents[i]` held before the call, for every i at
+        once (swaps, cycles and many-to-one included).  Slots with parents[i] == i cost nothing.  Moved slots share their
+        parent's closed pages and get a private copy of its open page, as in `fork`; the pages only the old contents of a
+        moved slot held go back to the pool after the call has taken its new pages.  Refused, with nothing changed: a
+        parent map of the wrong length (ValueError), a parent out of range (IndexError), too few free pages (RuntimeError)."""
+        self._require_paged("reorder")
+        parents = [int(p) for p in parents]
+        if len(parents) != self.N:
+            raise ValueError(f"reorder: {len(parents)} parents for {self.N} slots")
+        for p in parents:
+            if not 0 <= p < self.N:
+                raise IndexError(f"parent slot {p} outside 0..{self.N - 1}")
+        self._move(parents)
+
+    def _require_paged(self, what):
+        if not (self.ragged and self.paged):
+            raise ValueError(f"{what}: paging is required (DecodeSession.from_sequences(..., page_rows=...)): slots share "
+                             "closed pages and copy only their small state and the open page")
+
+    def _move(self, parents):
+        """Slot i := slot parents[i] as it was before the call (fork / reorder); one `sea_decode_fork` call."""
+        moves = [(p, i) for i, p in enumerate(parents) if p != i]
+        if not moves:
+            return
+        pr, alloc = self.page_rows, self.allocator
+        # each destination: the source's pages below its open index (shared), then a copy of the open page when it has one
+        opens = {}
+        for src, _ in moves:
+            o = self.lengths[src] // pr
+            opens[src] = (o, self.pages[src][o] if o < len(self.pages[src]) else -1)
+        copies = [dst for src, dst in moves if opens[src][1] >= 0]
+        if len(copies) > alloc.free_pages:
+            raise RuntimeError(f"page pool exhausted: slot(s) {copies} need a copy of their source's open page, "
+                               f"{alloc.free_pages} free")
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        # all new open pages are taken before any old page goes back: no page freed here is the target of a copy
+        fresh = alloc.take(len(copies))
+        new_open = dict(zip(copies, fresh))
+        dsts = {dst for _, dst in moves}
+        rows, n_staged = [], 0
+        for src, dst in moves:
+            stage = -1
+            if src in dsts:                           # (its state is overwritten by this call: read from a staged copy)
+                stage, n_staged = n_staged, n_staged + 1
+            rows.append((src, dst, opens[src][1], new_open.get(dst, -1), stage))
+        dev = self.kv_cache.device
+        nb = self.attention.performer.projection_matrix.shape[0]
+        staging = None
+        if n_staged:
+            per = ops.decode_fork_staging_bytes(self.image.numel() // self.N * 4, self.x_ring[0].numel() * self.x_ring.element_size(),
+                                                self.y1_ring[0].numel() * self.y1_ring.element_size(), -(-self.capacity // pr))
+            staging = torch.empty((n_staged * per,), dtype=torch.uint8, device=dev)
+        try:
+            moves_dev = torch.tensor(rows, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)   # (no host synchronise)
+            ops.decode_fork(moves_dev, n_staged, self.image, self.x_ring, self.y1_ring,
+                            self.ctr32, self.block_table, self.capacity, self.kv_cache, nb, staging)
+        except Exception:
+            alloc.give_back(fresh)
+            raise
+        # host mirrors: from the snapshot; shares before give-backs (a source's closed pages may be held by a moved slot only)
+        old_pages, old_lengths = [list(p) for p in self.pages], list(self.lengths)
+        for src, dst in moves:
+            o = opens[src][0]
+            alloc.share(old_pages[src][:o])
+            self.pages[dst] = old_pages[src][:o] + ([new_open[dst]] if dst in new_open else [])
+            self.lengths[dst] = old_lengths[src]
+        for _, dst in moves:
+            alloc.give_back(old_pages[dst])
 
     @property
     def win(self) -> torch.Tensor:

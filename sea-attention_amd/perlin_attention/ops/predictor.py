@@ -720,6 +720,40 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
                                     _p(kv_cache), kv_cache.shape[3], _p(counters), _lib.stream_ptr()), "sea_decode_stage")
 
 
+def decode_fork_staging_bytes(image_bytes: int, x_ring_bytes: int, y1_ring_bytes: int, table_entries: int) -> int:
+    """Bytes of one staging slot of `sea_decode_fork` (include/sea_hip.h): the small state of a slot, counters and table row
+    padded to 16-byte chunks."""
+    return image_bytes + x_ring_bytes + y1_ring_bytes + 16 + 16 * -(-table_entries // 4)
+
+
+@_lib.device_guarded
+def decode_fork(moves: torch.Tensor, n_staged: int, image: torch.Tensor, x_ring: torch.Tensor, y1_ring: torch.Tensor,
+                counters: torch.Tensor, block_table: torch.Tensor, capacity: int, kv_pool: torch.Tensor, nb: int,
+                staging: Optional[torch.Tensor]) -> None:
+    """`sea_decode_fork`: slots of a paged session continue as copies of other slots.  `moves` (M, 5) int32 on the device:
+    {src, dst, src_open, dst_open, stage} per destination; `image` (N * per,) fp32, rings (N, ...), counters an (N, 3) view,
+    block_table (N, n_tab) int32, kv_pool (2, P, H, page_rows, D); `staging` n_staged slots of `decode_fork_staging_bytes`
+    (None when n_staged = 0).  The caller guarantees the preconditions the header lists (distinct destinations and open pages,
+    a staging slot for every source that is also a destination)."""
+    lib = _lib.load()
+    _lib.require_gpu(moves, image, x_ring, y1_ring, counters, block_table, kv_pool, staging)
+    N = x_ring.shape[0]
+    _, P, H, page_rows, D = kv_pool.shape
+    assert moves.dtype == torch.int32 and moves.is_contiguous() and moves.dim() == 2 and moves.shape[1] == 5
+    assert image.dtype == torch.float32 and image.is_contiguous() and x_ring.is_contiguous() and y1_ring.is_contiguous()
+    assert y1_ring.shape[0] == N and kv_pool.is_contiguous() and x_ring.dtype == y1_ring.dtype == kv_pool.dtype
+    assert block_table.dtype == torch.int32 and block_table.shape[0] == N and block_table.stride(1) == 1
+    assert image.numel() * 4 == N * lib.sea_performer_state_bytes(1, H, D, int(nb), _lib.dtype_code(kv_pool.dtype)), \
+        "image: one Performer state image per slot"
+    stride = _lib.counter_stride(counters, N)
+    ring_bytes = lambda t: t[0].numel() * t.element_size()
+    _lib.check(lib.sea_decode_fork(_p(moves), moves.shape[0], int(n_staged), _lib.dtype_code(kv_pool.dtype), N, H, D, int(nb),
+                                   _p(image), _p(x_ring), ring_bytes(x_ring), _p(y1_ring), ring_bytes(y1_ring), _p(counters),
+                                   stride, _p(block_table), block_table.stride(0), int(capacity), _p(kv_pool), page_rows, P,
+                                   _p(staging), staging.numel() * staging.element_size() if staging is not None else 0, _lib.stream_ptr()),
+               "sea_decode_fork")
+
+
 def decode_cnn_supported(C: int, H: int, T_m: int, dtype) -> bool:
     """Shapes `sea_decode_cnn_tail_select` is instantiated for (csrc/sea_topk.hip: launch_decode_cnn)."""
     return (dtype in (torch.float16, torch.bfloat16) and T_m == 256 and H % 4 == 0 and 0 < H <= 40 and C == 2 * H and C % 8 == 0)
