@@ -41,12 +41,12 @@ extern "C" {
  *   4  one entry point per operator: the variants that were separate, suffixed entry points of sea_sparse_attention,
  *      sea_predictor_tail, sea_predictor_tail_select, sea_csr_emit, sea_causal_conv_c8, sea_performer_causal and
  *      sea_performer_causal_step are gone; each of these takes the variants' arguments instead (NULL / 0 / 1 = not wanted)
- *      Later, additive (no bump): the *_ragged entries of the decode step (per-sequence positions: sea_decode_stage,
- *      sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention, sea_csr_emit); then the *_paged
- *      entries (K / V in a pool of pages with a block table per sequence: sea_decode_stage, sea_performer_causal_step,
- *      sea_sparse_attention); then sea_decode_fork (fork / beam reorder of a paged session's slots)
+ *   5  one entry point per operator again: the decode step's per-sequence (*_ragged) and paged (*_paged) entries of
+ *      sea_decode_stage, sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention and sea_csr_emit are
+ *      gone; each of these takes their trailing arguments instead (stride 0 / NULL block table = the shared form); ABI 4 had
+ *      also gained sea_decode_fork
  *      */
-#define SEA_ABI_VERSION 4
+#define SEA_ABI_VERSION 5
 
 enum sea_dtype { SEA_F32 = 0, SEA_F16 = 1, SEA_BF16 = 2 };
 
@@ -111,23 +111,19 @@ int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst,
  * caches' row count), so sea_sparse_attention is called with that same T_src; values_out must be NULL.  A thinned pixel is
  * stepped in fp32 on the KEY alone and the head offset is added as an integer, so the capacity changes no id: needs
  * H * T_src < 2^31 (int32 ids) and T_src < 2^24 (fp32-exact keys).  Where H * T_src < 2^24 the ids are the stateless
- * form's bit for bit. */
+ * form's bit for bit.
+ * A length PER SEQUENCE, t_src_stride > 0 (the decode form of a batch whose sequences sit at different positions; 0 = one
+ * length for the batch): batch item n's rows follow t_src_dev[n * t_src_stride], ids are head * T_src + key with T_src the
+ * capacity as above.  A non-zero stride with t_src_dev = NULL, or a negative one: SEA_EINVAL; with values_out:
+ * SEA_EUNSUPPORTED. */
 int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off,
                  int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
                  int64_t T_src, int is_causal, int max_k,
                  void* col, int idx_bytes, int64_t col_stride_n, int64_t z_cap,
                  float* values_out,
                  const int32_t* t_src_dev, /* decode form, or NULL */
+                 int64_t t_src_stride,     /* per-sequence lengths, or 0 */
                  sea_stream_t stream);
-/* The decode form with a length PER SEQUENCE (a batch whose sequences sit at different positions): batch item n's rows
- * follow t_src_dev[n * t_src_stride] (t_src_stride >= 1), ids are head * T_cap + key.  No values output.  NULL t_src_dev or
- * a stride < 1: SEA_EINVAL; shapes as for sea_csr_emit's decode form. */
-int sea_csr_emit_ragged(const uint32_t* bits, const void* crow, const int32_t* head_off,
-                        int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
-                        int64_t T_cap, int is_causal, int max_k,
-                        void* col, int idx_bytes, int64_t col_stride_n, int64_t z_cap,
-                        const int32_t* t_src_dev, int64_t t_src_stride,
-                        sea_stream_t stream);
 
 /* Per-(row, head) offsets of a foreign flat CSR whose rows are grouped by ascending head
  * (replaces __flat_csr_sdbmm_tch_compute, flat_csr_sdbmm.py:48-127). */
@@ -239,6 +235,20 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * kernel does from `col`).  Same arithmetic in the same order as sea_csr_emit + the plain form: the step stays bitwise
  * the stateless forward; the emit launch (or the emit phase of sea_decode_cnn_tail_select: pass col = NULL there) and the
  * crow -> col -> K / V load chain leave the position's critical path.
+ *
+ * A length PER SEQUENCE, t_src_stride > 0 (the decode form only; 0 = one length for the batch): sequence n's row widths follow
+ * t_src_dev[n * t_src_stride]; T_src is the caches' capacity the ids are encoded with.  The gather path, no probs_out, no
+ * plan; bits and t_src_dev are required (NULL: SEA_EINVAL, as is a negative stride).  Per workgroup the length is one scalar
+ * load: the same kernels, the same bits per sequence as the shared-length form at that sequence's length.
+ *
+ * PAGED K / V, block_table != NULL (the one-row decode form with a length per sequence: T_dst = 1, 16-bit data, D in {64, 80,
+ * 128}, T_m <= 256).  k / v are the K / V halves of a page pool (P, H, page_rows, D) with element strides [page, head, row];
+ * sequence n's key r lives in page block_table[n * table_stride + r / page_rows] (int32, on the device) at row r % page_rows.
+ * Keys and column ids stay logical: ids are head * T_src + key as in the contiguous form, and the context rows are bitwise
+ * that form's.  page_rows: a power of two and a multiple of the Performer chunk of D (sea_performer_chunk_rows);
+ * table_stride >= ceil(T_src / page_rows), at most 4096 pages per table row; the page stride must stay below 4 GB and a page
+ * below 2 GB.  Null pointers, t_src_stride = 0, a bad page size or table stride: SEA_EINVAL; other dtypes / D / shapes:
+ * SEA_EUNSUPPORTED.  Without a table, page_rows and table_stride must be 0 (else SEA_EINVAL).
  */
 enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2 };
 int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
@@ -255,40 +265,9 @@ int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
                          int flags,
                          const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols, /* fused form */
                          const int32_t* t_src_dev, /* decode form, or NULL */
+                         int64_t t_src_stride,     /* per-sequence lengths, or 0 */
+                         const int32_t* block_table, int64_t table_stride, int64_t page_rows, /* paged K / V, or NULL, 0, 0 */
                          sea_stream_t stream);
-/* The decode form with a length PER SEQUENCE: sequence n's row widths follow t_src_dev[n * t_src_stride] (t_src_stride >= 1);
- * T_cap is the caches' capacity the ids are encoded with.  The gather path, no probs_out, no plan; bits and t_src_dev are
- * required (NULL: SEA_EINVAL).  Per workgroup the length is one scalar load: the same kernels, the same bits per sequence
- * as the shared-length form at that sequence's length. */
-int sea_sparse_attention_ragged(const void* q, const void* k, const void* v, int dtype,
-                                int64_t N, int64_t H, int64_t T_dst, int64_t T_cap, int64_t D,
-                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                const int32_t* crow, const int32_t* col, int64_t col_stride_n,
-                                const int32_t* head_off,
-                                const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
-                                void* out, int out_dtype, const int64_t* out_strides,
-                                const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                const int32_t* t_src_dev, int64_t t_src_stride,
-                                sea_stream_t stream);
-/* Paged K / V, the one-row decode form of sea_sparse_attention_ragged (T_dst = 1, 16-bit data, D in {64, 80, 128},
- * T_m <= 256; bits and t_src_dev required).  k / v are the K / V halves of a page pool (P, H, page_rows, D) with element
- * strides [page, head, row]; sequence n's key r lives in page block_table[n * table_stride + r / page_rows] (int32, on the
- * device) at row r % page_rows.  Keys and column ids stay logical: ids are head * T_cap + key as in the contiguous form, and the
- * context rows are bitwise that form's.  page_rows: a power of two and a multiple of the Performer chunk of D
- * (sea_performer_chunk_rows); table_stride >= ceil(T_cap / page_rows), at most 4096 pages per table row; the page stride must
- * stay below 4 GB and a page below 2 GB.  Null pointers, a bad page size or table stride: SEA_EINVAL; other dtypes / D /
- * shapes: SEA_EUNSUPPORTED. */
-int sea_sparse_attention_paged(const void* q, const void* k, const void* v, int dtype,
-                               int64_t N, int64_t H, int64_t T_dst, int64_t T_cap, int64_t D,
-                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                               const int32_t* crow, const int32_t* col, int64_t col_stride_n,
-                               const int32_t* head_off,
-                               const float* row_scale, const void* avg, const int64_t* avg_strides, const float* mix,
-                               void* out, int out_dtype, const int64_t* out_strides,
-                               const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                               const int32_t* t_src_dev, int64_t t_src_stride,
-                               const int32_t* block_table, int64_t table_stride, int64_t page_rows,
-                               sea_stream_t stream);
 int64_t sea_attention_few_rows(void);
 
 /* Backward of the fused operator WITHOUT its epilogue (o = sum_e softmax_e(q.k_e) v_e; the caller applies row scale and mix
@@ -428,7 +407,10 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  *   sea_csr_emit writes them, at most z_cap per item -- the emit of the one new row runs inside this launch too (one launch
  *   less per position); NULL = the caller runs that emit.
  * x_new (N, C/8, 64, 8); x_ring (N, ring_x, C/8, 64, 8); y1_ring (N, ring_y, C/8, 64, 8); y2 (N, C/8, 64, 8) scratch, all `dtype`
- * (16-bit); ring sizes > 2 * dilation.  C = 2 H <= 80, H % 4 == 0. */
+ * (16-bit); ring sizes > 2 * dilation.  C = 2 H <= 80, H % 4 == 0.
+ * A counter triple PER SEQUENCE, counter_stride > 0 (0 = the batch's one triple): sequence n's {seen, T_src, T_src just
+ * finished} at counters + n * counter_stride (counter_stride >= 3, else SEA_EINVAL).  Workgroup n reads its own triple (ring
+ * slots, row widths, the in-launch emit); the last workgroup advances all N triples as above. */
 int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
                                int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
                                const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
@@ -436,18 +418,7 @@ int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, v
                                const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
                                int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
                                int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                               int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream);
-/* The same with a counter triple PER SEQUENCE: sequence n's {seen, T_src, T_src just finished} at counters + n * counter_stride
- * (counter_stride >= 3, else SEA_EINVAL).  Workgroup n reads its own triple (ring slots, row widths, the in-launch emit); the
- * last workgroup advances all N triples as above. */
-int sea_decode_cnn_tail_select_ragged(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
-                                      int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                                      const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
-                                      int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
-                                      const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                                      int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                      int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                                      int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
+                               int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
 
 /* Causal cumulative average out[n,h,t,:] = sum_{s<=t} v[n,h,s,:] / (t+1), fp32 accumulation.
  * Replaces `avg_v.cumsum(-2) / arange(1..T)` (attention.py:1220-1222).  out (N,H,T,D) contiguous. */
@@ -572,36 +543,26 @@ int sea_performer_plan(int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb, i
  * argument is not read.  k / v are then the BASES (row 0) of the kv-caches -- they already hold the new rows -- and pos the
  * BASE of the value embedding: the kernel finds the chunk boundary itself and walks the open chunk from there.  q / out /
  * avg_out: the T new rows.  state_in and state_out are both required and may be one image (updated in place; it changes
- * only when a chunk completes).  One segment: n_segments = 1 (else SEA_EUNSUPPORTED), workspace not read. */
+ * only when a chunk completes).  One segment: n_segments = 1 (else SEA_EUNSUPPORTED), workspace not read.
+ * A position PER SEQUENCE, t_base_stride > 0 (the device-position form; 0 = one position for the batch): sequence n has seen
+ * t_base_dev[n * t_base_stride] rows.  Its chunk boundary, cache rows, embedding rows and state image (the n-th contiguous H
+ * images of state_in / state_out) follow from that.  t_base_dev NULL or a negative stride: SEA_EINVAL.
+ * PAGED K / V, block_table != NULL (a position per sequence, one new row each: T = 1): k / v are the K / V halves of a page pool
+ * (P, H, page_rows, D), strides [page, head, row].  Sequence n's open chunk c0 .. seen (c0 = floor(seen / C) * C) lies in page
+ * block_table[n * table_stride + c0 / page_rows] from row c0 % page_rows on: page_rows is a power of two and a multiple of C,
+ * so one table lookup per workgroup serves the step.  capacity: the logical rows a table row covers (table_stride >=
+ * ceil(capacity / page_rows)).  Everything else as in the per-sequence form, bitwise.  A table with t_base_stride = 0, or
+ * page_rows / table_stride / capacity non-zero without one: SEA_EINVAL. */
 int64_t sea_performer_chunk_rows(int64_t D, int64_t nb, int dtype);
 int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype);
 int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
                               const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                               int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
-                              int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev, int64_t n_segments,
-                              void* workspace, int64_t workspace_bytes, sea_stream_t stream);
-/* The device-position form with a position PER SEQUENCE: sequence n has seen t_base_dev[n * t_base_stride] rows
- * (t_base_stride >= 1).  Its chunk boundary, cache rows, embedding rows and state image (the n-th contiguous H images of
- * state_in / state_out) follow from that.  t_base_dev NULL or a stride < 1: SEA_EINVAL.  One segment. */
-int sea_performer_causal_step_ragged(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                     const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                     const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                     int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
-                                     int64_t state_bytes, const int32_t* t_base_dev, int64_t t_base_stride,
-                                     sea_stream_t stream);
-/* Paged K / V, one new row per sequence (T = 1): k / v are the K / V halves of a page pool (P, H, page_rows, D), strides
- * [page, head, row].  Sequence n's open chunk c0 .. seen (c0 = floor(seen / C) * C) lies in page
- * block_table[n * table_stride + c0 / page_rows] from row c0 % page_rows on: page_rows is a power of two and a multiple of C,
- * so one table lookup per workgroup serves the step.  capacity: the logical rows a table row covers (table_stride >=
- * ceil(capacity / page_rows)).  Everything else as in sea_performer_causal_step_ragged, bitwise. */
-int sea_performer_causal_step_paged(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                    const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                    const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                    int64_t pos_stride, void* out, void* avg_out, const void* state_in, void* state_out,
-                                    int64_t state_bytes, const int32_t* t_base_dev, int64_t t_base_stride,
-                                    const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t capacity,
-                                    sea_stream_t stream);
+                              int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev, int64_t t_base_stride,
+                              int64_t n_segments, void* workspace, int64_t workspace_bytes,
+                              const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t capacity,
+                              sea_stream_t stream);
 
 /* ---- decode step with the position in DEVICE memory ------------------------------------------------------------------
  * The reference's generation loop (src/main/opt_generate.py:131 -> attention.py use_cache branches + attention_state.py)
@@ -620,27 +581,21 @@ int64_t sea_sparse_attention_bytes(int64_t Z, int64_t N, int64_t H, int64_t T_ds
  *   strides {n, h}, feature stride 1, 16-byte aligned rows): q is copied into q_in (N,H,D), k / v are written into
  *   kv_cache (2,N,H,capacity,D) at row counters[0] (device int32: the rows the session's state has seen).  Replaces three
  *   input copies and an index_copy_ of the framework (four launches of ~4.5 us).
+ *   A counter PER SEQUENCE, counter_stride > 0 (0 = one counter for the batch): sequence n's k / v rows go to cache row
+ *   counters[n * counter_stride]; a sequence whose row lies outside the capacity writes nothing.  A negative stride: SEA_EINVAL.
+ *   PAGED, block_table != NULL (with a counter per sequence): kv_cache is a page pool (2, pool_pages, H, page_rows, D) dense
+ *   (K pages, then V pages: one page index for both); sequence n's k / v rows go to page block_table[n * table_stride +
+ *   ctr / page_rows], row ctr % page_rows (ctr = counters[n * counter_stride]).  A row at or beyond `capacity`, or whose table
+ *   entry is outside 0 .. pool_pages-1, writes nothing.  Page rule and refusals as for sea_sparse_attention's paged form; a
+ *   table with counter_stride = 0, or page_rows / table_stride / pool_pages non-zero without one: SEA_EINVAL.
  * sea_c8_window_shift: xs (N, rows, row_bytes) moved up by one row in place (xs[n, r] = xs[n, r + 1]): the predictor CNN's
  *   window after a step whose MLP wrote the new row behind it (sea_predictor_mlp with x_c8_stride_n).  `counters` (optional):
  *   two device int32 advanced by one by the same launch -- the LAST of a step, so every reader of the step is done. */
 int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
                      const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                     void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, sea_stream_t stream);
-/* sea_decode_stage with a counter PER SEQUENCE: sequence n's k / v rows go to cache row counters[n * counter_stride]
- * (counter_stride >= 1, else SEA_EINVAL); a sequence whose row lies outside the capacity writes nothing. */
-int sea_decode_stage_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                            void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
-                            sea_stream_t stream);
-/* sea_decode_stage_ragged into a page pool kv_pool (2, pool_pages, H, page_rows, D) dense (K pages, then V pages: one page
- * index for both): sequence n's k / v rows go to page block_table[n * table_stride + ctr / page_rows], row ctr % page_rows
- * (ctr = counters[n * counter_stride]).  A row at or beyond `capacity`, or whose table entry is outside 0 .. pool_pages-1,
- * writes nothing.  Page rule and refusals as for sea_sparse_attention_paged. */
-int sea_decode_stage_paged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                           void* q_in, void* kv_pool, int64_t capacity, const int32_t* counters, int64_t counter_stride,
-                           const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
-                           sea_stream_t stream);
+                     void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                     const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                     sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
 
 /* Fork / beam reorder of a paged ragged session's slots, between two steps (perlin_attention/decode.py: DecodeSession.fork and

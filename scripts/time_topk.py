@@ -20,7 +20,7 @@ head_off = torch.empty((NB, T, H + 1), dtype=torch.int32, device=dev); crow = to
 col = torch.empty((NB, z_cap), dtype=torch.int32, device=dev)
 def sel(): _lib.check(lib.sea_topk_select(P(probs), 2, NB, H, T, T_M, *probs.stride()[:3], P(keep), 0, T, 1, k, P(bits), None, P(row_nnz), P(head_off), st), "sel")
 def scan(): _lib.check(lib.sea_csr_row_scan(P(row_nnz), NB, T, P(crow), 4, st), "scan")
-def emit(): _lib.check(lib.sea_csr_emit(P(bits), P(crow), P(head_off), NB, H, T, T_M, T, 1, k, P(col), 4, col.stride(0), z_cap, None, None, st), "emit")
+def emit(): _lib.check(lib.sea_csr_emit(P(bits), P(crow), P(head_off), NB, H, T, T_M, T, 1, k, P(col), 4, col.stride(0), z_cap, None, None, 0, st), "emit")
 res = {}
 for name, fn in [("select", sel), ("scan", scan), ("emit", emit)]:
     for _ in range(3): fn()

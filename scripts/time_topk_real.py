@@ -31,7 +31,7 @@ head_off = torch.empty((NB, T, H + 1), dtype=torch.int32, device=dev); crow = to
 col = torch.empty((NB, z_cap), dtype=torch.int32, device=dev)
 def sel(p): _lib.check(lib.sea_topk_select(P(p), 2, NB, H, T, T_M, *p.stride()[:3], P(keep), 0, T, 1, k, P(bits), None, P(row_nnz), P(head_off), st), "sel")
 def scan(p): _lib.check(lib.sea_csr_row_scan(P(row_nnz), NB, T, P(crow), 4, st), "scan")
-def emit(p): _lib.check(lib.sea_csr_emit(P(bits), P(crow), P(head_off), NB, H, T, T_M, T, 1, k, P(col), 4, col.stride(0), z_cap, None, None, st), "emit")
+def emit(p): _lib.check(lib.sea_csr_emit(P(bits), P(crow), P(head_off), NB, H, T, T_M, T, 1, k, P(col), 4, col.stride(0), z_cap, None, None, 0, st), "emit")
 synth = torch.softmax(torch.randn((NB, H, T, T_M), device=dev), -1).to(dt)
 for tag, p in (("real", probs), ("synthetic", synth)):
     res = {}

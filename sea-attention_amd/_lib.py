@@ -9,7 +9,7 @@ import torch
 from . import _build
 
 SEA_F32, SEA_F16, SEA_BF16 = 0, 1, 2
-ABI_VERSION = 4            # include/sea_hip.h: SEA_ABI_VERSION
+ABI_VERSION = 5            # include/sea_hip.h: SEA_ABI_VERSION
 _DTYPES = {torch.float32: SEA_F32, torch.float16: SEA_F16, torch.bfloat16: SEA_BF16}
 
 _lib = None
@@ -26,8 +26,7 @@ _SIGNATURES = {
     "sea_mask_to_bits": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, i64, c_int, c_int,
                           ptr, ptr, ptr, ptr], c_int),
     "sea_csr_row_scan": ([ptr, i64, i64, ptr, c_int, ptr], c_int),
-    "sea_csr_emit": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, ptr, ptr], c_int),
-    "sea_csr_emit_ragged": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, i64, ptr], c_int),
+    "sea_csr_emit": ([ptr, ptr, ptr, i64, i64, i64, i64, i64, c_int, c_int, ptr, c_int, i64, i64, ptr, ptr, i64, ptr], c_int),
     "sea_csr_head_offsets": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr], c_int),
     "sea_csr_sddmm": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, ptr, ptr, c_int, i64, ptr, ptr], c_int),
     "sea_csr_softmax": ([ptr, ptr, i64, i64, i64, i64, ptr, ptr, c_int, i64, ptr], c_int),
@@ -35,13 +34,7 @@ _SIGNATURES = {
     "sea_csr_spmm": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, ptr, ptr, c_int, i64, ptr, ptr, ptr], c_int),
     "sea_sparse_attention": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
                               ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int,
-                              ptr, i64, c_int, c_int, c_int, ptr, ptr], c_int),
-    "sea_sparse_attention_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                                     ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p,
-                                     ptr, i64, c_int, c_int, c_int, ptr, i64, ptr], c_int),
-    "sea_sparse_attention_paged": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
-                                    ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p,
-                                    ptr, i64, c_int, c_int, c_int, ptr, i64, ptr, i64, i64, ptr], c_int),
+                              ptr, i64, c_int, c_int, c_int, ptr, i64, ptr, i64, i64, ptr], c_int),
     "sea_sparse_attention_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
                                   ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_sparse_attention_bwd_workspace_bytes": ([i64, i64, i64, i64], i64),
@@ -65,25 +58,16 @@ _SIGNATURES = {
                             ptr, i64, ptr, i64, ptr, ptr], c_int),
     "sea_decode_cnn_tail_select": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int, c_int,
                                     ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr, ptr, ptr, ptr,
-                                    ptr, i64, i64, i64, ptr, ptr], c_int),
-    "sea_decode_cnn_tail_select_ragged": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int,
-                                           c_int, ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr,
-                                           ptr, ptr, ptr, ptr, i64, i64, i64, ptr, i64, ptr], c_int),
+                                    ptr, i64, i64, i64, ptr, i64, ptr], c_int),
     "sea_performer_causal": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
                               i64, ptr, i64, ptr], c_int),
     "sea_performer_state_bytes": ([i64, i64, i64, i64, c_int], i64),
     "sea_performer_chunk_rows": ([i64, i64, c_int], i64),
     "sea_attention_few_rows": ([], i64),
     "sea_performer_causal_step": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
-                                   ptr, ptr, i64, i64, ptr, i64, ptr, i64, ptr], c_int),
-    "sea_performer_causal_step_ragged": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
-                                          ptr, ptr, ptr, ptr, i64, ptr, i64, ptr], c_int),
-    "sea_performer_causal_step_paged": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
-                                         ptr, ptr, ptr, ptr, i64, ptr, i64, ptr, i64, i64, i64, ptr], c_int),
-    "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, ptr], c_int),
-    "sea_decode_stage_ragged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr], c_int),
-    "sea_decode_stage_paged": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64,
-                                i64, ptr], c_int),
+                                   ptr, ptr, i64, i64, ptr, i64, i64, ptr, i64, ptr, i64, i64, i64, ptr], c_int),
+    "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64, i64,
+                          ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
     "sea_decode_fork": ([ptr, i64, i64, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr, i64, ptr, i64, ptr, i64, i64, ptr, i64, i64,
                          ptr, i64, ptr], c_int),
@@ -146,8 +130,9 @@ def strides3(t):
 
 
 def counter_stride(counter, N):
-    """Row stride of a decode step's device counter: a 1-D int32 tensor is ONE counter shared by the batch (0: the
-    shared-position entry points); a 2-D (N, k) view holds one row per sequence (its row stride: the *_ragged entries)."""
+    """Row stride of a decode step's device counter: a 1-D int32 tensor is ONE counter shared by the batch (0: the shared
+    position); a 2-D (N, k) view holds one row per sequence (its row stride: the per-sequence form).  The decode entry points
+    take it as their `counter_stride` / `t_base_stride` / `t_src_stride` argument."""
     assert counter.dtype == torch.int32 and counter.is_cuda
     if counter.dim() == 2:
         assert counter.shape[0] == N and counter.stride(1) == 1 and counter.stride(0) >= counter.shape[1], \

@@ -1121,16 +1121,42 @@ static int check_dtype(const char* name, int dtype) {
   return SEA_OK;
 }
 
-static int sparse_attention_entry(const char* nm, const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                  int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                  const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                  const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                  const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                  const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                  float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
-                                  const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                  const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream,
-                                  const int32_t* table = nullptr, int64_t table_stride = 0, int page_shift = 0) {
+// t_src_stride > 0 (the decode form only: bits and t_src_dev required): per-sequence lengths, sequence n's rows follow
+// t_src_dev[n * t_src_stride].  block_table != NULL (the one-row decode form with per-sequence lengths): paged K / V -- k / v
+// are the K / V halves of a page pool, strides [page, head, row]; sequence n's key r lives in page
+// block_table[n * table_stride + r / page_rows] at row r % page_rows.  Column ids stay head * T_src + key.
+extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
+                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
+                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
+                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
+                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
+                                    float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
+                                    const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
+                                    const int32_t* t_src_dev, int64_t t_src_stride, const int32_t* block_table,
+                                    int64_t table_stride, int64_t page_rows, sea_stream_t stream) {
+  const char* nm = "sea_sparse_attention";
+  if (t_src_stride || block_table) {
+    SEA_REQUIRE(bits && t_src_dev && (!block_table || (k_strides && v_strides)), SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
+  }
+  if (block_table) {
+    SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+    if (int e = paged_layout_check(nm, dtype, D, T_src, page_rows, table_stride, N)) return e;
+    SEA_REQUIRE(T_dst == 1 && T_m > 0 && T_m <= 256, SEA_EUNSUPPORTED, "%s: the one-row decode form (T_dst = 1, T_m <= 256)", nm);
+    SEA_REQUIRE((T_src + page_rows - 1) / page_rows <= 4096, SEA_EUNSUPPORTED,
+                "%s: a table row of %lld pages does not fit the kernel's LDS (4096 at most)", nm, (long long)((T_src + page_rows - 1) / page_rows));
+    // byte offsets: the page term is 64-bit (a page index times the page stride, which must fit 32 bits), the row term 32-bit
+    // (24-bit factors: __umul24 of the row and the row stride)
+    const int64_t esz = 2;
+    SEA_REQUIRE(k_strides[0] > 0 && v_strides[0] > 0 && k_strides[0] * esz < (1ll << 32) && v_strides[0] * esz < (1ll << 32) &&
+                    k_strides[2] * esz < (1ll << 24) && v_strides[2] * esz < (1ll << 24) &&
+                    page_rows * k_strides[2] * esz < (1ll << 31) && page_rows * v_strides[2] * esz < (1ll << 31),
+                SEA_EUNSUPPORTED, "%s: page / row strides whose byte offsets do not fit (page stride < 4 GB, page < 2 GB)", nm);
+  } else {
+    SEA_REQUIRE(page_rows == 0 && table_stride == 0, SEA_EINVAL,
+                "%s: null pointer: page_rows / table_stride without a block_table", nm);
+  }
   // bits != NULL: the fused form -- `col` is written by the launch, not read -- which runs on the gather kernels;
   // t_src_dev != NULL: its decode form (T_src is then the capacity of the K / V caches)
   SEA_REQUIRE(bits != nullptr || t_src_dev == nullptr, SEA_EINVAL, "%s: the decode form (t_src_dev) needs bits", nm);
@@ -1177,7 +1203,7 @@ static int sparse_attention_entry(const char* nm, const void* q, const void* k, 
   SEA_REQUIRE(t_src_stride >= 0 && t_src_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad T_src stride %lld", nm,
               (long long)t_src_stride);
   p.t_src_stride = (int)t_src_stride;
-  p.table = table; p.table_stride = (int)table_stride; p.page_shift = page_shift;
+  p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && probs_out == nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
                 "%s: the decode form takes T_dst <= %d rows per sequence, no probs_out", nm, SEA_ATTN_WARM_ROWS);
@@ -1218,70 +1244,6 @@ static int sparse_attention_entry(const char* nm, const void* q, const void* k, 
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: unsupported head size %lld", nm, (long long)D);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                    int64_t T_dst, int64_t T_src, int64_t D, const int64_t* q_strides,
-                                    const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                    const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                    const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                    const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                    float* probs_out, int64_t probs_stride_n, const uint8_t* block_path, int flags,
-                                    const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                    const int32_t* t_src_dev, sea_stream_t stream) {
-  return sparse_attention_entry("sea_sparse_attention", q, k, v, dtype, N, H, T_dst, T_src, D, q_strides, k_strides, v_strides,
-                                crow, col, col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides,
-                                probs_out, probs_stride_n, block_path, flags, bits, T_m, is_causal, max_k, write_cols, t_src_dev,
-                                0, stream);
-}
-
-// per-sequence lengths (the decode form only: bits and t_src_dev required): sequence n's rows follow t_src_dev[n * t_src_stride]
-extern "C" int sea_sparse_attention_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                           int64_t T_dst, int64_t T_cap, int64_t D, const int64_t* q_strides,
-                                           const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                           const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                           const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                           const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                           const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                           const int32_t* t_src_dev, int64_t t_src_stride, sea_stream_t stream) {
-  const char* nm = "sea_sparse_attention_ragged";
-  SEA_REQUIRE(bits && t_src_dev, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
-  return sparse_attention_entry(nm, q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides, crow, col,
-                                col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr, 0,
-                                nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_cols, t_src_dev, t_src_stride, stream);
-}
-
-// paged K / V (the one-row decode form only): k / v are the K / V halves of a page pool, strides [page, head, row]; sequence n's
-// key r lives in page block_table[n * table_stride + r / page_rows] at row r % page_rows.  Column ids stay head * T_cap + key.
-extern "C" int sea_sparse_attention_paged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                                          int64_t T_dst, int64_t T_cap, int64_t D, const int64_t* q_strides,
-                                          const int64_t* k_strides, const int64_t* v_strides, const int32_t* crow,
-                                          const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                          const float* row_scale, const void* avg, const int64_t* avg_strides,
-                                          const float* mix, void* out, int out_dtype, const int64_t* out_strides,
-                                          const uint32_t* bits, int64_t T_m, int is_causal, int max_k, int write_cols,
-                                          const int32_t* t_src_dev, int64_t t_src_stride, const int32_t* block_table,
-                                          int64_t table_stride, int64_t page_rows, sea_stream_t stream) {
-  const char* nm = "sea_sparse_attention_paged";
-  SEA_REQUIRE(bits && t_src_dev && block_table && k_strides && v_strides, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
-  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
-  if (int e = paged_layout_check(nm, dtype, D, T_cap, page_rows, table_stride, N)) return e;
-  SEA_REQUIRE(T_dst == 1 && T_m > 0 && T_m <= 256, SEA_EUNSUPPORTED, "%s: the one-row decode form (T_dst = 1, T_m <= 256)", nm);
-  SEA_REQUIRE((T_cap + page_rows - 1) / page_rows <= 4096, SEA_EUNSUPPORTED,
-              "%s: a table row of %lld pages does not fit the kernel's LDS (4096 at most)", nm, (long long)((T_cap + page_rows - 1) / page_rows));
-  // byte offsets: the page term is 64-bit (a page index times the page stride, which must fit 32 bits), the row term 32-bit
-  // (24-bit factors: __umul24 of the row and the row stride)
-  const int64_t esz = 2;
-  SEA_REQUIRE(k_strides[0] > 0 && v_strides[0] > 0 && k_strides[0] * esz < (1ll << 32) && v_strides[0] * esz < (1ll << 32) &&
-                  k_strides[2] * esz < (1ll << 24) && v_strides[2] * esz < (1ll << 24) &&
-                  page_rows * k_strides[2] * esz < (1ll << 31) && page_rows * v_strides[2] * esz < (1ll << 31),
-              SEA_EUNSUPPORTED, "%s: page / row strides whose byte offsets do not fit (page stride < 4 GB, page < 2 GB)", nm);
-  return sparse_attention_entry(nm, q, k, v, dtype, N, H, T_dst, T_cap, D, q_strides, k_strides, v_strides, crow, col,
-                                col_stride_n, head_off, row_scale, avg, avg_strides, mix, out, out_dtype, out_strides, nullptr, 0,
-                                nullptr, SEA_ATTN_GATHER, bits, T_m, is_causal, max_k, write_cols, t_src_dev, t_src_stride, stream,
-                                block_table, table_stride, __builtin_ctzll(page_rows));
 }
 
 extern "C" int64_t sea_attention_few_rows(void) { return SEA_ATTN_FEW_ROWS; }

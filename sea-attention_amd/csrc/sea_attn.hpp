@@ -44,8 +44,8 @@ struct AttnParams {
   // column ids are encoded with (head * T_src + key) and the K / V caches are laid out for.  NULL: widths follow T_src.
   const int32_t* t_src_dev;
   int t_src_stride;   // 0: one length for the batch; else sequence n's at t_src_dev[n * t_src_stride] (per-sequence positions)
-  // paged K / V (sea_sparse_attention_paged; sparse_attn_decode1_kernel's PAGED form): k / v are the K / V halves of a page
-  // pool, strides [page, head, row]; sequence n's key r lives in page table[n * table_stride + (r >> page_shift)] at row
+  // paged K / V (a block table; sparse_attn_decode1_kernel's PAGED form): k / v are the K / V halves of a page pool,
+  // strides [page, head, row]; sequence n's key r lives in page table[n * table_stride + (r >> page_shift)] at row
   // r & (page_rows - 1).  Keys and column ids stay logical (head * T_src + key): only the K / V loads translate
   const int32_t* table;
   int table_stride, page_shift;

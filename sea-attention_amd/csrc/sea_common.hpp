@@ -53,7 +53,7 @@ struct DevOnce {
     }                                                                                                                \
   } while (0)
 
-// ---- paged K / V (the *_paged decode entries) ------------------------------------------------
+// ---- paged K / V (the decode entries given a block table) ------------------------------------
 // page_rows is a power of two and a multiple of the Performer chunk C of the head size (sea_performer_chunk_rows: 64 at
 // d = 64, 32 at d = 80 / 128), so the rows a chunk-aligned step reads -- the open chunk and the new row -- lie in one page.
 // A sequence's table row covers its capacity: table_stride >= ceil(capacity / page_rows).

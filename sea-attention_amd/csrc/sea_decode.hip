@@ -26,7 +26,7 @@ struct StageParams {
   const int32_t* ctr;                // [seen, tsrc] of THIS step: the new token's cache row is ctr[0]
   int N, H, D, cap;
 };
-// PAGED (sea_decode_stage_paged): kv_cache is a pool (2, pool_pages, H, page_rows, D); sequence n's logical row r lives in
+// PAGED (a block table): kv_cache is a pool (2, pool_pages, H, page_rows, D); sequence n's logical row r lives in
 // page table[n * table_stride + r / page_rows] at row r % page_rows (page_rows = 1 << page_shift).  A type of its own, so that
 // the other forms' kernel arguments -- and code -- stay what they were
 struct StagePagedParams : StageParams {
@@ -154,11 +154,26 @@ __global__ __launch_bounds__(256) void decode_fork_kernel(ForkParams p) {
 
 using namespace sea;
 
-static int decode_stage_entry(const char* nm, const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H,
-                              int64_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                              void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
-                              const int32_t* table, int64_t table_stride, int page_shift, int64_t pool_pages,
-                              sea_stream_t stream) {
+// counter_stride > 0: a counter PER SEQUENCE, sequence n's new row goes to cache row counters[n * counter_stride];
+// block_table != NULL (with a counter per sequence): paged K / V, the rows go to page block_table[n * table_stride + ctr /
+// page_rows] of the pool (2, pool_pages, H, page_rows, D), row ctr % page_rows
+extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                                const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                                sea_stream_t stream) {
+  const char* nm = "sea_decode_stage";
+  if (counter_stride || block_table)
+    SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: counter_stride must be >= 1 (got %lld)", nm, (long long)counter_stride);
+  if (block_table) {
+    SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+    if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+    SEA_REQUIRE(pool_pages > 0 && 2 * pool_pages * H * page_rows * D < (1ll << 62) && pool_pages < (1ll << 31), SEA_EINVAL,
+                "%s: bad pool of %lld pages", nm, (long long)pool_pages);
+  } else {
+    SEA_REQUIRE(page_rows == 0 && table_stride == 0 && pool_pages == 0, SEA_EINVAL,
+                "%s: null pointer: page_rows / table_stride / pool_pages without a block_table", nm);
+  }
   SEA_REQUIRE(q && k && v && q_strides && k_strides && v_strides && q_in && kv_cache && counters, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
   SEA_REQUIRE(N > 0 && H > 0 && D > 0 && capacity > 0 && N * H * D < (1ll << 24), SEA_EINVAL, "%s: bad shape", nm);
@@ -172,13 +187,14 @@ static int decode_stage_entry(const char* nm, const void* q, const void* k, cons
   p.q = q; p.k = k; p.v = v; p.q_in = q_in; p.kv_cache = kv_cache; p.ctr = counters;
   for (int i = 0; i < 2; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
   p.N = (int)N; p.H = (int)H; p.D = (int)D; p.cap = (int)capacity;
-  p.table = table; p.table_stride = (int)table_stride; p.page_shift = page_shift; p.pool_pages = (int)pool_pages;
+  p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
+  p.pool_pages = (int)pool_pages;
   hipStream_t s = (hipStream_t)stream;
   const int64_t chunks = 3 * N * H * (D / 8);
   const unsigned blocks = (unsigned)((chunks + 255) / 256 > 1024 ? 1024 : (chunks + 255) / 256);
   const int cs = (int)counter_stride;
   const StageParams b = p;                                   // (the unpaged forms' arguments)
-  if (table) {
+  if (block_table) {
     if (dtype == SEA_F16) hipLaunchKernelGGL((decode_stage_kernel<__half, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
     else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
   } else if (dtype == SEA_F16) {
@@ -190,42 +206,6 @@ static int decode_stage_entry(const char* nm, const void* q, const void* k, cons
   }
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, sea_stream_t stream) {
-  return decode_stage_entry("sea_decode_stage", q, k, v, dtype, N, H, D, q_strides, k_strides, v_strides, q_in, kv_cache, capacity,
-                            counters, 0, nullptr, 0, 0, 0, stream);
-}
-
-// per-sequence positions: sequence n's new row goes to cache row counters[n * counter_stride] (counter_stride >= 1)
-extern "C" int sea_decode_stage_ragged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                                       const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                       void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters,
-                                       int64_t counter_stride, sea_stream_t stream) {
-  const char* nm = "sea_decode_stage_ragged";
-  SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: counter_stride must be >= 1 (got %lld)", nm, (long long)counter_stride);
-  return decode_stage_entry(nm, q, k, v, dtype, N, H, D, q_strides, k_strides, v_strides, q_in, kv_cache, capacity, counters,
-                            counter_stride, nullptr, 0, 0, 0, stream);
-}
-
-// paged K / V: sequence n's new rows go to page block_table[n * table_stride + ctr / page_rows] of the pool
-// (2, pool_pages, H, page_rows, D), row ctr % page_rows
-extern "C" int sea_decode_stage_paged(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                                      const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                      void* q_in, void* kv_pool, int64_t capacity, const int32_t* counters,
-                                      int64_t counter_stride, const int32_t* block_table, int64_t table_stride,
-                                      int64_t page_rows, int64_t pool_pages, sea_stream_t stream) {
-  const char* nm = "sea_decode_stage_paged";
-  SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: counter_stride must be >= 1 (got %lld)", nm, (long long)counter_stride);
-  SEA_REQUIRE(block_table, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
-  if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
-  SEA_REQUIRE(pool_pages > 0 && 2 * pool_pages * H * page_rows * D < (1ll << 62) && pool_pages < (1ll << 31), SEA_EINVAL,
-              "%s: bad pool of %lld pages", nm, (long long)pool_pages);
-  return decode_stage_entry(nm, q, k, v, dtype, N, H, D, q_strides, k_strides, v_strides, q_in, kv_pool, capacity, counters,
-                            counter_stride, block_table, table_stride, __builtin_ctzll(page_rows), pool_pages, stream);
 }
 
 extern "C" int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream) {

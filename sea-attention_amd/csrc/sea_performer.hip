@@ -65,8 +65,8 @@ struct PerfParams {
   // device-resident form of t_base (a captured decode step replayed as a HIP graph: the position lives in memory).  When
   // set, `pos` is the BASE of the embedding table and the kernel reads its rows from row *t_base_dev on.
   const int32_t* t_base_dev;
-  // per-sequence positions (sea_performer_causal_step_ragged, the SEQ instantiations of the 16-bit kernels): sequence n has
-  // seen t_base_dev[n * t_base_stride] rows.  0: the one position above
+  // per-sequence positions (t_base_stride > 0, the SEQ instantiations of the 16-bit kernels): sequence n has seen
+  // t_base_dev[n * t_base_stride] rows.  0: the one position above
   int t_base_stride;
   // chunk-aligned step (the 16-bit MFMA kernels): the state image is the state at the last CHUNK BOUNDARY c0 =
   // floor(t_base / C) * C, and the open chunk's rows c0 .. t_base-1 are walked again (k, v, pos from the caller's kv-cache,
@@ -74,8 +74,8 @@ struct PerfParams {
   // bitwise the stateless result for any split of the sequence into calls.  k / v / pos then point at row c0 (with
   // t_base_dev: at row 0 of the caches / the table, the kernel adds c0); q / out / avg at the first new row.
   int aligned;
-  // paged K / V (sea_performer_causal_step_paged, the PAGED instantiations of the SEQ forms): k / v are the K / V halves of a
-  // page pool, strides [page, head, row]; sequence n's chunk c0 lives in page table[n * table_stride + c0 / page_rows] at row
+  // paged K / V (a block table, the PAGED instantiations of the SEQ forms): k / v are the K / V halves of a page pool,
+  // strides [page, head, row]; sequence n's chunk c0 lives in page table[n * table_stride + c0 / page_rows] at row
   // c0 % page_rows (page_rows = 1 << page_shift, a multiple of C: the open chunk and the new row lie in that one page)
   const int32_t* table;
   int table_stride, page_shift;
@@ -1984,13 +1984,34 @@ extern "C" int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, in
 // state has seen, `t_base` is not read; k / v are the BASES (row 0) of the kv-caches, which already hold the new rows, pos
 // the BASE of the value-embedding table: the kernel finds the chunk boundary itself.  state_in and state_out may be the
 // same image (updated in place); one segment.
-static int perf_step_entry(const char* nm, const void* q, const void* k, const void* v, const void* pos, int dtype,
-                           const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                           int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                           void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
-                           int64_t t_base_stride, int64_t n_segments, void* workspace, int64_t workspace_bytes,
-                           sea_stream_t stream, const int32_t* table = nullptr, int64_t table_stride = 0, int page_shift = 0) {
+// t_base_stride > 0 (device-position form): a position PER SEQUENCE, sequence n has seen t_base_dev[n * t_base_stride] rows.
+// block_table != NULL (with per-sequence positions, one new row each): paged K / V -- k / v are the K / V halves of a page
+// pool (strides [page, head, row]); sequence n's open chunk c0 .. seen and its new row lie in page
+// block_table[n * table_stride + c0 / page_rows], from row c0 % page_rows on.
+extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
+                                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
+                                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                         int64_t pos_stride, void* out, void* avg_out, const void* state_in,
+                                         void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
+                                         int64_t t_base_stride, int64_t n_segments, void* workspace, int64_t workspace_bytes,
+                                         const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t capacity,
+                                         sea_stream_t stream) {
+  const char* nm = "sea_performer_causal_step";
+  if (t_base_stride || block_table) {
+    SEA_REQUIRE(t_base_dev, SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
+  }
+  if (block_table) {
+    SEA_REQUIRE(T == 1, SEA_EINVAL, "%s: one new row per sequence (T=%lld)", nm, (long long)T);
+    const PerfForm form = perf_form(dtype, D, nb);
+    SEA_REQUIRE(form.mfma16, SEA_EUNSUPPORTED, "%s: the chunk-aligned step runs on the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
+    if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+    SEA_REQUIRE(page_rows % form.C == 0, SEA_EINVAL, "%s: page_rows %lld is not a multiple of the chunk (%d rows)", nm,
+                (long long)page_rows, form.C);
+  } else {
+    SEA_REQUIRE(page_rows == 0 && table_stride == 0 && capacity == 0, SEA_EINVAL,
+                "%s: null pointer: page_rows / table_stride / capacity without a block_table", nm);
+  }
   if (t_base_dev) {
     SEA_REQUIRE(state_in && state_out, SEA_EINVAL, "%s: null pointer", nm);
     SEA_REQUIRE(n_segments == 1, SEA_EUNSUPPORTED, "%s: the device-position step runs one segment", nm);
@@ -1998,53 +2019,5 @@ static int perf_step_entry(const char* nm, const void* q, const void* k, const v
   }
   return perf_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
                     n_segments, workspace, workspace_bytes, state_in, state_out, state_bytes, t_base, t_base_dev, t_base_stride, 1,
-                    table, table_stride, page_shift, stream);
-}
-
-extern "C" int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                         const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                         int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                         void* state_out, int64_t state_bytes, int64_t t_base, const int32_t* t_base_dev,
-                                         int64_t n_segments, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
-  return perf_step_entry("sea_performer_causal_step", q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides,
-                         pos_stride, out, avg_out, state_in, state_out, state_bytes, t_base, t_base_dev, 0, n_segments, workspace,
-                         workspace_bytes, stream);
-}
-
-// per-sequence positions: sequence n has seen t_base_dev[n * t_base_stride] rows (t_base_stride >= 1; device-position form only)
-extern "C" int sea_performer_causal_step_ragged(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                                const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                                int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                                void* state_out, int64_t state_bytes, const int32_t* t_base_dev,
-                                                int64_t t_base_stride, sea_stream_t stream) {
-  const char* nm = "sea_performer_causal_step_ragged";
-  SEA_REQUIRE(t_base_dev, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
-  return perf_step_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
-                         state_in, state_out, state_bytes, 0, t_base_dev, t_base_stride, 1, nullptr, 0, stream);
-}
-
-// paged K / V: k / v are the K / V halves of a page pool (strides [page, head, row]); sequence n's open chunk c0 .. seen and its
-// new row lie in page block_table[n * table_stride + c0 / page_rows], from row c0 % page_rows on.  One new row per sequence.
-extern "C" int sea_performer_causal_step_paged(const void* q, const void* k, const void* v, const void* pos, int dtype,
-                                               const float* proj, int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb,
-                                               const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                               int64_t pos_stride, void* out, void* avg_out, const void* state_in,
-                                               void* state_out, int64_t state_bytes, const int32_t* t_base_dev,
-                                               int64_t t_base_stride, const int32_t* block_table, int64_t table_stride,
-                                               int64_t page_rows, int64_t capacity, sea_stream_t stream) {
-  const char* nm = "sea_performer_causal_step_paged";
-  SEA_REQUIRE(t_base_dev && block_table, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(t_base_stride > 0, SEA_EINVAL, "%s: t_base_stride must be >= 1 (got %lld)", nm, (long long)t_base_stride);
-  SEA_REQUIRE(T == 1, SEA_EINVAL, "%s: one new row per sequence (T=%lld)", nm, (long long)T);
-  const PerfForm form = perf_form(dtype, D, nb);
-  SEA_REQUIRE(form.mfma16, SEA_EUNSUPPORTED, "%s: the chunk-aligned step runs on the 16-bit MFMA kernels (bf16 / fp16 data, D = 64, 80, 128)", nm);
-  if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
-  SEA_REQUIRE(page_rows % form.C == 0, SEA_EINVAL, "%s: page_rows %lld is not a multiple of the chunk (%d rows)", nm,
-              (long long)page_rows, form.C);
-  return perf_step_entry(nm, q, k, v, pos, dtype, proj, N, H, T, D, nb, q_strides, k_strides, v_strides, pos_stride, out, avg_out,
-                         state_in, state_out, state_bytes, 0, t_base_dev, t_base_stride, 1, nullptr, 0, stream, block_table,
-                         table_stride, __builtin_ctzll(page_rows));
+                    block_table, table_stride, block_table ? __builtin_ctzll(page_rows) : 0, stream);
 }

@@ -1408,14 +1408,19 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
   return SEA_OK;
 }
 
-static int decode_cnn_entry(const char* nm, const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N,
-                            int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                            const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation, int pad_w,
-                            const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                            void* probs, const int32_t* keep_table, int32_t* counters, int32_t* ticket, int is_causal, int max_k,
-                            uint32_t* bits, int32_t* row_nnz, int32_t* head_off, int32_t* crow_out, int32_t* col,
-                            int64_t col_stride_n, int64_t z_cap, int64_t T_cap, const uint32_t* consts_tab,
-                            int64_t counter_stride, sea_stream_t stream) {
+// counter_stride > 0: a counter triple PER SEQUENCE, sequence n's at counters + n * counter_stride (counter_stride >= 3); the
+// last workgroup advances all N
+extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
+                                          int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
+                                          const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
+                                          int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
+                                          const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
+                                          int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
+                                          int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
+                                          int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream) {
+  const char* nm = "sea_decode_cnn_tail_select";
+  SEA_REQUIRE(counter_stride == 0 || counter_stride >= 3, SEA_EINVAL,
+              "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm, (long long)counter_stride);
   SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31) && T_cap < (1ll << 24)),
               SEA_EUNSUPPORTED,
               "%s: the in-launch emit serves C <= 64 channels (beyond that the weight image leaves no LDS for it: pass col = NULL "
@@ -1461,40 +1466,6 @@ static int decode_cnn_entry(const char* nm, const void* x_new, void* x_ring, voi
   return SEA_OK;
 }
 
-extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
-                                          int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                                          const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
-                                          int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
-                                          const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                                          int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                          int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                                          int64_t T_cap, const uint32_t* consts_tab, sea_stream_t stream) {
-  return decode_cnn_entry("sea_decode_cnn_tail_select", x_new, x_ring, y1_ring, y2, dtype, N, C, H, W4, ring_x, ring_y,
-                          w1_packed, bias1, w2_packed, bias2, CinP, dilation, pad_w, conv_b, conv_w16, Cp, gamma, beta, eps,
-                          probs, keep_table, counters, ticket, is_causal, max_k, bits, row_nnz, head_off, crow_out, col,
-                          col_stride_n, z_cap, T_cap, consts_tab, 0, stream);
-}
-
-// per-sequence counters: sequence n's triple at counters + n * counter_stride (counter_stride >= 3); the last workgroup advances all N
-extern "C" int sea_decode_cnn_tail_select_ragged(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N,
-                                                 int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
-                                                 const void* w1_packed, const float* bias1, const void* w2_packed,
-                                                 const float* bias2, int64_t CinP, int dilation, int pad_w, const void* conv_b,
-                                                 const void* conv_w16, int64_t Cp, const void* gamma, const void* beta,
-                                                 float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                                                 int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                                 int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n,
-                                                 int64_t z_cap, int64_t T_cap, const uint32_t* consts_tab,
-                                                 int64_t counter_stride, sea_stream_t stream) {
-  const char* nm = "sea_decode_cnn_tail_select_ragged";
-  SEA_REQUIRE(counter_stride >= 3, SEA_EINVAL, "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm,
-              (long long)counter_stride);
-  return decode_cnn_entry(nm, x_new, x_ring, y1_ring, y2, dtype, N, C, H, W4, ring_x, ring_y, w1_packed, bias1, w2_packed,
-                          bias2, CinP, dilation, pad_w, conv_b, conv_w16, Cp, gamma, beta, eps, probs, keep_table, counters,
-                          ticket, is_causal, max_k, bits, row_nnz, head_off, crow_out, col, col_stride_n, z_cap, T_cap,
-                          consts_tab, counter_stride, stream);
-}
-
 extern "C" int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst, void* crow, int idx_bytes,
                                 sea_stream_t stream) {
   SEA_REQUIRE(row_nnz && crow, SEA_EINVAL, "sea_csr_row_scan: null pointer");
@@ -1512,10 +1483,16 @@ extern "C" int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst
 // t_src_dev != NULL: the decode form (a step captured as a HIP graph): the rows' widths follow *t_src_dev (device memory:
 // the current sequence length), the column ids are head * T_src + key with T_src the FIXED capacity T_cap >= *t_src_dev,
 // so the attention launch that consumes them (K / V caches of T_cap rows) needs nothing position-dependent in its arguments.
-static int csr_emit_entry(const char* nm, const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
+// t_src_stride > 0 (the decode form only): batch item n's rows follow t_src_dev[n * t_src_stride]
+extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
                             int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
                             int64_t col_stride_n, int64_t z_cap, float* values_out, const int32_t* t_src_dev,
                             int64_t t_src_stride, sea_stream_t stream) {
+  const char* nm = "sea_csr_emit";
+  if (t_src_stride) {
+    SEA_REQUIRE(t_src_dev, SEA_EINVAL, "%s: null pointer", nm);
+    SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
+  }
   (void)head_off;  // offsets follow from the flat (head-major) emission order; kept in the ABI for symmetry
   SEA_REQUIRE(!(t_src_dev && values_out), SEA_EUNSUPPORTED, "%s: the decode form writes no values", nm);
   const int64_t T_enc = T_src;
@@ -1543,26 +1520,6 @@ static int csr_emit_entry(const char* nm, const uint32_t* bits, const void* crow
   else hipLaunchKernelGGL((csr_emit_kernel<int64_t>), grid, block, 0, s, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
-}
-
-extern "C" int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
-                            int64_t T_dst, int64_t T_m, int64_t T_src, int is_causal, int max_k, void* col, int idx_bytes,
-                            int64_t col_stride_n, int64_t z_cap, float* values_out, const int32_t* t_src_dev,
-                            sea_stream_t stream) {
-  return csr_emit_entry("sea_csr_emit", bits, crow, head_off, N, H, T_dst, T_m, T_src, is_causal, max_k, col, idx_bytes,
-                        col_stride_n, z_cap, values_out, t_src_dev, 0, stream);
-}
-
-// per-sequence lengths (decode form only): batch item n's rows follow t_src_dev[n * t_src_stride] (t_src_stride >= 1)
-extern "C" int sea_csr_emit_ragged(const uint32_t* bits, const void* crow, const int32_t* head_off, int64_t N, int64_t H,
-                                   int64_t T_dst, int64_t T_m, int64_t T_cap, int is_causal, int max_k, void* col, int idx_bytes,
-                                   int64_t col_stride_n, int64_t z_cap, const int32_t* t_src_dev, int64_t t_src_stride,
-                                   sea_stream_t stream) {
-  const char* nm = "sea_csr_emit_ragged";
-  SEA_REQUIRE(t_src_dev, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
-  return csr_emit_entry(nm, bits, crow, head_off, N, H, T_dst, T_m, T_cap, is_causal, max_k, col, idx_bytes, col_stride_n, z_cap,
-                        nullptr, t_src_dev, t_src_stride, stream);
 }
 
 extern "C" int sea_csr_head_offsets(const void* crow, const void* col, int idx_bytes, int64_t N, int64_t H,

@@ -36,8 +36,9 @@ pair (bitwise the same context).  Column ids are head * capacity + key, and the 
 pixel's keys are stepped in fp32 on the key alone, the head offset is added as an integer (include/sea_hip.h, sea_csr_emit).
 
 Sequences at different positions (`DecodeSession.from_sequences`): the counters are an (N, 3) block, a row per sequence, and
-every launch of the step takes the *_ragged entry of its operator (include/sea_hip.h).  Each of those kernels serves one
-sequence per workgroup, so a sequence's position is one scalar load from its row; the step is bitwise N sessions of N = 1.
+every launch of the step takes their row stride (the per-sequence form of its operator, include/sea_hip.h).  Each of those
+kernels serves one sequence per workgroup, so a sequence's position is one scalar load from its row; the step is bitwise N
+sessions of N = 1.
 `admit` puts a new prompt into one slot between steps (continuous batching) without a new capture: the graph holds pointers
 to the session's buffers only.
 
@@ -45,8 +46,8 @@ Paged K / V (`from_sequences(..., page_rows=...)`): one pool of fixed-size pages
 slots, and a device block table (N, ceil(capacity / page_rows)) int32 naming each sequence's pages in order.  A `PageAllocator`
 on the host hands pages out: seeding or `admit` gives a slot the pages of its prefix plus the next row, `step` a new page to
 every slot whose next row starts one (written into the device table in stream order, no host synchronise).  The three
-launches that touch K / V take their *_paged entries; keys and column ids stay logical (head * capacity + key), so every
-result is bitwise the contiguous ragged session's.  page_rows is a power of two and a multiple of the Performer chunk: the
+launches that touch K / V take the block table as an argument; keys and column ids stay logical (head * capacity + key), so
+every result is bitwise the contiguous ragged session's.  page_rows is a power of two and a multiple of the Performer chunk: the
 rows a chunk-aligned step walks again lie in one page.
 
 Fork and beam reorder (`fork`, `reorder`; paged ragged sessions, between steps): during a step only the stage writes K / V, row
@@ -572,11 +573,8 @@ class DecodeSession:
 
     # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new row
     def _stage(self, q, k, v):
-        if self.paged:
-            ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2], block_table=self.block_table,
-                             capacity=self.capacity)
-            return
-        ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2])
+        ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2],
+                         block_table=self.block_table, capacity=self.capacity)
 
     # the (captured) launches of one position; everything position-dependent is read from device memory
     def _launch(self):

@@ -218,7 +218,7 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
     sea_predictor_tail_select) -> FlatCSR.  Two launches, no host sync.
     Decode form (`sea_csr_emit` with `t_src_dev`): `t_src_dev` (one int32 on the device) is the sequence length the row widths
     follow, `T_src` the FIXED capacity the column ids are encoded with (the FlatCSR says T_src = capacity).  An (N, 1) view of
-    per-sequence counters gives each batch item its own length (`sea_csr_emit_ragged`); the handle keeps it for a deferred
+    per-sequence counters gives each batch item its own length (`t_src_stride` > 0); the handle keeps it for a deferred
     emit."""
     lib = _lib.load()
     N, T_dst = row_nnz.shape
@@ -238,14 +238,9 @@ def csr_from_selection(bits: torch.Tensor, row_nnz: torch.Tensor, head_off: torc
         assert t_stride > 0 or t_src_dev.numel() == 1
     def emit():
         with torch.cuda.device(dev):
-            if t_stride > 0:
-                _lib.check(lib.sea_csr_emit_ragged(
-                    _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
-                    _p(col), 4, col.stride(0), z_cap, _p(t_src_dev), t_stride, _lib.stream_ptr()), "sea_csr_emit_ragged")
-                return
             _lib.check(lib.sea_csr_emit(
                 _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
-                _p(col), 4, col.stride(0), z_cap, None, _p(t_src_dev), _lib.stream_ptr()), "sea_csr_emit")
+                _p(col), 4, col.stride(0), z_cap, None, _p(t_src_dev), t_stride, _lib.stream_ptr()), "sea_csr_emit")
     csr = FlatCSR(crow, col, head_off, H, T_src, bits=bits, row_nnz=row_nnz)
     csr.t_src_dev = t_src_dev
     if defer_emit:          # the fused attention launch (sparse_attention(..., fuse_emit=True)) will write `col`; any other
@@ -442,11 +437,11 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     keep_columns_pending: with a handle whose columns are pending and the fused launch serving it, do NOT write the column
     array (the launch keeps the expanded columns in LDS): the handle stays pending and whoever reads `.col` later runs the
     emit launch -- for callers that return the CSR without anybody reading it (the layer's hot path).
-    block_table: paged K / V (`sea_sparse_attention_paged`): k / v are the K / V halves of a page pool (P, H, page_rows, D),
-    sequence n's key r in page block_table[n, r // page_rows] (int32, (N, >= ceil(csr.T_src / page_rows))).  Only the one-row
-    decode form reads pages: a pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
+    block_table: paged K / V: k / v are the K / V halves of a page pool (P, H, page_rows, D), sequence n's key r in page
+    block_table[n, r // page_rows] (int32, (N, >= ceil(csr.T_src / page_rows))).  Only the one-row decode form reads pages: a
+    pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
     lib = _lib.load()
-    _lib.require_gpu(q, k, v, csr.crow)
+    _lib.require_gpu(q, k, v, csr.crow, block_table)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, row_scale, avg, mix)):
         assert out is None and not want_probs, "the differentiable form returns a new fp32 tensor"
         return sparse_attention_autograd(q, k, v, csr, row_scale, avg, mix)
@@ -456,13 +451,23 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     # (the tile kernel, a plan that may choose it, rows of 4 lanes / d = 80 / wider than 16 lanes) reads `.col`, which
     # runs the emit launch first
     decode_form = csr.t_src_dev is not None                   # a decoding step: the sequence length lives in device memory
-    fused = (csr.col_is_pending and fuse_emit and path != "tile" and not (path == "auto" and plan is not None)
-             and fused_interp_supported(q.dtype, D, csr._pending[0], None if decode_form else N * H * T_dst)
-             and not (decode_form and (want_probs or T_dst > 8)))
-    if block_table is not None:
-        return _sparse_attention_paged(q, k, v, csr, block_table, row_scale, avg, mix, out, out_dtype, keep_columns_pending)
-    T_src = k.shape[2]
-    assert k.shape == (N, H, T_src, D) and v.shape == (N, H, T_src, D)
+    paged = block_table is not None                           # (the one-row decode form of the fused launch, nothing else)
+    if paged and not (csr.col_is_pending and csr.t_src_stride and T_dst == 1 and q.dtype in (torch.float16, torch.bfloat16)
+                      and D in (64, 80, 128)):
+        raise ValueError("paged K / V: the one-row decode form only (a pending per-sequence decode CSR, T_dst = 1, "
+                         f"16-bit d = 64 / 80 / 128; got T_dst = {T_dst}, {q.dtype}, d = {D})")
+    fused = paged or (csr.col_is_pending and fuse_emit and path != "tile" and not (path == "auto" and plan is not None)
+                      and fused_interp_supported(q.dtype, D, csr._pending[0], None if decode_form else N * H * T_dst)
+                      and not (decode_form and (want_probs or T_dst > 8)))
+    T_src = csr.T_src if paged else k.shape[2]
+    table_stride, page_rows = 0, 0
+    if paged:
+        _P, Hk, page_rows, Dk = k.shape
+        assert (Hk, Dk) == (H, D) and v.shape == k.shape and k.stride(-1) == 1 and v.stride(-1) == 1
+        assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
+        table_stride = block_table.stride(0)
+    else:
+        assert k.shape == (N, H, T_src, D) and v.shape == (N, H, T_src, D)
     assert q.dtype == k.dtype == v.dtype
     assert (csr.N, csr.T_dst, csr.H, csr.T_src) == (N, T_dst, H, T_src)
     if out is None:
@@ -478,14 +483,6 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         assert plan.dtype == torch.uint8 and plan.numel() == ((nb_ + 3) & ~3) + 4 and plan.is_contiguous()
 
     def launch(col, probs, block_path, flags, bits=None, T_m=0, is_causal=0, max_k=0, write_cols=1, t_src_dev=None):
-        if t_src_dev is not None and csr.t_src_stride:      # per-sequence lengths (the decode form only)
-            return lib.sea_sparse_attention_ragged(
-                _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
-                _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
-                _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
-                _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
-                _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
-                _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), csr.t_src_stride, _lib.stream_ptr())
         return lib.sea_sparse_attention(
             _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
             _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
@@ -493,7 +490,8 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
             _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
             _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
             _p(probs), probs.stride(0) if probs is not None else 0, _p(block_path), flags,
-            _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), _lib.stream_ptr())
+            _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), csr.t_src_stride if t_src_dev is not None else 0,
+            _p(block_table), table_stride, page_rows, _lib.stream_ptr())
 
     if fused:
         T_m_, max_k_, causal_, _emit = csr._pending
@@ -505,7 +503,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
             if not keep_columns_pending:
                 csr._pending = None                         # the launch has written the columns
             return (out, probs) if want_probs else out
-        if rc != _lib.SEA_EUNSUPPORTED:
+        if rc != _lib.SEA_EUNSUPPORTED or paged:
             _lib.check(rc, "sea_sparse_attention")
         # a shape the fused form does not cover (nothing was launched): emit, then the plain operator below
     probs = torch.zeros(csr.col.shape, dtype=torch.float32, device=q.device) if want_probs else None
@@ -516,42 +514,6 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     block_path = plan if (plan is not None and path == "auto" and not want_probs) else None
     _lib.check(launch(csr.col, probs, block_path, flags), "sea_sparse_attention")
     return (out, probs) if want_probs else out
-
-
-def _sparse_attention_paged(q, k, v, csr: FlatCSR, block_table, row_scale, avg, mix, out, out_dtype, keep_columns_pending):
-    """`sparse_attention(..., block_table=...)`: the one-row decode form over a page pool (no other kernel reads pages)."""
-    lib = _lib.load()
-    _lib.require_gpu(k, v, block_table)
-    N, H, T_dst, D = q.shape
-    if not (csr.col_is_pending and csr.t_src_stride and T_dst == 1 and q.dtype in (torch.float16, torch.bfloat16)
-            and D in (64, 80, 128)):
-        raise ValueError("paged K / V: the one-row decode form only (a pending per-sequence decode CSR, T_dst = 1, "
-                         f"16-bit d = 64 / 80 / 128; got T_dst = {T_dst}, {q.dtype}, d = {D})")
-    P, Hk, page_rows, Dk = k.shape
-    assert (Hk, Dk) == (H, D) and v.shape == k.shape and q.dtype == k.dtype == v.dtype and k.stride(-1) == 1 and v.stride(-1) == 1
-    assert (csr.N, csr.T_dst, csr.H) == (N, T_dst, H)
-    assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
-    if out is None:
-        out = torch.empty((N, H, T_dst, D), dtype=out_dtype or torch.float32, device=q.device)
-    assert out.shape == (N, H, T_dst, D) and out.stride(-1) == 1
-    if row_scale is not None:
-        assert row_scale.dtype == torch.float32 and row_scale.shape == (N, H, T_dst) and row_scale.is_contiguous()
-    if mix is not None:
-        assert avg is not None and avg.shape == (N, H, T_dst, D) and avg.dtype == q.dtype
-        assert mix.dtype == torch.float32 and mix.shape == (N, H, T_dst) and mix.is_contiguous()
-    T_m, max_k, causal, _emit = csr._pending
-    col = csr._col
-    _lib.check(lib.sea_sparse_attention_paged(
-        _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, csr.T_src, D,
-        _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
-        _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
-        _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
-        _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
-        _p(csr.bits), T_m, int(causal), max_k, 0 if keep_columns_pending else 1, _p(csr.t_src_dev), csr.t_src_stride,
-        _p(block_table), block_table.stride(0), page_rows, _lib.stream_ptr()), "sea_sparse_attention_paged")
-    if not keep_columns_pending:
-        csr._pending = None                                 # the launch has written the columns
-    return out
 
 
 def plan_blocks(plan: torch.Tensor, N: int, H: int, T_dst: int) -> torch.Tensor:
@@ -617,7 +579,7 @@ def resize_from_m_to_t_csr(x, masked_fill_value, k, target_width=None, training=
     if Z > 0:
         _lib.check(lib.sea_csr_emit(
             _p(bits), _p(crow), _p(head_off), N, H, T_dst, T_m, T_src, int(is_causal), int(k),
-            _p(col), 8, col.stride(0), Z, None, None, st), "sea_csr_emit")
+            _p(col), 8, col.stride(0), Z, None, None, 0, st), "sea_csr_emit")
     return torch.sparse_csr_tensor(crow, col, values, size=(N, T_dst, H * T_src))
 
 

@@ -433,10 +433,10 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     Decode form (`sea_performer_causal_step` with `t_base_dev`, a step replayed as a HIP graph): `t_base_dev` is a one-element int32
     device tensor holding the rows seen so far, k / v the fixed-capacity caches (already holding the new row), and
     `state_in` is updated in place.  An (N, 1) view of a per-sequence counter block gives each sequence its own position
-    (`sea_performer_causal_step_ragged`; sequence n's state image is the n-th contiguous slice of `state_in`).
+    (`t_base_stride` > 0; sequence n's state image is the n-th contiguous slice of `state_in`).
     Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32 with per-sequence `t_base_dev`, one new row each): k / v
-    are the K / V halves of a page pool, (P, H, page_rows, D); sequence n's row r lives in page block_table[n, r // page_rows]
-    (`sea_performer_causal_step_paged`).  `capacity`: the logical rows per sequence the table covers."""
+    are the K / V halves of a page pool, (P, H, page_rows, D); sequence n's row r lives in page block_table[n, r // page_rows].
+    `capacity`: the logical rows per sequence the table covers."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, pos, projection, block_table)
     N, H, T, D = q.shape
@@ -452,6 +452,7 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     proj = _cached("proj", (projection,), q.dtype, lambda: projection.to(q.dtype).float().contiguous())
     sb = int(lib.sea_performer_state_bytes(N, H, D, nb, _lib.dtype_code(q.dtype)))
     assert sb > 0, "unsupported head size / feature count"
+    t_stride = 0
     if t_base_dev is not None:
         t_stride = _lib.counter_stride(t_base_dev, N)
         assert t_stride > 0 or t_base_dev.numel() == 1
@@ -479,24 +480,16 @@ def performer_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch
     if n_segments > 1:
         ws_bytes = N * H * (n_segments - 1) * lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(q.dtype))
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
+    table_stride, page_rows, cap = 0, 0, 0
     if paged:
         assert t_base_dev is not None and t_stride > 0 and capacity is not None, "the paged step: per-sequence positions, a capacity"
         assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
-        _lib.check(lib.sea_performer_causal_step_paged(
-            _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
-            _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, _p(t_base_dev), t_stride,
-            _p(block_table), block_table.stride(0), k.shape[2], int(capacity), _lib.stream_ptr()), "sea_performer_causal_step_paged")
-        return out, avg, state_out
-    if t_base_dev is not None and t_stride > 0:
-        _lib.check(lib.sea_performer_causal_step_ragged(
-            _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
-            _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, _p(t_base_dev), t_stride,
-            _lib.stream_ptr()), "sea_performer_causal_step_ragged")
-        return out, avg, state_out
+        table_stride, page_rows, cap = block_table.stride(0), k.shape[2], int(capacity)
     _lib.check(lib.sea_performer_causal_step(
         _p(q), _p(kc), _p(vc), _p(pc), _lib.dtype_code(q.dtype), _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(kc),
-        _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, int(t_base), _p(t_base_dev),
-        int(n_segments), _p(ws), ws_bytes, _lib.stream_ptr()), "sea_performer_causal_step")
+        _lib.strides3(vc), pc.stride(0), _p(out), _p(avg), _p(state_in), _p(state_out), sb, int(t_base), _p(t_base_dev), t_stride,
+        int(n_segments), _p(ws), ws_bytes, _p(block_table), table_stride, page_rows, cap, _lib.stream_ptr()),
+        "sea_performer_causal_step")
     return out, avg, state_out
 
 
@@ -685,9 +678,9 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
     """`sea_decode_stage`: the new rows of a decoding step, (N,H,1,D) each (any [n,h] strides), into the session's static
     buffers -- q into q_in (N,H,1,D), k / v into kv_cache (2,N,H,capacity,D) at the row the device counters name
     (int32 [seen, tsrc]: row = counters[0]).  An (N, >= 1) view of a per-sequence counter block writes sequence n's rows at
-    counters[n, 0] (`sea_decode_stage_ragged`).  Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32, per-sequence
-    counters): kv_cache is a page pool (2, P, H, page_rows, D) and sequence n's rows go to page block_table[n, row // page_rows]
-    (`sea_decode_stage_paged`); `capacity` is the logical rows per sequence."""
+    counters[n, 0] (`counter_stride` > 0).  Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32, per-sequence
+    counters): kv_cache is a page pool (2, P, H, page_rows, D) and sequence n's rows go to page block_table[n, row // page_rows];
+    `capacity` is the logical rows per sequence (unpaged: kv_cache's own, the argument is not read)."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, q_in, kv_cache, counters, block_table)
     N, H, one, D = q.shape
@@ -703,21 +696,14 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
     ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
     q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
     st = lambda t: (ctypes_i64 * 2)(t.stride(0), t.stride(1))
+    cap, table_stride, page_rows, pool_pages = kv_cache.shape[3], 0, 0, 0
     if paged:
         assert stride > 0 and capacity is not None, "the paged stage: per-sequence counters and a capacity"
         assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
-        _lib.check(lib.sea_decode_stage_paged(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v),
-                                              _p(q_in), _p(kv_cache), int(capacity), _p(counters), stride, _p(block_table),
-                                              block_table.stride(0), kv_cache.shape[3], kv_cache.shape[1], _lib.stream_ptr()),
-                   "sea_decode_stage_paged")
-        return
-    if stride > 0:
-        _lib.check(lib.sea_decode_stage_ragged(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v),
-                                               _p(q_in), _p(kv_cache), kv_cache.shape[3], _p(counters), stride, _lib.stream_ptr()),
-                   "sea_decode_stage_ragged")
-        return
+        cap, table_stride, page_rows, pool_pages = int(capacity), block_table.stride(0), kv_cache.shape[3], kv_cache.shape[1]
     _lib.check(lib.sea_decode_stage(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v), _p(q_in),
-                                    _p(kv_cache), kv_cache.shape[3], _p(counters), _lib.stream_ptr()), "sea_decode_stage")
+                                    _p(kv_cache), cap, _p(counters), stride, _p(block_table), table_stride, page_rows, pool_pages,
+                                    _lib.stream_ptr()), "sea_decode_stage")
 
 
 def decode_fork_staging_bytes(image_bytes: int, x_ring_bytes: int, y1_ring_bytes: int, table_entries: int) -> int:
@@ -774,8 +760,8 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     selection and the advance of the session's device counters (`sea_decode_cnn_tail_select`).  `conv1` / `conv2` are the
     `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  `col_out` (N, z_cap) int32 with `T_cap` (C <=
     64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.  `counters` (3,) is the batch's
-    one triple; an (N, 3) block holds one per sequence (`sea_decode_cnn_tail_select_ragged`: each workgroup reads its own
-    sequence's, the launch advances all of them).  Returns (probs or None, (bits, row_nnz, head_off))."""
+    one triple; an (N, 3) block holds one per sequence (`counter_stride` > 0: each workgroup reads its own sequence's, the
+    launch advances all of them).  Returns (probs or None, (bits, row_nnz, head_off))."""
     lib = _lib.load()
     _lib.require_gpu(x_new, x_ring, y1_ring, y2, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket, crow_out)
     N, C8, W4, _e = x_new.shape[0], x_new.shape[-3], x_new.shape[-2], x_new.shape[-1]
@@ -802,15 +788,12 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     bits = torch.empty((N, 1, Wb), dtype=torch.int32, device=dev)
     row_nnz = torch.empty((N, 1), dtype=torch.int32, device=dev)
     head_off = torch.empty((N, 1, H + 1), dtype=torch.int32, device=dev)
-    args = (_p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _lib.dtype_code(dt), N, C, H, W4, x_ring.shape[1], y1_ring.shape[1],
-            _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp, _p(g), _p(b),
-            float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
-            _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
-            int(T_cap), _p(tab))
-    if stride > 0:
-        _lib.check(lib.sea_decode_cnn_tail_select_ragged(*args, stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select_ragged")
-    else:
-        _lib.check(lib.sea_decode_cnn_tail_select(*args, _lib.stream_ptr()), "sea_decode_cnn_tail_select")
+    _lib.check(lib.sea_decode_cnn_tail_select(
+        _p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _lib.dtype_code(dt), N, C, H, W4, x_ring.shape[1], y1_ring.shape[1],
+        _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp, _p(g), _p(b),
+        float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
+        _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
+        int(T_cap), _p(tab), stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select")
     return probs, (bits, row_nnz, head_off)
 
 

@@ -25,15 +25,15 @@ def test_header_symbols_are_bound():
     assert sorted(_lib.EXPORTED_SYMBOLS) == decl
 
 
-def test_library_builds_and_exports_everything_at_abi_4():
-    """ABI 4: one entry point per operator (include/sea_hip.h lists what changed from 3)."""
+def test_library_builds_and_exports_everything_at_abi_5():
+    """ABI 5: one entry point per operator, the decode step's included (include/sea_hip.h lists what changed from 4)."""
     path = _build.build_library()
     assert os.path.exists(path)
     lib = ctypes.CDLL(path)
     for name in _declared_symbols():
         assert hasattr(lib, name), f"{name} not exported"
     lib.sea_version.restype = ctypes.c_int
-    assert lib.sea_version() == 4 == _lib.ABI_VERSION
+    assert lib.sea_version() == 5 == _lib.ABI_VERSION
     # host-only helper: algorithmic bytes, SURVEY 8d (cfg 3, bf16, Z = 8.32 M -> 2.20 GB)
     lib.sea_sparse_attention_bytes.restype = ctypes.c_int64
     lib.sea_sparse_attention_bytes.argtypes = [ctypes.c_int64] * 5 + [ctypes.c_int]
