@@ -420,6 +420,32 @@ int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, v
                                int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
                                int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
 
+/* The same for a step of `rows` new rows per sequence, rows in 1 .. 8 (speculative decoding: a draft's tokens verified in one
+ * step; perlin_attention/decode.py, DecodeSession.from_sequences(..., max_step_rows=...)).  One workgroup per (sequence n, row j)
+ * serves position t = counters[n * counter_stride] + j:
+ *   - conv1's rows t - 2 dil, t - dil, t: those at positions >= seen (new in this step) are recomputed from x rows -- x_new's
+ *     row (q - seen) for a position q >= seen, the x ring's slot q % ring_x below it -- into the workgroup's own two rows of
+ *     y1_scratch (N, rows, 2, C/8, 64, 8), row t into the y1 ring; older ones are read from the y1 ring;
+ *   - conv2's row t into y2 (N, rows, C/8, 64, 8), then the tail + selection of that row (keep_table[t], width t + 1): bits
+ *     (N, rows, W), row_nnz (N, rows), head_off (N, rows, H+1), optional probs (N, H, rows, 256).  No crow: run
+ *     sea_csr_row_scan on row_nnz;
+ *   - x_new's row j joins the x ring at slot t % ring_x.
+ * No data passes between the workgroups of a launch: the ring slots read (positions seen - 2 dil .. seen - 1) and written
+ * (seen .. seen + rows - 1) are disjoint, which needs ring_x, ring_y >= 2 * dilation + rows (else SEA_EINVAL).  A session
+ * that may drop rows of a step again (rewind) needs more: x_ring >= LB + max rows (the window it exports), y1_ring >=
+ * 2 * dilation + max rows.  The last of the N * rows workgroups advances every triple: counters[2] = counters[0] + rows,
+ * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what sea_decode_cnn_tail_select does).  x_new (N, rows, C/8,
+ * 64, 8) dense.  Everything else, and the other refusals, as for sea_decode_cnn_tail_select; rows outside 1 .. 8: SEA_EINVAL.
+ * (A later ABI version can fold sea_decode_cnn_tail_select into this entry: rows = 1 plus the one-row form's crow_out / col.) */
+int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
+                                    int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
+                                    const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2,
+                                    int64_t CinP, int dilation, int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp,
+                                    const void* gamma, const void* beta, float eps, void* probs, const int32_t* keep_table,
+                                    int32_t* counters, int32_t* ticket, int is_causal, int max_k, uint32_t* bits,
+                                    int32_t* row_nnz, int32_t* head_off, const uint32_t* consts_tab, int64_t counter_stride,
+                                    sea_stream_t stream);
+
 /* Causal cumulative average out[n,h,t,:] = sum_{s<=t} v[n,h,s,:] / (t+1), fp32 accumulation.
  * Replaces `avg_v.cumsum(-2) / arange(1..T)` (attention.py:1220-1222).  out (N,H,T,D) contiguous. */
 int sea_cumavg(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
@@ -597,6 +623,15 @@ int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int
                      const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
                      sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
+/* sea_decode_stage_rows: the stage of a step of `rows` new rows per sequence (1 .. 8; sea_decode_cnn_tail_select_rows): q / k /
+ *   v (N,H,rows,D) with element strides {n, h, t}, feature stride 1, 16-byte aligned rows; q is copied into q_in (N,H,rows,D)
+ *   dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at row counters[n * counter_stride] + j (counter_stride 0:
+ *   the batch's one counter).  A row at or beyond the capacity writes nothing.  Contiguous caches only.  Refusals as for
+ *   sea_decode_stage; rows outside 1 .. 8: SEA_EINVAL.  (A later ABI version can fold sea_decode_stage into this entry.) */
+int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows, int64_t D,
+                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, void* q_in,
+                          void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
+                          sea_stream_t stream);
 
 /* Fork / beam reorder of a paged ragged session's slots, between two steps (perlin_attention/decode.py: DecodeSession.fork and
  * reorder).  `moves`: DEVICE int32 (M, 5), one row per destination slot: {src, dst, src_open, dst_open, stage}.  Destination

@@ -69,6 +69,10 @@ _SIGNATURES = {
     "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64, i64,
                           ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
+    "sea_decode_stage_rows": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr], c_int),
+    "sea_decode_cnn_tail_select_rows": ([ptr, ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64,
+                                         c_int, c_int, ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int,
+                                         ptr, ptr, ptr, ptr, i64, ptr], c_int),
     "sea_decode_fork": ([ptr, i64, i64, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr, i64, ptr, i64, ptr, i64, i64, ptr, i64, i64,
                          ptr, i64, ptr], c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),

@@ -66,6 +66,38 @@ __global__ __launch_bounds__(256) void decode_stage_kernel(std::conditional_t<PA
   }
 }
 
+// ROWS (sea_decode_stage_rows): `rows` new rows per sequence, (N, H, rows, D) with [n, h, t] strides; q_in (N, H, rows, D)
+// dense; row j of sequence n goes to cache row ctr[n * ctr_stride] + j, nothing for a row at or beyond the capacity.  A kernel
+// of its own, so that the one-row form's code stays what it was
+struct StageRowsParams {
+  const void *q, *k, *v;
+  int64_t qs[3], ks[3], vs[3];       // element strides [n, h, t] (feature stride 1)
+  void* q_in;                        // (N, H, rows, D) dense
+  void* kv_cache;                    // (2, N, H, cap, D) dense
+  const int32_t* ctr;
+  int N, H, rows, D, cap, ctr_stride;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void decode_stage_rows_kernel(StageRowsParams p) {
+  const int items = p.N * p.H * p.rows;                      // (n, h, j), j fastest: q_in's row order
+  const int per = p.D / 8;
+  const T* srcs[3] = {reinterpret_cast<const T*>(p.q), reinterpret_cast<const T*>(p.k), reinterpret_cast<const T*>(p.v)};
+  const int64_t* strs[3] = {p.qs, p.ks, p.vs};
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < 3 * items * per; c += gridDim.x * blockDim.x) {
+    const int which = c / (items * per);
+    const int r = (c - which * items * per) / per, i = c % per;
+    const int nh = r / p.rows, j = r - nh * p.rows;
+    const int n = nh / p.H, h = nh - n * p.H;
+    const int pos = p.ctr[n * p.ctr_stride] + j;
+    if (which != 0 && (pos < 0 || pos >= p.cap)) continue;
+    const uint4 val = *reinterpret_cast<const uint4*>(srcs[which] + n * strs[which][0] + h * strs[which][1] + j * strs[which][2] + i * 8);
+    T* dst = which == 0 ? reinterpret_cast<T*>(p.q_in) + (int64_t)r * p.D
+                        : reinterpret_cast<T*>(p.kv_cache) + (((int64_t)(which - 1) * p.N * p.H + nh) * p.cap + pos) * p.D;
+    *reinterpret_cast<uint4*>(dst + i * 8) = val;
+  }
+}
+
 __global__ __launch_bounds__(256) void c8_window_shift_kernel(uint4* xs, int rows, int64_t chunks_per_row, int64_t items_chunks,
                                                               int32_t* counters) {
   // xs (N, rows, chunks_per_row) in 16-byte chunks: xs[n, r] = xs[n, r + 1] for r < rows - 1
@@ -204,6 +236,35 @@ extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int
     if (cs) hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true>), dim3(blocks), dim3(256), 0, s, b, cs);
     else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, false>), dim3(blocks), dim3(256), 0, s, b, 0);
   }
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+
+// `rows` (1 .. 8) new rows per sequence: row j of sequence n goes to cache row counters[n * counter_stride] + j (include/sea_hip.h)
+extern "C" int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows,
+                                     int64_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                     void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters,
+                                     int64_t counter_stride, sea_stream_t stream) {
+  const char* nm = "sea_decode_stage_rows";
+  SEA_REQUIRE(q && k && v && q_strides && k_strides && v_strides && q_in && kv_cache && counters, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(rows >= 1 && rows <= 8, SEA_EINVAL, "%s: rows %lld outside 1 .. 8", nm, (long long)rows);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && D > 0 && capacity > 0 && capacity < (1ll << 31) && N * H * rows * D < (1ll << 24), SEA_EINVAL,
+              "%s: bad shape", nm);
+  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
+              (long long)counter_stride);
+  SEA_REQUIRE(D % 8 == 0, SEA_EUNSUPPORTED, "%s: D must be a multiple of 8 (16-byte rows)", nm);
+  bool al = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_in | (uintptr_t)kv_cache) & 15) == 0;
+  for (int i = 0; i < 3; ++i) al = al && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
+  SEA_REQUIRE(al, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
+  StageRowsParams p;
+  p.q = q; p.k = k; p.v = v; p.q_in = q_in; p.kv_cache = kv_cache; p.ctr = counters;
+  for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
+  p.N = (int)N; p.H = (int)H; p.rows = (int)rows; p.D = (int)D; p.cap = (int)capacity; p.ctr_stride = (int)counter_stride;
+  const int64_t chunks = 3 * N * H * rows * (D / 8);
+  const unsigned blocks = (unsigned)((chunks + 255) / 256 > 1024 ? 1024 : (chunks + 255) / 256);
+  if (dtype == SEA_F16) hipLaunchKernelGGL(decode_stage_rows_kernel<__half>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(decode_stage_rows_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

@@ -1122,6 +1122,88 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
   }
 }
 
+// ---- the same for a step of `rows` (1 .. 8) new rows per sequence (sea_decode_cnn_tail_select_rows) -----------------------------
+// One workgroup per (sequence n, row j), serving position t = seen + j: conv1's rows t - 2 dil, t - dil, t are recomputed where
+// they are new in this step (>= seen; their x rows come from x_new, older ones from the x ring), read from the y1 ring where they
+// are older; then conv2's row t and the unchanged tail_select_row of row t.  Rows the workgroup recomputes for positions of
+// OTHER workgroups go to its own scratch (two rows); it files only position t's x row and conv1 row in the rings.  So no
+// data passes between workgroups: within the launch the ring slots read (positions seen - 2 dil .. seen - 1) and written (seen
+// .. seen + rows - 1) are disjoint when a ring holds 2 dil + rows slots.  The selection runs as the decode form at T_src =
+// seen + rows over T_dst = rows rows; its crow comes from the row scan behind this launch.  The last workgroup of all N * rows
+// advances every triple: counters[2] = counters[0] + rows, counters[0] += rows, counters[1] = counters[0] + 1.
+template <typename T, int EPT, int NT, int KCH>
+__global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_rows_kernel(DecodeCnnParams dp, TailParams tp, TopkParams p,
+                                                                                 void* y1_scratch) {
+  extern __shared__ __attribute__((aligned(16))) float s_z[];
+  const int rows = tp.T;
+  const int b = (int)blockIdx.x, n = b / rows, j = b - n * rows;
+  const int seen = dp.counters[n * dp.ctr_stride];
+  const int t = seen + j;                                          // this workgroup's position
+  const int64_t row = (int64_t)dp.C * dp.W;
+  const T* xn = reinterpret_cast<const T*>(dp.x_new) + (int64_t)n * rows * row;      // the MLP's rows of positions seen ..
+  T* xr = reinterpret_cast<T*>(dp.x_ring) + (int64_t)n * dp.RX * row;
+  T* yr = reinterpret_cast<T*>(dp.y1_ring) + (int64_t)n * dp.RY * row;
+  T* y2 = reinterpret_cast<T*>(dp.y2) + (int64_t)b * row;
+  T* scr = reinterpret_cast<T*>(y1_scratch) + (int64_t)b * 2 * row;
+  auto slot = [](int p_, int r_) { return ((p_ % r_) + r_) % r_; };
+  auto x_at = [&](int q) { return q >= seen ? xn + (int64_t)(q - seen) * row : xr + slot(q, dp.RX) * row; };
+  T* sW = reinterpret_cast<T*>(s_z);                               // the weight image lives where the tail's z tile will
+  ConvRowC8<T, NT, KCH> c1, c2;
+  c1.load_weights(reinterpret_cast<const T*>(dp.w1), dp.C);
+  c1.load_bias(dp.b1, dp.C);
+  c2.load_bias(dp.b2, dp.C);
+  c1.store_weights(sW);
+  const T* y1p[3];                                                 // conv1's rows t - 2 dil, t - dil, t
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int q = t - (2 - i) * dp.dil;
+    if (q >= seen) {                                               // (block-uniform) new in this step: computed here
+      T* dst = i == 2 ? yr + slot(t, dp.RY) * row : scr + (int64_t)i * row;
+      c1.fetch_row(0, x_at(q - 2 * dp.dil), dp.C, dp.W, dp.dil, dp.pad_w);
+      c1.fetch_row(1, x_at(q - dp.dil), dp.C, dp.W, dp.dil, dp.pad_w);
+      c1.fetch_row(2, x_at(q), dp.C, dp.W, dp.dil, dp.pad_w);
+      c1.run(sW, dst, dp.C, dp.W, 1);                              // (ends with a barrier: the row is visible to the workgroup)
+      y1p[i] = dst;
+    } else {
+      y1p[i] = yr + slot(q, dp.RY) * row;
+    }
+  }
+  c2.load_weights(reinterpret_cast<const T*>(dp.w2), dp.C);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) c2.fetch_row(i, y1p[i], dp.C, dp.W, dp.dil, dp.pad_w);
+  c2.store_weights(sW);
+  c2.run(sW, y2, dp.C, dp.W, 1);
+  {                                                                // position t's MLP row joins the ring
+    const uint4* src = reinterpret_cast<const uint4*>(xn + (int64_t)j * row);
+    uint4* dst = reinterpret_cast<uint4*>(xr + slot(t, dp.RX) * row);
+    for (int i = threadIdx.x; i < (int)(row / 8); i += TK_THREADS) dst[i] = src[i];
+  }
+  __syncthreads();
+  // the decode selection of row j of T_dst = rows rows at T_src = seen + rows: keep_table[t], width t + 1
+  TopkParams ps = p;
+  ps.t_src_dev = nullptr;
+  ps.T_src = seen + rows;
+  ps.keep = p.keep + seen;
+  tail_select_row<T, EPT, false>(tp, ps, s_z, b);                 // row b = n * rows + j of the call
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const int done = atomicAdd(dp.ticket, 1);
+    if (done == (int)gridDim.x - 1) {                              // every workgroup has read the counters and finished
+      const int seqs = dp.ctr_stride ? (int)gridDim.x / rows : 1;
+      for (int m = 0; m < seqs; ++m) {
+        int32_t* c = dp.counters + m * dp.ctr_stride;
+        const int s0 = c[0] + rows;
+        c[2] = s0;
+        c[0] = s0;
+        c[1] = s0 + 1;
+      }
+      *dp.ticket = 0;
+      __threadfence();
+    }
+  }
+}
+
 // ---- per-(row, head) offsets of a foreign flat CSR (rows grouped by ascending head) ----------------
 template <typename I>
 __global__ __launch_bounds__(TK_THREADS) void head_offsets_kernel(const I* crow_all, const I* col_all, int H, int T_dst,
@@ -1461,6 +1543,85 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
   ep.t_src_dev = counters + 1; ep.t_src_stride = (int)counter_stride;
   hipStream_t s = (hipStream_t)stream;
   const int rc = dtype == SEA_F16 ? launch_decode_cnn<__half>(dp, tp, p, ep, s) : launch_decode_cnn<__hip_bfloat16>(dp, tp, p, ep, s);
+  SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+
+template <typename T>
+static int launch_decode_cnn_rows(const DecodeCnnParams& dp, const TailParams& tp, const TopkParams& p, void* scratch, hipStream_t s) {
+  const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
+  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
+  if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
+  const int nt = (dp.C + 15) / 16, kch = (dp.C + 31) / 32;
+  const size_t wimg = (size_t)(16 * nt) * 9 * kch * 64;
+  if (lds < wimg) lds = wimg;
+  dim3 grid((unsigned)(tp.N * tp.T)), block(TK_THREADS);
+#define SEA_DCNNR(EE, NTV, KV)                                                                                         \
+  do {                                                                                                                 \
+    static DevOnce once;                                                                                               \
+    if (lds > 32 * 1024 && once.first()) SEA_MAX_LDS((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), lds);       \
+    hipLaunchKernelGGL((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), grid, block, lds, s, dp, tp, p, scratch); \
+  } while (0)
+  if (ept <= 8 && nt == 1 && kch == 1) { if (ept <= 4) SEA_DCNNR(4, 1, 1); else SEA_DCNNR(8, 1, 1); }
+  else if (ept <= 16 && nt == 2 && kch == 1) SEA_DCNNR(16, 2, 1);
+  else if (ept <= 32 && nt == 3 && kch == 2) SEA_DCNNR(32, 3, 2);
+  else if (ept <= 32 && nt == 4 && kch == 2) SEA_DCNNR(32, 4, 2);
+  else if (ept <= 40 && nt == 5 && kch == 3) SEA_DCNNR(40, 5, 3);
+  else return SEA_EUNSUPPORTED;
+#undef SEA_DCNNR
+  return SEA_OK;
+}
+
+// `rows` (1 .. 8) new rows per sequence (include/sea_hip.h); one workgroup per (sequence, row), the last advances the counters
+extern "C" int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
+                                               int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x,
+                                               int64_t ring_y, const void* w1_packed, const float* bias1, const void* w2_packed,
+                                               const float* bias2, int64_t CinP, int dilation, int pad_w, const void* conv_b,
+                                               const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
+                                               void* probs, const int32_t* keep_table, int32_t* counters, int32_t* ticket,
+                                               int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
+                                               const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream) {
+  const char* nm = "sea_decode_cnn_tail_select_rows";
+  SEA_REQUIRE(x_new && x_ring && y1_ring && y2 && y1_scratch && w1_packed && bias1 && w2_packed && bias2 && conv_b && conv_w16 &&
+                  gamma && beta && keep_table && counters && ticket && bits && row_nnz && head_off, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(rows >= 1 && rows <= 8, SEA_EINVAL, "%s: rows %lld outside 1 .. 8", nm, (long long)rows);
+  SEA_REQUIRE(counter_stride == 0 || counter_stride >= 3, SEA_EINVAL,
+              "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm, (long long)counter_stride);
+  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
+              (long long)counter_stride);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  SEA_REQUIRE(N > 0 && N * rows < (1 << 20) && H > 0 && H <= 64 && H % 4 == 0 && C == 2 * H && C % 8 == 0 && W4 == 64 && max_k > 0,
+              SEA_EUNSUPPORTED, "%s: needs T_m = 256 (W4 = 64), H %% 4 == 0, C = 2 H channels in whole blocks of 8", nm);
+  SEA_REQUIRE(CinP == (C + 31) / 32 * 32 && Cp % 32 == 0 && Cp >= C && dilation > 0 && 2 * pad_w == 2 * dilation, SEA_EUNSUPPORTED,
+              "%s: 3 x 3 width-preserving convolutions with CinP = C rounded up to 32", nm);
+  SEA_REQUIRE(ring_x >= 2 * dilation + rows && ring_y >= 2 * dilation + rows, SEA_EINVAL,
+              "%s: rings of %lld / %lld slots for %lld rows: each needs 2 * dilation + rows = %lld (the slots the step reads and "
+              "writes are disjoint)", nm, (long long)ring_x, (long long)ring_y, (long long)rows, (long long)(2 * dilation + rows));
+  SEA_REQUIRE((((uintptr_t)x_new | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)y2 | (uintptr_t)y1_scratch |
+                (uintptr_t)w1_packed | (uintptr_t)w2_packed | (uintptr_t)conv_w16 | (uintptr_t)probs) & 15) == 0,
+              SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
+  DecodeCnnParams dp;
+  dp.x_new = x_new; dp.x_ring = x_ring; dp.y1_ring = y1_ring; dp.y2 = y2; dp.w1 = w1_packed; dp.w2 = w2_packed; dp.b1 = bias1; dp.b2 = bias2;
+  dp.counters = counters; dp.ctr_stride = (int)counter_stride; dp.ticket = ticket;
+  dp.C = (int)C; dp.W = (int)W4; dp.RX = (int)ring_x; dp.RY = (int)ring_y; dp.dil = dilation; dp.pad_w = pad_w;
+  TailParams tp;
+  tp.y = y2; tp.w4 = nullptr; tp.b4 = conv_b; tp.gamma = gamma; tp.beta = beta; tp.probs = probs; tp.scores = nullptr; tp.eps = eps;
+  tp.N = (int)N; tp.C = (int)C; tp.H = (int)H; tp.T = (int)rows; tp.W4 = (int)W4; tp.UP = 4; tp.T_M = 256;
+  tp.ys_n = rows * C * W4; tp.ys_c = 1; tp.ys_t = C * W4; tp.ys_w = 8; tp.ys_c8 = W4 * 8;    // one C8 row per (item, row)
+  tp.w16 = conv_w16; tp.Cp = (int)Cp; tp.z = nullptr;
+  tp.tab = (consts_tab != nullptr && (((uintptr_t)consts_tab) & 15) == 0) ? consts_tab : nullptr;
+  TopkParams p;
+  p.src = nullptr; p.sn = H * 256; p.sh = 256; p.st = 256;
+  p.H = (int)H; p.T_dst = (int)rows; p.T_m = 256; p.T_src = (int)rows;          // (T_src: per workgroup, from its counters)
+  p.is_causal = is_causal; p.max_k = max_k;
+  p.M = (int)(H * 256); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes(256);
+  p.keep = keep_table; p.keep_stride_n = 0;
+  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = nullptr; p.t_src_stride = 0;
+  p.crow1 = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == SEA_F16 ? launch_decode_cnn_rows<__half>(dp, tp, p, y1_scratch, s)
+                                  : launch_decode_cnn_rows<__hip_bfloat16>(dp, tp, p, y1_scratch, s);
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;

@@ -55,6 +55,18 @@ Fork and beam reorder (`fork`, `reorder`; paged ragged sessions, between steps):
 may continue as a copy of another by sharing that slot's closed pages (the allocator counts holders) and copying only its
 small state -- Performer image slice, rings, counter row, block-table row -- and its open page: one `sea_decode_fork` call
 (include/sea_hip.h), snapshot semantics for swaps, cycles and many-to-one parent maps.
+
+Multi-token steps and rewind (`from_sequences(..., max_step_rows=S)`, contiguous K / V, S <= 8): `step` takes s = 1 .. S new
+rows of every slot, (N, H, s, D) -> context (N, s, H*D), and `rewind(drop)` removes the last drop[n] rows of that step from
+slot n again (speculative decoding: the target verifies a draft's s tokens in one step and drops the rejected ones).  A graph
+per distinct s, captured on first use over views of buffers allocated once for S.  The per-sequence forms of the Performer,
+the MLP, the attention and the emit take s rows already; `sea_decode_stage_rows` and `sea_decode_cnn_tail_select_rows` (a
+workgroup per (sequence, row), recomputing the conv1 rows of this step that its row needs into its own scratch) are the two
+entries of their own.  Rewind is host work plus one counter copy: the rings keep LB + S x rows and 2 dil + S conv1 rows, so
+a slot read after any rewind is still where it was, K / V rows past the kept length are overwritten by the next stage before
+anything reads them, and the Performer image -- which changes only when a chunk completes, at most once per step (s <= 8 <=
+chunk) -- is copied aside before a step that completes one and copied back when the rewind falls below that boundary.  A
+rewound slot is bitwise a plain session that stepped only the kept rows.
 """
 from collections import deque
 from typing import List, Optional
@@ -77,7 +89,7 @@ def _fused_cnn_ok(convs, C, H, T_M, dt, LB) -> bool:
     return (len(convs) == 2 and all(c.kernel_size == 3 and c.in_channels == C and c.out_channels == C
                                     and isinstance(c.dilation, int) and c.dilation == convs[0].dilation
                                     and c.padding[1] == c.dilation for c in convs)
-            and ops.decode_cnn_supported(C, H, T_M, dt) and LB > 2 * convs[0].dilation)
+            and ops.decode_cnn_supported(C, H, T_M, dt) and LB >= 4 * convs[0].dilation)   # (the y1 ring's seed: 2 dil rows)
 
 
 class PageAllocator:
@@ -149,6 +161,8 @@ class DecodeSession:
     paged = False                # (from_sequences(..., page_rows=...): K / V in a page pool, see the module docstring)
     page_rows = None
     block_table = None
+    max_step_rows = None         # (from_sequences(..., max_step_rows=S): steps of 1 .. S rows and `rewind`)
+    _last_step = None            # (what `rewind` may undo: (s, lengths before, slots whose image was copied aside))
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -239,7 +253,7 @@ class DecodeSession:
 
     @classmethod
     def from_sequences(cls, attention, sequences, capacity: int, use_graph: bool = True, fused_attention: bool = True,
-                       page_rows: Optional[int] = None, pool_pages: Optional[int] = None):
+                       page_rows: Optional[int] = None, pool_pages: Optional[int] = None, max_step_rows: Optional[int] = None):
         """A session over sequences of DIFFERENT lengths.  `sequences`: [(state, key_prefix, value_prefix), ...], each the
         output of an N = 1 cached forward, (1, H, L_i, D) with its own L_i.  Slot n of the batch is sequence n; `step` takes
         and returns (N, ...) rows as for a uniform session, and every row equals that sequence's own N = 1 session bit for
@@ -249,7 +263,10 @@ class DecodeSession:
         `page_rows`: K / V in a pool of `pool_pages` pages of that many rows (default: enough for every slot at capacity; it
         may be far fewer), bitwise the contiguous session.  page_rows is a power of two and a multiple of the Performer chunk
         (`ops.performer_chunk_rows`: 64 at d = 64, 32 at d = 80 / 128); paging needs the fused decode attention
-        (`fused_attention=True`, d in {64, 80, 128}).  ValueError otherwise, or when the prefixes do not fit the pool."""
+        (`fused_attention=True`, d in {64, 80, 128}).  ValueError otherwise, or when the prefixes do not fit the pool.
+        `max_step_rows` S in 1 .. 8: `step` takes 1 .. S new rows per slot and `rewind` drops rows of the last step again
+        (module docstring); contiguous K / V with the fused decode attention only (ValueError with `page_rows` or
+        `fused_attention=False`).  None: one row per step, no rewind."""
         self = cls.__new__(cls)
         at = self.attention = attention
         pc = at.pconfig
@@ -275,6 +292,13 @@ class DecodeSession:
                              f"H <= 40 with H % 4 == 0, 16-bit data (got {len(convs)} convolutions, T_M = {self.T_M}, H = {self.H})")
         if not self.capacity <= at.v_eye_learned_causal.shape[2]:
             raise ValueError(f"capacity {self.capacity} beyond the value embedding ({at.v_eye_learned_causal.shape[2]} rows)")
+        if max_step_rows is not None:
+            if isinstance(max_step_rows, bool) or int(max_step_rows) != max_step_rows or not 1 <= max_step_rows <= 8:
+                raise ValueError(f"max_step_rows {max_step_rows}: an integer in 1 .. 8")
+            if page_rows is not None or not fused_attention:
+                raise ValueError("multi-row steps run on contiguous K / V with the fused decode attention (no page_rows, "
+                                 "fused_attention=True)")
+            self.max_step_rows = int(max_step_rows)
         lengths = [self._check_sequence(*sq) for sq in seqs]
         N, H, D, dt, dev = self.N, self.H, self.D, self.dtype, kp0.device
         n_tab = None
@@ -301,10 +325,23 @@ class DecodeSession:
         row_shape = (C // 8, self.T_M // 4, 8)
         per = seqs[0][0].states[PerlinAttentionState.PERFORMER].image.numel()
         self.image = torch.empty((N * per,), dtype=torch.float32, device=dev)          # sequence n's H images: the n-th slice
-        self.x_ring = torch.zeros((N, self.LB) + row_shape, dtype=dt, device=dev)
-        self.y1_ring = torch.zeros((N, 2 * 2 * dil + 1) + row_shape, dtype=dt, device=dev)
-        self.x_new = torch.zeros((N, 1) + row_shape, dtype=dt, device=dev)
-        self.y2 = torch.zeros((N,) + row_shape, dtype=dt, device=dev)
+        S = self.max_step_rows
+        if S is None:
+            self.x_ring = torch.zeros((N, self.LB) + row_shape, dtype=dt, device=dev)
+            self.y1_ring = torch.zeros((N, 2 * 2 * dil + 1) + row_shape, dtype=dt, device=dev)
+            self.x_new = torch.zeros((N, 1) + row_shape, dtype=dt, device=dev)
+            self.y2 = torch.zeros((N,) + row_shape, dtype=dt, device=dev)
+        else:
+            # rings that survive a rewind: the LB x rows an export reads and the 2 dil conv1 rows a step reads lie below the
+            # kept length, the step wrote up to S positions above it.  Step buffers for S rows; an s-row step uses views
+            self.x_ring = torch.zeros((N, self.LB + S) + row_shape, dtype=dt, device=dev)
+            self.y1_ring = torch.zeros((N, 2 * dil + S) + row_shape, dtype=dt, device=dev)
+            self.x_new = torch.zeros((N * S,) + row_shape, dtype=dt, device=dev)
+            self.y2 = torch.zeros((N * S,) + row_shape, dtype=dt, device=dev)
+            self.y1_scratch = torch.zeros((N * S * 2,) + row_shape, dtype=dt, device=dev)
+            self.image_backup = torch.empty((N, per), dtype=torch.float32, device=dev)
+            self.chunk = ops.performer_chunk_rows(D, at.performer.projection_matrix.shape[0], dt)
+            self._graphs = {}                                                # s -> (graph, csr, pending emit, probs, ctx)
         self.ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.xs = None
         if n_tab is not None:
@@ -327,7 +364,11 @@ class DecodeSession:
         for n, (st, kp, vp) in enumerate(seqs):
             self._seed_slot(n, st, kp, vp)
         self._static_buffers(dev, dt, fused_attention)
-        if use_graph:
+        if S is not None:
+            self.q_in = torch.zeros((N * H * S * D,), dtype=dt, device=dev)
+            self.ctx = torch.zeros((N * S * H * D,), dtype=self.ctx.dtype, device=dev)
+            self.use_graph = bool(use_graph)                                 # (graphs are captured per s, on first use)
+        elif use_graph:
             self._capture()
         return self
 
@@ -366,7 +407,7 @@ class DecodeSession:
         dil, RY = conv1.dilation, self.y1_ring.shape[1]
         self.image.view(self.N, -1)[n].copy_(ps.image.view(-1))
         pos = torch.arange(L - LB, L, device=rows.device)
-        self.x_ring[n, pos % LB] = rows[0]
+        self.x_ring[n, pos % self.x_ring.shape[1]] = rows[0]
         y1 = ops.causal_conv_c8(rows.contiguous(), conv1.weight, conv1.bias, 3, dil, dil, relu=True)
         keep_rows = min(RY - 1, LB - 2 * dil)
         p1 = torch.arange(L - keep_rows, L, device=rows.device)
@@ -465,6 +506,7 @@ class DecodeSession:
         if self.csr is not None and self.csr.col_is_pending:
             self.csr.col                              # the last step's pending columns follow the counters: emit before they move
         self._seed_slot(slot, state, key_prefix, value_prefix)
+        self._last_step = None                        # (an admit ends the chance to rewind)
 
     @torch.no_grad()
     def fork(self, src: int, dsts) -> None:
@@ -565,10 +607,10 @@ class DecodeSession:
         if self.ragged:                                            # (each sequence's ring by its own age)
             dev = self.x_ring.device
             pos = torch.tensor(self.lengths, device=dev).view(-1, 1) + torch.arange(-self.LB, 0, device=dev).view(1, -1)
-            return self.x_ring[torch.arange(self.N, device=dev).view(-1, 1), pos % self.LB]
+            return self.x_ring[torch.arange(self.N, device=dev).view(-1, 1), pos % self.x_ring.shape[1]]
         if self.fused_cnn:
             pos = torch.arange(self.length - self.LB, self.length, device=self.x_ring.device)
-            return self.x_ring[:, pos % self.LB]
+            return self.x_ring[:, pos % self.x_ring.shape[1]]
         return self.xs[:, :self.LB]
 
     # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new row
@@ -632,7 +674,41 @@ class DecodeSession:
         self.csr, self._col_emit = csr, None                                  # (the emit launch above wrote the columns)
         ops.c8_window_shift(self.xs, counters=self.ctr32[:2])                 # the window of the next position; counters += 1
 
-    def _capture(self):
+    # a step of s rows (max_step_rows sessions): the same launches over s rows per sequence, on views of the S-row buffers
+    def _rows_views(self, s):
+        N, H, D, rs = self.N, self.H, self.D, tuple(self.x_new.shape[1:])
+        return (self.q_in[:N * H * s * D].view(N, H, s, D), self.x_new[:N * s].view((N, s) + rs), self.y2[:N * s].view((N, s) + rs),
+                self.y1_scratch[:N * s * 2].view((N, s, 2) + rs), self.ctx[:N * s * H * D].view(N, s, H * D))
+
+    def _stage_rows(self, q, k, v):
+        ops.decode_stage_rows(q, k, v, self._rows_views(q.shape[2])[0], self.kv_cache, self.ctr32[:, :2])
+
+    def _launch_rows(self, s):
+        at, N, H, D, T_M = self.attention, self.N, self.H, self.D, self.T_M
+        q_in, x_new, y2, y1_scratch, ctx = self._rows_views(s)
+        performer_value, avg_rows, _ = ops.performer_step(
+            q_in, self.k_cache, self.v_cache, at.v_eye_learned_causal[0, 0], at.performer.projection_matrix,
+            state_in=self.image, t_base_dev=self.seen32)
+        _x, _t, row_scale, avg_scale = ops.predictor_mlp(
+            performer_value, at.attention_predictor_enc[0], at.attention_predictor_enc[1],
+            at.attention_predictor_dec_row[0], at.attention_predictor_cnn[0].module,
+            at.attention_predictor_dec_scaler[0], want_tpred=False, x_c8_out=x_new)
+        keepres, ln2 = at.attention_predictor_cnn[1].module, at.attention_predictor_cnn[2].module
+        body = list(keepres.net.children())
+        conv4 = body[-1].module
+        self.probs, sel = ops.decode_cnn_tail_select_rows(
+            x_new, self.x_ring, self.y1_ring, y2, y1_scratch, body[0].module, body[2].module, conv4.weight[:, :, 0, 0], conv4.bias,
+            ln2.weight, ln2.bias, T_M, self.keep_table, self.k, self.ctr32, self.ticket, eps=ln2.eps)
+        fused_attn = ops.fused_interp_supported(self.dtype, D, T_M)
+        csr = ops.csr_from_selection(*sel, H, T_M, self.capacity, self.k, True, s * self.z_cap, t_src_dev=self.tsrc_done32,
+                                     defer_emit=fused_attn)
+        ops.sparse_attention(q_in, self.k_cache, self.v_cache, csr,
+                             row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
+                             avg=avg_rows, mix=avg_scale, out=ctx.view(N, s, H, D).permute(0, 2, 1, 3),
+                             path="gather", keep_columns_pending=True)
+        self.csr, self._col_emit = csr, csr._pending
+
+    def _capture(self, s=None):
         """One eager step on a side stream would advance the state, so the capture runs against SAVED copies of the
         mutable buffers, restored afterwards (a capture records launches, it does not execute them).
 
@@ -641,7 +717,8 @@ class DecodeSession:
         tensors its launches took from the cache (`ops.pinned_prep`), so a cache eviction -- `clear_prep_cache()` from
         another layer's `.to()` / `load_state_dict`, or the cache's own size bound -- cannot free memory a replay still
         reads; and it remembers the cache generation: `step()` re-captures when that has moved, because a cleared cache
-        means the weights may have been edited and the pinned packs may be stale."""
+        means the weights may have been edited and the pinned packs may be stale.
+        `s` (max_step_rows sessions): the graph of an s-row step, one per distinct s (kept in `_graphs`)."""
         mutable = [self.image, self.kv_cache, self.ctr32]
         mutable += [self.x_ring, self.y1_ring, self.ticket] if self.fused_cnn else [self.xs]
         saved = [t.clone() for t in mutable]
@@ -649,19 +726,27 @@ class DecodeSession:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), torch.no_grad():                    # warm-up: lazy library work happens outside the capture
-                zero = torch.zeros_like(self.q_in)
-                self._stage(zero, zero, zero)
-                self._launch()
+                if s is None:
+                    zero = torch.zeros_like(self.q_in)
+                    self._stage(zero, zero, zero)
+                    self._launch()
+                else:
+                    zero = torch.zeros((self.N, self.H, s, self.D), dtype=self.dtype, device=self.q_in.device)
+                    self._stage_rows(zero, zero, zero)
+                    self._launch_rows(s)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g), torch.no_grad():
-                self._launch()
+                self._launch() if s is None else self._launch_rows(s)
         for dst, src in zip(mutable, saved):
             dst.copy_(src)
-        self.graph = g
+        if s is None:
+            self.graph = g
+            self._pinned = pins
+        else:
+            self._graphs[s] = (g, self.csr, self._col_emit, self.probs, pins)
         self.captures = getattr(self, "captures", 0) + 1
-        self._pinned = pins
         self._prep_generation = ops.prep_generation()
 
     def export_state(self, slot: Optional[int] = None) -> PerlinAttentionState:
@@ -689,6 +774,13 @@ class DecodeSession:
 
     @torch.no_grad()
     def step(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """The new rows of every slot, (N, H, 1, D) each -> the context rows (N, 1, H*D), a static buffer.  A session built
+        with `max_step_rows` S takes (N, H, s, D) with 1 <= s <= S and returns (N, s, H*D); `rewind` may then undo it."""
+        if self.max_step_rows is not None:
+            return self._step_rows(q, k, v)
+        if self.ragged and q.dim() == 4 and q.shape[2] != 1:
+            raise ValueError(f"a step of {q.shape[2]} rows: this session takes one row per step "
+                             "(DecodeSession.from_sequences(..., max_step_rows=...) takes several)")
         if self.ragged:
             full = [n for n, L in enumerate(self.lengths) if L >= self.capacity]
             if full:
@@ -716,11 +808,78 @@ class DecodeSession:
             self.length += 1
         return self.ctx
 
+    def _step_rows(self, q, k, v):
+        N, H, D = self.N, self.H, self.D
+        if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)) or k.shape != q.shape or v.shape != q.shape \
+                or (q.shape[0], q.shape[1], q.shape[3]) != (N, H, D):
+            raise ValueError(f"step: q, k, v are (N, H, s, D) = ({N}, {H}, s, {D}) each (got {[tuple(t.shape) for t in (q, k, v)]})")
+        if not all(t.dtype == self.dtype and t.is_cuda for t in (q, k, v)):
+            raise ValueError(f"step: {self.dtype} rows on the GPU")
+        s = int(q.shape[2])
+        if not 1 <= s <= self.max_step_rows:
+            raise ValueError(f"a step of {s} rows: this session takes 1 .. {self.max_step_rows}")
+        full = [n for n, L in enumerate(self.lengths) if L + s > self.capacity]
+        if full:
+            raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full} (a step of {s} rows)")
+        if self._graphs and ops.prep_generation() != self._prep_generation:
+            self._graphs = {}                                      # (re-captured lazily, before this step's stage launch)
+        if self.use_graph and s not in self._graphs:
+            self._capture(s)
+        # the Performer image changes only when a chunk completes (at most once: s <= 8 <= chunk): a copy of the slices that
+        # this step moves to the next boundary, for `rewind`
+        C = self.chunk
+        crossed = [n for n, L in enumerate(self.lengths) if (L + s) // C > L // C]
+        img = self.image.view(N, -1)
+        for n in crossed:
+            self.image_backup[n].copy_(img[n])
+        self._stage_rows(q, k, v)
+        if self.use_graph:
+            g, self.csr, self._col_emit, self.probs, _pins = self._graphs[s]
+            g.replay()
+            self.csr._wire = None                                  # (as in `step`: the handle is every replay's)
+            if self._col_emit is not None:
+                self.csr._pending = self._col_emit
+        else:
+            self._launch_rows(s)
+        self._last_step = (s, list(self.lengths), crossed)
+        self.lengths = [L + s for L in self.lengths]
+        return self._rows_views(s)[4]
+
+    @torch.no_grad()
+    def rewind(self, drop) -> None:
+        """Undo the last drop[n] rows of the last step in slot n (0 <= drop[n] <= s of that step; speculative decoding drops
+        the rejected draft tokens).  Slot n is then bitwise what a plain session is after stepping only the kept rows: its
+        Performer image, CNN rings, K / V rows below its length and every later step.  Only the last step, once, and only
+        while nothing else has changed the session (another `step` or an `admit` ends the chance).  Sessions built with
+        `max_step_rows`; ValueError otherwise, and for a rewind without a step to undo or a bad `drop`, with nothing changed."""
+        if self.max_step_rows is None:
+            raise ValueError("rewind: a session built with DecodeSession.from_sequences(..., max_step_rows=...)")
+        if self._last_step is None:
+            raise ValueError("rewind: no step to undo (only the last step, once, and not after an admit)")
+        s, before, crossed = self._last_step
+        drop = [int(d) for d in drop]
+        if len(drop) != self.N:
+            raise ValueError(f"rewind: {len(drop)} counts for {self.N} slots")
+        if not all(0 <= d <= s for d in drop):
+            raise ValueError(f"rewind: counts {drop} outside 0 .. {s} (the rows of the last step)")
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        kept = [L + s - d for L, d in zip(before, drop)]
+        img, C = self.image.view(self.N, -1), self.chunk
+        for n in crossed:
+            if kept[n] // C == before[n] // C:        # back below the boundary the step completed: the image from before it
+                img[n].copy_(self.image_backup[n])
+        ctr = torch.tensor([[L, L + 1, L] for L in kept], dtype=torch.int32).pin_memory()
+        self.ctr32.copy_(ctr, non_blocking=True)
+        self.lengths = kept
+        self._last_step = None
+
 
 class SessionState:
     """What a graph-replayed step hands back in the place of a `PerlinAttentionState` (e.g. as the third element of the
     OPT block's cache tuple): a ticket for the NEXT step of the same session.  It is valid while the session has not moved
-    on; `materialize()` turns it into a real state for a call the session cannot serve (several tokens at once)."""
+    on; `materialize()` turns it into a real state for a call the session cannot serve (several tokens at once: the OPT
+    block's uniform session takes one; a ragged session built with `max_step_rows` takes several itself)."""
 
     def __init__(self, session: DecodeSession):
         self.session = session

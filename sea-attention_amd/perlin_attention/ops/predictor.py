@@ -706,6 +706,27 @@ def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.
                                     _lib.stream_ptr()), "sea_decode_stage")
 
 
+@_lib.device_guarded
+def decode_stage_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.Tensor, kv_cache: torch.Tensor,
+                      counters: torch.Tensor) -> None:
+    """`sea_decode_stage_rows`: the s new rows of a decoding step, (N,H,s,D) each with 1 <= s <= 8 (any [n,h,t] strides), into
+    the session's static buffers -- q into q_in (N,H,s,D) dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at
+    row counters[n, 0] + j (an (N, >= 1) view of a per-sequence counter block; a 1-D counter is the batch's one)."""
+    lib = _lib.load()
+    _lib.require_gpu(q, k, v, q_in, kv_cache, counters)
+    N, H, s, D = q.shape
+    assert k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
+    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, s, D) and kv_cache.is_contiguous()
+    assert kv_cache.shape[0] == 2 and kv_cache.shape[1] == N and kv_cache.shape[2] == H
+    stride = _lib.counter_stride(counters, N)
+    ok = lambda t: t.stride(-1) == 1 and all(t.stride(i) % 8 == 0 for i in range(3)) and t.data_ptr() % 16 == 0
+    q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
+    st = lambda t: (ctypes_i64 * 3)(t.stride(0), t.stride(1), t.stride(2))
+    _lib.check(lib.sea_decode_stage_rows(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, s, D, st(q), st(k), st(v), _p(q_in),
+                                         _p(kv_cache), kv_cache.shape[3], _p(counters), stride, _lib.stream_ptr()),
+               "sea_decode_stage_rows")
+
+
 def decode_fork_staging_bytes(image_bytes: int, x_ring_bytes: int, y1_ring_bytes: int, table_entries: int) -> int:
     """Bytes of one staging slot of `sea_decode_fork` (include/sea_hip.h): the small state of a slot, counters and table row
     padded to 16-byte chunks."""
@@ -794,6 +815,51 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
         float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
         _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
         int(T_cap), _p(tab), stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select")
+    return probs, (bits, row_nnz, head_off)
+
+
+@_lib.device_guarded
+def decode_cnn_tail_select_rows(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: torch.Tensor, y2: torch.Tensor,
+                                y1_scratch: torch.Tensor, conv1, conv2, conv_w: torch.Tensor, conv_b: torch.Tensor,
+                                ln_w: torch.Tensor, ln_b: torch.Tensor, T_m: int, keep: torch.Tensor, k: int,
+                                counters: torch.Tensor, ticket: torch.Tensor, is_causal: bool = True, eps: float = 1e-5,
+                                want_probs: bool = True):
+    """`sea_decode_cnn_tail_select_rows`: `decode_cnn_tail_select` for a step of s = x_new.shape[1] new rows per sequence (1 ..
+    8).  x_new and y2 (N, s, C/8, 64, 8), y1_scratch (N, s, 2, C/8, 64, 8) dense; rings of at least 2 * dilation + s slots.
+    No crow: the caller runs the row scan (`csr_from_selection`).  Returns (probs (N,H,s,T_m) or None, (bits, row_nnz,
+    head_off))."""
+    lib = _lib.load()
+    _lib.require_gpu(x_new, x_ring, y1_ring, y2, y1_scratch, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket)
+    N, s, C8, W4, _e = x_new.shape
+    C, H, dt, dev = C8 * 8, conv_w.shape[0], x_new.dtype, x_new.device
+    assert _e == 8 and x_new.is_contiguous() and x_ring.is_contiguous() and y1_ring.is_contiguous()
+    assert y2.is_contiguous() and tuple(y2.shape) == tuple(x_new.shape)
+    assert y1_scratch.is_contiguous() and tuple(y1_scratch.shape) == (N, s, 2, C8, W4, 8)
+    assert x_ring.shape[0] == N and tuple(x_ring.shape[2:]) == (C8, W4, 8) and tuple(y1_ring.shape[2:]) == (C8, W4, 8)
+    assert decode_cnn_supported(C, H, T_m, dt) and W4 * 4 == T_m
+    for cv in (conv1, conv2):
+        assert cv.kernel_size == 3 and cv.in_channels == C and cv.out_channels == C and cv.padding[1] == cv.dilation == conv1.dilation
+    stride = _lib.counter_stride(counters, N)
+    assert (counters.numel() == 3 or stride > 0) and counters.shape[-1] == 3 and counters.is_contiguous()
+    assert ticket.dtype == torch.int32 and ticket.numel() == 1 and keep.dtype == torch.int32 and keep.ndim == 1
+    packs = []
+    for cv in (conv1, conv2):
+        packs.append(_cached("conv", (cv.weight, cv.bias), dt,
+                             lambda cv=cv: (pack_conv_weight(cv.weight, 3, dt), cv.bias.to(dt).float().contiguous())))
+    (w1p, CinP), b1 = packs[0]
+    (w2p, _c), b2 = packs[1]
+    _cw, cb, g, b, w16, Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, dev)
+    tab = _tail_consts(ln_w, ln_b, 4, T_m, dt, dev)
+    probs = torch.empty((N, H, s, T_m), dtype=dt, device=dev) if want_probs else None
+    Wb = (H * T_m + 31) // 32
+    bits = torch.empty((N, s, Wb), dtype=torch.int32, device=dev)
+    row_nnz = torch.empty((N, s), dtype=torch.int32, device=dev)
+    head_off = torch.empty((N, s, H + 1), dtype=torch.int32, device=dev)
+    _lib.check(lib.sea_decode_cnn_tail_select_rows(
+        _p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _p(y1_scratch), _lib.dtype_code(dt), N, s, C, H, W4, x_ring.shape[1],
+        y1_ring.shape[1], _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp,
+        _p(g), _p(b), float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz),
+        _p(head_off), _p(tab), stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select_rows")
     return probs, (bits, row_nnz, head_off)
 
 
