@@ -115,7 +115,9 @@ int sea_csr_row_scan(const int32_t* row_nnz, int64_t N, int64_t T_dst,
  * A length PER SEQUENCE, t_src_stride > 0 (the decode form of a batch whose sequences sit at different positions; 0 = one
  * length for the batch): batch item n's rows follow t_src_dev[n * t_src_stride], ids are head * T_src + key with T_src the
  * capacity as above.  A non-zero stride with t_src_dev = NULL, or a negative one: SEA_EINVAL; with values_out:
- * SEA_EUNSUPPORTED. */
+ * SEA_EUNSUPPORTED.
+ * A sequence that SITS OUT a decoding step (below, sea_decode_cnn_tail_select) has an empty crow row, written by that launch:
+ * a row with crow[t] == crow[t + 1] returns before it reads its length, so nothing is emitted for it. */
 int sea_csr_emit(const uint32_t* bits, const void* crow, const int32_t* head_off,
                  int64_t N, int64_t H, int64_t T_dst, int64_t T_m,
                  int64_t T_src, int is_causal, int max_k,
@@ -249,6 +251,11 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * table_stride >= ceil(T_src / page_rows), at most 4096 pages per table row; the page stride must stay below 4 GB and a page
  * below 2 GB.  Null pointers, t_src_stride = 0, a bad page size or table stride: SEA_EINVAL; other dtypes / D / shapes:
  * SEA_EUNSUPPORTED.  Without a table, page_rows and table_stride must be 0 (else SEA_EINVAL).
+ * A sequence that sits out the step (per-sequence decode form: t_src_dev[n * t_src_stride] < 0, see sea_decode_cnn_tail_select):
+ * its workgroups read no block table entry, K or V row and store ZEROS to its output rows (no row scale, no mix with avg) --
+ * the one-row kernel in all its forms, the paged ones included, and the T_dst = 2 .. 8 lane-group forms.  The test is on the
+ * length the workgroup loads anyway, at its first use: q, crow and head_off of the sequence (valid memory; crow / head_off as
+ * the selection launch wrote its empty rows) may have been read by then.
  */
 enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2 };
 int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
@@ -410,7 +417,13 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  * (16-bit); ring sizes > 2 * dilation.  C = 2 H <= 80, H % 4 == 0.
  * A counter triple PER SEQUENCE, counter_stride > 0 (0 = the batch's one triple): sequence n's {seen, T_src, T_src just
  * finished} at counters + n * counter_stride (counter_stride >= 3, else SEA_EINVAL).  Workgroup n reads its own triple (ring
- * slots, row widths, the in-launch emit); the last workgroup advances all N triples as above. */
+ * slots, row widths, the in-launch emit); the last workgroup advances all N triples as above.
+ * SITTING OUT (per-sequence triples; DecodeSession.pause / release): a sequence whose triple is NEGATIVE takes no part in the
+ * step.  The convention of every decode entry that takes per-sequence counters: the caller stores the bitwise complement of
+ * each value, {~seen, ~T_src, ~T_src just finished} (reversible; -1 = ~0 for a slot that holds no sequence), a value no live
+ * sequence reaches, and writes the plain values back to let it take part again.  Here workgroup n of such a sequence leaves
+ * both rings alone, writes its selection as an EMPTY row (bits 0, head_off 0, row_nnz 0, crow_out {0, 0}; probs, y2 and col
+ * keep what they held) and STILL takes its ticket; the last workgroup's advance leaves a negative triple as it is. */
 int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
                                int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
                                const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
@@ -436,7 +449,10 @@ int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, v
  * 2 * dilation + max rows.  The last of the N * rows workgroups advances every triple: counters[2] = counters[0] + rows,
  * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what sea_decode_cnn_tail_select does).  x_new (N, rows, C/8,
  * 64, 8) dense.  Everything else, and the other refusals, as for sea_decode_cnn_tail_select; rows outside 1 .. 8: SEA_EINVAL.
- * (A later ABI version can fold sea_decode_cnn_tail_select into this entry: rows = 1 plus the one-row form's crow_out / col.) */
+ * (A later ABI version can fold sea_decode_cnn_tail_select into this entry: rows = 1 plus the one-row form's crow_out / col.)
+ * A sequence that sits out (negative triple, as for sea_decode_cnn_tail_select): each of its `rows` workgroups writes an empty
+ * row (the row scan behind the launch then gives it an empty crow), touches neither ring nor scratch and takes its ticket; the
+ * advance skips the triple. */
 int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
                                     int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
                                     const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2,
@@ -578,7 +594,11 @@ int sea_performer_plan(int64_t N, int64_t H, int64_t T, int64_t D, int64_t nb, i
  * block_table[n * table_stride + c0 / page_rows] from row c0 % page_rows on: page_rows is a power of two and a multiple of C,
  * so one table lookup per workgroup serves the step.  capacity: the logical rows a table row covers (table_stride >=
  * ceil(capacity / page_rows)).  Everything else as in the per-sequence form, bitwise.  A table with t_base_stride = 0, or
- * page_rows / table_stride / capacity non-zero without one: SEA_EINVAL. */
+ * page_rows / table_stride / capacity non-zero without one: SEA_EINVAL.
+ * A sequence that sits out the step (per-sequence form, 16-bit kernels: t_base_dev[n * t_base_stride] < 0, the convention of
+ * sea_decode_cnn_tail_select): its workgroups return before their first q / K / V load, the state image untouched; its rows
+ * of `out` and `avg_out` keep what they held (stale, never mixed into another sequence's rows).  The paged form has read
+ * entry 0 of the sequence's table row by then (the index is clamped; the entry may be anything and is used for nothing). */
 int64_t sea_performer_chunk_rows(int64_t D, int64_t nb, int dtype);
 int64_t sea_performer_state_bytes(int64_t N, int64_t H, int64_t D, int64_t nb, int dtype);
 int sea_performer_causal_step(const void* q, const void* k, const void* v, const void* pos, int dtype,
@@ -614,6 +634,8 @@ int64_t sea_sparse_attention_bytes(int64_t Z, int64_t N, int64_t H, int64_t T_ds
  *   ctr / page_rows], row ctr % page_rows (ctr = counters[n * counter_stride]).  A row at or beyond `capacity`, or whose table
  *   entry is outside 0 .. pool_pages-1, writes nothing.  Page rule and refusals as for sea_sparse_attention's paged form; a
  *   table with counter_stride = 0, or page_rows / table_stride / pool_pages non-zero without one: SEA_EINVAL.
+ *   A sequence that sits out the step (counter < 0, the convention of sea_decode_cnn_tail_select) is such a row: no k / v row
+ *   is written and no table entry read; its q row is handed over and read by nobody.
  * sea_c8_window_shift: xs (N, rows, row_bytes) moved up by one row in place (xs[n, r] = xs[n, r + 1]): the predictor CNN's
  *   window after a step whose MLP wrote the new row behind it (sea_predictor_mlp with x_c8_stride_n).  `counters` (optional):
  *   two device int32 advanced by one by the same launch -- the LAST of a step, so every reader of the step is done. */
@@ -627,7 +649,9 @@ int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, in
  *   v (N,H,rows,D) with element strides {n, h, t}, feature stride 1, 16-byte aligned rows; q is copied into q_in (N,H,rows,D)
  *   dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at row counters[n * counter_stride] + j (counter_stride 0:
  *   the batch's one counter).  A row at or beyond the capacity writes nothing.  Contiguous caches only.  Refusals as for
- *   sea_decode_stage; rows outside 1 .. 8: SEA_EINVAL.  (A later ABI version can fold sea_decode_stage into this entry.) */
+ *   sea_decode_stage; rows outside 1 .. 8: SEA_EINVAL.  (A later ABI version can fold sea_decode_stage into this entry.)
+ *   A sequence whose counter is negative sits out the step: none of its k / v rows is written (the test is on the counter, not
+ *   on counter + j). */
 int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows, int64_t D,
                           const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, void* q_in,
                           void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
@@ -657,7 +681,10 @@ int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype
  * This is the only entry that writes one slot's state from another's; it must not run concurrently with a step of the same
  * session (call it in the step's stream, between steps).  Null pointers (staging: when n_staged > 0), M outside 1 .. N,
  * n_staged outside 0 .. M, a counter_stride below 3, a bad page size / table stride / pool, a staging buffer too small:
- * SEA_EINVAL; other dtypes / D, ring bytes that are not whole 16-byte chunks, unaligned buffers: SEA_EUNSUPPORTED. */
+ * SEA_EINVAL; other dtypes / D, ring bytes that are not whole 16-byte chunks, unaligned buffers: SEA_EUNSUPPORTED.
+ * A source that sits out steps (negative counters = the complement of its values, sea_decode_cnn_tail_select): the counters
+ * are copied as they are -- the copy sits out too -- and the open page index is taken from the DECODED `seen` (~counter).  The
+ * kernel decodes; the caller passes the slot's open page in `moves` as for any source. */
 int sea_decode_fork(const int32_t* moves, int64_t M, int64_t n_staged, int dtype, int64_t N, int64_t H, int64_t D, int64_t nb,
                     void* image, void* x_ring, int64_t x_ring_bytes, void* y1_ring, int64_t y1_ring_bytes,
                     int32_t* counters, int64_t counter_stride, int32_t* block_table, int64_t table_stride, int64_t capacity,

@@ -358,7 +358,21 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? p.t_src_dev[n * p.t_src_stride] : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  int t_src = p.T_src;
+  if constexpr (DEC) {
+    t_src = p.t_src_dev[n * p.t_src_stride];               // the sequence's length (block-uniform; the one load of it)
+    if (t_src < 0) {                                       // the sequence sits out this step (DecodeSession.pause / release): no
+      const int t0 = tb * RPB + gi;                        // K or V access (its CSR rows are empty), its context rows are zeros
+      if (t0 < p.T_dst && dact) {
+        float o[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o[j] = 0.f;
+        store_frag<TO, VEC>(reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t0 * p.os[2] + sub * VEC, o);
+      }
+      return;
+    }
+  }
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, t_src, s_keys, &lbase, &fits, &ltotal);
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, lane_off);
 
   // ---- a decoding step: T_dst of one or a few rows, so all but a few of the block's lane groups have no row -- and the one
@@ -550,7 +564,23 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
   int lbase = 0;
   bool fits = false;
   int ltotal = 0;
-  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, DEC ? p.t_src_dev[n * p.t_src_stride] : p.T_src, s_keys, &lbase, &fits, &ltotal);
+  int t_src = p.T_src;
+  if constexpr (DEC) {
+    t_src = p.t_src_dev[n * p.t_src_stride];               // the sequence's length (block-uniform; the one load of it)
+    if (t_src < 0) {                                       // the sequence sits out this step: zeros, as in sparse_attn_rows_kernel
+      const int t0 = tb * RPB + gi;
+      if (t0 < p.T_dst) {
+        float o[VEC + XT];
+#pragma unroll
+        for (int j = 0; j < VEC + XT; ++j) o[j] = 0.f;
+        TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t0 * p.os[2];
+        store_frag<TO, VEC>(op + sub * VEC, o);
+        store2<TO>(op + DM + sub * XT, o[VEC], o[VEC + 1]);
+      }
+      return;
+    }
+  }
+  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, t_src, s_keys, &lbase, &fits, &ltotal);
   // (the 16-byte fragments of the lists' K / V rows: 128 of a row's 160 bytes, i.e. both of its cache lines)
   if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, off_m);
 
@@ -669,14 +699,15 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
   const int n = (int)blockIdx.x / p.H, h = (int)blockIdx.x - n * p.H;
   const bool dact = X80 || sub * VEC < p.D;
   const int sube = dact ? sub : 0;
+  const int t_src = p.t_src_dev[n * p.t_src_stride];       // the sequence's length (block-uniform; the one load of it)
   const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + (PAGED ? 0 : n * p.ks[0]) + h * p.ks[1]);
   const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + (PAGED ? 0 : n * p.vs[0]) + h * p.vs[1]);
   const uint32_t kst = (uint32_t)p.ks[2] * (uint32_t)sizeof(T), vst = (uint32_t)p.vs[2] * (uint32_t)sizeof(T);
   int* s_tab = reinterpret_cast<int*>(s_v + (size_t)CH * DL);          // PAGED: [ceil(T_src / page_rows)] the table row
   if constexpr (PAGED) {
-    const int npg = (p.t_src_dev[n * p.t_src_stride] + (1 << p.page_shift) - 1) >> p.page_shift;   // pages holding keys
+    const int npg = (t_src + (1 << p.page_shift) - 1) >> p.page_shift;   // pages holding keys
     const int32_t* trow = p.table + (int64_t)n * p.table_stride;
-    for (int i = tid; i < npg; i += NT) s_tab[i] = trow[i];            // (read after phase B's barrier)
+    for (int i = tid; i < npg; i += NT) s_tab[i] = trow[i];            // (read after phase B's barrier; none when t_src < 0)
   }
   const uint32_t lane_off = (uint32_t)(sube * VEC) * (uint32_t)sizeof(T);
   uint4 qraw = make_uint4(0, 0, 0, 0);
@@ -688,8 +719,22 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
   const int beg = p.crow[(int64_t)n * 2] + p.head_off[(int64_t)n * (p.H + 1) + h];
   const int hcol = h * p.T_src;
 
+  // the sequence sits out this step (DecodeSession.pause / release; block-uniform, at the first use of the length so that the
+  // loads above do not wait for it): no table, K or V access, its context row is zeros
+  if (t_src < 0) {
+    if (grp == 0 && dact) {
+      float o[VEC + 2];
+#pragma unroll
+      for (int j = 0; j < VEC + 2; ++j) o[j] = 0.f;
+      TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1];
+      store_frag<TO, VEC>(op + sub * VEC, o);
+      if constexpr (X80) store2<TO>(op + DM + sub * 2, o[VEC], o[VEC + 1]);
+    }
+    return;
+  }
+
   // ---- B: one thread per pixel of the head --------------------------------------------------------------------------
-  const int w_t = row_width(0, 1, p.t_src_dev[n * p.t_src_stride], p.is_causal);
+  const int w_t = row_width(0, 1, t_src, p.is_causal);
   const float scale = interp_scale(w_t, p.T_m);
   const uint32_t* brow = p.bits + (int64_t)n * p.W + h * (p.T_m >> 5);
   const bool kept = tid < p.T_m && ((brow[tid >> 5] >> (tid & 31)) & 1u);

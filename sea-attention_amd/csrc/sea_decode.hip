@@ -35,7 +35,9 @@ struct StagePagedParams : StageParams {
 };
 
 // RAGGED: a counter pair per sequence, sequence n's at ctr + n * ctr_stride (read per item: the items of a workgroup span
-// sequences); a sequence whose row lies outside the caches writes nothing.  PAGED (with RAGGED): the row goes to the page the
+// sequences); a sequence whose row lies outside the caches writes nothing -- which is also how a sequence that sits out a step
+// (DecodeSession.pause / release: its counters are negative, ~seen) keeps its K / V; its q row is handed over and never read.
+// PAGED (with RAGGED): the row goes to the page the
 // sequence's block table names; a row without a page (an entry outside 0 .. pool_pages-1) writes nothing either
 template <typename T, bool RAGGED, bool PAGED = false>
 __global__ __launch_bounds__(256) void decode_stage_kernel(std::conditional_t<PAGED, StagePagedParams, StageParams> p, int ctr_stride) {
@@ -67,8 +69,9 @@ __global__ __launch_bounds__(256) void decode_stage_kernel(std::conditional_t<PA
 }
 
 // ROWS (sea_decode_stage_rows): `rows` new rows per sequence, (N, H, rows, D) with [n, h, t] strides; q_in (N, H, rows, D)
-// dense; row j of sequence n goes to cache row ctr[n * ctr_stride] + j, nothing for a row at or beyond the capacity.  A kernel
-// of its own, so that the one-row form's code stays what it was
+// dense; row j of sequence n goes to cache row ctr[n * ctr_stride] + j, nothing for a row at or beyond the capacity and nothing
+// for a sequence whose counter is negative (it sits out the step).  A kernel of its own, so that the one-row form's code stays
+// what it was
 struct StageRowsParams {
   const void *q, *k, *v;
   int64_t qs[3], ks[3], vs[3];       // element strides [n, h, t] (feature stride 1)
@@ -89,8 +92,9 @@ __global__ __launch_bounds__(256) void decode_stage_rows_kernel(StageRowsParams 
     const int r = (c - which * items * per) / per, i = c % per;
     const int nh = r / p.rows, j = r - nh * p.rows;
     const int n = nh / p.H, h = nh - n * p.H;
-    const int pos = p.ctr[n * p.ctr_stride] + j;
-    if (which != 0 && (pos < 0 || pos >= p.cap)) continue;
+    const int seen = p.ctr[n * p.ctr_stride];                // (negative: the sequence sits out this step, no K / V row of it)
+    const int pos = seen + j;
+    if (which != 0 && (seen < 0 || pos >= p.cap)) continue;
     const uint4 val = *reinterpret_cast<const uint4*>(srcs[which] + n * strs[which][0] + h * strs[which][1] + j * strs[which][2] + i * 8);
     T* dst = which == 0 ? reinterpret_cast<T*>(p.q_in) + (int64_t)r * p.D
                         : reinterpret_cast<T*>(p.kv_cache) + (((int64_t)(which - 1) * p.N * p.H + nh) * p.cap + pos) * p.D;
@@ -166,7 +170,10 @@ __global__ __launch_bounds__(256) void decode_fork_kernel(ForkParams p) {
       if (STAGE) { slot_tab[j] = p.table[(int64_t)src * p.table_stride + j]; continue; }
       // below the source's open page index (the page row `seen` lies in): the shared closed pages; at it: the destination's
       // own open page (or -1: the source has none); behind it: no page
-      const int seen = staged ? slot_ctr[0] : p.ctr[(int64_t)src * p.ctr_stride];
+      // (a paused source holds ~seen, negative: the copy takes the counters as they are -- it is paused too -- and the open
+      // page index comes from the decoded value)
+      const int enc = staged ? slot_ctr[0] : p.ctr[(int64_t)src * p.ctr_stride];
+      const int seen = enc < 0 ? ~enc : enc;
       const int open = seen >> p.page_shift;
       int32_t e = -1;
       if (j < open) e = staged ? slot_tab[j] : p.table[(int64_t)src * p.table_stride + j];

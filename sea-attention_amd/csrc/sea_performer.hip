@@ -493,7 +493,7 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   int64_t kv_n = n;
   if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
     static_assert(SEQ, "the paged step has a position per sequence");
-    kv_n = p.table[(int64_t)n * p.table_stride + (row_base >> p.page_shift)];
+    kv_n = p.table[(int64_t)n * p.table_stride + (max(row_base, 0) >> p.page_shift)];   // (tb < 0, a sequence sitting out: entry 0, unused)
     cache_row = row_base & ((1 << p.page_shift) - 1);
   }
   const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
@@ -548,6 +548,10 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
     if (tid < FP) sKsum[tid] = ks0;
   }
 
+  // a sequence that sits out this step (DecodeSession.pause / release: its counter row is negative, tb < 0) does nothing: no
+  // K / V / q read, state image and output rows untouched (a paged one has read entry 0 of its table row and uses it for
+  // nothing).  Block-uniform; here, at the position's first use, so that the staging above does not wait for the counter
+  if constexpr (SEQ) { if (tb < 0) return; }
   // one 16-byte piece of each tensor per thread and chunk; prefetched one chunk ahead
   const int sr = tid >> 3, sc = tid & 7;        // staging row, 8-element column chunk
   // All global traffic goes through buffer instructions with hardware range checking: a row beyond T reads zeros /
@@ -1023,7 +1027,7 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   int64_t kv_n = n;
   if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
     static_assert(SEQ, "the paged step has a position per sequence");
-    kv_n = p.table[(int64_t)n * p.table_stride + (row_base >> p.page_shift)];
+    kv_n = p.table[(int64_t)n * p.table_stride + (max(row_base, 0) >> p.page_shift)];   // (tb < 0, a sequence sitting out: entry 0, unused)
     cache_row = row_base & ((1 << p.page_shift) - 1);
   }
   const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
@@ -1090,6 +1094,10 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
     if (tid < FP) sKsum[tid] = ks0;
   }
 
+  // a sequence that sits out this step (DecodeSession.pause / release: its counter row is negative, tb < 0) does nothing: no
+  // K / V / q read, state image and output rows untouched (a paged one has read entry 0 of its table row and uses it for
+  // nothing).  Block-uniform; here, at the position's first use, so that the staging above does not wait for the counter
+  if constexpr (SEQ) { if (tb < 0) return; }
   // one 16-byte piece of each tensor per thread and chunk; q, k prefetched two chunks ahead, [pos | v] one
   // (D = 80: the LAST C * D / 8 = 320 threads stage -- waves 0 and 1 carry a second column block in (d)(e))
   const bool stager = tid >= NTH - STG;

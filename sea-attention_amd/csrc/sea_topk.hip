@@ -1047,6 +1047,60 @@ struct DecodeCnnParams {
   int C, W, RX, RY, dil, pad_w;
 };
 
+// A sequence that sits out the step (DecodeSession.pause / release): its counter triple holds ~seen, ~tsrc, ~tsrc_done -- negative,
+// which no live sequence reaches -- and its workgroup leaves the rings alone, writes the selection of its row as an EMPTY row
+// (no kept pixel, head offsets and entry count zero, crow [0, 0]) and still takes its ticket.  Block-uniform: the position is
+// the scalar the workgroup has loaded anyway.
+__device__ __forceinline__ void select_empty_row(const TopkParams& p, const int row) {
+  for (int i = threadIdx.x; i < p.W; i += TK_THREADS) p.bits[(int64_t)row * p.W + i] = 0u;
+  for (int i = threadIdx.x; i <= p.H; i += TK_THREADS) p.head_off[(int64_t)row * (p.H + 1) + i] = 0;
+  if (threadIdx.x == 0) {
+    p.row_nnz[row] = 0;
+    if (p.crow1 != nullptr) { p.crow1[2 * row] = 0; p.crow1[2 * row + 1] = 0; }
+  }
+}
+
+// The ticket of the fused CNN launches: the LAST workgroup to finish (every one has read the counters by then) advances the
+// triples by `rows` positions -- [seen + rows, seen + rows + 1, T_src of the step just closed] -- and resets the ticket.  A
+// negative triple (a sequence sitting out) stays as it is.  `seqs`: triples (1: one for the batch).  One thread walks them, so
+// the loads of eight triples leave together and the stores follow: a load -> test -> store chain per triple would put a memory
+// round trip per sequence at the end of every step.
+template <bool ROWS>
+__device__ __forceinline__ void decode_cnn_ticket(const DecodeCnnParams& dp, const int seqs, const int rows) {
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const int done = atomicAdd(dp.ticket, 1);
+    if (done == (int)gridDim.x - 1) {
+      constexpr int B = 8;
+      for (int m0 = 0; m0 < seqs; m0 += B) {
+        int seen[B], ts[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+          const int32_t* c = dp.counters + min(m0 + i, seqs - 1) * dp.ctr_stride;      // (past the end: the last triple again)
+          seen[i] = c[0];
+          ts[i] = ROWS ? 0 : c[1];
+        }
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+          if (m0 + i >= seqs || seen[i] < 0) continue;
+          int32_t* c = dp.counters + (m0 + i) * dp.ctr_stride;
+          if constexpr (ROWS) {
+            c[2] = seen[i] + rows;
+            c[0] = seen[i] + rows;
+            c[1] = seen[i] + rows + 1;
+          } else {
+            c[2] = ts[i];                                          // (the emit launch behind this one reads the step's T_src here)
+            c[0] = seen[i] + 1;
+            c[1] = ts[i] + 1;
+          }
+        }
+      }
+      *dp.ticket = 0;
+      __threadfence();
+    }
+  }
+}
+
 // EMIT: the selection's one CSR row is expanded into its column ids here too (csr_emit_row: the decode-form sea_csr_emit launch that
 // followed); instantiated wherever the emit's 20 KB of LDS fit beside the weight image (all but the 80-channel form).
 template <typename T, int EPT, int NT, int KCH, bool EMIT>
@@ -1072,6 +1126,13 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
   c1.load_bias(dp.b1, dp.C);
   c2.load_bias(dp.b2, dp.C);
   c1.fetch_row(2, xn, dp.C, dp.W, dp.dil, dp.pad_w);
+  // (the first use of the position, so the loads above do not wait for it.)  Block-uniform: the sequence sits out, see
+  // select_empty_row; what is in flight lands in registers nobody reads
+  if (pos < 0) {
+    select_empty_row(p, n);
+    decode_cnn_ticket<false>(dp, dp.ctr_stride ? (int)gridDim.x : 1, 1);
+    return;
+  }
   c1.fetch_row(0, xr + slot(pos - 2 * dp.dil, dp.RX) * row, dp.C, dp.W, dp.dil, dp.pad_w);
   c1.fetch_row(1, xr + slot(pos - dp.dil, dp.RX) * row, dp.C, dp.W, dp.dil, dp.pad_w);
   c2.fetch_row(0, yr + slot(pos - 2 * dp.dil, dp.RY) * row, dp.C, dp.W, dp.dil, dp.pad_w);      // (conv1's rows of earlier positions)
@@ -1104,22 +1165,7 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
     }
   }
   STAMP(13);  // decode: emit
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const int done = atomicAdd(dp.ticket, 1);
-    if (done == (int)gridDim.x - 1) {                              // every workgroup has read the counters and finished
-      const int rows = dp.ctr_stride ? (int)gridDim.x : 1;         // (per-sequence counters: every sequence's triple)
-      for (int m = 0; m < rows; ++m) {
-        int32_t* c = dp.counters + m * dp.ctr_stride;
-        const int ts = c[1];
-        c[2] = ts;                                                 // (the emit launch behind this one reads the step's T_src here)
-        c[0] = c[0] + 1;
-        c[1] = ts + 1;
-      }
-      *dp.ticket = 0;
-      __threadfence();
-    }
-  }
+  decode_cnn_ticket<false>(dp, dp.ctr_stride ? (int)gridDim.x : 1, 1);   // (per-sequence counters: every sequence's triple)
 }
 
 // ---- the same for a step of `rows` (1 .. 8) new rows per sequence (sea_decode_cnn_tail_select_rows) -----------------------------
@@ -1153,6 +1199,11 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_rows_kernel
   c1.load_bias(dp.b1, dp.C);
   c2.load_bias(dp.b2, dp.C);
   c1.store_weights(sW);
+  if (seen < 0) {                                                  // (block-uniform; the first use of the position) the sequence sits
+    select_empty_row(p, b);                                        // out: see select_empty_row
+    decode_cnn_ticket<true>(dp, dp.ctr_stride ? (int)gridDim.x / rows : 1, rows);
+    return;
+  }
   const T* y1p[3];                                                 // conv1's rows t - 2 dil, t - dil, t
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -1186,22 +1237,7 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_rows_kernel
   ps.keep = p.keep + seen;
   tail_select_row<T, EPT, false>(tp, ps, s_z, b);                 // row b = n * rows + j of the call
   __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const int done = atomicAdd(dp.ticket, 1);
-    if (done == (int)gridDim.x - 1) {                              // every workgroup has read the counters and finished
-      const int seqs = dp.ctr_stride ? (int)gridDim.x / rows : 1;
-      for (int m = 0; m < seqs; ++m) {
-        int32_t* c = dp.counters + m * dp.ctr_stride;
-        const int s0 = c[0] + rows;
-        c[2] = s0;
-        c[0] = s0;
-        c[1] = s0 + 1;
-      }
-      *dp.ticket = 0;
-      __threadfence();
-    }
-  }
+  decode_cnn_ticket<true>(dp, dp.ctr_stride ? (int)gridDim.x / rows : 1, rows);
 }
 
 // ---- per-(row, head) offsets of a foreign flat CSR (rows grouped by ascending head) ----------------

@@ -67,6 +67,23 @@ a slot read after any rewind is still where it was, K / V rows past the kept len
 anything reads them, and the Performer image -- which changes only when a chunk completes, at most once per step (s <= 8 <=
 chunk) -- is copied aside before a step that completes one and copied back when the rewind falls below that boundary.  A
 rewound slot is bitwise a plain session that stepped only the kept rows.
+
+Slots that sit out steps (`pause`, `resume`, `release`; `None` entries of `from_sequences`; ragged sessions): the captured
+graph has a fixed grid and static arguments, so "slot n does nothing this step" is a fact in device memory -- the slot's
+counter row holds the bitwise complement of its values, (~seen, ~tsrc, ~tsrc_done): negative, which no live sequence reaches,
+and every launch that carries per-sequence state already loads one of the three.  Its workgroups leave by a block-uniform
+early-out on that scalar: the stage writes no K / V row, the Performer touches neither the image nor a page, the CNN launch
+leaves the rings alone and writes an empty selection row (crow [0, 0], so the emit writes nothing), the attention stores zeros
+(include/sea_hip.h, at each entry).  The CNN workgroup still takes its ticket -- the last one advances the counters and resets
+the ticket -- and the advance skips negative rows.  The true position lives in the host mirror `lengths`; `pause` / `resume`
+/ `release` rewrite the counter block with one small stream-ordered copy, as `rewind` does, so `captures` does not move.  A
+paused slot keeps everything (a parked prompt: `pause` it, `fork` from it as requests arrive -- `sea_decode_fork` decodes the
+source's `seen` for the open page and copies the counters as they are, so the copy is paused too -- then `resume` the copies);
+`release` also drops the sequence and gives its pages back: the slot is EMPTY (counters ~0, length 0) until `admit`, `fork` or
+`reorder` fills it.  Capacity and page growth look at the slots that take part only.  The slots that do take part are
+bitwise what they are without the others (tests/test_gpu_decode_pause.py).  The emit + unfused attention pair
+(`fused_attention=False`) knows only an empty CSR row, whose context is the average mix; there the zeros of sitting-out slots
+are small fills behind the step.
 """
 from collections import deque
 from typing import List, Optional
@@ -163,6 +180,8 @@ class DecodeSession:
     block_table = None
     max_step_rows = None         # (from_sequences(..., max_step_rows=S): steps of 1 .. S rows and `rewind`)
     _last_step = None            # (what `rewind` may undo: (s, lengths before, slots whose image was copied aside))
+    _paused = None               # (ragged sessions: host mirrors of the slots that sit out steps / hold no sequence)
+    _empty = None
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -266,16 +285,20 @@ class DecodeSession:
         (`fused_attention=True`, d in {64, 80, 128}).  ValueError otherwise, or when the prefixes do not fit the pool.
         `max_step_rows` S in 1 .. 8: `step` takes 1 .. S new rows per slot and `rewind` drops rows of the last step again
         (module docstring); contiguous K / V with the fused decode attention only (ValueError with `page_rows` or
-        `fused_attention=False`).  None: one row per step, no rewind."""
+        `fused_attention=False`).  None: one row per step, no rewind.
+        An entry of `sequences` may be None: that slot starts EMPTY (as after `release`) and sits out until `admit`, `fork`
+        or `reorder` fills it; at least one entry is a real sequence."""
         self = cls.__new__(cls)
         at = self.attention = attention
         pc = at.pconfig
         seqs = list(sequences)
         if not (pc.causal and not at.training):
             raise ValueError("decoding is the causal inference path")
-        if not seqs:
-            raise ValueError("from_sequences needs at least one (state, key_prefix, value_prefix)")
-        kp0 = seqs[0][1]
+        real = [sq for sq in seqs if sq is not None]
+        if not real:
+            raise ValueError("from_sequences needs at least one (state, key_prefix, value_prefix): H, D, dtype and device "
+                             "are those of the first real sequence")
+        kp0 = real[0][1]
         if kp0.dim() != 4:
             raise ValueError("key / value prefixes are (1, H, L, D)")
         self.N, self.H, self.D, self.capacity = len(seqs), int(kp0.shape[1]), int(kp0.shape[3]), int(capacity)
@@ -299,7 +322,7 @@ class DecodeSession:
                 raise ValueError("multi-row steps run on contiguous K / V with the fused decode attention (no page_rows, "
                                  "fused_attention=True)")
             self.max_step_rows = int(max_step_rows)
-        lengths = [self._check_sequence(*sq) for sq in seqs]
+        lengths = [0 if sq is None else self._check_sequence(*sq) for sq in seqs]       # (None: the slot starts empty)
         N, H, D, dt, dev = self.N, self.H, self.D, self.dtype, kp0.device
         n_tab = None
         if page_rows is not None:
@@ -314,7 +337,7 @@ class DecodeSession:
             if page_rows < 1 or page_rows & (page_rows - 1) or page_rows % chunk:
                 raise ValueError(f"page_rows {page_rows}: a power of two and a multiple of the Performer chunk ({chunk} rows)")
             n_tab = -(-self.capacity // page_rows)
-            need = sum(-(-(L + 1) // page_rows) for L in lengths)
+            need = sum(-(-(L + 1) // page_rows) for L, sq in zip(lengths, seqs) if sq is not None)
             pool_pages = N * n_tab if pool_pages is None else int(pool_pages)
             if pool_pages < need:
                 raise ValueError(f"a pool of {pool_pages} pages of {page_rows} rows cannot hold the prefixes ({need} pages)")
@@ -323,8 +346,8 @@ class DecodeSession:
         self.ragged = True
         dil = convs[0].dilation
         row_shape = (C // 8, self.T_M // 4, 8)
-        per = seqs[0][0].states[PerlinAttentionState.PERFORMER].image.numel()
-        self.image = torch.empty((N * per,), dtype=torch.float32, device=dev)          # sequence n's H images: the n-th slice
+        per = real[0][0].states[PerlinAttentionState.PERFORMER].image.numel()
+        self.image = torch.zeros((N * per,), dtype=torch.float32, device=dev)          # sequence n's H images: the n-th slice
         S = self.max_step_rows
         if S is None:
             self.x_ring = torch.zeros((N, self.LB) + row_shape, dtype=dt, device=dev)
@@ -360,9 +383,14 @@ class DecodeSession:
         self.ctr32 = torch.zeros((N, 3), dtype=torch.int32, device=dev)
         self.seen32, self.tsrc32, self.tsrc_done32 = self.ctr32[:, 0:1], self.ctr32[:, 1:2], self.ctr32[:, 2:3]
         self.crow = torch.zeros((N, 2), dtype=torch.int32, device=dev)
-        self.lengths = list(lengths)                                         # host mirror (bounds checks only)
-        for n, (st, kp, vp) in enumerate(seqs):
-            self._seed_slot(n, st, kp, vp)
+        self.lengths = list(lengths)                                         # host mirror (bounds checks; a sitting-out slot's position)
+        self._paused = [sq is None for sq in seqs]                           # (an empty slot sits out like a paused one)
+        self._empty = [sq is None for sq in seqs]
+        for n, sq in enumerate(seqs):
+            if sq is not None:
+                self._seed_slot(n, *sq)
+        if any(self._empty):
+            self._write_counters()
         self._static_buffers(dev, dt, fused_attention)
         if S is not None:
             self.q_in = torch.zeros((N * H * S * D,), dtype=dt, device=dev)
@@ -467,6 +495,8 @@ class DecodeSession:
             raise ValueError("sequence_kv: a ragged session (DecodeSession.from_sequences)")
         if not 0 <= slot < self.N:
             raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        if self._empty[slot]:
+            raise ValueError(f"sequence_kv: slot {slot} is empty (released, or never admitted)")
         L = self.lengths[slot]
         if self.paged:
             idx = torch.tensor(self.pages[slot], dtype=torch.long, device=self.kv_cache.device)
@@ -476,10 +506,10 @@ class DecodeSession:
         return kv[0:1].clone(), kv[1:2].clone()
 
     def _grow_pages(self):
-        """Before a step's first launch: a page for every slot whose next row starts one.  Refused (RuntimeError naming the
+        """Before a step's first launch: a page for every slot that takes part and whose next row starts one.  Refused (RuntimeError naming the
         slots, nothing changed) when the pool has too few; the table entries are written in stream order behind the host's
         decision (small fills, no synchronise)."""
-        want = [n for n, L in enumerate(self.lengths) if L >= len(self.pages[n]) * self.page_rows]
+        want = [n for n, L in enumerate(self.lengths) if not self._paused[n] and L >= len(self.pages[n]) * self.page_rows]
         if not want:
             return
         if len(want) > self.allocator.free_pages:
@@ -506,6 +536,7 @@ class DecodeSession:
         if self.csr is not None and self.csr.col_is_pending:
             self.csr.col                              # the last step's pending columns follow the counters: emit before they move
         self._seed_slot(slot, state, key_prefix, value_prefix)
+        self._paused[slot] = self._empty[slot] = False                       # (a paused or empty slot: active on the new sequence)
         self._last_step = None                        # (an admit ends the chance to rewind)
 
     @torch.no_grad()
@@ -514,8 +545,9 @@ class DecodeSession:
         the same length, Performer image, CNN rings and counters.  Its block table names `src`'s closed pages -- shared,
         never copied -- and a private copy of `src`'s open page (the page the next row goes to; none when `src`'s last step
         filled a page: the next step gives every slot a page of its own).  Paged ragged sessions only, between steps, one
-        `sea_decode_fork` call; the captured graph stays.  Refused, with nothing changed: a slot out of range (IndexError),
-        `src` in `dsts` or a repeated slot (ValueError), too few free pages (RuntimeError naming the slots)."""
+        `sea_decode_fork` call; the captured graph stays.  A copy of a paused slot is paused (`resume` it); an empty
+        destination is filled.  Refused, with nothing changed: a slot out of range (IndexError), `src` in `dsts`, a
+        repeated slot or an empty `src` (ValueError), too few free pages (RuntimeError naming the slots)."""
         self._require_paged("fork")
         dsts = [int(d) for d in dsts]
         for n in [src] + dsts:
@@ -523,6 +555,8 @@ class DecodeSession:
                 raise IndexError(f"slot {n} outside 0..{self.N - 1}")
         if src in dsts or len(set(dsts)) != len(dsts):
             raise ValueError(f"fork({src}, {dsts}): the destinations are distinct slots other than the source")
+        if self._empty[src]:
+            raise ValueError(f"fork: slot {src} is empty (released, or never admitted): nothing to copy")
         parents = list(range(self.N))
         for d in dsts:
             parents[d] = src
@@ -534,7 +568,8 @@ class DecodeSession:
         once (swaps, cycles and many-to-one included).  Slots with parents[i] == i cost nothing.  Moved slots share their
         parent's closed pages and get a private copy of its open page, as in `fork`; the pages only the old contents of a
         moved slot held go back to the pool after the call has taken its new pages.  Refused, with nothing changed: a
-        parent map of the wrong length (ValueError), a parent out of range (IndexError), too few free pages (RuntimeError)."""
+        parent map of the wrong length or an empty parent of another slot (ValueError), a parent out of range (IndexError),
+        too few free pages (RuntimeError).  Whether a slot is paused travels with its contents."""
         self._require_paged("reorder")
         parents = [int(p) for p in parents]
         if len(parents) != self.N:
@@ -542,7 +577,98 @@ class DecodeSession:
         for p in parents:
             if not 0 <= p < self.N:
                 raise IndexError(f"parent slot {p} outside 0..{self.N - 1}")
+        gone = sorted({p for i, p in enumerate(parents) if p != i and self._empty[p]})
+        if gone:
+            raise ValueError(f"reorder: parent slot(s) {gone} are empty (released, or never admitted): nothing to copy")
         self._move(parents)
+
+    @property
+    def paused(self) -> List[bool]:
+        """Which slots sit out the steps (host mirror): paused ones, and empty ones -- `release` is a pause that also drops
+        the sequence.  All False for a uniform session."""
+        return list(self._paused) if self.ragged else [False] * self.N
+
+    @property
+    def empty(self) -> List[bool]:
+        """Which slots hold no sequence (released, or built from a None entry) until `admit`, `fork` or `reorder` fills them."""
+        return list(self._empty) if self.ragged else [False] * self.N
+
+    def _write_counters(self):
+        """The device counter rows from the host mirrors, one small stream-ordered copy: [L, L + 1, L] for a slot that takes
+        part (what a step leaves behind), the bitwise complement of each for one that sits out (the module docstring)."""
+        rows = [[~L, ~(L + 1), ~L] if out else [L, L + 1, L] for L, out in zip(self.lengths, self._paused)]
+        self.ctr32.copy_(torch.tensor(rows, dtype=torch.int32).pin_memory(), non_blocking=True)
+
+    def _zero_sitting_rows(self, ctx):
+        """The fused decode attention stores the zeros of a sitting-out slot itself.  The emit + unfused launch pair
+        (`fused_attention=False`, head sizes without the fused form) knows an empty CSR row only, whose context is the
+        average mix: there the zeros are small fills behind the step, for the sitting-out slots alone."""
+        if any(self._paused) and not (self.fused_attention and ops.fused_interp_supported(self.dtype, self.D, self.T_M)):
+            for n, out in enumerate(self._paused):
+                if out:
+                    ctx[n].zero_()
+
+    def _between_steps(self, what, slots):
+        """Common front of pause / resume / release: a ragged session, slots in range; returns them as a list."""
+        if not self.ragged:
+            raise ValueError(f"{what}: only a ragged session (DecodeSession.from_sequences) has slots that sit out steps; "
+                             "a uniform session's sequences share one position")
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        slots = [int(n) for n in slots]
+        bad = [n for n in slots if not 0 <= n < self.N]
+        if bad:
+            raise IndexError(f"{what}: slot(s) {bad} outside 0..{self.N - 1}")
+        return slots
+
+    def _flags_changed(self):
+        self._write_counters()
+        self._last_step = None                        # (as an admit: the chance to rewind ends)
+
+    @torch.no_grad()
+    def pause(self, slots) -> None:
+        """From the next step on the listed slots (one index or several) sit out: `step` ignores their input rows, returns
+        zeros for them with an empty CSR row, and leaves their length, Performer image, CNN rings, K / V rows and pages as
+        they are.  Between steps; no new capture.  Pausing a paused or empty slot changes nothing.  ValueError on a uniform
+        session, IndexError for a slot out of range (nothing changed)."""
+        slots = self._between_steps("pause", slots)
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        for n in slots:
+            self._paused[n] = True
+        self._flags_changed()
+
+    @torch.no_grad()
+    def resume(self, slots) -> None:
+        """The listed slots take part again from exactly where they stood.  A slot that is full gives `step`'s RuntimeError
+        at the next step.  ValueError for an empty slot (there is nothing to resume: `admit` or `fork` into it), naming the
+        slots, with nothing changed; otherwise as `pause`."""
+        slots = self._between_steps("resume", slots)
+        gone = [n for n in slots if self._empty[n]]
+        if gone:
+            raise ValueError(f"resume: slot(s) {gone} are empty (released, or never admitted): admit or fork into them")
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col
+        for n in slots:
+            self._paused[n] = False
+        self._flags_changed()
+
+    @torch.no_grad()
+    def release(self, slots) -> None:
+        """A pause that also drops the sequence: the listed slots are EMPTY afterwards.  A paged session gives their pages
+        back (a page another slot still shares stays out until its last holder lets go).  `admit`, or `fork` / `reorder`
+        into the slot, fills it again; `resume`, `export_state`, `sequence_kv` and `fork` / `reorder` from it raise
+        ValueError.  Releasing an empty slot changes nothing.  Errors as `pause`."""
+        slots = self._between_steps("release", slots)
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col
+        for n in slots:
+            if self.paged and self.pages[n]:
+                self.allocator.give_back(self.pages[n])
+                self.pages[n] = []
+                self.block_table[n].fill_(-1)
+            self._paused[n] = self._empty[n] = True
+            self.lengths[n] = 0
+        self._flags_changed()
 
     def _require_paged(self, what):
         if not (self.ragged and self.paged):
@@ -591,12 +717,14 @@ class DecodeSession:
             alloc.give_back(fresh)
             raise
         # host mirrors: from the snapshot; shares before give-backs (a source's closed pages may be held by a moved slot only)
-        old_pages, old_lengths = [list(p) for p in self.pages], list(self.lengths)
+        # (whether a slot sits out belongs to its contents: the kernel copied the parent's counter row as it is, paused or not)
+        old_pages, old_lengths, old_paused = [list(p) for p in self.pages], list(self.lengths), list(self._paused)
         for src, dst in moves:
             o = opens[src][0]
             alloc.share(old_pages[src][:o])
             self.pages[dst] = old_pages[src][:o] + ([new_open[dst]] if dst in new_open else [])
             self.lengths[dst] = old_lengths[src]
+            self._paused[dst], self._empty[dst] = old_paused[src], False
         for _, dst in moves:
             alloc.give_back(old_pages[dst])
 
@@ -758,6 +886,8 @@ class DecodeSession:
             raise ValueError("a ragged session exports one sequence at a time: export_state(slot)")
         if slot is not None and not 0 <= slot < self.N:
             raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        if self.ragged and self._empty[slot or 0]:
+            raise ValueError(f"export_state: slot {slot or 0} is empty (released, or never admitted)")
         length = self.lengths[slot or 0] if self.ragged else self.length
         image, win = self.image, self.win
         if slot is not None:
@@ -775,14 +905,16 @@ class DecodeSession:
     @torch.no_grad()
     def step(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
         """The new rows of every slot, (N, H, 1, D) each -> the context rows (N, 1, H*D), a static buffer.  A session built
-        with `max_step_rows` S takes (N, H, s, D) with 1 <= s <= S and returns (N, s, H*D); `rewind` may then undo it."""
+        with `max_step_rows` S takes (N, H, s, D) with 1 <= s <= S and returns (N, s, H*D); `rewind` may then undo it.
+        Slots that sit out (`paused`, `empty`): their input rows are ignored (anything, NaN included), their context rows are
+        zeros and their CSR rows empty; capacity and the page pool are checked for the slots that take part only."""
         if self.max_step_rows is not None:
             return self._step_rows(q, k, v)
         if self.ragged and q.dim() == 4 and q.shape[2] != 1:
             raise ValueError(f"a step of {q.shape[2]} rows: this session takes one row per step "
                              "(DecodeSession.from_sequences(..., max_step_rows=...) takes several)")
         if self.ragged:
-            full = [n for n, L in enumerate(self.lengths) if L >= self.capacity]
+            full = [n for n, L in enumerate(self.lengths) if L >= self.capacity and not self._paused[n]]
             if full:
                 raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full}")
             if self.paged:
@@ -803,7 +935,8 @@ class DecodeSession:
         else:
             self._launch()
         if self.ragged:
-            self.lengths = [L + 1 for L in self.lengths]
+            self._zero_sitting_rows(self.ctx)
+            self.lengths = [L if out else L + 1 for L, out in zip(self.lengths, self._paused)]
         else:
             self.length += 1
         return self.ctx
@@ -818,7 +951,7 @@ class DecodeSession:
         s = int(q.shape[2])
         if not 1 <= s <= self.max_step_rows:
             raise ValueError(f"a step of {s} rows: this session takes 1 .. {self.max_step_rows}")
-        full = [n for n, L in enumerate(self.lengths) if L + s > self.capacity]
+        full = [n for n, L in enumerate(self.lengths) if L + s > self.capacity and not self._paused[n]]
         if full:
             raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full} (a step of {s} rows)")
         if self._graphs and ops.prep_generation() != self._prep_generation:
@@ -828,7 +961,7 @@ class DecodeSession:
         # the Performer image changes only when a chunk completes (at most once: s <= 8 <= chunk): a copy of the slices that
         # this step moves to the next boundary, for `rewind`
         C = self.chunk
-        crossed = [n for n, L in enumerate(self.lengths) if (L + s) // C > L // C]
+        crossed = [n for n, L in enumerate(self.lengths) if (L + s) // C > L // C and not self._paused[n]]
         img = self.image.view(N, -1)
         for n in crossed:
             self.image_backup[n].copy_(img[n])
@@ -842,15 +975,18 @@ class DecodeSession:
         else:
             self._launch_rows(s)
         self._last_step = (s, list(self.lengths), crossed)
-        self.lengths = [L + s for L in self.lengths]
-        return self._rows_views(s)[4]
+        self.lengths = [L if out else L + s for L, out in zip(self.lengths, self._paused)]
+        ctx = self._rows_views(s)[4]
+        self._zero_sitting_rows(ctx)
+        return ctx
 
     @torch.no_grad()
     def rewind(self, drop) -> None:
         """Undo the last drop[n] rows of the last step in slot n (0 <= drop[n] <= s of that step; speculative decoding drops
         the rejected draft tokens).  Slot n is then bitwise what a plain session is after stepping only the kept rows: its
         Performer image, CNN rings, K / V rows below its length and every later step.  Only the last step, once, and only
-        while nothing else has changed the session (another `step` or an `admit` ends the chance).  Sessions built with
+        while nothing else has changed the session (another `step`, an `admit`, `pause`, `resume` or `release` ends the
+        chance).  A slot that sat out the step has nothing to drop (drop[n] = 0, else ValueError).  Sessions built with
         `max_step_rows`; ValueError otherwise, and for a rewind without a step to undo or a bad `drop`, with nothing changed."""
         if self.max_step_rows is None:
             raise ValueError("rewind: a session built with DecodeSession.from_sequences(..., max_step_rows=...)")
@@ -862,16 +998,18 @@ class DecodeSession:
             raise ValueError(f"rewind: {len(drop)} counts for {self.N} slots")
         if not all(0 <= d <= s for d in drop):
             raise ValueError(f"rewind: counts {drop} outside 0 .. {s} (the rows of the last step)")
+        sat_out = [n for n, d in enumerate(drop) if d and self._paused[n]]
+        if sat_out:
+            raise ValueError(f"rewind: slot(s) {sat_out} sat out the last step (paused or empty): nothing of it to drop")
         if self.csr is not None and self.csr.col_is_pending:
             self.csr.col                              # the last step's pending columns follow the counters: emit before they move
-        kept = [L + s - d for L, d in zip(before, drop)]
+        kept = [L if out else L + s - d for L, d, out in zip(before, drop, self._paused)]
         img, C = self.image.view(self.N, -1), self.chunk
         for n in crossed:
             if kept[n] // C == before[n] // C:        # back below the boundary the step completed: the image from before it
                 img[n].copy_(self.image_backup[n])
-        ctr = torch.tensor([[L, L + 1, L] for L in kept], dtype=torch.int32).pin_memory()
-        self.ctr32.copy_(ctr, non_blocking=True)
         self.lengths = kept
+        self._write_counters()
         self._last_step = None
 
 
