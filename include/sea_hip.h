@@ -691,6 +691,50 @@ int sea_decode_fork(const int32_t* moves, int64_t M, int64_t n_staged, int dtype
                     void* kv_pool, int64_t page_rows, int64_t pool_pages, void* staging, int64_t staging_bytes,
                     sea_stream_t stream);
 
+/* Extending ONE slot of a ragged session by many rows between two steps (perlin_attention/decode.py: DecodeSession.extend).
+ * The rows themselves are the module's cached forward over the new rows, which reads contiguous K / V; these two entries move
+ * the slot's rows between its pages and a contiguous buffer and file the forward's result into the slot.  Grid-stride loops
+ * over 16-byte chunks, no LDS, no flag between workgroups, no host synchronisation.  Additive: the ABI version stays.
+ *
+ * sea_decode_gather_rows: rows [r0, r1) of sequence `slot`, K and V, from kv_pool (2, pool_pages, H, page_rows, D) into `out`
+ *   (2, H, out_rows, D) dense, row r at out row r - r0, through the sequence's block-table row (block_table + slot *
+ *   table_stride, on the device).  A row whose table entry is outside 0 .. pool_pages-1 is skipped (its out row keeps what
+ *   it held); r0 == r1 launches nothing.  Null pointers, a bad page size / table stride / pool (as for sea_decode_stage's paged
+ *   form), a slot outside 0 .. N-1, r0 > r1, r0 < 0, r1 > capacity, out_rows < r1 - r0: SEA_EINVAL; other dtypes than f16 /
+ *   bf16, D outside {64, 80, 128}, unaligned buffers: SEA_EUNSUPPORTED.
+ *
+ * sea_decode_append_rows: slot `slot` stood at `seen` rows and now stands at t = seen + rows.  ONE launch writes
+ *   - K / V rows seen .. t-1 into the slot's pages through its table row: row seen + i of head h is read at
+ *     k_rows + h * k_strides[0] + i * k_strides[1] elements (v alike; feature stride 1, 16-byte aligned rows).  kv_pool NULL
+ *     (a contiguous session: its rows lie in its cache already): no K / V part, and k_rows / v_rows / the strides /
+ *     block_table are not read (block_table, table_stride, page_rows, pool_pages must be NULL / 0).  A row at or beyond
+ *     `capacity`, or whose table entry is outside the pool, is skipped, as in sea_decode_stage;
+ *   - the x ring: `window` (window_rows, row_bytes) dense holds the predictor CNN's input rows of positions t - window_rows ..
+ *     t-1; each goes to ring row position % x_ring_rows of the slot's slice (x_ring (N, x_ring_rows, row_bytes)); the other
+ *     ring rows keep what they held;
+ *   - the y1 ring: `conv1_rows` (window_rows, row_bytes) is the first convolution over that window; its last keep_rows rows
+ *     (positions t - keep_rows .. t-1: the rows whose taps lie inside the window) go to ring row position % y1_ring_rows,
+ *     EVERY other row of the slot's ring slice is zeroed (what seeding a slot of length t leaves);
+ *   - the Performer image: sea_performer_state_bytes(1, H, D, nb, dtype) bytes from image_src into the slot's slice of `image`;
+ *   - the counter row: counters[slot * counter_stride + 0 .. 2] = {ctr_seen, ctr_tsrc, ctr_done}, as the host gives them
+ *     (plain {t, t + 1, t}, or the bitwise complement of each for a slot that sits out steps).
+ *   Every written chunk is written by exactly one work item and no item reads what another writes.  It must not run
+ *   concurrently with a step of the same session (call it in the step's stream, between steps).
+ *   Null pointers, a slot outside 0 .. N-1, a counter_stride below 3, rows < 1 or seen + rows > capacity (r0 > r1), a window
+ *   that does not fit the rings (window_rows outside 1 .. min(x_ring_rows, t), keep_rows outside 0 .. min(window_rows,
+ *   y1_ring_rows - 1)), a bad page size / table stride / pool: SEA_EINVAL; other dtypes / D, image or ring rows that are not
+ *   whole 16-byte chunks, unaligned rows or strides: SEA_EUNSUPPORTED. */
+int sea_decode_gather_rows(const void* kv_pool, int dtype, int64_t N, int64_t H, int64_t D, int64_t capacity,
+                           const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                           int64_t slot, int64_t r0, int64_t r1, void* out, int64_t out_rows, sea_stream_t stream);
+int sea_decode_append_rows(int dtype, int64_t slot, int64_t N, int64_t H, int64_t D, int64_t nb, int64_t seen, int64_t rows,
+                           int64_t capacity, const void* k_rows, const void* v_rows, const int64_t* k_strides,
+                           const int64_t* v_strides, void* kv_pool, const int32_t* block_table, int64_t table_stride,
+                           int64_t page_rows, int64_t pool_pages, const void* window, int64_t window_rows,
+                           const void* conv1_rows, int64_t keep_rows, int64_t row_bytes, void* x_ring, int64_t x_ring_rows,
+                           void* y1_ring, int64_t y1_ring_rows, const void* image_src, void* image, int32_t* counters,
+                           int64_t counter_stride, int32_t ctr_seen, int32_t ctr_tsrc, int32_t ctr_done, sea_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

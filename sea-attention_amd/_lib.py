@@ -75,6 +75,10 @@ _SIGNATURES = {
                                          ptr, ptr, ptr, ptr, i64, ptr], c_int),
     "sea_decode_fork": ([ptr, i64, i64, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr, i64, ptr, i64, ptr, i64, i64, ptr, i64, i64,
                          ptr, i64, ptr], c_int),
+    "sea_decode_gather_rows": ([ptr, c_int, i64, i64, i64, i64, ptr, i64, i64, i64, i64, i64, i64, ptr, i64, ptr], c_int),
+    "sea_decode_append_rows": ([c_int, i64, i64, i64, i64, i64, i64, i64, i64, ptr, ptr, _i64p, _i64p, ptr, ptr, i64, i64, i64,
+                                ptr, i64, ptr, i64, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, c_int32, c_int32, c_int32, ptr],
+                               c_int),
     "sea_performer_avg_supported": ([i64, i64, c_int], c_int),
     "sea_performer_plan": ([i64, i64, i64, i64, i64, c_int, _i64p, _i64p], c_int),
 }

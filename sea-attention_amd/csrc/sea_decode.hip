@@ -14,6 +14,10 @@
 //                         row sees): every reader of this step has finished (stream order), the next step's have not begun.
 //   decode_fork_kernel    between two steps, slots of a paged session continue as copies of other slots (fork / beam
 //                         reorder): a slot's small state and its open page are copied, its closed pages are shared.
+//   decode_gather_rows_kernel / decode_append_rows_kernel  between two steps, one slot takes MANY new rows at once
+//                         (DecodeSession.extend): the module's cached forward reads contiguous K / V, so the slot's rows are
+//                         gathered from its pages into a contiguous scratch, and the result -- the new K / V rows, the CNN
+//                         rings, the Performer image and the counter row -- is filed into the slot by one launch.
 #include "sea_common.hpp"
 
 namespace sea {
@@ -189,6 +193,105 @@ __global__ __launch_bounds__(256) void decode_fork_kernel(ForkParams p) {
   }
 }
 
+// sea_decode_gather_rows: rows [r0, r1) of ONE sequence, K and V, from the page pool (2, pool_pages, H, page_rows, D) into a
+// contiguous (2, H, out_rows, D) buffer (row r at out row r - r0), through the sequence's block-table row on the device.  A
+// grid-stride loop over (half, head, row, 16-byte chunk), chunk fastest: a wave reads whole rows of a page and writes whole
+// rows of the buffer.  A row at or beyond the capacity, or whose table entry is outside the pool, is skipped.
+struct GatherRowsParams {
+  const uint4* pool;
+  uint4* out;
+  const int32_t* table;                 // the sequence's table row
+  int H, per, r0, rows, cap, out_rows, page_shift, pool_pages;       // per = D / 8 chunks per row; rows = r1 - r0
+};
+
+__global__ __launch_bounds__(256) void decode_gather_rows_kernel(GatherRowsParams p) {
+  const int64_t total = (int64_t)2 * p.H * p.rows * p.per;
+  const int64_t page16 = ((int64_t)p.H << p.page_shift) * p.per;     // chunks of one half of a page
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(c % p.per);
+    const int64_t t = c / p.per;
+    const int i = (int)(t % p.rows);
+    const int hh = (int)(t / p.rows);                                 // half * H + head
+    const int half = hh / p.H, h = hh - half * p.H;
+    const int r = p.r0 + i;
+    if (r >= p.cap) continue;
+    const int pg = p.table[r >> p.page_shift];
+    if (pg < 0 || pg >= p.pool_pages) continue;
+    const int prow = r & ((1 << p.page_shift) - 1);
+    p.out[((int64_t)hh * p.out_rows + i) * p.per + j] =
+        p.pool[((int64_t)half * p.pool_pages + pg) * page16 + (((int64_t)h << p.page_shift) + prow) * p.per + j];
+  }
+}
+
+// sea_decode_append_rows: slot `slot` of a ragged session, which stood at `seen` rows, takes the result of an extend by `rows`
+// rows (it stands at t = seen + rows afterwards).  One grid-stride loop over the items of five parts, each 16-byte chunks but
+// the last:
+//   K / V   rows seen .. t-1 from contiguous buffers ([h, row] strides) into the slot's pages through its table row (paged
+//           sessions only: a contiguous session's rows are staged where the forward reads them);
+//   x ring  the window's `win_rows` rows (positions t - win_rows .. t-1) at position % ring; the other ring rows stay;
+//   y1 ring conv1's last `keep_rows` rows over that window (positions t - keep_rows .. t-1) at position % ring, zeros in
+//           every other ring row (keep_rows < ring rows: a ring row takes one position at most, so every chunk of the ring
+//           is written by exactly one item -- no item reads or writes what another one writes);
+//   image   the slot's Performer image slice;
+//   counters the slot's three int32, as given by the host (plain or complement).
+struct AppendRowsParams {
+  const uint4 *k_rows, *v_rows;         // row seen + i of head h at h * src_h16 + i * src_t16 chunks
+  uint4* pool;                          // nullptr: no K / V part
+  const int32_t* table;                 // the slot's table row
+  const uint4 *window, *conv1, *image_src;
+  uint4 *x_ring, *y1_ring, *image;      // the slot's slices
+  int32_t* ctr;                         // the slot's counter row
+  int64_t src_h16[2], src_t16[2];
+  int H, per, seen, rows, cap, page_shift, pool_pages;
+  int row16, win_rows, keep_rows, x_rows, y_rows, img16;
+  int32_t c0, c1, c2;
+};
+
+__global__ __launch_bounds__(256) void decode_append_rows_kernel(AppendRowsParams p) {
+  const int64_t n_kv = p.pool ? (int64_t)2 * p.H * p.rows * p.per : 0;
+  const int64_t n_x = (int64_t)p.win_rows * p.row16, n_y = (int64_t)p.y_rows * p.row16;
+  const int64_t total = n_kv + n_x + n_y + p.img16 + 3;               // (host: < 2^31 each)
+  const int t = p.seen + p.rows;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (int64_t)gridDim.x * blockDim.x) {
+    if (c < n_kv) {
+      const int j = (int)(c % p.per);
+      const int64_t u = c / p.per;
+      const int i = (int)(u % p.rows);
+      const int hh = (int)(u / p.rows);
+      const int half = hh / p.H, h = hh - half * p.H;
+      const int r = p.seen + i;
+      if (r >= p.cap) continue;
+      const int pg = p.table[r >> p.page_shift];
+      if (pg < 0 || pg >= p.pool_pages) continue;
+      const int prow = r & ((1 << p.page_shift) - 1);
+      const uint4* src = half ? p.v_rows : p.k_rows;
+      p.pool[(((int64_t)half * p.pool_pages + pg) * p.H + h) * (((int64_t)1 << p.page_shift) * p.per) + (int64_t)prow * p.per + j] =
+          src[h * p.src_h16[half] + i * p.src_t16[half] + j];
+      continue;
+    }
+    int64_t k = c - n_kv;
+    if (k < n_x) {                                           // window row i is position t - win_rows + i
+      const int i = (int)(k / p.row16), j = (int)(k - (int64_t)i * p.row16);
+      const int pos = t - p.win_rows + i;
+      p.x_ring[(int64_t)(pos % p.x_rows) * p.row16 + j] = p.window[k];
+      continue;
+    }
+    k -= n_x;
+    if (k < n_y) {                                           // ring row q: the one position of t - keep_rows .. t-1 it holds, else 0
+      const int q = (int)(k / p.row16), j = (int)(k - (int64_t)q * p.row16);
+      const int back = ((t - 1) % p.y_rows - q + p.y_rows) % p.y_rows;        // position t - 1 - back sits in ring row q
+      uint4 val = make_uint4(0u, 0u, 0u, 0u);
+      if (back < p.keep_rows) val = p.conv1[(int64_t)(p.win_rows - 1 - back) * p.row16 + j];
+      p.y1_ring[k] = val;
+      continue;
+    }
+    k -= n_y;
+    if (k < p.img16) { p.image[k] = p.image_src[k]; continue; }
+    k -= p.img16;
+    p.ctr[k] = k == 0 ? p.c0 : k == 1 ? p.c1 : p.c2;
+  }
+}
+
 }  // namespace sea
 
 using namespace sea;
@@ -339,6 +442,106 @@ extern "C" int sea_decode_fork(const int32_t* moves, int64_t M, int64_t n_staged
     SEA_CHECK_LAUNCH(nm);
   }
   hipLaunchKernelGGL(decode_fork_kernel<false>, dim3(grid(per * M)), dim3(256), 0, s, p);
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+
+// DecodeSession.extend: rows [r0, r1) of sequence `slot` from the page pool into a contiguous (2, H, out_rows, D) buffer
+// (include/sea_hip.h)
+extern "C" int sea_decode_gather_rows(const void* kv_pool, int dtype, int64_t N, int64_t H, int64_t D, int64_t capacity,
+                                      const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                                      int64_t slot, int64_t r0, int64_t r1, void* out, int64_t out_rows, sea_stream_t stream) {
+  const char* nm = "sea_decode_gather_rows";
+  SEA_REQUIRE(kv_pool && block_table && out, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && D > 0 && H < (1ll << 16), SEA_EINVAL, "%s: bad shape", nm);
+  if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+  SEA_REQUIRE(pool_pages > 0 && pool_pages < (1ll << 31) && 2 * pool_pages * H * page_rows * D < (1ll << 62), SEA_EINVAL,
+              "%s: bad pool of %lld pages", nm, (long long)pool_pages);
+  SEA_REQUIRE(slot >= 0 && slot < N, SEA_EINVAL, "%s: slot %lld outside 0 .. %lld", nm, (long long)slot, (long long)(N - 1));
+  SEA_REQUIRE(r0 >= 0 && r0 <= r1 && r1 <= capacity, SEA_EINVAL, "%s: rows [%lld, %lld) outside 0 <= r0 <= r1 <= capacity = %lld",
+              nm, (long long)r0, (long long)r1, (long long)capacity);
+  SEA_REQUIRE(out_rows >= r1 - r0 && out_rows < (1ll << 24), SEA_EINVAL, "%s: a buffer of %lld rows for %lld", nm,
+              (long long)out_rows, (long long)(r1 - r0));
+  SEA_REQUIRE((((uintptr_t)kv_pool | (uintptr_t)out) & 15) == 0, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
+  if (r0 == r1) return SEA_OK;
+  GatherRowsParams p;
+  p.pool = (const uint4*)kv_pool; p.out = (uint4*)out; p.table = block_table + slot * table_stride;
+  p.H = (int)H; p.per = (int)(D / 8); p.r0 = (int)r0; p.rows = (int)(r1 - r0); p.cap = (int)capacity; p.out_rows = (int)out_rows;
+  p.page_shift = __builtin_ctzll(page_rows); p.pool_pages = (int)pool_pages;
+  const int64_t chunks = 2 * H * (r1 - r0) * (D / 8);
+  const unsigned blocks = (unsigned)((chunks + 255) / 256 < 2048 ? (chunks + 255) / 256 : 2048);
+  hipLaunchKernelGGL(decode_gather_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+
+// DecodeSession.extend: the result of an extend by `rows` rows, filed into slot `slot` by one launch (include/sea_hip.h)
+extern "C" int sea_decode_append_rows(int dtype, int64_t slot, int64_t N, int64_t H, int64_t D, int64_t nb, int64_t seen,
+                                      int64_t rows, int64_t capacity, const void* k_rows, const void* v_rows,
+                                      const int64_t* k_strides, const int64_t* v_strides, void* kv_pool,
+                                      const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
+                                      const void* window, int64_t window_rows, const void* conv1_rows, int64_t keep_rows,
+                                      int64_t row_bytes, void* x_ring, int64_t x_ring_rows, void* y1_ring, int64_t y1_ring_rows,
+                                      const void* image_src, void* image, int32_t* counters, int64_t counter_stride,
+                                      int32_t ctr_seen, int32_t ctr_tsrc, int32_t ctr_done, sea_stream_t stream) {
+  const char* nm = "sea_decode_append_rows";
+  SEA_REQUIRE(window && conv1_rows && x_ring && y1_ring && image_src && image && counters, SEA_EINVAL,
+              "%s: null pointer", nm);
+  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && D > 0 && nb > 0 && N < (1ll << 24) && H < (1ll << 16), SEA_EINVAL, "%s: bad shape", nm);
+  SEA_REQUIRE(slot >= 0 && slot < N, SEA_EINVAL, "%s: slot %lld outside 0 .. %lld", nm, (long long)slot, (long long)(N - 1));
+  SEA_REQUIRE(counter_stride >= 3 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: counter_stride %lld (3 counters per slot)",
+              nm, (long long)counter_stride);
+  SEA_REQUIRE(capacity > 0 && capacity < (1ll << 24) && seen >= 0 && rows >= 1 && seen + rows <= capacity, SEA_EINVAL,
+              "%s: rows [%lld, %lld) outside 0 <= r0 < r1 <= capacity = %lld", nm, (long long)seen, (long long)(seen + rows),
+              (long long)capacity);
+  SEA_REQUIRE(window_rows >= 1 && window_rows <= x_ring_rows && window_rows <= seen + rows && keep_rows >= 0 &&
+              keep_rows <= window_rows && keep_rows < y1_ring_rows && x_ring_rows < (1ll << 16) && y1_ring_rows < (1ll << 16),
+              SEA_EINVAL, "%s: a window of %lld rows (%lld of conv1 kept) does not fit rings of %lld and %lld rows", nm,
+              (long long)window_rows, (long long)keep_rows, (long long)x_ring_rows, (long long)y1_ring_rows);
+  const int64_t img_bytes = sea_performer_state_bytes(1, H, D, nb, dtype);
+  SEA_REQUIRE(img_bytes > 0 && img_bytes % 16 == 0 && row_bytes > 0 && row_bytes % 16 == 0 && D % 8 == 0, SEA_EUNSUPPORTED,
+              "%s: image bytes %lld, ring row bytes %lld and K / V rows (D = %lld) must be whole 16-byte chunks", nm,
+              (long long)img_bytes, (long long)row_bytes, (long long)D);
+  SEA_REQUIRE((x_ring_rows + y1_ring_rows) * row_bytes * N < (1ll << 34) && img_bytes * N < (1ll << 34), SEA_EUNSUPPORTED,
+              "%s: slot state too large", nm);
+  uintptr_t al = (uintptr_t)window | (uintptr_t)conv1_rows | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)image_src |
+                 (uintptr_t)image;
+  AppendRowsParams p;
+  p.pool = nullptr; p.table = nullptr; p.k_rows = p.v_rows = nullptr;
+  p.page_shift = 0; p.pool_pages = 0;
+  for (int i = 0; i < 2; ++i) p.src_h16[i] = p.src_t16[i] = 0;
+  if (kv_pool) {
+    SEA_REQUIRE(k_rows && v_rows && k_strides && v_strides && block_table, SEA_EINVAL, "%s: null pointer", nm);
+    if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
+    SEA_REQUIRE(pool_pages > 0 && pool_pages < (1ll << 31) && 2 * pool_pages * H * page_rows * D < (1ll << 62), SEA_EINVAL,
+                "%s: bad pool of %lld pages", nm, (long long)pool_pages);
+    bool ok = true;
+    for (int i = 0; i < 2; ++i) ok = ok && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
+    al |= (uintptr_t)kv_pool | (uintptr_t)k_rows | (uintptr_t)v_rows;
+    SEA_REQUIRE(ok && (al & 15) == 0, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
+    p.pool = (uint4*)kv_pool; p.table = block_table + slot * table_stride;
+    p.k_rows = (const uint4*)k_rows; p.v_rows = (const uint4*)v_rows;
+    p.src_h16[0] = k_strides[0] / 8; p.src_t16[0] = k_strides[1] / 8; p.src_h16[1] = v_strides[0] / 8; p.src_t16[1] = v_strides[1] / 8;
+    p.page_shift = __builtin_ctzll(page_rows); p.pool_pages = (int)pool_pages;
+  } else {
+    SEA_REQUIRE(!block_table && page_rows == 0 && table_stride == 0 && pool_pages == 0, SEA_EINVAL,
+                "%s: null pointer: a block_table / page_rows / table_stride / pool_pages without a kv_pool", nm);
+  }
+  SEA_REQUIRE((al & 15) == 0, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
+  p.H = (int)H; p.per = (int)(D / 8); p.seen = (int)seen; p.rows = (int)rows; p.cap = (int)capacity;
+  p.row16 = (int)(row_bytes / 16); p.win_rows = (int)window_rows; p.keep_rows = (int)keep_rows;
+  p.x_rows = (int)x_ring_rows; p.y_rows = (int)y1_ring_rows; p.img16 = (int)(img_bytes / 16);
+  p.window = (const uint4*)window; p.conv1 = (const uint4*)conv1_rows; p.image_src = (const uint4*)image_src;
+  p.x_ring = (uint4*)x_ring + slot * x_ring_rows * p.row16;
+  p.y1_ring = (uint4*)y1_ring + slot * y1_ring_rows * p.row16;
+  p.image = (uint4*)image + slot * p.img16;
+  p.ctr = counters + slot * counter_stride;
+  p.c0 = ctr_seen; p.c1 = ctr_tsrc; p.c2 = ctr_done;
+  const int64_t items = (kv_pool ? 2 * H * rows * (D / 8) : 0) + (window_rows + y1_ring_rows) * p.row16 + p.img16 + 3;
+  const unsigned blocks = (unsigned)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+  hipLaunchKernelGGL(decode_append_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

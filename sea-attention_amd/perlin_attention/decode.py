@@ -84,6 +84,20 @@ source's `seen` for the open page and copies the counters as they are, so the co
 bitwise what they are without the others (tests/test_gpu_decode_pause.py).  The emit + unfused attention pair
 (`fused_attention=False`) knows only an empty CSR row, whose context is the average mix; there the zeros of sitting-out slots
 are small fills behind the step.
+
+Many rows into one slot between steps (`extend(slot, q, k, v)`; ragged sessions, eager, no capture): a forked request is the
+shared prompt plus a suffix of its own, tens to hundreds of rows.  One row per replayed step is s replays; the cached forward
+followed by `admit` re-seeds all L + s rows into fresh pages, and the slot stops sharing its parent's closed pages.  `extend`
+runs the module's cached forward over the s rows against the slot's K / V, continued from the slot's own image and window --
+DESIGN section 8: that path is bitwise the stateless forward for any piece sizes, and a step is that path one position at a
+time, so the rows and every later step are bitwise what one-row steps give -- and files the result with ONE launch,
+`sea_decode_append_rows`: K / V rows L .. L+s-1 into the slot's pages, the window and conv1 over it into the rings at
+position % ring (what `_seed_slot` files for a prefix of L + s rows), the image slice, the counter row (the complement form when
+the slot is paused: it stays paused).  The forward reads contiguous K / V: a paged slot's rows are gathered through its device
+table row into a per-session scratch (`sea_decode_gather_rows`, no host-built index), a contiguous session hands out a view
+of its cache.  Only rows >= L are written -- the open page and new pages, taken before anything is launched; table entries
+below the open index, the closed pages a fork shares, are untouched.  The parked-prompt flow, complete: `pause` the prompt,
+`fork` it as requests arrive, `extend` each copy by its request's rows, `resume` the copies, `release` them at EOS.
 """
 from collections import deque
 from typing import List, Optional
@@ -182,6 +196,7 @@ class DecodeSession:
     _last_step = None            # (what `rewind` may undo: (s, lengths before, slots whose image was copied aside))
     _paused = None               # (ragged sessions: host mirrors of the slots that sit out steps / hold no sequence)
     _empty = None
+    _extend_kv = None            # (paged sessions: `extend`'s contiguous K / V scratch (2, H, capacity, D), allocated on first use)
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -538,6 +553,112 @@ class DecodeSession:
         self._seed_slot(slot, state, key_prefix, value_prefix)
         self._paused[slot] = self._empty[slot] = False                       # (a paused or empty slot: active on the new sequence)
         self._last_step = None                        # (an admit ends the chance to rewind)
+
+    @torch.no_grad()
+    def extend(self, slot: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """Slot `slot` of a ragged session takes s >= 1 new rows at once, between two steps: q, k, v (1, H, s, D) -> the s context
+        rows (1, s, H*D), a fresh tensor.  The rows are the module's cached forward (`PerlinAttention.forward(...,
+        last_state=...)`) over the s rows against the slot's K / V, continued from the slot's own image and window, so they --
+        and every later step -- are bitwise what one-row steps over the same rows give.  Eager: no capture, `captures` does not
+        move.  Afterwards the slot stands at L + s with its Performer image, rings, K / V rows and counter row as `admit`
+        leaves a prefix of L + s rows; an active slot stays active, a paused one paused (the parked prompt: `fork` the paused
+        prompt, `extend` each copy by its request's own rows, `resume` them).  Every other slot keeps every bit.
+        A paged session writes rows >= L only: the slot's table entries below its open index L // page_rows -- the closed pages
+        it may share with other slots -- are not touched; it takes the pages it lacks up to ceil((L + s + 1) / page_rows) (the
+        prefix and the next step's row, as seeding does; no page beyond the table for a slot filled to capacity) before
+        anything is launched, and its rows travel through a contiguous scratch of the session ((2, H, capacity, D), allocated at
+        the first call): `sea_decode_gather_rows` in, `sea_decode_append_rows` out (include/sea_hip.h).
+        It ends the chance to `rewind`.  Refused with nothing changed: a uniform session, an empty slot (that is `admit`'s),
+        wrong shapes / dtype / device, L + s > capacity (ValueError); a slot out of range (IndexError); a pool that cannot
+        supply the pages, or an open page another slot holds too (RuntimeError)."""
+        if not self.ragged:
+            raise ValueError("extend: only a ragged session (DecodeSession.from_sequences) extends one slot")
+        slot = int(slot)
+        if not 0 <= slot < self.N:
+            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        if self._empty[slot]:
+            raise ValueError(f"extend: slot {slot} is empty (released, or never admitted): admit or fork into it")
+        H, D, L, pr = self.H, self.D, self.lengths[slot], self.page_rows
+        if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)) or k.shape != q.shape or v.shape != q.shape \
+                or (q.shape[0], q.shape[1], q.shape[3]) != (1, H, D) or q.shape[2] < 1:
+            raise ValueError(f"extend: q, k, v are (1, H, s, D) = (1, {H}, s, {D}) each with s >= 1 "
+                             f"(got {[tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in (q, k, v)]})")
+        if not all(t.dtype == self.dtype and t.device == self.kv_cache.device for t in (q, k, v)):
+            raise ValueError(f"extend: {self.dtype} rows on {self.kv_cache.device}")
+        s = int(q.shape[2])
+        T = L + s
+        if T > self.capacity:
+            raise ValueError(f"extend: slot {slot} stands at {L} rows, {s} more pass the capacity of {self.capacity}")
+        fresh = []
+        if self.paged:
+            o = L // pr
+            if o < len(self.pages[slot]) and self.allocator.holders(self.pages[slot][o]) > 1:
+                raise RuntimeError(f"extend: slot {slot}'s open page {self.pages[slot][o]} has other holders; only closed pages "
+                                   "are shared (fork gives every copy an open page of its own)")
+            want = -(-min(T + 1, self.capacity) // pr) - len(self.pages[slot])
+            if want > self.allocator.free_pages:
+                raise RuntimeError(f"page pool exhausted: slot {slot} needs {want} new page(s) for {s} more rows, "
+                                   f"{self.allocator.free_pages} free")
+            fresh = self.allocator.take(max(want, 0))
+        at, dev = self.attention, self.kv_cache.device
+        try:
+            if self.csr is not None and self.csr.col_is_pending:
+                self.csr.col                          # the last step's pending columns follow the counters: emit before they move
+            # contiguous K / V rows 0 .. T-1 for the forward: a paged slot's rows are gathered into the scratch, a contiguous
+            # session's are its cache (the new rows are staged where they belong; rows >= L are read by nobody before)
+            if self.paged:
+                if self._extend_kv is None:
+                    self._extend_kv = torch.empty((2, H, self.capacity, D), dtype=self.dtype, device=dev)
+                kv = self._extend_kv
+                ops.decode_gather_rows(self.kv_cache, self.block_table, self.capacity, slot, 0, L, kv)
+            else:
+                kv = self.kv_cache[:, slot]
+            kv[0, :, L:T].copy_(k[0])
+            kv[1, :, L:T].copy_(v[0])
+            k_all, v_all = kv[0:1, :, :T], kv[1:2, :, :T]
+            # the session's own image and window, as `export_state(slot)` hands them out (the image as a view: the Performer
+            # step reads it and returns a new one)
+            from .attention_state import PerformerState, CnnWindowState, CumAvgState
+            pos = torch.arange(L - self.LB, L, device=dev)
+            st = PerlinAttentionState(at)
+            ps, cs, cav = PerformerState(), CnnWindowState(self.LB), CumAvgState()
+            ps.image, ps.seq_index = self.image.view(self.N, -1)[slot], L
+            cs.rows_c8 = self.x_ring[slot:slot + 1, pos % self.x_ring.shape[1]]
+            cav.prev_len, cav.in_image = L, True
+            st.states = {PerlinAttentionState.PERFORMER: ps, PerlinAttentionState.CNN: cs, PerlinAttentionState.CUMAVG: cav}
+            fp_min = torch.finfo(torch.float16).min / 2
+            mask = torch.triu(torch.full((s, T), fp_min, dtype=self.dtype, device=dev), diagonal=L + 1).view(1, 1, s, T)
+            out = at(q, k_all, v_all, q, k_all, v_all, q, k_all, mask, None, None, st)
+            new_ps = out.state.states.get(PerlinAttentionState.PERFORMER)
+            new_cs = out.state.states.get(PerlinAttentionState.CNN)
+            if new_ps is None or new_ps.image is None or new_cs is None or not torch.is_tensor(new_cs.rows_c8) \
+                    or new_cs.rows_c8.shape[1] != self.LB:
+                raise ValueError("extend: the cached forward did not continue the session's state on the HIP estimator")
+            window = new_cs.rows_c8.contiguous()
+            conv1 = _cnn_convs(at)[0]
+            dil, RY = conv1.dilation, self.y1_ring.shape[1]
+            y1 = ops.causal_conv_c8(window, conv1.weight, conv1.bias, 3, dil, dil, relu=True)
+            keep_rows = min(RY - 1, self.LB - 2 * dil)               # (the rows `_seed_slot` keeps: conv1's true values)
+            if fresh:                                 # the new table entries: one small stream-ordered copy, no synchronise
+                n0 = len(self.pages[slot])
+                self.block_table[slot, n0:n0 + len(fresh)].copy_(torch.tensor(fresh, dtype=torch.int32).pin_memory(), non_blocking=True)
+            row = [~T, ~(T + 1), ~T] if self._paused[slot] else [T, T + 1, T]
+            nb = at.performer.projection_matrix.shape[0]
+            paged = dict(kv_pool=self.kv_cache, block_table=self.block_table) if self.paged else {}
+            ops.decode_append_rows(slot, L, s, kv[0, :, L:T] if self.paged else None, kv[1, :, L:T] if self.paged else None, window, y1,
+                                   keep_rows, new_ps.image.view(-1), self.image, self.x_ring, self.y1_ring, self.ctr32, row,
+                                   self.capacity, H, D, nb, **paged)
+        except Exception:
+            if fresh:                                 # (the host mirror `pages` has not moved: the slot is what it was)
+                n0 = len(self.pages[slot])
+                self.block_table[slot, n0:n0 + len(fresh)].fill_(-1)
+                self.allocator.give_back(fresh)
+            raise
+        if fresh:
+            self.pages[slot].extend(fresh)
+        self.lengths[slot] = T
+        self._last_step = None                        # (as an admit: the chance to rewind ends)
+        return out.context_layer
 
     @torch.no_grad()
     def fork(self, src: int, dsts) -> None:

@@ -761,6 +761,62 @@ def decode_fork(moves: torch.Tensor, n_staged: int, image: torch.Tensor, x_ring:
                "sea_decode_fork")
 
 
+@_lib.device_guarded
+def decode_gather_rows(kv_pool: torch.Tensor, block_table: torch.Tensor, capacity: int, slot: int, r0: int, r1: int,
+                       out: torch.Tensor) -> None:
+    """`sea_decode_gather_rows`: rows [r0, r1) of sequence `slot`, K and V, from the page pool (2, P, H, page_rows, D) into
+    `out` (2, H, >= r1 - r0, D) dense (row r at out row r - r0), through the device block table (N, n_tab) int32."""
+    lib = _lib.load()
+    _lib.require_gpu(kv_pool, block_table, out)
+    _, P, H, page_rows, D = kv_pool.shape
+    assert kv_pool.is_contiguous() and out.is_contiguous() and out.dtype == kv_pool.dtype
+    assert out.dim() == 4 and out.shape[0] == 2 and out.shape[1] == H and out.shape[3] == D
+    assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1
+    _lib.check(lib.sea_decode_gather_rows(_p(kv_pool), _lib.dtype_code(kv_pool.dtype), block_table.shape[0], H, D, int(capacity),
+                                          _p(block_table), block_table.stride(0), page_rows, P, int(slot), int(r0), int(r1),
+                                          _p(out), out.shape[2], _lib.stream_ptr()), "sea_decode_gather_rows")
+
+
+@_lib.device_guarded
+def decode_append_rows(slot: int, seen: int, rows: int, k_rows: Optional[torch.Tensor], v_rows: Optional[torch.Tensor], window: torch.Tensor,
+                       conv1_rows: torch.Tensor, keep_rows: int, image_src: torch.Tensor, image: torch.Tensor,
+                       x_ring: torch.Tensor, y1_ring: torch.Tensor, counters: torch.Tensor, counter_row, capacity: int, H: int,
+                       D: int, nb: int, kv_pool: Optional[torch.Tensor] = None, block_table: Optional[torch.Tensor] = None) -> None:
+    """`sea_decode_append_rows`: the result of extending slot `slot` (which stood at `seen` rows) by `rows` rows, filed by
+    one launch.  `window` / `conv1_rows` (1, LB, ...) dense: the CNN window of the new length and conv1 over it; `image_src` one
+    Performer image; `image` (N * per,) fp32, rings (N, rows, ...), `counters` an (N, 3) view, `counter_row` three host ints.
+    Paged (`kv_pool` (2, P, H, page_rows, D) with `block_table`): `k_rows` / `v_rows` (H, rows, D) views (any [h, t] strides in
+    multiples of 8 elements) go to the slot's pages; a contiguous session passes None for the four."""
+    lib = _lib.load()
+    _lib.require_gpu(k_rows, v_rows, window, conv1_rows, image_src, image, x_ring, y1_ring, counters, kv_pool, block_table)
+    N, LB = x_ring.shape[0], window.shape[1]
+    assert window.is_contiguous() and conv1_rows.is_contiguous() and conv1_rows.shape == window.shape and window.shape[0] == 1
+    assert x_ring.is_contiguous() and y1_ring.is_contiguous() and y1_ring.shape[0] == N
+    assert window.dtype == conv1_rows.dtype == x_ring.dtype == y1_ring.dtype
+    assert x_ring.shape[2:] == window.shape[2:] and y1_ring.shape[2:] == window.shape[2:]
+    assert image.dtype == image_src.dtype == torch.float32 and image.is_contiguous() and image_src.is_contiguous()
+    per = int(lib.sea_performer_state_bytes(1, H, D, int(nb), _lib.dtype_code(x_ring.dtype))) // 4
+    assert image_src.numel() == per and image.numel() == N * per, "image: one Performer state image per slot"
+    stride = _lib.counter_stride(counters, N)
+    row_bytes = window[0, 0].numel() * window.element_size()
+    ks = vs = None
+    table_stride = page_rows = pool_pages = 0
+    if kv_pool is not None:
+        _, pool_pages, Hp, page_rows, Dp = kv_pool.shape
+        assert kv_pool.is_contiguous() and (Hp, Dp) == (H, D) and kv_pool.dtype == x_ring.dtype == k_rows.dtype == v_rows.dtype
+        assert tuple(k_rows.shape) == tuple(v_rows.shape) == (H, int(rows), D)
+        assert k_rows.stride(2) == 1 and v_rows.stride(2) == 1
+        assert block_table.dtype == torch.int32 and block_table.shape[0] == N and block_table.stride(1) == 1
+        ks, vs = (ctypes_i64 * 2)(k_rows.stride(0), k_rows.stride(1)), (ctypes_i64 * 2)(v_rows.stride(0), v_rows.stride(1))
+        table_stride = block_table.stride(0)
+    c = [int(x) for x in counter_row]
+    _lib.check(lib.sea_decode_append_rows(
+        _lib.dtype_code(x_ring.dtype), int(slot), N, int(H), int(D), int(nb), int(seen), int(rows), int(capacity), _p(k_rows), _p(v_rows),
+        ks, vs, _p(kv_pool), _p(block_table), table_stride, page_rows, pool_pages, _p(window), LB, _p(conv1_rows), int(keep_rows),
+        row_bytes, _p(x_ring), x_ring.shape[1], _p(y1_ring), y1_ring.shape[1], _p(image_src), _p(image), _p(counters), stride,
+        c[0], c[1], c[2], _lib.stream_ptr()), "sea_decode_append_rows")
+
+
 def decode_cnn_supported(C: int, H: int, T_m: int, dtype) -> bool:
     """Shapes `sea_decode_cnn_tail_select` is instantiated for (csrc/sea_topk.hip: launch_decode_cnn)."""
     return (dtype in (torch.float16, torch.bfloat16) and T_m == 256 and H % 4 == 0 and 0 < H <= 40 and C == 2 * H and C % 8 == 0)
