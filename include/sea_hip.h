@@ -45,8 +45,12 @@ extern "C" {
  *      sea_decode_stage, sea_performer_causal_step, sea_decode_cnn_tail_select, sea_sparse_attention and sea_csr_emit are
  *      gone; each of these takes their trailing arguments instead (stride 0 / NULL block table = the shared form); ABI 4 had
  *      also gained sea_decode_fork
+ *   6  one entry point per operator once more: the multi-row (*_rows) entries of sea_decode_stage and
+ *      sea_decode_cnn_tail_select and the sliced entry sea_cumavg_sliced, added beside ABI 5, are gone; sea_decode_stage takes
+ *      `rows` (and [n, h, t] strides), sea_decode_cnn_tail_select takes `y1_scratch` and `rows` (NULL, 1 = the one-row form),
+ *      sea_cumavg takes `n_slices, workspace, workspace_bytes` (1, NULL, 0 = one pass)
  *      */
-#define SEA_ABI_VERSION 5
+#define SEA_ABI_VERSION 6
 
 enum sea_dtype { SEA_F32 = 0, SEA_F16 = 1, SEA_BF16 = 2 };
 
@@ -423,54 +427,44 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  * each value, {~seen, ~T_src, ~T_src just finished} (reversible; -1 = ~0 for a slot that holds no sequence), a value no live
  * sequence reaches, and writes the plain values back to let it take part again.  Here workgroup n of such a sequence leaves
  * both rings alone, writes its selection as an EMPTY row (bits 0, head_off 0, row_nnz 0, crow_out {0, 0}; probs, y2 and col
- * keep what they held) and STILL takes its ticket; the last workgroup's advance leaves a negative triple as it is. */
-int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
-                               int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                               const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
-                               int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
-                               const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                               int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                               int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                               int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
-
-/* The same for a step of `rows` new rows per sequence, rows in 1 .. 8 (speculative decoding: a draft's tokens verified in one
- * step; perlin_attention/decode.py, DecodeSession.from_sequences(..., max_step_rows=...)).  One workgroup per (sequence n, row j)
- * serves position t = counters[n * counter_stride] + j:
+ * keep what they held) and STILL takes its ticket; the last workgroup's advance leaves a negative triple as it is.
+ *
+ * MULTI-ROW form, y1_scratch != NULL: a step of `rows` new rows per sequence, rows in 1 .. 8 (speculative decoding: a draft's
+ * tokens verified in one step; perlin_attention/decode.py, DecodeSession.from_sequences(..., max_step_rows=...)).  One workgroup
+ * per (sequence n, row j) serves position t = counters[n * counter_stride] + j:
  *   - conv1's rows t - 2 dil, t - dil, t: those at positions >= seen (new in this step) are recomputed from x rows -- x_new's
  *     row (q - seen) for a position q >= seen, the x ring's slot q % ring_x below it -- into the workgroup's own two rows of
  *     y1_scratch (N, rows, 2, C/8, 64, 8), row t into the y1 ring; older ones are read from the y1 ring;
  *   - conv2's row t into y2 (N, rows, C/8, 64, 8), then the tail + selection of that row (keep_table[t], width t + 1): bits
- *     (N, rows, W), row_nnz (N, rows), head_off (N, rows, H+1), optional probs (N, H, rows, 256).  No crow: run
- *     sea_csr_row_scan on row_nnz;
+ *     (N, rows, W), row_nnz (N, rows), head_off (N, rows, H+1), optional probs (N, H, rows, 256).  No crow and no in-launch emit:
+ *     crow_out and col must be NULL, col_stride_n / z_cap / T_cap 0 (else SEA_EINVAL); run sea_csr_row_scan on row_nnz;
  *   - x_new's row j joins the x ring at slot t % ring_x.
  * No data passes between the workgroups of a launch: the ring slots read (positions seen - 2 dil .. seen - 1) and written
  * (seen .. seen + rows - 1) are disjoint, which needs ring_x, ring_y >= 2 * dilation + rows (else SEA_EINVAL).  A session
  * that may drop rows of a step again (rewind) needs more: x_ring >= LB + max rows (the window it exports), y1_ring >=
  * 2 * dilation + max rows.  The last of the N * rows workgroups advances every triple: counters[2] = counters[0] + rows,
- * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what sea_decode_cnn_tail_select does).  x_new (N, rows, C/8,
- * 64, 8) dense.  Everything else, and the other refusals, as for sea_decode_cnn_tail_select; rows outside 1 .. 8: SEA_EINVAL.
- * (A later ABI version can fold sea_decode_cnn_tail_select into this entry: rows = 1 plus the one-row form's crow_out / col.)
- * A sequence that sits out (negative triple, as for sea_decode_cnn_tail_select): each of its `rows` workgroups writes an empty
- * row (the row scan behind the launch then gives it an empty crow), touches neither ring nor scratch and takes its ticket; the
- * advance skips the triple. */
-int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
-                                    int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
-                                    const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2,
-                                    int64_t CinP, int dilation, int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp,
-                                    const void* gamma, const void* beta, float eps, void* probs, const int32_t* keep_table,
-                                    int32_t* counters, int32_t* ticket, int is_causal, int max_k, uint32_t* bits,
-                                    int32_t* row_nnz, int32_t* head_off, const uint32_t* consts_tab, int64_t counter_stride,
-                                    sea_stream_t stream);
+ * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what the one-row form does).  x_new (N, rows, C/8, 64, 8) dense.
+ * Everything else, and the other refusals, as for the one-row form; rows outside 1 .. 8: SEA_EINVAL.  Without y1_scratch
+ * (the one-row form) rows must be 1, else SEA_EINVAL.
+ * A sequence that sits out (negative triple): each of its `rows` workgroups writes an empty row (the row scan behind the launch
+ * then gives it an empty crow), touches neither ring nor scratch and takes its ticket; the advance skips the triple. */
+int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype, int64_t N,
+                               int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
+                               const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP,
+                               int dilation, int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
+                               const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
+                               int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
+                               int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
+                               int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream);
 
 /* Causal cumulative average out[n,h,t,:] = sum_{s<=t} v[n,h,s,:] / (t+1), fp32 accumulation.
- * Replaces `avg_v.cumsum(-2) / arange(1..T)` (attention.py:1220-1222).  out (N,H,T,D) contiguous. */
-int sea_cumavg(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
-               void* out, sea_stream_t stream);
-/* The same with the T rows cut into n_slices slices (two launches: column totals per slice, then the averages
+ * Replaces `avg_v.cumsum(-2) / arange(1..T)` (attention.py:1220-1222).  out (N,H,T,D) contiguous.
+ * n_slices > 1: the T rows are cut into n_slices slices (two launches: column totals per slice, then the averages
  * starting from the totals before a slice) -- for the few (n,h) pairs of a one-sequence-per-GPU shard.
- * workspace: N*H*n_slices*D floats, caller-owned.  16-bit data, D in {32,64,80,128}. */
-int sea_cumavg_sliced(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
-                      void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes, sea_stream_t stream);
+ * workspace: N*H*n_slices*D floats, caller-owned; 16-bit data, D in {32,64,80,128}.  n_slices = 1: one pass, workspace may be
+ * NULL (bytes 0). */
+int sea_cumavg(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
+               void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes, sea_stream_t stream);
 
 /* Channel-blocked ("C8") predictor CNN for 16-bit data.
  * C8 layout of a logical (N, C, T, W) activation, C % 8 == 0:  memory (N, T, C/8, W, 8) -- 16-byte blocks of 8
@@ -623,10 +617,10 @@ int sea_performer_causal_step(const void* q, const void* k, const void* v, const
 int64_t sea_sparse_attention_bytes(int64_t Z, int64_t N, int64_t H, int64_t T_dst, int64_t D, int elem_bytes);
 
 /* Glue of a graph-replayed decoding step (round 4; perlin_attention/decode.py, reference loop src/main/opt_generate.py:131).
- * sea_decode_stage: the ONE launch of a step whose arguments change (the caller's new q / k / v rows, (N,H,1,D) with element
- *   strides {n, h}, feature stride 1, 16-byte aligned rows): q is copied into q_in (N,H,D), k / v are written into
- *   kv_cache (2,N,H,capacity,D) at row counters[0] (device int32: the rows the session's state has seen).  Replaces three
- *   input copies and an index_copy_ of the framework (four launches of ~4.5 us).
+ * sea_decode_stage: the ONE launch of a step whose arguments change (rows = 1: the caller's new q / k / v rows, (N,H,1,D) with
+ *   element strides {n, h, t} of which t is not read, feature stride 1, 16-byte aligned rows): q is copied into q_in (N,H,D),
+ *   k / v are written into kv_cache (2,N,H,capacity,D) at row counters[0] (device int32: the rows the session's state has
+ *   seen).  Replaces three input copies and an index_copy_ of the framework (four launches of ~4.5 us).
  *   A counter PER SEQUENCE, counter_stride > 0 (0 = one counter for the batch): sequence n's k / v rows go to cache row
  *   counters[n * counter_stride]; a sequence whose row lies outside the capacity writes nothing.  A negative stride: SEA_EINVAL.
  *   PAGED, block_table != NULL (with a counter per sequence): kv_cache is a page pool (2, pool_pages, H, page_rows, D) dense
@@ -636,26 +630,21 @@ int64_t sea_sparse_attention_bytes(int64_t Z, int64_t N, int64_t H, int64_t T_ds
  *   table with counter_stride = 0, or page_rows / table_stride / pool_pages non-zero without one: SEA_EINVAL.
  *   A sequence that sits out the step (counter < 0, the convention of sea_decode_cnn_tail_select) is such a row: no k / v row
  *   is written and no table entry read; its q row is handed over and read by nobody.
+ *   `rows` in 2 .. 8 (the stage of a multi-row step, see sea_decode_cnn_tail_select): q / k / v (N,H,rows,D) with element strides
+ *   {n, h, t}; q is copied into q_in (N,H,rows,D) dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at row
+ *   counters[n * counter_stride] + j (counter_stride 0: the batch's one counter).  A row at or beyond the capacity writes
+ *   nothing; a sequence whose counter is negative sits out the step: none of its k / v rows is written (the test is on the
+ *   counter, not on counter + j).  Contiguous caches only: with a block_table SEA_EUNSUPPORTED (paged K / V takes one row per
+ *   step).  rows outside 1 .. 8: SEA_EINVAL.
  * sea_c8_window_shift: xs (N, rows, row_bytes) moved up by one row in place (xs[n, r] = xs[n, r + 1]): the predictor CNN's
  *   window after a step whose MLP wrote the new row behind it (sea_predictor_mlp with x_c8_stride_n).  `counters` (optional):
  *   two device int32 advanced by one by the same launch -- the LAST of a step, so every reader of the step is done. */
-int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
+int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows, int64_t D,
                      const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                      void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
                      const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
                      sea_stream_t stream);
 int sea_c8_window_shift(void* xs, int64_t N, int64_t rows, int64_t row_bytes, int32_t* counters, sea_stream_t stream);
-/* sea_decode_stage_rows: the stage of a step of `rows` new rows per sequence (1 .. 8; sea_decode_cnn_tail_select_rows): q / k /
- *   v (N,H,rows,D) with element strides {n, h, t}, feature stride 1, 16-byte aligned rows; q is copied into q_in (N,H,rows,D)
- *   dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at row counters[n * counter_stride] + j (counter_stride 0:
- *   the batch's one counter).  A row at or beyond the capacity writes nothing.  Contiguous caches only.  Refusals as for
- *   sea_decode_stage; rows outside 1 .. 8: SEA_EINVAL.  (A later ABI version can fold sea_decode_stage into this entry.)
- *   A sequence whose counter is negative sits out the step: none of its k / v rows is written (the test is on the counter, not
- *   on counter + j). */
-int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows, int64_t D,
-                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, void* q_in,
-                          void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
-                          sea_stream_t stream);
 
 /* Fork / beam reorder of a paged ragged session's slots, between two steps (perlin_attention/decode.py: DecodeSession.fork and
  * reorder).  `moves`: DEVICE int32 (M, 5), one row per destination slot: {src, dst, src_open, dst_open, stage}.  Destination

@@ -9,7 +9,7 @@ import torch
 from . import _build
 
 SEA_F32, SEA_F16, SEA_BF16 = 0, 1, 2
-ABI_VERSION = 5            # include/sea_hip.h: SEA_ABI_VERSION
+ABI_VERSION = 6            # include/sea_hip.h: SEA_ABI_VERSION
 _DTYPES = {torch.float32: SEA_F32, torch.float16: SEA_F16, torch.bfloat16: SEA_BF16}
 
 _lib = None
@@ -45,8 +45,7 @@ _SIGNATURES = {
     "sea_split_layernorm": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr, ctypes.c_float, c_int, ptr, ptr], c_int),
     "sea_predictor_tail": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, ptr, i64, ptr, ptr,
                             ctypes.c_float, ptr, ptr, ptr], c_int),
-    "sea_cumavg": ([ptr, c_int, i64, i64, i64, i64, _i64p, ptr, ptr], c_int),
-    "sea_cumavg_sliced": ([ptr, c_int, i64, i64, i64, i64, _i64p, ptr, i64, ptr, i64, ptr], c_int),
+    "sea_cumavg": ([ptr, c_int, i64, i64, i64, i64, _i64p, ptr, i64, ptr, i64, ptr], c_int),
     "sea_predictor_tail_select": ([ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, i64, ptr, ptr,
                                    ctypes.c_float, ptr, ptr, ptr, i64, i64, ptr, c_int, c_int, ptr, ptr, ptr, ptr, ptr, ptr],
                                   c_int),
@@ -56,9 +55,9 @@ _SIGNATURES = {
     "sea_split_layernorm_c8": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr, ctypes.c_float, ptr, ptr], c_int),
     "sea_causal_conv_c8": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, i64, ptr, c_int, c_int, c_int, c_int, ptr,
                             ptr, i64, ptr, i64, ptr, ptr], c_int),
-    "sea_decode_cnn_tail_select": ([ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, c_int, c_int,
-                                    ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int, ptr, ptr, ptr, ptr,
-                                    ptr, i64, i64, i64, ptr, i64, ptr], c_int),
+    "sea_decode_cnn_tail_select": ([ptr, ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64,
+                                    c_int, c_int, ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int,
+                                    ptr, ptr, ptr, ptr, ptr, i64, i64, i64, ptr, i64, ptr], c_int),
     "sea_performer_causal": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
                               i64, ptr, i64, ptr], c_int),
     "sea_performer_state_bytes": ([i64, i64, i64, i64, c_int], i64),
@@ -66,13 +65,9 @@ _SIGNATURES = {
     "sea_attention_few_rows": ([], i64),
     "sea_performer_causal_step": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64, ptr, ptr,
                                    ptr, ptr, i64, i64, ptr, i64, i64, ptr, i64, ptr, i64, i64, i64, ptr], c_int),
-    "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64, i64,
-                          ptr], c_int),
+    "sea_decode_stage": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr, i64, i64,
+                          i64, ptr], c_int),
     "sea_c8_window_shift": ([ptr, i64, i64, i64, ptr, ptr], c_int),
-    "sea_decode_stage_rows": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr, i64, ptr], c_int),
-    "sea_decode_cnn_tail_select_rows": ([ptr, ptr, ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64,
-                                         c_int, c_int, ptr, ptr, i64, ptr, ptr, ctypes.c_float, ptr, ptr, ptr, ptr, c_int, c_int,
-                                         ptr, ptr, ptr, ptr, i64, ptr], c_int),
     "sea_decode_fork": ([ptr, i64, i64, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr, i64, ptr, i64, ptr, i64, i64, ptr, i64, i64,
                          ptr, i64, ptr], c_int),
     "sea_decode_gather_rows": ([ptr, c_int, i64, i64, i64, i64, ptr, i64, i64, i64, i64, i64, i64, ptr, i64, ptr], c_int),

@@ -72,8 +72,8 @@ __global__ __launch_bounds__(256) void decode_stage_kernel(std::conditional_t<PA
   }
 }
 
-// ROWS (sea_decode_stage_rows): `rows` new rows per sequence, (N, H, rows, D) with [n, h, t] strides; q_in (N, H, rows, D)
-// dense; row j of sequence n goes to cache row ctr[n * ctr_stride] + j, nothing for a row at or beyond the capacity and nothing
+// ROWS (sea_decode_stage with rows in 2 .. 8): `rows` new rows per sequence, (N, H, rows, D) with [n, h, t] strides; q_in (N, H,
+// rows, D) dense; row j of sequence n goes to cache row ctr[n * ctr_stride] + j, nothing for a row at or beyond the capacity and nothing
 // for a sequence whose counter is negative (it sits out the step).  A kernel of its own, so that the one-row form's code stays
 // what it was
 struct StageRowsParams {
@@ -298,16 +298,19 @@ using namespace sea;
 
 // counter_stride > 0: a counter PER SEQUENCE, sequence n's new row goes to cache row counters[n * counter_stride];
 // block_table != NULL (with a counter per sequence): paged K / V, the rows go to page block_table[n * table_stride + ctr /
-// page_rows] of the pool (2, pool_pages, H, page_rows, D), row ctr % page_rows
-extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t D,
-                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+// page_rows] of the pool (2, pool_pages, H, page_rows, D), row ctr % page_rows;
+// rows in 2 .. 8 (contiguous caches): row j of sequence n goes to cache row counters[n * counter_stride] + j (include/sea_hip.h)
+extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows,
+                                int64_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                                 void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters, int64_t counter_stride,
                                 const int32_t* block_table, int64_t table_stride, int64_t page_rows, int64_t pool_pages,
                                 sea_stream_t stream) {
   const char* nm = "sea_decode_stage";
   if (counter_stride || block_table)
-    SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: counter_stride must be >= 1 (got %lld)", nm, (long long)counter_stride);
+    SEA_REQUIRE(counter_stride > 0, SEA_EINVAL, "%s: bad counter stride: counter_stride must be >= 1 (got %lld)", nm,
+                (long long)counter_stride);
   if (block_table) {
+    SEA_REQUIRE(rows <= 1, SEA_EUNSUPPORTED, "%s: paged K / V takes one row per step (rows %lld)", nm, (long long)rows);
     SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
     if (int e = paged_layout_check(nm, dtype, D, capacity, page_rows, table_stride, N)) return e;
     SEA_REQUIRE(pool_pages > 0 && 2 * pool_pages * H * page_rows * D < (1ll << 62) && pool_pages < (1ll << 31), SEA_EINVAL,
@@ -317,46 +320,6 @@ extern "C" int sea_decode_stage(const void* q, const void* k, const void* v, int
                 "%s: null pointer: page_rows / table_stride / pool_pages without a block_table", nm);
   }
   SEA_REQUIRE(q && k && v && q_strides && k_strides && v_strides && q_in && kv_cache && counters, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
-  SEA_REQUIRE(N > 0 && H > 0 && D > 0 && capacity > 0 && N * H * D < (1ll << 24), SEA_EINVAL, "%s: bad shape", nm);
-  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
-              (long long)counter_stride);
-  SEA_REQUIRE(D % 8 == 0, SEA_EUNSUPPORTED, "%s: D must be a multiple of 8 (16-byte rows)", nm);
-  bool al = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_in | (uintptr_t)kv_cache) & 15) == 0;
-  for (int i = 0; i < 2; ++i) al = al && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
-  SEA_REQUIRE(al, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
-  StagePagedParams p;
-  p.q = q; p.k = k; p.v = v; p.q_in = q_in; p.kv_cache = kv_cache; p.ctr = counters;
-  for (int i = 0; i < 2; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
-  p.N = (int)N; p.H = (int)H; p.D = (int)D; p.cap = (int)capacity;
-  p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
-  p.pool_pages = (int)pool_pages;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t chunks = 3 * N * H * (D / 8);
-  const unsigned blocks = (unsigned)((chunks + 255) / 256 > 1024 ? 1024 : (chunks + 255) / 256);
-  const int cs = (int)counter_stride;
-  const StageParams b = p;                                   // (the unpaged forms' arguments)
-  if (block_table) {
-    if (dtype == SEA_F16) hipLaunchKernelGGL((decode_stage_kernel<__half, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
-    else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
-  } else if (dtype == SEA_F16) {
-    if (cs) hipLaunchKernelGGL((decode_stage_kernel<__half, true>), dim3(blocks), dim3(256), 0, s, b, cs);
-    else hipLaunchKernelGGL((decode_stage_kernel<__half, false>), dim3(blocks), dim3(256), 0, s, b, 0);
-  } else {
-    if (cs) hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true>), dim3(blocks), dim3(256), 0, s, b, cs);
-    else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, false>), dim3(blocks), dim3(256), 0, s, b, 0);
-  }
-  SEA_CHECK_LAUNCH(nm);
-  return SEA_OK;
-}
-
-// `rows` (1 .. 8) new rows per sequence: row j of sequence n goes to cache row counters[n * counter_stride] + j (include/sea_hip.h)
-extern "C" int sea_decode_stage_rows(const void* q, const void* k, const void* v, int dtype, int64_t N, int64_t H, int64_t rows,
-                                     int64_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                     void* q_in, void* kv_cache, int64_t capacity, const int32_t* counters,
-                                     int64_t counter_stride, sea_stream_t stream) {
-  const char* nm = "sea_decode_stage_rows";
-  SEA_REQUIRE(q && k && v && q_strides && k_strides && v_strides && q_in && kv_cache && counters, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(rows >= 1 && rows <= 8, SEA_EINVAL, "%s: rows %lld outside 1 .. 8", nm, (long long)rows);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
   SEA_REQUIRE(N > 0 && H > 0 && D > 0 && capacity > 0 && capacity < (1ll << 31) && N * H * rows * D < (1ll << 24), SEA_EINVAL,
@@ -364,17 +327,40 @@ extern "C" int sea_decode_stage_rows(const void* q, const void* k, const void* v
   SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
               (long long)counter_stride);
   SEA_REQUIRE(D % 8 == 0, SEA_EUNSUPPORTED, "%s: D must be a multiple of 8 (16-byte rows)", nm);
+  const int ns = rows > 1 ? 3 : 2;                           // (one row: the t stride is not read)
   bool al = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_in | (uintptr_t)kv_cache) & 15) == 0;
-  for (int i = 0; i < 3; ++i) al = al && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
+  for (int i = 0; i < ns; ++i) al = al && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0;
   SEA_REQUIRE(al, SEA_EUNSUPPORTED, "%s: rows must be 16-byte aligned", nm);
-  StageRowsParams p;
-  p.q = q; p.k = k; p.v = v; p.q_in = q_in; p.kv_cache = kv_cache; p.ctr = counters;
-  for (int i = 0; i < 3; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
-  p.N = (int)N; p.H = (int)H; p.rows = (int)rows; p.D = (int)D; p.cap = (int)capacity; p.ctr_stride = (int)counter_stride;
+  hipStream_t s = (hipStream_t)stream;
   const int64_t chunks = 3 * N * H * rows * (D / 8);
   const unsigned blocks = (unsigned)((chunks + 255) / 256 > 1024 ? 1024 : (chunks + 255) / 256);
-  if (dtype == SEA_F16) hipLaunchKernelGGL(decode_stage_rows_kernel<__half>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(decode_stage_rows_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+  if (rows == 1) {
+    StagePagedParams p;
+    p.q = q; p.k = k; p.v = v; p.q_in = q_in; p.kv_cache = kv_cache; p.ctr = counters;
+    for (int i = 0; i < 2; ++i) { p.qs[i] = q_strides[i]; p.ks[i] = k_strides[i]; p.vs[i] = v_strides[i]; }
+    p.N = (int)N; p.H = (int)H; p.D = (int)D; p.cap = (int)capacity;
+    p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
+    p.pool_pages = (int)pool_pages;
+    const int cs = (int)counter_stride;
+    const StageParams b = p;                                   // (the unpaged forms' arguments)
+    if (block_table) {
+      if (dtype == SEA_F16) hipLaunchKernelGGL((decode_stage_kernel<__half, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
+      else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true, true>), dim3(blocks), dim3(256), 0, s, p, cs);
+    } else if (dtype == SEA_F16) {
+      if (cs) hipLaunchKernelGGL((decode_stage_kernel<__half, true>), dim3(blocks), dim3(256), 0, s, b, cs);
+      else hipLaunchKernelGGL((decode_stage_kernel<__half, false>), dim3(blocks), dim3(256), 0, s, b, 0);
+    } else {
+      if (cs) hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, true>), dim3(blocks), dim3(256), 0, s, b, cs);
+      else hipLaunchKernelGGL((decode_stage_kernel<__hip_bfloat16, false>), dim3(blocks), dim3(256), 0, s, b, 0);
+    }
+  } else {
+    StageRowsParams r;
+    r.q = q; r.k = k; r.v = v; r.q_in = q_in; r.kv_cache = kv_cache; r.ctr = counters;
+    for (int i = 0; i < 3; ++i) { r.qs[i] = q_strides[i]; r.ks[i] = k_strides[i]; r.vs[i] = v_strides[i]; }
+    r.N = (int)N; r.H = (int)H; r.rows = (int)rows; r.D = (int)D; r.cap = (int)capacity; r.ctr_stride = (int)counter_stride;
+    if (dtype == SEA_F16) hipLaunchKernelGGL(decode_stage_rows_kernel<__half>, dim3(blocks), dim3(256), 0, s, r);
+    else hipLaunchKernelGGL(decode_stage_rows_kernel<__hip_bfloat16>, dim3(blocks), dim3(256), 0, s, r);
+  }
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

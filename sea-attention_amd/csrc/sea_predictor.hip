@@ -606,23 +606,10 @@ extern "C" int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int6
   return SEA_OK;
 }
 
-static int cumavg_entry(const char* nm, const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D,
-                        const int64_t* v_strides, void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes,
-                        sea_stream_t stream);
-
+// n_slices > 1: the T rows cut into slices with carried column totals (two launches); 1, NULL, 0 = one pass
 extern "C" int sea_cumavg(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
-                          void* out, sea_stream_t stream) {
-  return cumavg_entry("sea_cumavg", v, dtype, N, H, T, D, v_strides, out, 1, nullptr, 0, stream);
-}
-
-extern "C" int sea_cumavg_sliced(const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D, const int64_t* v_strides,
-                                 void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
-  return cumavg_entry("sea_cumavg_sliced", v, dtype, N, H, T, D, v_strides, out, n_slices, workspace, workspace_bytes, stream);
-}
-
-static int cumavg_entry(const char* nm, const void* v, int dtype, int64_t N, int64_t H, int64_t T, int64_t D,
-                        const int64_t* v_strides, void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes,
-                        sea_stream_t stream) {
+                          void* out, int64_t n_slices, void* workspace, int64_t workspace_bytes, sea_stream_t stream) {
+  const char* nm = "sea_cumavg";
   SEA_REQUIRE(v && v_strides && out, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_F16 || dtype == SEA_BF16, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
   SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0, SEA_EINVAL, "%s: bad shape", nm);

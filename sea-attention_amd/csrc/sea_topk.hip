@@ -1168,7 +1168,7 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
   decode_cnn_ticket<false>(dp, dp.ctr_stride ? (int)gridDim.x : 1, 1);   // (per-sequence counters: every sequence's triple)
 }
 
-// ---- the same for a step of `rows` (1 .. 8) new rows per sequence (sea_decode_cnn_tail_select_rows) -----------------------------
+// ---- the same for a step of `rows` (1 .. 8) new rows per sequence (sea_decode_cnn_tail_select with y1_scratch) ------------------
 // One workgroup per (sequence n, row j), serving position t = seen + j: conv1's rows t - 2 dil, t - dil, t are recomputed where
 // they are new in this step (>= seen; their x rows come from x_new, older ones from the x ring), read from the y1 ring where they
 // are older; then conv2's row t and the unchanged tail_select_row of row t.  Rows the workgroup recomputes for positions of
@@ -1499,22 +1499,30 @@ extern "C" int sea_predictor_tail_select(const void* y, const float* z, int dtyp
 }
 
 // One launch for a decoding step's predictor CNN + tail + selection + state advance (DecodeCnnParams above; round 5).
+// scratch == NULL: the one-row kernel, a workgroup per sequence, with its in-launch emit; else the multi-row kernel, a workgroup
+// per (sequence, row) with two rows of `scratch` each.
 template <typename T>
-static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, const TopkParams& p, const EmitParams& ep, hipStream_t s) {
+static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, const TopkParams& p, const EmitParams& ep, void* scratch,
+                             hipStream_t s) {
   const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
   size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
   if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
   const int nt = (dp.C + 15) / 16, kch = (dp.C + 31) / 32;
   const size_t wimg = (size_t)(16 * nt) * 9 * kch * 64;                    // the weight image overlays the (later) z tile
   if (lds < wimg) lds = wimg;
-  dim3 grid((unsigned)tp.N), block(TK_THREADS);
+  dim3 grid((unsigned)(tp.N * tp.T)), block(TK_THREADS);
+#define SEA_DCNN_GO(KERNEL, ...)                                                                                       \
+  do {                                                                                                                 \
+    static DevOnce once;                                                                                               \
+    if (lds > 32 * 1024 && once.first()) SEA_MAX_LDS(KERNEL, lds);                                                     \
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, s, dp, tp, p, __VA_ARGS__);                                           \
+  } while (0)
 #define SEA_DCNN(EE, NTV, KV)                                                                                          \
   do {                                                                                                                 \
     constexpr bool EM = (NTV) <= 4;                                                                                    \
-    if (!EM && ep.col != nullptr) return SEA_EUNSUPPORTED;                                                             \
-    static DevOnce once;                                                                                               \
-    if (lds > 32 * 1024 && once.first()) SEA_MAX_LDS((decode_cnn_tail_select_kernel<T, EE, NTV, KV, EM>), lds);        \
-    hipLaunchKernelGGL((decode_cnn_tail_select_kernel<T, EE, NTV, KV, EM>), grid, block, lds, s, dp, tp, p, ep);       \
+    if (scratch) SEA_DCNN_GO((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), scratch);                           \
+    else if (!EM && ep.col != nullptr) return SEA_EUNSUPPORTED;                                                        \
+    else SEA_DCNN_GO((decode_cnn_tail_select_kernel<T, EE, NTV, KV, EM>), ep);                                         \
   } while (0)
   if (ept <= 8 && nt == 1 && kch == 1) { if (ept <= 4) SEA_DCNN(4, 1, 1); else SEA_DCNN(8, 1, 1); }
   else if (ept <= 16 && nt == 2 && kch == 1) SEA_DCNN(16, 2, 1);
@@ -1523,107 +1531,40 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
   else if (ept <= 40 && nt == 5 && kch == 3) SEA_DCNN(40, 5, 3);
   else return SEA_EUNSUPPORTED;
 #undef SEA_DCNN
+#undef SEA_DCNN_GO
   return SEA_OK;
 }
 
 // counter_stride > 0: a counter triple PER SEQUENCE, sequence n's at counters + n * counter_stride (counter_stride >= 3); the
-// last workgroup advances all N
-extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, int dtype, int64_t N, int64_t C,
-                                          int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y, const void* w1_packed,
-                                          const float* bias1, const void* w2_packed, const float* bias2, int64_t CinP, int dilation,
-                                          int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp, const void* gamma,
-                                          const void* beta, float eps, void* probs, const int32_t* keep_table, int32_t* counters,
-                                          int32_t* ticket, int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz,
-                                          int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n, int64_t z_cap,
-                                          int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream) {
+// last workgroup advances all N.  y1_scratch != NULL: the multi-row form, `rows` (1 .. 8) new rows per sequence, one workgroup
+// per (sequence, row), no crow and no in-launch emit (include/sea_hip.h)
+extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
+                                          int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x, int64_t ring_y,
+                                          const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2,
+                                          int64_t CinP, int dilation, int pad_w, const void* conv_b, const void* conv_w16, int64_t Cp,
+                                          const void* gamma, const void* beta, float eps, void* probs, const int32_t* keep_table,
+                                          int32_t* counters, int32_t* ticket, int is_causal, int max_k, uint32_t* bits,
+                                          int32_t* row_nnz, int32_t* head_off, int32_t* crow_out, int32_t* col, int64_t col_stride_n,
+                                          int64_t z_cap, int64_t T_cap, const uint32_t* consts_tab, int64_t counter_stride,
+                                          sea_stream_t stream) {
   const char* nm = "sea_decode_cnn_tail_select";
+  const bool multi = y1_scratch != nullptr;
   SEA_REQUIRE(counter_stride == 0 || counter_stride >= 3, SEA_EINVAL,
               "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm, (long long)counter_stride);
+  if (multi)
+    SEA_REQUIRE(!crow_out && !col && col_stride_n == 0 && z_cap == 0 && T_cap == 0, SEA_EINVAL,
+                "%s: the multi-row form (y1_scratch) writes no crow and emits no columns: crow_out / col must be NULL, col_stride_n / "
+                "z_cap / T_cap 0 (run sea_csr_row_scan on row_nnz)", nm);
+  else
+    SEA_REQUIRE(rows == 1, SEA_EINVAL, "%s: null pointer: rows = %lld needs y1_scratch (the multi-row form)", nm, (long long)rows);
   SEA_REQUIRE(col == nullptr || (C <= 64 && col_stride_n >= z_cap && z_cap > 0 && T_cap > 0 && H * T_cap < (1ll << 31) && T_cap < (1ll << 24)),
               SEA_EUNSUPPORTED,
               "%s: the in-launch emit serves C <= 64 channels (beyond that the weight image leaves no LDS for it: pass col = NULL "
               "and call sea_csr_emit with t_src_dev = counters + 2)", nm);
   SEA_REQUIRE(x_new && x_ring && y1_ring && y2 && w1_packed && bias1 && w2_packed && bias2 && conv_b && conv_w16 && gamma && beta &&
-                  keep_table && counters && ticket && bits && row_nnz && head_off && crow_out, SEA_EINVAL, "%s: null pointer", nm);
-  SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
-  SEA_REQUIRE(N > 0 && N < (1 << 20) && H > 0 && H <= 64 && H % 4 == 0 && C == 2 * H && C % 8 == 0 && W4 == 64 && max_k > 0, SEA_EUNSUPPORTED,
-              "%s: needs T_m = 256 (W4 = 64), H %% 4 == 0, C = 2 H channels in whole blocks of 8", nm);
-  SEA_REQUIRE(CinP == (C + 31) / 32 * 32 && Cp % 32 == 0 && Cp >= C && dilation > 0 && 2 * pad_w == 2 * dilation, SEA_EUNSUPPORTED,
-              "%s: 3 x 3 width-preserving convolutions with CinP = C rounded up to 32", nm);
-  SEA_REQUIRE(ring_x > 2 * dilation && ring_y > 2 * dilation, SEA_EINVAL,
-              "%s: a ring must hold the rows t - 2 dil .. t in distinct slots (more than 2 * dilation of them)", nm);
-  SEA_REQUIRE((((uintptr_t)x_new | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)y2 | (uintptr_t)w1_packed | (uintptr_t)w2_packed |
-                (uintptr_t)conv_w16 | (uintptr_t)probs) & 15) == 0, SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
-  SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
-              (long long)counter_stride);
-  DecodeCnnParams dp;
-  dp.x_new = x_new; dp.x_ring = x_ring; dp.y1_ring = y1_ring; dp.y2 = y2; dp.w1 = w1_packed; dp.w2 = w2_packed; dp.b1 = bias1; dp.b2 = bias2;
-  dp.counters = counters; dp.ctr_stride = (int)counter_stride; dp.ticket = ticket;
-  dp.C = (int)C; dp.W = (int)W4; dp.RX = (int)ring_x; dp.RY = (int)ring_y; dp.dil = dilation; dp.pad_w = pad_w;
-  TailParams tp;
-  tp.y = y2; tp.w4 = nullptr; tp.b4 = conv_b; tp.gamma = gamma; tp.beta = beta; tp.probs = probs; tp.scores = nullptr; tp.eps = eps;
-  tp.N = (int)N; tp.C = (int)C; tp.H = (int)H; tp.T = 1; tp.W4 = (int)W4; tp.UP = 4; tp.T_M = 256;
-  tp.ys_n = C * W4; tp.ys_c = 1; tp.ys_t = 0; tp.ys_w = 8; tp.ys_c8 = W4 * 8;          // one C8 row per batch item
-  tp.w16 = conv_w16; tp.Cp = (int)Cp; tp.z = nullptr;
-  tp.tab = (consts_tab != nullptr && (((uintptr_t)consts_tab) & 15) == 0) ? consts_tab : nullptr;
-  TopkParams p;
-  p.src = nullptr; p.sn = H * 256; p.sh = 256; p.st = 256;
-  p.H = (int)H; p.T_dst = 1; p.T_m = 256; p.T_src = 1;
-  p.is_causal = is_causal; p.max_k = max_k;
-  p.M = (int)(H * 256); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes(256);
-  p.keep = keep_table; p.keep_stride_n = 0;
-  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = counters + 1; p.t_src_stride = (int)counter_stride; p.crow1 = crow_out;
-  EmitParams ep;
-  ep.bits = bits; ep.crow = crow_out; ep.H = (int)H; ep.T_dst = 1; ep.T_m = 256; ep.T_src = 1; ep.is_causal = is_causal; ep.max_k = max_k;
-  ep.W = p.W; ep.col = col; ep.col_stride_n = col_stride_n; ep.z_cap = z_cap; ep.values_out = nullptr; ep.T_enc = (int)T_cap;
-  ep.t_src_dev = counters + 1; ep.t_src_stride = (int)counter_stride;
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == SEA_F16 ? launch_decode_cnn<__half>(dp, tp, p, ep, s) : launch_decode_cnn<__hip_bfloat16>(dp, tp, p, ep, s);
-  SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
-  SEA_CHECK_LAUNCH(nm);
-  return SEA_OK;
-}
-
-template <typename T>
-static int launch_decode_cnn_rows(const DecodeCnnParams& dp, const TailParams& tp, const TopkParams& p, void* scratch, hipStream_t s) {
-  const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
-  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
-  if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
-  const int nt = (dp.C + 15) / 16, kch = (dp.C + 31) / 32;
-  const size_t wimg = (size_t)(16 * nt) * 9 * kch * 64;
-  if (lds < wimg) lds = wimg;
-  dim3 grid((unsigned)(tp.N * tp.T)), block(TK_THREADS);
-#define SEA_DCNNR(EE, NTV, KV)                                                                                         \
-  do {                                                                                                                 \
-    static DevOnce once;                                                                                               \
-    if (lds > 32 * 1024 && once.first()) SEA_MAX_LDS((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), lds);       \
-    hipLaunchKernelGGL((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), grid, block, lds, s, dp, tp, p, scratch); \
-  } while (0)
-  if (ept <= 8 && nt == 1 && kch == 1) { if (ept <= 4) SEA_DCNNR(4, 1, 1); else SEA_DCNNR(8, 1, 1); }
-  else if (ept <= 16 && nt == 2 && kch == 1) SEA_DCNNR(16, 2, 1);
-  else if (ept <= 32 && nt == 3 && kch == 2) SEA_DCNNR(32, 3, 2);
-  else if (ept <= 32 && nt == 4 && kch == 2) SEA_DCNNR(32, 4, 2);
-  else if (ept <= 40 && nt == 5 && kch == 3) SEA_DCNNR(40, 5, 3);
-  else return SEA_EUNSUPPORTED;
-#undef SEA_DCNNR
-  return SEA_OK;
-}
-
-// `rows` (1 .. 8) new rows per sequence (include/sea_hip.h); one workgroup per (sequence, row), the last advances the counters
-extern "C" int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, void* y1_ring, void* y2, void* y1_scratch, int dtype,
-                                               int64_t N, int64_t rows, int64_t C, int64_t H, int64_t W4, int64_t ring_x,
-                                               int64_t ring_y, const void* w1_packed, const float* bias1, const void* w2_packed,
-                                               const float* bias2, int64_t CinP, int dilation, int pad_w, const void* conv_b,
-                                               const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
-                                               void* probs, const int32_t* keep_table, int32_t* counters, int32_t* ticket,
-                                               int is_causal, int max_k, uint32_t* bits, int32_t* row_nnz, int32_t* head_off,
-                                               const uint32_t* consts_tab, int64_t counter_stride, sea_stream_t stream) {
-  const char* nm = "sea_decode_cnn_tail_select_rows";
-  SEA_REQUIRE(x_new && x_ring && y1_ring && y2 && y1_scratch && w1_packed && bias1 && w2_packed && bias2 && conv_b && conv_w16 &&
-                  gamma && beta && keep_table && counters && ticket && bits && row_nnz && head_off, SEA_EINVAL, "%s: null pointer", nm);
+                  keep_table && counters && ticket && bits && row_nnz && head_off && (multi || crow_out), SEA_EINVAL,
+              "%s: null pointer", nm);
   SEA_REQUIRE(rows >= 1 && rows <= 8, SEA_EINVAL, "%s: rows %lld outside 1 .. 8", nm, (long long)rows);
-  SEA_REQUIRE(counter_stride == 0 || counter_stride >= 3, SEA_EINVAL,
-              "%s: counter_stride must be >= 3 (a triple per sequence; got %lld)", nm, (long long)counter_stride);
   SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
               (long long)counter_stride);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
@@ -1631,9 +1572,13 @@ extern "C" int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, 
               SEA_EUNSUPPORTED, "%s: needs T_m = 256 (W4 = 64), H %% 4 == 0, C = 2 H channels in whole blocks of 8", nm);
   SEA_REQUIRE(CinP == (C + 31) / 32 * 32 && Cp % 32 == 0 && Cp >= C && dilation > 0 && 2 * pad_w == 2 * dilation, SEA_EUNSUPPORTED,
               "%s: 3 x 3 width-preserving convolutions with CinP = C rounded up to 32", nm);
-  SEA_REQUIRE(ring_x >= 2 * dilation + rows && ring_y >= 2 * dilation + rows, SEA_EINVAL,
-              "%s: rings of %lld / %lld slots for %lld rows: each needs 2 * dilation + rows = %lld (the slots the step reads and "
-              "writes are disjoint)", nm, (long long)ring_x, (long long)ring_y, (long long)rows, (long long)(2 * dilation + rows));
+  if (multi)
+    SEA_REQUIRE(ring_x >= 2 * dilation + rows && ring_y >= 2 * dilation + rows, SEA_EINVAL,
+                "%s: rings of %lld / %lld slots for %lld rows: each needs 2 * dilation + rows = %lld (the slots the step reads and "
+                "writes are disjoint)", nm, (long long)ring_x, (long long)ring_y, (long long)rows, (long long)(2 * dilation + rows));
+  else
+    SEA_REQUIRE(ring_x > 2 * dilation && ring_y > 2 * dilation, SEA_EINVAL,
+                "%s: a ring must hold the rows t - 2 dil .. t in distinct slots (more than 2 * dilation of them)", nm);
   SEA_REQUIRE((((uintptr_t)x_new | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)y2 | (uintptr_t)y1_scratch |
                 (uintptr_t)w1_packed | (uintptr_t)w2_packed | (uintptr_t)conv_w16 | (uintptr_t)probs) & 15) == 0,
               SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
@@ -1644,7 +1589,8 @@ extern "C" int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, 
   TailParams tp;
   tp.y = y2; tp.w4 = nullptr; tp.b4 = conv_b; tp.gamma = gamma; tp.beta = beta; tp.probs = probs; tp.scores = nullptr; tp.eps = eps;
   tp.N = (int)N; tp.C = (int)C; tp.H = (int)H; tp.T = (int)rows; tp.W4 = (int)W4; tp.UP = 4; tp.T_M = 256;
-  tp.ys_n = rows * C * W4; tp.ys_c = 1; tp.ys_t = C * W4; tp.ys_w = 8; tp.ys_c8 = W4 * 8;    // one C8 row per (item, row)
+  // one C8 row per batch item (one-row form), per (item, row) (multi-row form)
+  tp.ys_n = rows * C * W4; tp.ys_c = 1; tp.ys_t = multi ? C * W4 : 0; tp.ys_w = 8; tp.ys_c8 = W4 * 8;
   tp.w16 = conv_w16; tp.Cp = (int)Cp; tp.z = nullptr;
   tp.tab = (consts_tab != nullptr && (((uintptr_t)consts_tab) & 15) == 0) ? consts_tab : nullptr;
   TopkParams p;
@@ -1653,11 +1599,15 @@ extern "C" int sea_decode_cnn_tail_select_rows(const void* x_new, void* x_ring, 
   p.is_causal = is_causal; p.max_k = max_k;
   p.M = (int)(H * 256); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes(256);
   p.keep = keep_table; p.keep_stride_n = 0;
-  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.t_src_dev = nullptr; p.t_src_stride = 0;
-  p.crow1 = nullptr;
+  p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.crow1 = crow_out;
+  p.t_src_dev = multi ? nullptr : counters + 1; p.t_src_stride = multi ? 0 : (int)counter_stride;
+  EmitParams ep;                                                                // (read by the one-row form alone)
+  ep.bits = bits; ep.crow = crow_out; ep.H = (int)H; ep.T_dst = 1; ep.T_m = 256; ep.T_src = 1; ep.is_causal = is_causal; ep.max_k = max_k;
+  ep.W = p.W; ep.col = col; ep.col_stride_n = col_stride_n; ep.z_cap = z_cap; ep.values_out = nullptr; ep.T_enc = (int)T_cap;
+  ep.t_src_dev = counters + 1; ep.t_src_stride = (int)counter_stride;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == SEA_F16 ? launch_decode_cnn_rows<__half>(dp, tp, p, y1_scratch, s)
-                                  : launch_decode_cnn_rows<__hip_bfloat16>(dp, tp, p, y1_scratch, s);
+  const int rc = dtype == SEA_F16 ? launch_decode_cnn<__half>(dp, tp, p, ep, y1_scratch, s)
+                                  : launch_decode_cnn<__hip_bfloat16>(dp, tp, p, ep, y1_scratch, s);
   SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;

@@ -60,10 +60,10 @@ Multi-token steps and rewind (`from_sequences(..., max_step_rows=S)`, contiguous
 rows of every slot, (N, H, s, D) -> context (N, s, H*D), and `rewind(drop)` removes the last drop[n] rows of that step from
 slot n again (speculative decoding: the target verifies a draft's s tokens in one step and drops the rejected ones).  A graph
 per distinct s, captured on first use over views of buffers allocated once for S.  The per-sequence forms of the Performer,
-the MLP, the attention and the emit take s rows already; `sea_decode_stage_rows` and `sea_decode_cnn_tail_select_rows` (a
-workgroup per (sequence, row), recomputing the conv1 rows of this step that its row needs into its own scratch) are the two
-entries of their own.  Rewind is host work plus one counter copy: the rings keep LB + S x rows and 2 dil + S conv1 rows, so
-a slot read after any rewind is still where it was, K / V rows past the kept length are overwritten by the next stage before
+the MLP, the attention and the emit take s rows already; `sea_decode_stage` takes them through its `rows` argument and
+`sea_decode_cnn_tail_select` through its multi-row form (`y1_scratch`: a workgroup per (sequence, row), recomputing the conv1
+rows of this step that its row needs into its own scratch).  Rewind is host work plus one counter copy: the rings keep
+LB + S x rows and 2 dil + S conv1 rows, so a slot read after any rewind is still where it was, K / V rows past the kept length are overwritten by the next stage before
 anything reads them, and the Performer image -- which changes only when a chunk completes, at most once per step (s <= 8 <=
 chunk) -- is copied aside before a step that completes one and copied back when the rewind falls below that boundary.  A
 rewound slot is bitwise a plain session that stepped only the kept rows.
@@ -862,9 +862,11 @@ class DecodeSession:
             return self.x_ring[:, pos % self.x_ring.shape[1]]
         return self.xs[:, :self.LB]
 
-    # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new row
+    # the one launch of a position whose arguments change: q -> q_in, k / v -> the caches' new rows (a max_step_rows session:
+    # the s rows of the step, into the view of q_in that an s-row step reads)
     def _stage(self, q, k, v):
-        ops.decode_stage(q, k, v, self.q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2],
+        q_in = self.q_in if self.max_step_rows is None else self._rows_views(q.shape[2])[0]
+        ops.decode_stage(q, k, v, q_in, self.kv_cache, self.ctr32[:, :2] if self.ragged else self.ctr32[:2],
                          block_table=self.block_table, capacity=self.capacity)
 
     # the (captured) launches of one position; everything position-dependent is read from device memory
@@ -929,9 +931,6 @@ class DecodeSession:
         return (self.q_in[:N * H * s * D].view(N, H, s, D), self.x_new[:N * s].view((N, s) + rs), self.y2[:N * s].view((N, s) + rs),
                 self.y1_scratch[:N * s * 2].view((N, s, 2) + rs), self.ctx[:N * s * H * D].view(N, s, H * D))
 
-    def _stage_rows(self, q, k, v):
-        ops.decode_stage_rows(q, k, v, self._rows_views(q.shape[2])[0], self.kv_cache, self.ctr32[:, :2])
-
     def _launch_rows(self, s):
         at, N, H, D, T_M = self.attention, self.N, self.H, self.D, self.T_M
         q_in, x_new, y2, y1_scratch, ctx = self._rows_views(s)
@@ -945,9 +944,9 @@ class DecodeSession:
         keepres, ln2 = at.attention_predictor_cnn[1].module, at.attention_predictor_cnn[2].module
         body = list(keepres.net.children())
         conv4 = body[-1].module
-        self.probs, sel = ops.decode_cnn_tail_select_rows(
-            x_new, self.x_ring, self.y1_ring, y2, y1_scratch, body[0].module, body[2].module, conv4.weight[:, :, 0, 0], conv4.bias,
-            ln2.weight, ln2.bias, T_M, self.keep_table, self.k, self.ctr32, self.ticket, eps=ln2.eps)
+        self.probs, sel = ops.decode_cnn_tail_select(
+            x_new, self.x_ring, self.y1_ring, y2, body[0].module, body[2].module, conv4.weight[:, :, 0, 0], conv4.bias,
+            ln2.weight, ln2.bias, T_M, self.keep_table, self.k, self.ctr32, self.ticket, eps=ln2.eps, y1_scratch=y1_scratch)
         fused_attn = ops.fused_interp_supported(self.dtype, D, T_M)
         csr = ops.csr_from_selection(*sel, H, T_M, self.capacity, self.k, True, s * self.z_cap, t_src_dev=self.tsrc_done32,
                                      defer_emit=fused_attn)
@@ -975,14 +974,9 @@ class DecodeSession:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side), torch.no_grad():                    # warm-up: lazy library work happens outside the capture
-                if s is None:
-                    zero = torch.zeros_like(self.q_in)
-                    self._stage(zero, zero, zero)
-                    self._launch()
-                else:
-                    zero = torch.zeros((self.N, self.H, s, self.D), dtype=self.dtype, device=self.q_in.device)
-                    self._stage_rows(zero, zero, zero)
-                    self._launch_rows(s)
+                zero = torch.zeros((self.N, self.H, s or 1, self.D), dtype=self.q_in.dtype, device=self.q_in.device)
+                self._stage(zero, zero, zero)
+                self._launch() if s is None else self._launch_rows(s)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -1086,7 +1080,7 @@ class DecodeSession:
         img = self.image.view(N, -1)
         for n in crossed:
             self.image_backup[n].copy_(img[n])
-        self._stage_rows(q, k, v)
+        self._stage(q, k, v)
         if self.use_graph:
             g, self.csr, self._col_emit, self.probs, _pins = self._graphs[s]
             g.replay()

@@ -16,4 +16,4 @@ from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value
                         predictor_mlp, predictor_mlp_supported, predictor_tail_select,
                         predictor_tail_select_supported, clear_prep_cache, prep_generation, pinned_prep, LazyTensor, realize,
                         decode_stage, c8_window_shift, decode_fork, decode_fork_staging_bytes, decode_cnn_tail_select, decode_cnn_supported, decode_cnn_emits,
-                        decode_stage_rows, decode_cnn_tail_select_rows, decode_gather_rows, decode_append_rows)
+                        decode_gather_rows, decode_append_rows)

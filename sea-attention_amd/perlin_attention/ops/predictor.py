@@ -338,13 +338,9 @@ def cumavg(v: torch.Tensor, out: Optional[torch.Tensor] = None, n_slices: int = 
     ns = n_slices if n_slices is not None else (min(16, 256 // (N * H)) if N * H <= 128 and T >= 2048 else 1)
     vec_ok = (v.dtype != torch.float32 and D in (32, 64, 80, 128) and all(st % 8 == 0 for st in v.stride()[:3])
               and v.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
-    if ns > 1 and vec_ok:
-        ws = torch.empty((N * H * ns * D,), dtype=torch.float32, device=v.device)
-        _lib.check(lib.sea_cumavg_sliced(_p(v), _lib.dtype_code(v.dtype), N, H, T, D, _lib.strides3(v), _p(out), ns, _p(ws),
-                                         ws.numel() * 4, _lib.stream_ptr()), "sea_cumavg_sliced")
-        return out
-    _lib.check(lib.sea_cumavg(_p(v), _lib.dtype_code(v.dtype), N, H, T, D, _lib.strides3(v), _p(out),
-                              _lib.stream_ptr()), "sea_cumavg")
+    ws = torch.empty((N * H * ns * D,), dtype=torch.float32, device=v.device) if ns > 1 and vec_ok else None
+    _lib.check(lib.sea_cumavg(_p(v), _lib.dtype_code(v.dtype), N, H, T, D, _lib.strides3(v), _p(out), ns if ws is not None else 1,
+                              _p(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_ptr()), "sea_cumavg")
     return out
 
 
@@ -675,56 +671,35 @@ def causal_conv_c8_z(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
 @_lib.device_guarded
 def decode_stage(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.Tensor, kv_cache: torch.Tensor,
                  counters: torch.Tensor, block_table: Optional[torch.Tensor] = None, capacity: Optional[int] = None) -> None:
-    """`sea_decode_stage`: the new rows of a decoding step, (N,H,1,D) each (any [n,h] strides), into the session's static
-    buffers -- q into q_in (N,H,1,D), k / v into kv_cache (2,N,H,capacity,D) at the row the device counters name
-    (int32 [seen, tsrc]: row = counters[0]).  An (N, >= 1) view of a per-sequence counter block writes sequence n's rows at
-    counters[n, 0] (`counter_stride` > 0).  Paged form (`block_table` (N, >= ceil(capacity / page_rows)) int32, per-sequence
-    counters): kv_cache is a page pool (2, P, H, page_rows, D) and sequence n's rows go to page block_table[n, row // page_rows];
-    `capacity` is the logical rows per sequence (unpaged: kv_cache's own, the argument is not read)."""
+    """`sea_decode_stage`: the s new rows of a decoding step, (N,H,s,D) each with 1 <= s <= 8 (any [n,h,t] strides), into the
+    session's static buffers -- q into q_in (N,H,s,D) dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at the
+    row the device counters name plus j (int32 [seen, tsrc]: row = counters[0]).  An (N, >= 1) view of a per-sequence counter
+    block writes sequence n's rows from counters[n, 0] on (`counter_stride` > 0).  Paged form (s = 1; `block_table` (N, >=
+    ceil(capacity / page_rows)) int32, per-sequence counters): kv_cache is a page pool (2, P, H, page_rows, D) and sequence n's
+    row goes to page block_table[n, row // page_rows]; `capacity` is the logical rows per sequence (unpaged: kv_cache's own,
+    the argument is not read)."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, q_in, kv_cache, counters, block_table)
-    N, H, one, D = q.shape
+    N, H, s, D = q.shape
     paged = block_table is not None
-    assert one == 1 and k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
-    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, 1, D) and kv_cache.is_contiguous()
+    assert k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
+    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, s, D) and kv_cache.is_contiguous()
     assert kv_cache.shape[0] == 2 and kv_cache.shape[2] == H and (paged or kv_cache.shape[1] == N)
     stride = _lib.counter_stride(counters, N) if counters.dim() == 2 else 0      # (an (N, k) view: a counter per sequence)
     assert stride > 0 or (counters.dtype == torch.int32 and counters.numel() == 2 and counters.is_contiguous())
-    # the kernel moves whole 16-byte vectors: rows contiguous along D, [n, h] strides in multiples of 8 elements, 16-byte aligned
-    # base.  Anything else (e.g. rows sliced out of a fused qkv buffer at an odd offset) is repacked here -- the session used
-    # to take any layout through `.copy_` (ADVICE r4)
-    ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+    # the kernel moves whole 16-byte vectors: rows contiguous along D, [n, h, t] strides (t: of a step of several rows) in
+    # multiples of 8 elements, 16-byte aligned base.  Anything else (e.g. rows sliced out of a fused qkv buffer at an odd
+    # offset) is repacked here -- the session used to take any layout through `.copy_` (ADVICE r4)
+    ok = lambda t: t.stride(-1) == 1 and all(t.stride(i) % 8 == 0 for i in range(3 if s > 1 else 2)) and t.data_ptr() % 16 == 0
     q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
-    st = lambda t: (ctypes_i64 * 2)(t.stride(0), t.stride(1))
     cap, table_stride, page_rows, pool_pages = kv_cache.shape[3], 0, 0, 0
     if paged:
         assert stride > 0 and capacity is not None, "the paged stage: per-sequence counters and a capacity"
         assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.shape[0] == N and block_table.stride(1) == 1
         cap, table_stride, page_rows, pool_pages = int(capacity), block_table.stride(0), kv_cache.shape[3], kv_cache.shape[1]
-    _lib.check(lib.sea_decode_stage(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, D, st(q), st(k), st(v), _p(q_in),
-                                    _p(kv_cache), cap, _p(counters), stride, _p(block_table), table_stride, page_rows, pool_pages,
-                                    _lib.stream_ptr()), "sea_decode_stage")
-
-
-@_lib.device_guarded
-def decode_stage_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_in: torch.Tensor, kv_cache: torch.Tensor,
-                      counters: torch.Tensor) -> None:
-    """`sea_decode_stage_rows`: the s new rows of a decoding step, (N,H,s,D) each with 1 <= s <= 8 (any [n,h,t] strides), into
-    the session's static buffers -- q into q_in (N,H,s,D) dense, k / v row j of sequence n into kv_cache (2,N,H,capacity,D) at
-    row counters[n, 0] + j (an (N, >= 1) view of a per-sequence counter block; a 1-D counter is the batch's one)."""
-    lib = _lib.load()
-    _lib.require_gpu(q, k, v, q_in, kv_cache, counters)
-    N, H, s, D = q.shape
-    assert k.shape == q.shape and v.shape == q.shape and q.dtype == k.dtype == v.dtype == q_in.dtype == kv_cache.dtype
-    assert q_in.is_contiguous() and tuple(q_in.shape) == (N, H, s, D) and kv_cache.is_contiguous()
-    assert kv_cache.shape[0] == 2 and kv_cache.shape[1] == N and kv_cache.shape[2] == H
-    stride = _lib.counter_stride(counters, N)
-    ok = lambda t: t.stride(-1) == 1 and all(t.stride(i) % 8 == 0 for i in range(3)) and t.data_ptr() % 16 == 0
-    q, k, v = (t if ok(t) else t.contiguous() for t in (q, k, v))
-    st = lambda t: (ctypes_i64 * 3)(t.stride(0), t.stride(1), t.stride(2))
-    _lib.check(lib.sea_decode_stage_rows(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, s, D, st(q), st(k), st(v), _p(q_in),
-                                         _p(kv_cache), kv_cache.shape[3], _p(counters), stride, _lib.stream_ptr()),
-               "sea_decode_stage_rows")
+    _lib.check(lib.sea_decode_stage(_p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, s, D, _lib.strides3(q), _lib.strides3(k),
+                                    _lib.strides3(v), _p(q_in), _p(kv_cache), cap, _p(counters), stride, _p(block_table),
+                                    table_stride, page_rows, pool_pages, _lib.stream_ptr()), "sea_decode_stage")
 
 
 def decode_fork_staging_bytes(image_bytes: int, x_ring_bytes: int, y1_ring_bytes: int, table_entries: int) -> int:
@@ -830,67 +805,26 @@ def decode_cnn_emits(C: int) -> bool:
 @_lib.device_guarded
 def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: torch.Tensor, y2: torch.Tensor, conv1, conv2,
                            conv_w: torch.Tensor, conv_b: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, T_m: int,
-                           keep: torch.Tensor, k: int, counters: torch.Tensor, ticket: torch.Tensor, crow_out: torch.Tensor,
-                           is_causal: bool = True, eps: float = 1e-5, want_probs: bool = True,
-                           col_out: Optional[torch.Tensor] = None, T_cap: int = 0):
+                           keep: torch.Tensor, k: int, counters: torch.Tensor, ticket: torch.Tensor,
+                           crow_out: Optional[torch.Tensor] = None, is_causal: bool = True, eps: float = 1e-5,
+                           want_probs: bool = True, col_out: Optional[torch.Tensor] = None, T_cap: int = 0,
+                           y1_scratch: Optional[torch.Tensor] = None):
     """One launch for a decoding step's predictor CNN (two 3 x 3 dilated causal convolutions, one new row each), tail,
     selection and the advance of the session's device counters (`sea_decode_cnn_tail_select`).  `conv1` / `conv2` are the
-    `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  `col_out` (N, z_cap) int32 with `T_cap` (C <=
-    64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.  `counters` (3,) is the batch's
-    one triple; an (N, 3) block holds one per sequence (`counter_stride` > 0: each workgroup reads its own sequence's, the
-    launch advances all of them).  Returns (probs or None, (bits, row_nnz, head_off))."""
+    `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  x_new (N, s, C/8, 64, 8) and y2 of as many
+    elements, dense.  `counters` (3,) is the batch's one triple; an (N, 3) block holds one per sequence (`counter_stride` > 0:
+    each workgroup reads its own sequence's, the launch advances all of them).
+    One-row form (no `y1_scratch`; s = 1): `crow_out` (N, 2) receives the one-row CSR's crow; `col_out` (N, z_cap) int32 with
+    `T_cap` (C <= 64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.
+    Multi-row form (`y1_scratch` (N, s, 2, C/8, 64, 8) dense; 1 <= s <= 8, rings of at least 2 * dilation + s slots): a
+    workgroup per (sequence, row); no crow and no columns (`crow_out` / `col_out` None): the caller runs the row scan
+    (`csr_from_selection`).  Returns (probs (N,H,s,T_m) or None, (bits, row_nnz, head_off))."""
     lib = _lib.load()
-    _lib.require_gpu(x_new, x_ring, y1_ring, y2, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket, crow_out)
-    N, C8, W4, _e = x_new.shape[0], x_new.shape[-3], x_new.shape[-2], x_new.shape[-1]
-    C, H, dt, dev = C8 * 8, conv_w.shape[0], x_new.dtype, x_new.device
-    assert _e == 8 and x_new.is_contiguous() and x_ring.is_contiguous() and y1_ring.is_contiguous() and y2.is_contiguous()
-    assert x_ring.shape[0] == N and tuple(x_ring.shape[2:]) == (C8, W4, 8) and tuple(y1_ring.shape[2:]) == (C8, W4, 8)
-    assert decode_cnn_supported(C, H, T_m, dt) and W4 * 4 == T_m
-    for cv in (conv1, conv2):
-        assert cv.kernel_size == 3 and cv.in_channels == C and cv.out_channels == C and cv.padding[1] == cv.dilation == conv1.dilation
-    stride = _lib.counter_stride(counters, N)
-    assert (counters.numel() == 3 or stride > 0) and counters.shape[-1] == 3 and counters.is_contiguous()
-    assert ticket.dtype == torch.int32 and ticket.numel() == 1
-    assert keep.dtype == torch.int32 and keep.ndim == 1 and crow_out.dtype == torch.int32 and tuple(crow_out.shape) == (N, 2)
-    packs = []
-    for cv in (conv1, conv2):
-        packs.append(_cached("conv", (cv.weight, cv.bias), dt,
-                             lambda cv=cv: (pack_conv_weight(cv.weight, 3, dt), cv.bias.to(dt).float().contiguous())))
-    (w1p, CinP), b1 = packs[0]
-    (w2p, _c), b2 = packs[1]
-    _cw, cb, g, b, w16, Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, dev)
-    tab = _tail_consts(ln_w, ln_b, 4, T_m, dt, dev)
-    probs = torch.empty((N, H, 1, T_m), dtype=dt, device=dev) if want_probs else None
-    Wb = (H * T_m + 31) // 32
-    bits = torch.empty((N, 1, Wb), dtype=torch.int32, device=dev)
-    row_nnz = torch.empty((N, 1), dtype=torch.int32, device=dev)
-    head_off = torch.empty((N, 1, H + 1), dtype=torch.int32, device=dev)
-    _lib.check(lib.sea_decode_cnn_tail_select(
-        _p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _lib.dtype_code(dt), N, C, H, W4, x_ring.shape[1], y1_ring.shape[1],
-        _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp, _p(g), _p(b),
-        float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz), _p(head_off),
-        _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0, col_out.shape[1] if col_out is not None else 0,
-        int(T_cap), _p(tab), stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select")
-    return probs, (bits, row_nnz, head_off)
-
-
-@_lib.device_guarded
-def decode_cnn_tail_select_rows(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: torch.Tensor, y2: torch.Tensor,
-                                y1_scratch: torch.Tensor, conv1, conv2, conv_w: torch.Tensor, conv_b: torch.Tensor,
-                                ln_w: torch.Tensor, ln_b: torch.Tensor, T_m: int, keep: torch.Tensor, k: int,
-                                counters: torch.Tensor, ticket: torch.Tensor, is_causal: bool = True, eps: float = 1e-5,
-                                want_probs: bool = True):
-    """`sea_decode_cnn_tail_select_rows`: `decode_cnn_tail_select` for a step of s = x_new.shape[1] new rows per sequence (1 ..
-    8).  x_new and y2 (N, s, C/8, 64, 8), y1_scratch (N, s, 2, C/8, 64, 8) dense; rings of at least 2 * dilation + s slots.
-    No crow: the caller runs the row scan (`csr_from_selection`).  Returns (probs (N,H,s,T_m) or None, (bits, row_nnz,
-    head_off))."""
-    lib = _lib.load()
-    _lib.require_gpu(x_new, x_ring, y1_ring, y2, y1_scratch, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket)
+    _lib.require_gpu(x_new, x_ring, y1_ring, y2, y1_scratch, conv_w, conv_b, ln_w, ln_b, keep, counters, ticket, crow_out, col_out)
     N, s, C8, W4, _e = x_new.shape
     C, H, dt, dev = C8 * 8, conv_w.shape[0], x_new.dtype, x_new.device
     assert _e == 8 and x_new.is_contiguous() and x_ring.is_contiguous() and y1_ring.is_contiguous()
-    assert y2.is_contiguous() and tuple(y2.shape) == tuple(x_new.shape)
-    assert y1_scratch.is_contiguous() and tuple(y1_scratch.shape) == (N, s, 2, C8, W4, 8)
+    assert y2.is_contiguous() and y2.numel() == x_new.numel()
     assert x_ring.shape[0] == N and tuple(x_ring.shape[2:]) == (C8, W4, 8) and tuple(y1_ring.shape[2:]) == (C8, W4, 8)
     assert decode_cnn_supported(C, H, T_m, dt) and W4 * 4 == T_m
     for cv in (conv1, conv2):
@@ -898,6 +832,10 @@ def decode_cnn_tail_select_rows(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ri
     stride = _lib.counter_stride(counters, N)
     assert (counters.numel() == 3 or stride > 0) and counters.shape[-1] == 3 and counters.is_contiguous()
     assert ticket.dtype == torch.int32 and ticket.numel() == 1 and keep.dtype == torch.int32 and keep.ndim == 1
+    if y1_scratch is None:
+        assert s == 1 and crow_out.dtype == torch.int32 and tuple(crow_out.shape) == (N, 2)
+    else:
+        assert y1_scratch.is_contiguous() and tuple(y1_scratch.shape) == (N, s, 2, C8, W4, 8) and crow_out is None and col_out is None
     packs = []
     for cv in (conv1, conv2):
         packs.append(_cached("conv", (cv.weight, cv.bias), dt,
@@ -911,11 +849,13 @@ def decode_cnn_tail_select_rows(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ri
     bits = torch.empty((N, s, Wb), dtype=torch.int32, device=dev)
     row_nnz = torch.empty((N, s), dtype=torch.int32, device=dev)
     head_off = torch.empty((N, s, H + 1), dtype=torch.int32, device=dev)
-    _lib.check(lib.sea_decode_cnn_tail_select_rows(
+    _lib.check(lib.sea_decode_cnn_tail_select(
         _p(x_new), _p(x_ring), _p(y1_ring), _p(y2), _p(y1_scratch), _lib.dtype_code(dt), N, s, C, H, W4, x_ring.shape[1],
         y1_ring.shape[1], _p(w1p), _p(b1), _p(w2p), _p(b2), CinP, int(conv1.dilation), int(conv1.padding[1]), _p(cb), _p(w16), Cp,
         _p(g), _p(b), float(eps), _p(probs), _p(keep), _p(counters), _p(ticket), int(is_causal), int(k), _p(bits), _p(row_nnz),
-        _p(head_off), _p(tab), stride, _lib.stream_ptr()), "sea_decode_cnn_tail_select_rows")
+        _p(head_off), _p(crow_out), _p(col_out), col_out.stride(0) if col_out is not None else 0,
+        col_out.shape[1] if col_out is not None else 0, int(T_cap) if y1_scratch is None else 0, _p(tab), stride,
+        _lib.stream_ptr()), "sea_decode_cnn_tail_select")
     return probs, (bits, row_nnz, head_off)
 
 

@@ -25,15 +25,16 @@ def test_header_symbols_are_bound():
     assert sorted(_lib.EXPORTED_SYMBOLS) == decl
 
 
-def test_library_builds_and_exports_everything_at_abi_5():
-    """ABI 5: one entry point per operator, the decode step's included (include/sea_hip.h lists what changed from 4)."""
+def test_library_builds_and_exports_everything_at_abi_6():
+    """ABI 6: one entry point per operator, the decode step's included (include/sea_hip.h lists what changed from 4 and 5)."""
     path = _build.build_library()
     assert os.path.exists(path)
     lib = ctypes.CDLL(path)
     for name in _declared_symbols():
         assert hasattr(lib, name), f"{name} not exported"
     lib.sea_version.restype = ctypes.c_int
-    assert lib.sea_version() == 5 == _lib.ABI_VERSION
+    assert len(_declared_symbols()) == 38
+    assert lib.sea_version() == 6 == _lib.ABI_VERSION
     # host-only helper: algorithmic bytes, SURVEY 8d (cfg 3, bf16, Z = 8.32 M -> 2.20 GB)
     lib.sea_sparse_attention_bytes.restype = ctypes.c_int64
     lib.sea_sparse_attention_bytes.argtypes = [ctypes.c_int64] * 5 + [ctypes.c_int]
@@ -49,6 +50,10 @@ def test_bad_arguments_return_error_codes_not_crashes():
     assert b"null pointer" in lib.sea_last_error()
     rc = lib.sea_topk_select(None, 0, 1, 1, 1, 4, 0, 0, 0, None, 0, 1, 1, 1, None, None, None, None, None)
     assert rc == -1
+    # sea_cumavg: slices without their workspace (fake aligned addresses, never dereferenced: the entry refuses first)
+    v, out, st = ctypes.c_void_p(1 << 20), ctypes.c_void_p(1 << 21), (ctypes.c_int64 * 3)(2 * 64 * 64, 64 * 64, 64)
+    rc = lib.sea_cumavg(v, _lib.SEA_BF16, 1, 2, 64, 64, st, out, 4, None, 0, None)
+    assert rc == -1 and b"sea_cumavg: workspace of" in lib.sea_last_error()
 
 
 def test_ops_refuse_cpu_tensors():

@@ -660,7 +660,7 @@ def test_performer_step_continues_the_sequence(ops, dtype, N, H, T, D):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("N,H,T,D", [(1, 4, 5000, 80), (1, 2, 4096, 128), (2, 2, 2500, 64)])
 def test_cumavg_sliced(ops, dtype, N, H, T, D):
-    """`sea_cumavg_sliced`: the rows cut into slices with carried column totals (two launches) -- the averages of the
+    """`sea_cumavg` with n_slices > 1: the rows cut into slices with carried column totals (two launches) -- the averages of the
     one-launch kernel up to fp32 summation order; the default picks slices by itself when N*H is small."""
     g = torch.Generator().manual_seed(4)
     v = torch.randn((N, H, T, D), generator=g).to(dtype).to(DEV)
@@ -675,8 +675,8 @@ def test_cumavg_sliced(ops, dtype, N, H, T, D):
     with pytest.raises(RuntimeError, match="workspace"):
         from sea_attention_amd import _lib
         out = torch.empty_like(v)
-        _lib.check(_lib.load().sea_cumavg_sliced(v.data_ptr(), _lib.dtype_code(dtype), N, H, T, D, _lib.strides3(v), out.data_ptr(),
-                                                 4, None, 0, None), "sea_cumavg_sliced")
+        _lib.check(_lib.load().sea_cumavg(v.data_ptr(), _lib.dtype_code(dtype), N, H, T, D, _lib.strides3(v), out.data_ptr(),
+                                          4, None, 0, None), "sea_cumavg")
 
 
 @pytest.mark.gpu
