@@ -43,12 +43,17 @@ sessions of N = 1.
 to the session's buffers only.
 
 Paged K / V (`from_sequences(..., page_rows=...)`): one pool of fixed-size pages, (2, P, H, page_rows, D), shared by all
-slots, and a device block table (N, ceil(capacity / page_rows)) int32 naming each sequence's pages in order.  A `PageAllocator`
-on the host hands pages out: seeding or `admit` gives a slot the pages of its prefix plus the next row, `step` a new page to
+slots, and a device block table (N, ceil(capacity / page_rows)) int32 naming each sequence's pages in order.  Pages are
+handed out on the host: seeding or `admit` gives a slot the pages of its prefix plus the next row, `step` a new page to
 every slot whose next row starts one (written into the device table in stream order, no host synchronise).  The three
 launches that touch K / V take the block table as an argument; keys and column ids stay logical (head * capacity + key), so
 every result is bitwise the contiguous ragged session's.  page_rows is a power of two and a multiple of the Performer chunk: the
 rows a chunk-aligned step walks again lie in one page.
+Who owns what: `PageAllocator` is the pool's free list and holder counts; `SlotPages` (host only, no torch) owns the slots'
+page lists and every decision about them -- what seeding, `admit`, `step`, `extend`, `release`, `fork` and `reorder` take,
+share and give back, and each refusal, made before anything changes (tests/test_decode_slot_pages.py runs it without a
+GPU).  `DecodeSession` owns the device: it applies what `SlotPages` returns to the block table and the pool, and keeps
+`lengths`, the paused / empty flags and the counter rows.  `session.pages` and `session.allocator` are `SlotPages`' own.
 
 Fork and beam reorder (`fork`, `reorder`; paged ragged sessions, between steps): during a step only the stage writes K / V, row
 `seen` of each slot, in the slot's last ("open") page; every page below it is immutable while the sequence lives.  So a slot
@@ -106,7 +111,7 @@ import torch
 
 from .. import _lib
 from . import ops
-from .attention_state import PerlinAttentionState, cnn_lookback
+from .attention_state import CnnWindowState, CumAvgState, PerformerState, PerlinAttentionState, cnn_lookback
 
 
 def _cnn_convs(at):
@@ -181,6 +186,103 @@ class PageAllocator:
                 self._free.appendleft(pg)
 
 
+class SlotPages:
+    """Which pages of the pool each slot of a paged session names, and every decision about them: host only, plain lists,
+    no torch.  `pages[n]` is slot n's pages in order (the host mirror of row n of the device block table, `n_tab` entries
+    wide); `DecodeSession` applies what these methods return to the device.  A refusal (RuntimeError) has changed nothing."""
+
+    def __init__(self, slots: int, capacity: int, page_rows: int, pool_pages: Optional[int] = None):
+        self.page_rows, self.capacity = int(page_rows), int(capacity)
+        self.n_tab = self.count(self.capacity)
+        self.allocator = PageAllocator(slots * self.n_tab if pool_pages is None else pool_pages)
+        self.pages = [[] for _ in range(slots)]
+
+    def count(self, rows: int) -> int:
+        """Pages that hold `rows` rows."""
+        return -(-rows // self.page_rows)
+
+    @property
+    def free_pages(self) -> int:
+        return self.allocator.free_pages
+
+    def shared(self) -> List[int]:
+        """The pages more than one slot holds, ascending."""
+        return sorted({pg for row in self.pages for pg in row if self.allocator.holders(pg) > 1})
+
+    def reclaimable(self, n: int) -> int:
+        """Pages slot n gives back to the free list when it lets go of them: those it is the last holder of."""
+        return sum(1 for pg in self.pages[n] if self.allocator.holders(pg) == 1)
+
+    def open_page(self, n: int, L: int) -> int:
+        """The page row L of slot n lies in (the slot's next row, when it stands at L), or -1: that row starts a new page."""
+        o = L // self.page_rows
+        return self.pages[n][o] if o < len(self.pages[n]) else -1
+
+    def reseat(self, n: int, L: int) -> List[int]:
+        """Slot n starts over on a prefix of L rows: its pages go back first, then it takes count(L + 1) -- the prefix and
+        the row of the next step -- and returns them."""
+        count, free, own = self.count(L + 1), self.free_pages, self.reclaimable(n)
+        if count > free + own:
+            raise RuntimeError(f"page pool exhausted: slot {n} needs {count} pages for a prefix of {L} rows, {free} free + {own} of its own")
+        self.allocator.give_back(self.pages[n])
+        self.pages[n] = self.allocator.take(count)
+        return self.pages[n]
+
+    def grow(self, lengths, sitting):
+        """Before a step: a page for every slot that takes part and whose next row starts one.  Returns the new table
+        entries [(slot, table index, page)]; RuntimeError naming the slots when the pool has too few."""
+        want = [n for n, L in enumerate(lengths) if not sitting[n] and L >= len(self.pages[n]) * self.page_rows]
+        if len(want) > self.free_pages:
+            raise RuntimeError(f"page pool exhausted: slot(s) {want} need a new page, {self.free_pages} free")
+        new = [(n, len(self.pages[n]), pg) for n, pg in zip(want, self.allocator.take(len(want)))]
+        for n, _, pg in new:
+            self.pages[n].append(pg)
+        return new
+
+    def extend_take(self, n: int, L: int, s: int) -> List[int]:
+        """The pages slot n lacks for s more rows behind its L, up to the row of the next step and within the table.  They
+        are taken but not yet slot n's: the session appends them to `pages[n]` once the rows are written, or `cancel`s them."""
+        pg = self.open_page(n, L)
+        if self.allocator.holders(pg) > 1:
+            raise RuntimeError(f"extend: slot {n}'s open page {pg} has other holders; only closed pages are shared (fork gives "
+                               "every copy an open page of its own)")
+        want = self.count(min(L + s + 1, self.capacity)) - len(self.pages[n])
+        if want > self.free_pages:
+            raise RuntimeError(f"page pool exhausted: slot {n} needs {want} new page(s) for {s} more rows, {self.free_pages} free")
+        return self.allocator.take(max(want, 0))
+
+    def cancel(self, fresh) -> None:
+        """Pages taken by `extend_take` / `move_plan` go back: the launch they were for did not happen."""
+        self.allocator.give_back(list(fresh))
+
+    def release(self, n: int) -> None:
+        self.allocator.give_back(self.pages[n])
+        self.pages[n] = []
+
+    def move_plan(self, moves, lengths):
+        """fork / reorder, before the launch.  moves: [(src, dst)], dst := src as it is now: the source's pages below its
+        open page, shared, and a copy of the open page when there is one.  Returns dst -> (the source's open page, the fresh
+        page of its copy) for those; every fresh page is taken here, before any old page goes back, so that no page the move
+        frees is the target of a copy."""
+        copies = [(dst, self.open_page(src, lengths[src])) for src, dst in moves]
+        copies = [(dst, pg) for dst, pg in copies if pg >= 0]
+        if len(copies) > self.free_pages:
+            raise RuntimeError(f"page pool exhausted: slot(s) {[dst for dst, _ in copies]} need a copy of their source's open page, "
+                               f"{self.free_pages} free")
+        return {dst: (pg, new) for (dst, pg), new in zip(copies, self.allocator.take(len(copies)))}
+
+    def move_commit(self, moves, lengths, new_open) -> None:
+        """After the launch (`lengths` as `move_plan` saw them): the destinations' rows from a snapshot (swaps, cycles,
+        many-to-one); shares before give-backs (a source's closed pages may be held by a moved slot only)."""
+        old = [list(p) for p in self.pages]
+        for src, dst in moves:
+            closed = old[src][:lengths[src] // self.page_rows]
+            self.allocator.share(closed)
+            self.pages[dst] = closed + ([new_open[dst][1]] if dst in new_open else [])
+        for _, dst in moves:
+            self.allocator.give_back(old[dst])
+
+
 class DecodeSession:
     """Built from the state of a cached forward (`PerlinAttentionOutput.state`, HIP estimator: 16-bit inference) and the
     K / V prefix that forward saw.  `step(q, k, v)` takes the NEW row of each tensor, (N, H, 1, D), and returns the
@@ -197,6 +299,7 @@ class DecodeSession:
     _paused = None               # (ragged sessions: host mirrors of the slots that sit out steps / hold no sequence)
     _empty = None
     _extend_kv = None            # (paged sessions: `extend`'s contiguous K / V scratch (2, H, capacity, D), allocated on first use)
+    csr = None                   # (the CSR row of the last step; none while `from_sequences` seeds its slots)
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
                  capacity: int, use_graph: bool = True, fused_attention: bool = True):
@@ -235,9 +338,8 @@ class DecodeSession:
             pos = torch.arange(L - LB, L, device=dev)
             self.x_ring = torch.zeros((N, LB) + row_shape, dtype=dt, device=dev)
             self.x_ring[:, pos % LB] = cs.rows_c8                            # window row i is position L - LB + i
-            y1 = ops.causal_conv_c8(cs.rows_c8.contiguous(), convs[0].weight, convs[0].bias, 3, dil, dil, relu=True)
             self.y1_ring = torch.zeros((N, RY) + row_shape, dtype=dt, device=dev)
-            keep_rows = min(RY - 1, LB - 2 * dil)                            # rows whose taps lie inside the window: conv1's true values
+            y1, keep_rows = self._conv1_seed(cs.rows_c8)
             p1 = torch.arange(L - keep_rows, L, device=dev)
             self.y1_ring[:, p1 % RY] = y1[:, LB - keep_rows:]
             self.x_new = torch.zeros((N, 1) + row_shape, dtype=dt, device=dev)   # where the MLP writes the new row
@@ -339,7 +441,6 @@ class DecodeSession:
             self.max_step_rows = int(max_step_rows)
         lengths = [0 if sq is None else self._check_sequence(*sq) for sq in seqs]       # (None: the slot starts empty)
         N, H, D, dt, dev = self.N, self.H, self.D, self.dtype, kp0.device
-        n_tab = None
         if page_rows is not None:
             page_rows = int(page_rows)
             nb = at.performer.projection_matrix.shape[0]
@@ -351,9 +452,9 @@ class DecodeSession:
                 raise ValueError(f"paged K / V needs the one-row decode attention form (16-bit d = 64 / 80 / 128; got d = {D})")
             if page_rows < 1 or page_rows & (page_rows - 1) or page_rows % chunk:
                 raise ValueError(f"page_rows {page_rows}: a power of two and a multiple of the Performer chunk ({chunk} rows)")
-            n_tab = -(-self.capacity // page_rows)
-            need = sum(-(-(L + 1) // page_rows) for L, sq in zip(lengths, seqs) if sq is not None)
-            pool_pages = N * n_tab if pool_pages is None else int(pool_pages)
+            sp = SlotPages(N, self.capacity, page_rows, pool_pages)
+            need = sum(sp.count(L + 1) for L, sq in zip(lengths, seqs) if sq is not None)
+            pool_pages = sp.free_pages                                       # (nothing is out yet)
             if pool_pages < need:
                 raise ValueError(f"a pool of {pool_pages} pages of {page_rows} rows cannot hold the prefixes ({need} pages)")
         elif pool_pages is not None:
@@ -382,13 +483,12 @@ class DecodeSession:
             self._graphs = {}                                                # s -> (graph, csr, pending emit, probs, ctx)
         self.ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.xs = None
-        if n_tab is not None:
+        if page_rows is not None:
             # the pool (2, P, H, page_rows, D): K pages and V pages share one page index; kv_cache names the pool (what the
             # stage writes and the capture saves), k_cache / v_cache its two halves (P, H, page_rows, D)
-            self.paged, self.page_rows = True, page_rows
-            self.allocator = PageAllocator(pool_pages)
-            self.pages = [[] for _ in range(N)]                             # host mirror of the table: slot n's pages in order
-            self.block_table = torch.full((N, n_tab), -1, dtype=torch.int32, device=dev)
+            self.paged, self.page_rows, self.slot_pages = True, page_rows, sp
+            self.allocator, self.pages = sp.allocator, sp.pages            # (host mirror of the table: slot n's pages in order)
+            self.block_table = torch.full((N, sp.n_tab), -1, dtype=torch.int32, device=dev)
             self.kv_cache = torch.zeros((2, pool_pages, H, page_rows, D), dtype=dt, device=dev)
         else:
             self.kv_cache = torch.zeros((2, N, H, self.capacity, D), dtype=dt, device=dev)
@@ -443,22 +543,20 @@ class DecodeSession:
     def _seed_slot(self, n, state, key_prefix, value_prefix):
         """Slot n of a ragged session := the sequence (state, prefixes): its Performer image, rings (slot = position % ring,
         seeded as a uniform session seeds them), cache rows and counters."""
-        L, LB, at = int(key_prefix.shape[2]), self.LB, self.attention
+        L, LB, RY = int(key_prefix.shape[2]), self.LB, self.y1_ring.shape[1]
         ps = state.states[PerlinAttentionState.PERFORMER]
         rows = state.states[PerlinAttentionState.CNN].rows_c8
-        conv1 = _cnn_convs(at)[0]
-        dil, RY = conv1.dilation, self.y1_ring.shape[1]
+        if self.paged:                                # first: a pool that cannot hold the prefix refuses with nothing changed
+            self._seed_pages(n, key_prefix, value_prefix)
+        self._flush_columns()
         self.image.view(self.N, -1)[n].copy_(ps.image.view(-1))
         pos = torch.arange(L - LB, L, device=rows.device)
         self.x_ring[n, pos % self.x_ring.shape[1]] = rows[0]
-        y1 = ops.causal_conv_c8(rows.contiguous(), conv1.weight, conv1.bias, 3, dil, dil, relu=True)
-        keep_rows = min(RY - 1, LB - 2 * dil)
+        y1, keep_rows = self._conv1_seed(rows)
         p1 = torch.arange(L - keep_rows, L, device=rows.device)
         self.y1_ring[n].zero_()
         self.y1_ring[n, p1 % RY] = y1[0, LB - keep_rows:]
-        if self.paged:
-            self._seed_pages(n, key_prefix, value_prefix)
-        else:
+        if not self.paged:
             self.kv_cache[:, n].zero_()
             self.k_cache[n, :, :L] = key_prefix[0]
             self.v_cache[n, :, :L] = value_prefix[0]
@@ -469,14 +567,8 @@ class DecodeSession:
         """Slot n of a paged session := the prefix: its old pages go back first, then ceil((L + 1) / page_rows) pages (the
         prefix and the row of the next step) take the prefix rows, zero behind them, and the device table row names them."""
         L, H, D, pr = int(key_prefix.shape[2]), self.H, self.D, self.page_rows
-        count = -(-(L + 1) // pr)
-        own = self._reclaimable(n)
-        if count > self.allocator.free_pages + own:
-            raise RuntimeError(f"page pool exhausted: slot {n} needs {count} pages, {self.allocator.free_pages} free "
-                               f"+ {own} of its own")
-        self.allocator.give_back(self.pages[n])
-        self.pages[n] = pages = self.allocator.take(count)
-        dev = self.kv_cache.device
+        pages = self.slot_pages.reseat(n, L)
+        count, dev = len(pages), self.kv_cache.device
         rows = torch.zeros((2, H, count * pr, D), dtype=self.dtype, device=dev)
         rows[0, :, :L] = key_prefix[0]
         rows[1, :, :L] = value_prefix[0]
@@ -485,31 +577,24 @@ class DecodeSession:
         self.block_table[n].fill_(-1)
         self.block_table[n, :count] = idx.to(torch.int32)
 
-    def _reclaimable(self, n) -> int:
-        """Pages slot n gives back to the free list when it lets go of them: those it is the last holder of."""
-        return sum(1 for pg in self.pages[n] if self.allocator.holders(pg) == 1)
-
     @property
     def free_pages(self) -> Optional[int]:
         """Pages of the pool no slot holds (a paged session; None otherwise): what a scheduler may still admit or grow into.
         free_pages + the distinct pages the slots hold = the pool (a shared page counts once)."""
-        return self.allocator.free_pages if self.paged else None
+        return self.slot_pages.free_pages if self.paged else None
 
     @property
     def shared_pages(self) -> Optional[List[int]]:
         """The pages more than one slot holds (after `fork` / `reorder`: closed pages, never written again while they are
         shared), ascending; None when the session is not paged."""
-        if not self.paged:
-            return None
-        return sorted({pg for row in self.pages for pg in row if self.allocator.holders(pg) > 1})
+        return self.slot_pages.shared() if self.paged else None
 
     def sequence_kv(self, slot: int):
         """Sequence `slot`'s logical K and V rows, (1, H, L, D) each (copies; a paged session gathers them from its pages):
         what a cached forward continues from, with `export_state(slot)`."""
         if not self.ragged:
             raise ValueError("sequence_kv: a ragged session (DecodeSession.from_sequences)")
-        if not 0 <= slot < self.N:
-            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        self._check_slot(slot)
         if self._empty[slot]:
             raise ValueError(f"sequence_kv: slot {slot} is empty (released, or never admitted)")
         L = self.lengths[slot]
@@ -520,19 +605,6 @@ class DecodeSession:
             kv = self.kv_cache[:, slot, :, :L]
         return kv[0:1].clone(), kv[1:2].clone()
 
-    def _grow_pages(self):
-        """Before a step's first launch: a page for every slot that takes part and whose next row starts one.  Refused (RuntimeError naming the
-        slots, nothing changed) when the pool has too few; the table entries are written in stream order behind the host's
-        decision (small fills, no synchronise)."""
-        want = [n for n, L in enumerate(self.lengths) if not self._paused[n] and L >= len(self.pages[n]) * self.page_rows]
-        if not want:
-            return
-        if len(want) > self.allocator.free_pages:
-            raise RuntimeError(f"page pool exhausted: slot(s) {want} need a new page, {self.allocator.free_pages} free")
-        for n, pg in zip(want, self.allocator.take(len(want))):
-            self.block_table[n, len(self.pages[n])].fill_(pg)
-            self.pages[n].append(pg)
-
     @torch.no_grad()
     def admit(self, slot: int, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor):
         """Continuous batching: slot `slot` of a ragged session starts over on a new sequence (an N = 1 cached forward's
@@ -542,15 +614,9 @@ class DecodeSession:
         the slot as it was."""
         if not self.ragged:
             raise ValueError("admit: only a ragged session (DecodeSession.from_sequences) takes new sequences")
-        if not 0 <= slot < self.N:
-            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
-        L = self._check_sequence(state, key_prefix, value_prefix)
-        if self.paged and -(-(L + 1) // self.page_rows) > self.allocator.free_pages + self._reclaimable(slot):
-            raise RuntimeError(f"page pool exhausted: slot {slot} needs {-(-(L + 1) // self.page_rows)} pages for a prefix of {L} "
-                               f"rows, {self.allocator.free_pages} free + {self._reclaimable(slot)} of its own")
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
-        self._seed_slot(slot, state, key_prefix, value_prefix)
+        self._check_slot(slot)
+        self._check_sequence(state, key_prefix, value_prefix)
+        self._seed_slot(slot, state, key_prefix, value_prefix)    # (a paged session: the refusal comes first, see there)
         self._paused[slot] = self._empty[slot] = False                       # (a paused or empty slot: active on the new sequence)
         self._last_step = None                        # (an admit ends the chance to rewind)
 
@@ -563,7 +629,7 @@ class DecodeSession:
         move.  Afterwards the slot stands at L + s with its Performer image, rings, K / V rows and counter row as `admit`
         leaves a prefix of L + s rows; an active slot stays active, a paused one paused (the parked prompt: `fork` the paused
         prompt, `extend` each copy by its request's own rows, `resume` them).  Every other slot keeps every bit.
-        A paged session writes rows >= L only: the slot's table entries below its open index L // page_rows -- the closed pages
+        A paged session writes rows >= L only: the slot's table entries below its open page (the one row L lies in) -- the closed pages
         it may share with other slots -- are not touched; it takes the pages it lacks up to ceil((L + s + 1) / page_rows) (the
         prefix and the next step's row, as seeding does; no page beyond the table for a slot filled to capacity) before
         anything is launched, and its rows travel through a contiguous scratch of the session ((2, H, capacity, D), allocated at
@@ -574,11 +640,10 @@ class DecodeSession:
         if not self.ragged:
             raise ValueError("extend: only a ragged session (DecodeSession.from_sequences) extends one slot")
         slot = int(slot)
-        if not 0 <= slot < self.N:
-            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        self._check_slot(slot)
         if self._empty[slot]:
             raise ValueError(f"extend: slot {slot} is empty (released, or never admitted): admit or fork into it")
-        H, D, L, pr = self.H, self.D, self.lengths[slot], self.page_rows
+        H, D, L = self.H, self.D, self.lengths[slot]
         if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)) or k.shape != q.shape or v.shape != q.shape \
                 or (q.shape[0], q.shape[1], q.shape[3]) != (1, H, D) or q.shape[2] < 1:
             raise ValueError(f"extend: q, k, v are (1, H, s, D) = (1, {H}, s, {D}) each with s >= 1 "
@@ -589,21 +654,10 @@ class DecodeSession:
         T = L + s
         if T > self.capacity:
             raise ValueError(f"extend: slot {slot} stands at {L} rows, {s} more pass the capacity of {self.capacity}")
-        fresh = []
-        if self.paged:
-            o = L // pr
-            if o < len(self.pages[slot]) and self.allocator.holders(self.pages[slot][o]) > 1:
-                raise RuntimeError(f"extend: slot {slot}'s open page {self.pages[slot][o]} has other holders; only closed pages "
-                                   "are shared (fork gives every copy an open page of its own)")
-            want = -(-min(T + 1, self.capacity) // pr) - len(self.pages[slot])
-            if want > self.allocator.free_pages:
-                raise RuntimeError(f"page pool exhausted: slot {slot} needs {want} new page(s) for {s} more rows, "
-                                   f"{self.allocator.free_pages} free")
-            fresh = self.allocator.take(max(want, 0))
+        fresh = self.slot_pages.extend_take(slot, L, s) if self.paged else []
         at, dev = self.attention, self.kv_cache.device
         try:
-            if self.csr is not None and self.csr.col_is_pending:
-                self.csr.col                          # the last step's pending columns follow the counters: emit before they move
+            self._flush_columns()
             # contiguous K / V rows 0 .. T-1 for the forward: a paged slot's rows are gathered into the scratch, a contiguous
             # session's are its cache (the new rows are staged where they belong; rows >= L are read by nobody before)
             if self.paged:
@@ -618,14 +672,8 @@ class DecodeSession:
             k_all, v_all = kv[0:1, :, :T], kv[1:2, :, :T]
             # the session's own image and window, as `export_state(slot)` hands them out (the image as a view: the Performer
             # step reads it and returns a new one)
-            from .attention_state import PerformerState, CnnWindowState, CumAvgState
             pos = torch.arange(L - self.LB, L, device=dev)
-            st = PerlinAttentionState(at)
-            ps, cs, cav = PerformerState(), CnnWindowState(self.LB), CumAvgState()
-            ps.image, ps.seq_index = self.image.view(self.N, -1)[slot], L
-            cs.rows_c8 = self.x_ring[slot:slot + 1, pos % self.x_ring.shape[1]]
-            cav.prev_len, cav.in_image = L, True
-            st.states = {PerlinAttentionState.PERFORMER: ps, PerlinAttentionState.CNN: cs, PerlinAttentionState.CUMAVG: cav}
+            st = self._state(self.image.view(self.N, -1)[slot], self.x_ring[slot:slot + 1, pos % self.x_ring.shape[1]], L)
             fp_min = torch.finfo(torch.float16).min / 2
             mask = torch.triu(torch.full((s, T), fp_min, dtype=self.dtype, device=dev), diagonal=L + 1).view(1, 1, s, T)
             out = at(q, k_all, v_all, q, k_all, v_all, q, k_all, mask, None, None, st)
@@ -635,10 +683,7 @@ class DecodeSession:
                     or new_cs.rows_c8.shape[1] != self.LB:
                 raise ValueError("extend: the cached forward did not continue the session's state on the HIP estimator")
             window = new_cs.rows_c8.contiguous()
-            conv1 = _cnn_convs(at)[0]
-            dil, RY = conv1.dilation, self.y1_ring.shape[1]
-            y1 = ops.causal_conv_c8(window, conv1.weight, conv1.bias, 3, dil, dil, relu=True)
-            keep_rows = min(RY - 1, self.LB - 2 * dil)               # (the rows `_seed_slot` keeps: conv1's true values)
+            y1, keep_rows = self._conv1_seed(window)                 # (the rows `_seed_slot` keeps: conv1's true values)
             if fresh:                                 # the new table entries: one small stream-ordered copy, no synchronise
                 n0 = len(self.pages[slot])
                 self.block_table[slot, n0:n0 + len(fresh)].copy_(torch.tensor(fresh, dtype=torch.int32).pin_memory(), non_blocking=True)
@@ -652,7 +697,7 @@ class DecodeSession:
             if fresh:                                 # (the host mirror `pages` has not moved: the slot is what it was)
                 n0 = len(self.pages[slot])
                 self.block_table[slot, n0:n0 + len(fresh)].fill_(-1)
-                self.allocator.give_back(fresh)
+                self.slot_pages.cancel(fresh)
             raise
         if fresh:
             self.pages[slot].extend(fresh)
@@ -714,6 +759,40 @@ class DecodeSession:
         """Which slots hold no sequence (released, or built from a None entry) until `admit`, `fork` or `reorder` fills them."""
         return list(self._empty) if self.ragged else [False] * self.N
 
+    def _check_slot(self, slot):
+        if not 0 <= slot < self.N:
+            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+
+    def _flush_columns(self):
+        """The last step's pending columns follow the counters: emit them before the counters move."""
+        if self.csr is not None and self.csr.col_is_pending:
+            self.csr.col
+
+    @staticmethod
+    def _rearm(csr, col_emit):
+        """After a replay: the handle of the capture is every replay's.  Its cached wire format is the first step's, and
+        columns that no replayed launch writes are pending again (the emit launcher reads this step's bits / crow / counter)."""
+        csr._wire = None
+        if col_emit is not None:
+            csr._pending = col_emit
+
+    def _conv1_seed(self, window):
+        """What seeds the y1 ring behind a window of LB rows: conv1 over the window, and how many of its last rows are conv1's
+        true values (all their taps lie inside the window)."""
+        conv1 = _cnn_convs(self.attention)[0]
+        dil = conv1.dilation
+        y1 = ops.causal_conv_c8(window.contiguous(), conv1.weight, conv1.bias, 3, dil, dil, relu=True)
+        return y1, min(self.y1_ring.shape[1] - 1, self.LB - 2 * dil)
+
+    def _state(self, image, window, length) -> PerlinAttentionState:
+        """The `PerlinAttentionState` a cached forward continues from: a Performer image and a CNN window at `length` rows."""
+        st = PerlinAttentionState(self.attention)
+        ps, cs, cav = PerformerState(), CnnWindowState(self.LB), CumAvgState()
+        ps.image, ps.seq_index, cs.rows_c8 = image, length, window
+        cav.prev_len, cav.in_image = length, True
+        st.states = {PerlinAttentionState.PERFORMER: ps, PerlinAttentionState.CNN: cs, PerlinAttentionState.CUMAVG: cav}
+        return st
+
     def _write_counters(self):
         """The device counter rows from the host mirrors, one small stream-ordered copy: [L, L + 1, L] for a slot that takes
         part (what a step leaves behind), the bitwise complement of each for one that sits out (the module docstring)."""
@@ -752,8 +831,7 @@ class DecodeSession:
         they are.  Between steps; no new capture.  Pausing a paused or empty slot changes nothing.  ValueError on a uniform
         session, IndexError for a slot out of range (nothing changed)."""
         slots = self._between_steps("pause", slots)
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        self._flush_columns()
         for n in slots:
             self._paused[n] = True
         self._flags_changed()
@@ -767,8 +845,7 @@ class DecodeSession:
         gone = [n for n in slots if self._empty[n]]
         if gone:
             raise ValueError(f"resume: slot(s) {gone} are empty (released, or never admitted): admit or fork into them")
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col
+        self._flush_columns()
         for n in slots:
             self._paused[n] = False
         self._flags_changed()
@@ -780,12 +857,10 @@ class DecodeSession:
         into the slot, fills it again; `resume`, `export_state`, `sequence_kv` and `fork` / `reorder` from it raise
         ValueError.  Releasing an empty slot changes nothing.  Errors as `pause`."""
         slots = self._between_steps("release", slots)
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col
+        self._flush_columns()
         for n in slots:
             if self.paged and self.pages[n]:
-                self.allocator.give_back(self.pages[n])
-                self.pages[n] = []
+                self.slot_pages.release(n)
                 self.block_table[n].fill_(-1)
             self._paused[n] = self._empty[n] = True
             self.lengths[n] = 0
@@ -801,53 +876,37 @@ class DecodeSession:
         moves = [(p, i) for i, p in enumerate(parents) if p != i]
         if not moves:
             return
-        pr, alloc = self.page_rows, self.allocator
-        # each destination: the source's pages below its open index (shared), then a copy of the open page when it has one
-        opens = {}
-        for src, _ in moves:
-            o = self.lengths[src] // pr
-            opens[src] = (o, self.pages[src][o] if o < len(self.pages[src]) else -1)
-        copies = [dst for src, dst in moves if opens[src][1] >= 0]
-        if len(copies) > alloc.free_pages:
-            raise RuntimeError(f"page pool exhausted: slot(s) {copies} need a copy of their source's open page, "
-                               f"{alloc.free_pages} free")
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
-        # all new open pages are taken before any old page goes back: no page freed here is the target of a copy
-        fresh = alloc.take(len(copies))
-        new_open = dict(zip(copies, fresh))
+        sp = self.slot_pages
+        new_open = sp.move_plan(moves, self.lengths)          # (refused here, or every copy's fresh open page is taken)
         dsts = {dst for _, dst in moves}
         rows, n_staged = [], 0
         for src, dst in moves:
             stage = -1
             if src in dsts:                           # (its state is overwritten by this call: read from a staged copy)
                 stage, n_staged = n_staged, n_staged + 1
-            rows.append((src, dst, opens[src][1], new_open.get(dst, -1), stage))
+            rows.append((src, dst, *new_open.get(dst, (-1, -1)), stage))      # (the source's open page, its copy's page)
         dev = self.kv_cache.device
         nb = self.attention.performer.projection_matrix.shape[0]
         staging = None
         if n_staged:
             per = ops.decode_fork_staging_bytes(self.image.numel() // self.N * 4, self.x_ring[0].numel() * self.x_ring.element_size(),
-                                                self.y1_ring[0].numel() * self.y1_ring.element_size(), -(-self.capacity // pr))
+                                                self.y1_ring[0].numel() * self.y1_ring.element_size(), sp.n_tab)
             staging = torch.empty((n_staged * per,), dtype=torch.uint8, device=dev)
         try:
+            self._flush_columns()
             moves_dev = torch.tensor(rows, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)   # (no host synchronise)
             ops.decode_fork(moves_dev, n_staged, self.image, self.x_ring, self.y1_ring,
                             self.ctr32, self.block_table, self.capacity, self.kv_cache, nb, staging)
         except Exception:
-            alloc.give_back(fresh)
+            sp.cancel(pg for _, pg in new_open.values())
             raise
-        # host mirrors: from the snapshot; shares before give-backs (a source's closed pages may be held by a moved slot only)
+        # host mirrors: from the snapshot
         # (whether a slot sits out belongs to its contents: the kernel copied the parent's counter row as it is, paused or not)
-        old_pages, old_lengths, old_paused = [list(p) for p in self.pages], list(self.lengths), list(self._paused)
+        sp.move_commit(moves, self.lengths, new_open)
+        old_lengths, old_paused = list(self.lengths), list(self._paused)
         for src, dst in moves:
-            o = opens[src][0]
-            alloc.share(old_pages[src][:o])
-            self.pages[dst] = old_pages[src][:o] + ([new_open[dst]] if dst in new_open else [])
             self.lengths[dst] = old_lengths[src]
             self._paused[dst], self._empty[dst] = old_paused[src], False
-        for _, dst in moves:
-            alloc.give_back(old_pages[dst])
 
     @property
     def win(self) -> torch.Tensor:
@@ -996,26 +1055,17 @@ class DecodeSession:
         """The session's state as the `PerlinAttentionState` a cached forward continues from (copies: the session keeps
         running on its own buffers).  `slot`: that sequence alone, as an N = 1 state (a ragged session exports one
         sequence at a time)."""
-        from .attention_state import PerformerState, CnnWindowState, CumAvgState
         if slot is None and self.ragged and self.N > 1:
             raise ValueError("a ragged session exports one sequence at a time: export_state(slot)")
-        if slot is not None and not 0 <= slot < self.N:
-            raise IndexError(f"slot {slot} outside 0..{self.N - 1}")
+        if slot is not None:
+            self._check_slot(slot)
         if self.ragged and self._empty[slot or 0]:
             raise ValueError(f"export_state: slot {slot or 0} is empty (released, or never admitted)")
         length = self.lengths[slot or 0] if self.ragged else self.length
         image, win = self.image, self.win
         if slot is not None:
             image, win = image.view(self.N, -1)[slot], win[slot:slot + 1]
-        st = PerlinAttentionState(self.attention)
-        ps = PerformerState()
-        ps.image, ps.seq_index = image.clone(), length
-        cs = CnnWindowState(self.LB)
-        cs.rows_c8 = win.clone()
-        cav = CumAvgState()
-        cav.prev_len, cav.in_image = length, True
-        st.states = {PerlinAttentionState.PERFORMER: ps, PerlinAttentionState.CNN: cs, PerlinAttentionState.CUMAVG: cav}
-        return st
+        return self._state(image.clone(), win.clone(), length)
 
     @torch.no_grad()
     def step(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -1032,8 +1082,9 @@ class DecodeSession:
             full = [n for n, L in enumerate(self.lengths) if L >= self.capacity and not self._paused[n]]
             if full:
                 raise RuntimeError(f"cache capacity {self.capacity} reached by slot(s) {full}")
-            if self.paged:
-                self._grow_pages()
+            if self.paged:                             # new pages (or RuntimeError, nothing changed): their table entries are
+                for n, i, pg in self.slot_pages.grow(self.lengths, self._paused):    # small fills in stream order, no synchronise
+                    self.block_table[n, i].fill_(pg)
         else:
             assert self.length < self.capacity, "cache capacity reached"
         if self.graph is not None and ops.prep_generation() != self._prep_generation:
@@ -1042,11 +1093,7 @@ class DecodeSession:
         self._stage(q, k, v)
         if self.graph is not None:
             self.graph.replay()
-            # the handle of the capture is every replay's: its cached wire format is the first step's, and columns that no
-            # replayed launch writes are pending again (the emit launcher reads this step's bits / crow / counter)
-            self.csr._wire = None
-            if self._col_emit is not None:
-                self.csr._pending = self._col_emit
+            self._rearm(self.csr, self._col_emit)
         else:
             self._launch()
         if self.ragged:
@@ -1084,9 +1131,7 @@ class DecodeSession:
         if self.use_graph:
             g, self.csr, self._col_emit, self.probs, _pins = self._graphs[s]
             g.replay()
-            self.csr._wire = None                                  # (as in `step`: the handle is every replay's)
-            if self._col_emit is not None:
-                self.csr._pending = self._col_emit
+            self._rearm(self.csr, self._col_emit)                  # (as in `step`: the handle is every replay's)
         else:
             self._launch_rows(s)
         self._last_step = (s, list(self.lengths), crossed)
@@ -1116,8 +1161,7 @@ class DecodeSession:
         sat_out = [n for n, d in enumerate(drop) if d and self._paused[n]]
         if sat_out:
             raise ValueError(f"rewind: slot(s) {sat_out} sat out the last step (paused or empty): nothing of it to drop")
-        if self.csr is not None and self.csr.col_is_pending:
-            self.csr.col                              # the last step's pending columns follow the counters: emit before they move
+        self._flush_columns()
         kept = [L if out else L + s - d for L, d, out in zip(before, drop, self._paused)]
         img, C = self.image.view(self.N, -1), self.chunk
         for n in crossed:
