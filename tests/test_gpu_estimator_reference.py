@@ -1,8 +1,8 @@
 """-m gpu: the fp32 forms of the estimator kernels held to a float64 evaluation of the same operation on the same inputs,
 at production sizes -- the predictor convolution's fp32 form (`causal_conv_c8f_kernel`) at OPT-1.3B x 8 and the fp32-MFMA
 Performer (`performer_kernel`) at T = 4096 ... 32768, with the plan's segment count and with one segment.  Until now these
-were pinned only to other forms of this build or checked against fp64 at T <= 1024.  (The 16-bit forms are not covered
-here.)
+were pinned only to other forms of this build or checked against fp64 at T <= 1024.  (The 16-bit forms -- convolution, 1x1
+epilogue, tail and MLP -- are held to fp64 the same way in `test_gpu_estimator_reference_16bit.py`.)
 
 Every bar is elementwise and follows from where the kernel rounds, not from observed errors: a value the kernel forms in
 fp32 (the fp32 MFMA is a k-ordered fma chain, one rounding per product) is within n * 2^-24 * sum|terms| of the exact sum,
