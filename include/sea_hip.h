@@ -199,6 +199,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  *                    may hold anything (their scores are replaced before use).  The gather kernels read kept keys only:
  *                    a kv-cache whose unused slots are uninitialised takes SEA_ATTN_GATHER (as DecodeSession does) or
  *                    zero-fills them;
+ *   SEA_ATTN_KEYRANGE  the key-range form, for K + V per head beyond an XCD's L2 (see below); range_keys in bits 16..30;
  *   bits 8..11: row tiles per wave for the tile kernel (1 or 2; 0 = default for the head size);
  *   bits 12..15: log2 of its key window (6..12; 0 = default 2048).
  *
@@ -227,6 +228,34 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * sea_attention_few_rows(): for a launch of at most that many rows (N * H * T_dst: a decoding step) sea_csr_emit + the
  * plain form is the faster pair -- with T_dst <= 8 that kernel's idle lane groups first touch every K / V row the step
  * will gather, so the rows' dependent walks find them in cache (same arithmetic, bit for bit).
+ *
+ * KEY-RANGE form, flags & 0xff == SEA_ATTN_KEYRANGE (a fused form: bits != NULL; sea_attn_keyrange.hip).  The gather kernels
+ * walk each query row's kept keys over the whole key axis, so every row block of a head drags the head's whole K and V through
+ * the L2 (8 MB at 32 768 bf16 d = 64 keys against 4 MB per XCD).  Here the key axis [0, T_src) is cut into
+ * n_ranges = ceil(T_src / range_keys) ranges (range_keys = bits 16..30 of flags, 1 .. 32767; n_ranges <= 64) and two ordinary
+ * launches on `stream` do the work, stream order being the only hand-off (no flag, no atomics, no workgroup waits for another;
+ * graph-capturable; the same bits from run to run):
+ *   1. per (n, h, t, range) the online-softmax state -- running maximum m, sum l, unnormalised accumulator acc[D] -- over the
+ *      kept pixels whose LOWEST key lies in the range (pixels are not split; a pixel's keys may run past the range's end).  Per
+ *      entry exactly the fused gather form: the same expansion arithmetic, score and online softmax with the same keys in flight.
+ *      Workgroups are numbered so that all row blocks of one ((n, h), range) are dispatched next to each other on that pair's XCD,
+ *      ranges ascending; a causal row block that lies entirely below a range reads no K or V row.  Only kept keys are read (the
+ *      gather kernels' contract).  A row's list of one range that exceeds its share of the kernel's LDS list (8192 entries per
+ *      workgroup, shared out evenly to its 64 / 32 rows) passes through it in pieces, the state staying in registers;
+ *   2. M = max_r m_r, L = sum_r l_r exp(m_r - M), A = sum_r acc_r exp(m_r - M) over the ranges in ascending order (a range that
+ *      held nothing for a row contributes exactly nothing), then the gather kernel's epilogue: A / L * row_scale (0 where L = 0),
+ *      the mix with avg, out_dtype, out_strides.
+ * With one range (range_keys >= T_src) the result is the fused gather form's bit for bit; with more it agrees to fp32 rounding
+ * (another summation order): per range one exp, one multiply and one add more per output element.
+ *   probs_out / probs_stride_n carry the WORKSPACE (the per-entry probabilities are not available in this form): probs_out the
+ *             16-byte aligned fp32 base, probs_stride_n the floats per batch item, >= H * n_ranges * T_dst * (D + 2) and, with
+ *             N > 1, a multiple of 4; NULL or too small: SEA_EINVAL (the message gives the floats needed).  Caller-owned,
+ *             contents undefined before and after;
+ *   col       neither read nor written (the columns stay pending: sea_csr_emit writes them for whoever reads them);
+ *   write_cols must be 0, block_path NULL (SEA_EINVAL), range_keys 0 is SEA_EINVAL.
+ * 16-bit data with D = 64 or 128, fp32 with D = 32 or 64; T_m % 32 == 0; is_causal 0 or 1; H * T_src < 2^24 as in the fused
+ * form.  bits == NULL, any other D (80 included), t_src_dev / block_table (no decode or paged form), write_cols != 0, more than
+ * 64 ranges: SEA_EUNSUPPORTED, before anything is launched.
  *
  * DECODE form of the fused launch, bits and t_src_dev != NULL (round 5; SURVEY 8f-3, src/main/opt_generate.py:131,
  * PA/attention.py:410-426): a position of a graph-replayed decoding session has static kernel arguments, so the sequence
@@ -261,7 +290,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * length the workgroup loads anyway, at its first use: q, crow and head_off of the sequence (valid memory; crow / head_off as
  * the selection launch wrote its empty rows) may have been read by then.
  */
-enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2 };
+enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2, SEA_ATTN_KEYRANGE = 3 };
 int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
                          int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,

@@ -85,7 +85,7 @@ def library_path():
     return _build.LIB_PATH
 
 
-SEA_ATTN_AUTO, SEA_ATTN_GATHER, SEA_ATTN_TILE = 0, 1, 2
+SEA_ATTN_AUTO, SEA_ATTN_GATHER, SEA_ATTN_TILE, SEA_ATTN_KEYRANGE = 0, 1, 2, 3
 SEA_OK, SEA_EINVAL, SEA_EUNSUPPORTED = 0, -1, -2
 
 

@@ -21,45 +21,6 @@
 
 namespace sea {
 
-template <int CTRL> __device__ inline float dpp_f(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-
-// sum over the LPR lanes of an aligned group; result in every lane of the group
-template <int LPR> __device__ inline float group_sum(float x) {
-  if (LPR >= 2) x += dpp_f<0xB1>(x);    // quad_perm [1,0,3,2]
-  if (LPR >= 4) x += dpp_f<0x4E>(x);    // quad_perm [2,3,0,1]
-  if (LPR >= 8) x += dpp_f<0x141>(x);   // row_half_mirror (values are quad-uniform here)
-  if (LPR >= 16) x += dpp_f<0x140>(x);  // row_mirror      (values are 8-uniform here)
-  if (LPR >= 32) x += __shfl_xor(x, 16);
-  if (LPR >= 64) x += __shfl_xor(x, 32);
-  return x;
-}
-
-// q . k over one 16-byte lane fragment.  16-bit inputs use the packed dot-product instructions
-// (v_dot2c_f32_bf16 / v_dot2_f32_f16: exact products, fp32 accumulation) on the raw registers -- no unpacking.
-typedef __attribute__((ext_vector_type(2))) __bf16 sea_bf2;
-typedef __attribute__((ext_vector_type(2))) _Float16 sea_h2;
-template <typename T> __device__ inline float frag_dot(const uint4& q, const uint4& k);
-template <> __device__ inline float frag_dot<float>(const uint4& q, const uint4& k) {
-  float d = __uint_as_float(q.x) * __uint_as_float(k.x);
-  d = fmaf(__uint_as_float(q.y), __uint_as_float(k.y), d);
-  d = fmaf(__uint_as_float(q.z), __uint_as_float(k.z), d);
-  return fmaf(__uint_as_float(q.w), __uint_as_float(k.w), d);
-}
-template <> __device__ inline float frag_dot<__hip_bfloat16>(const uint4& q, const uint4& k) {
-  float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.x), __builtin_bit_cast(sea_bf2, k.x), 0.f, false);
-  d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.y), __builtin_bit_cast(sea_bf2, k.y), d, false);
-  d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.z), __builtin_bit_cast(sea_bf2, k.z), d, false);
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.w), __builtin_bit_cast(sea_bf2, k.w), d, false);
-}
-template <> __device__ inline float frag_dot<__half>(const uint4& q, const uint4& k) {
-  float d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.x), __builtin_bit_cast(sea_h2, k.x), 0.f, false);
-  d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.y), __builtin_bit_cast(sea_h2, k.y), d, false);
-  d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.z), __builtin_bit_cast(sea_h2, k.z), d, false);
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.w), __builtin_bit_cast(sea_h2, k.w), d, false);
-}
-
 // WP: also write the per-entry values rs * softmax to p.probs (`partial_attention_probs`, attention.py:1162-1171).  Pass 1
 // leaves the raw score at the entry's slot, a second walk turns it into the probability once (m, l) are final; every slot
 // is re-read by the lane that wrote it (a thread sees its own stores), so no fence is needed.
@@ -1181,6 +1142,34 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
                                     const int32_t* t_src_dev, int64_t t_src_stride, const int32_t* block_table,
                                     int64_t table_stride, int64_t page_rows, sea_stream_t stream) {
   const char* nm = "sea_sparse_attention";
+  // SEA_ATTN_KEYRANGE: range_keys in bits 16..30 of flags, the workspace in probs_out / probs_stride_n (sea_hip.h)
+  const bool keyrange = (flags & 0xff) == SEA_ATTN_KEYRANGE;
+  KeyRangeParams kr = {nullptr, 0, 0, 0};
+  if (keyrange) {
+    SEA_REQUIRE(bits != nullptr, SEA_EUNSUPPORTED, "%s: the key-range form is a fused form (bits is NULL)", nm);
+    SEA_REQUIRE(t_src_dev == nullptr && block_table == nullptr && t_src_stride == 0, SEA_EUNSUPPORTED,
+                "%s: the key-range form has no decode or paged form (t_src_dev / block_table)", nm);
+    SEA_REQUIRE(write_cols == 0, SEA_EUNSUPPORTED, "%s: the key-range form writes no columns (write_cols must be 0)", nm);
+    SEA_REQUIRE(N > 0 && H > 0 && T_dst > 0 && T_src > 0 && D > 0, SEA_EINVAL, "%s: bad shape", nm);
+    SEA_REQUIRE(dtype == SEA_F32 ? (D == 32 || D == 64) : (D == 64 || D == 128), SEA_EUNSUPPORTED,
+                "%s: the key-range form takes 16-bit D in {64, 128} or fp32 D in {32, 64} (dtype %d, D=%lld)", nm, dtype, (long long)D);
+    const int64_t rk = (flags >> 16) & 0x7fff;
+    SEA_REQUIRE(rk > 0, SEA_EINVAL, "%s: the key-range form needs range_keys (1 .. 32767) in bits 16..30 of flags", nm);
+    const int64_t nr = (T_src + rk - 1) / rk;
+    SEA_REQUIRE(nr <= 64, SEA_EUNSUPPORTED, "%s: the key-range form takes at most 64 ranges (%lld keys in ranges of %lld: %lld)", nm,
+                (long long)T_src, (long long)rk, (long long)nr);
+    SEA_REQUIRE(block_path == nullptr, SEA_EINVAL, "%s: the key-range form takes no plan (block_path must be NULL)", nm);
+    const int64_t need = H * nr * T_dst * (D + 2);
+    SEA_REQUIRE(probs_out != nullptr && aligned16(probs_out) && probs_stride_n >= need, SEA_EINVAL,
+                "%s: the key-range form needs a 16-byte aligned fp32 workspace in probs_out with probs_stride_n >= %lld floats per "
+                "batch item (got %lld)", nm, (long long)need, (long long)probs_stride_n);
+    SEA_REQUIRE(N == 1 || probs_stride_n % 4 == 0, SEA_EINVAL,
+                "%s: the key-range form needs every batch item of its workspace 16-byte aligned: probs_stride_n %lld is no "
+                "multiple of 4", nm, (long long)probs_stride_n);
+    kr.ws = probs_out; kr.ws_stride_n = probs_stride_n; kr.range_keys = (int)rk; kr.n_ranges = (int)nr;
+    probs_out = nullptr;                                   // (the per-entry probabilities are not available in this form)
+    probs_stride_n = 0;
+  }
   if (t_src_stride || block_table) {
     SEA_REQUIRE(bits && t_src_dev && (!block_table || (k_strides && v_strides)), SEA_EINVAL, "%s: null pointer", nm);
     SEA_REQUIRE(t_src_stride > 0, SEA_EINVAL, "%s: t_src_stride must be >= 1 (got %lld)", nm, (long long)t_src_stride);
@@ -1205,7 +1194,7 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   // bits != NULL: the fused form -- `col` is written by the launch, not read -- which runs on the gather kernels;
   // t_src_dev != NULL: its decode form (T_src is then the capacity of the K / V caches)
   SEA_REQUIRE(bits != nullptr || t_src_dev == nullptr, SEA_EINVAL, "%s: the decode form (t_src_dev) needs bits", nm);
-  if (bits) flags = SEA_ATTN_GATHER;
+  if (bits && !keyrange) flags = SEA_ATTN_GATHER;
   SEA_REQUIRE(q && k && v && crow && col && head_off && out && q_strides && k_strides && v_strides && out_strides,
               SEA_EINVAL, "%s: null pointer", nm);
   if (int e = check_dtype(nm, dtype)) return e;
@@ -1214,7 +1203,7 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   SEA_REQUIRE(!avg || avg_strides, SEA_EINVAL, "%s: avg_strides is null", nm);
   SEA_REQUIRE(N > 0 && H > 0 && T_dst > 0 && T_src > 0 && D > 0, SEA_EINVAL, "%s: bad shape", nm);
   const int path = flags & 0xff;
-  SEA_REQUIRE(path == SEA_ATTN_AUTO || path == SEA_ATTN_GATHER || path == SEA_ATTN_TILE, SEA_EINVAL, "%s: bad path %d", nm, path);
+  SEA_REQUIRE(path == SEA_ATTN_AUTO || path == SEA_ATTN_GATHER || path == SEA_ATTN_TILE || path == SEA_ATTN_KEYRANGE, SEA_EINVAL, "%s: bad path %d", nm, path);
   const int vec = dtype == SEA_F32 ? 4 : 8;
   SEA_REQUIRE(D % vec == 0 && D <= 64 * vec, SEA_EUNSUPPORTED, "%s: D=%lld must be a multiple of %d and <= %d", nm,
               (long long)D, vec, 64 * vec);
@@ -1263,6 +1252,12 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   }
   p.TB = (int)((T_dst + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
+  if (keyrange) {                                          // two launches in stream order (sea_attn_keyrange.hip)
+    const int rc = launch_attn_keyrange(p, kr, dtype, out_dtype, s);
+    SEA_REQUIRE(rc == SEA_OK, rc, "%s: the key-range form needs K / V byte offsets below 2^31 and a grid below 2^31 workgroups", nm);
+    SEA_CHECK_LAUNCH(nm);
+    return SEA_OK;
+  }
   const bool tile_ok = attn_tile_supported(dtype, (int)D, (int)T_src, p) && probs_out == nullptr;
   if (path == SEA_ATTN_TILE) {
     SEA_REQUIRE(tile_ok, SEA_EUNSUPPORTED, "%s: the tile kernel takes 16-bit data with D in {64, 80, 128} and no probs_out", nm);

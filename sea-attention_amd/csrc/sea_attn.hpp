@@ -108,6 +108,46 @@ __device__ inline bool map_block(int NH, int TB, int* pair, int* tb) {
   return true;
 }
 
+// ---- the gather kernels' score: q . k over a lane group (sea_attn.hip, sea_attn_keyrange.hip) -----------------------------
+template <int CTRL> __device__ inline float dpp_f(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
+}
+
+// sum over the LPR lanes of an aligned group; result in every lane of the group
+template <int LPR> __device__ inline float group_sum(float x) {
+  if (LPR >= 2) x += dpp_f<0xB1>(x);    // quad_perm [1,0,3,2]
+  if (LPR >= 4) x += dpp_f<0x4E>(x);    // quad_perm [2,3,0,1]
+  if (LPR >= 8) x += dpp_f<0x141>(x);   // row_half_mirror (values are quad-uniform here)
+  if (LPR >= 16) x += dpp_f<0x140>(x);  // row_mirror      (values are 8-uniform here)
+  if (LPR >= 32) x += __shfl_xor(x, 16);
+  if (LPR >= 64) x += __shfl_xor(x, 32);
+  return x;
+}
+
+// q . k over one 16-byte lane fragment.  16-bit inputs use the packed dot-product instructions
+// (v_dot2c_f32_bf16 / v_dot2_f32_f16: exact products, fp32 accumulation) on the raw registers -- no unpacking.
+typedef __attribute__((ext_vector_type(2))) __bf16 sea_bf2;
+typedef __attribute__((ext_vector_type(2))) _Float16 sea_h2;
+template <typename T> __device__ inline float frag_dot(const uint4& q, const uint4& k);
+template <> __device__ inline float frag_dot<float>(const uint4& q, const uint4& k) {
+  float d = __uint_as_float(q.x) * __uint_as_float(k.x);
+  d = fmaf(__uint_as_float(q.y), __uint_as_float(k.y), d);
+  d = fmaf(__uint_as_float(q.z), __uint_as_float(k.z), d);
+  return fmaf(__uint_as_float(q.w), __uint_as_float(k.w), d);
+}
+template <> __device__ inline float frag_dot<__hip_bfloat16>(const uint4& q, const uint4& k) {
+  float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.x), __builtin_bit_cast(sea_bf2, k.x), 0.f, false);
+  d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.y), __builtin_bit_cast(sea_bf2, k.y), d, false);
+  d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.z), __builtin_bit_cast(sea_bf2, k.z), d, false);
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q.w), __builtin_bit_cast(sea_bf2, k.w), d, false);
+}
+template <> __device__ inline float frag_dot<__half>(const uint4& q, const uint4& k) {
+  float d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.x), __builtin_bit_cast(sea_h2, k.x), 0.f, false);
+  d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.y), __builtin_bit_cast(sea_h2, k.y), d, false);
+  d = __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.z), __builtin_bit_cast(sea_h2, k.z), d, false);
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.w), __builtin_bit_cast(sea_h2, k.w), d, false);
+}
+
 // true when the plan hands this launch to the OTHER kernel (uniform over the whole grid: every workgroup returns at once)
 __device__ inline bool kernel_is_idle(const AttnParams& p) {
   if (p.sel == nullptr) return false;
@@ -165,5 +205,17 @@ bool attn_tile_supported(int dtype, int D, int T_src, const AttnParams& p);
 int launch_attn_tile(const AttnParams& p, int dtype, int out_dtype, int flags, hipStream_t s);
 int launch_attn_plan(const uint32_t* bits, int N, int H, int T_dst, int T_src, int T_m, int causal, float entries_per_tile,
                      uint8_t* sel, hipStream_t s);
+
+
+// ---- key-range form (sea_attn_keyrange.hip; SEA_ATTN_KEYRANGE in sea_hip.h) ----------------------------------------------
+// ws: the caller's fp32 workspace, per batch item H * n_ranges * T_dst * (D + 2) floats -- the unnormalised accumulators
+// [h][range][t][D], then the pairs (m, l) [h][range][t][2]
+struct KeyRangeParams {
+  float* ws;
+  int64_t ws_stride_n;
+  int range_keys, n_ranges;
+};
+constexpr int SEA_KEYRANGE_LIST = 8192;          // entries of a workgroup's key lists in LDS (32 KB), shared out evenly to its rows
+int launch_attn_keyrange(const AttnParams& p, const KeyRangeParams& kr, int dtype, int out_dtype, hipStream_t s);
 
 }  // namespace sea

@@ -152,6 +152,11 @@ class PerlinAttention(nn.Module):
         # sparse mode: kernel of steps J-L: "gather" (row-indexed gathers), "tile" (MFMA tile kernel, 16-bit data,
         # d in {64, 80, 128}; wins when neighbouring query rows keep mostly the same keys -- trained predictors), "auto"
         self.sparse_kernel = "auto"
+        # sparse mode, long contexts: an integer = the attention launch takes the key-range form (`ops.sparse_attention(path=
+        # "keyrange", range_keys=key_range)`: the key axis in ranges of that many keys, walked range-major per head so that the
+        # K / V rows in flight fit an XCD's L2) wherever it exists -- pending CSR columns, no probabilities wanted, 16-bit d = 64 /
+        # 128 or fp32 d = 32 / 64, at most 64 ranges, `lazy_csr_columns` (the form writes no columns) -- and the keys exceed one range; None = never (DESIGN 5.4h has the measurements)
+        self.key_range: Optional[int] = None
         # HIP Performer: None = the library's plan for the shape (it cuts ONE long sequence into segments so that all CUs
         # work: another fp32 summation order than the one-pass kernel a full batch takes), 1 = always the one-pass kernel
         # (bench.py's self-check runs a batch item alone with it, so that the item reproduces its batched rows bit for bit)
@@ -998,10 +1003,17 @@ class PerlinAttention(nn.Module):
                         # blocks whose rows share most of their keys; the MFMA tile kernel runs the launch when they are
                         # the majority, the gather kernels otherwise (the idle kernel's workgroups exit at once)
                         plan = ops.attention_plan(csr, T_M, is_causal=True)
-                    res = ops.sparse_attention(qs, ks, vs, csr, row_scale=row_scale, avg=average_context_layer,
-                                               mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
-                                               want_probs=want_probs, path="gather" if want_probs else self.sparse_kernel,
-                                               plan=plan, keep_columns_pending=self.lazy_csr_columns and not want_probs)
+                    if (self.key_range is not None and not want_probs and csr.col_is_pending and self.lazy_csr_columns
+                            and T_SRC > self.key_range
+                            and ops.keyrange_supported(qs.dtype, HID, T_M, T_SRC, int(self.key_range))):
+                        res = ops.sparse_attention(qs, ks, vs, csr, row_scale=row_scale, avg=average_context_layer,
+                                                   mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
+                                                   path="keyrange", range_keys=int(self.key_range))
+                    else:
+                        res = ops.sparse_attention(qs, ks, vs, csr, row_scale=row_scale, avg=average_context_layer,
+                                                   mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
+                                                   want_probs=want_probs, path="gather" if want_probs else self.sparse_kernel,
+                                                   plan=plan, keep_columns_pending=self.lazy_csr_columns and not want_probs)
                     if want_probs:
                         probs_csr = csr.with_values(res[1])
         if probs_csr is not None:

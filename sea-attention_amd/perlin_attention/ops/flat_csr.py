@@ -273,7 +273,8 @@ def topk_mask(probs: torch.Tensor, keep: torch.Tensor, k: int, target_width=None
     return mask
 
 
-_PATHS = {"auto": _lib.SEA_ATTN_AUTO, "gather": _lib.SEA_ATTN_GATHER, "tile": _lib.SEA_ATTN_TILE}
+_PATHS = {"auto": _lib.SEA_ATTN_AUTO, "gather": _lib.SEA_ATTN_GATHER, "tile": _lib.SEA_ATTN_TILE, "keyrange": _lib.SEA_ATTN_KEYRANGE}
+KEYRANGE_MAX_RANGES = 64
 
 
 _FEW_ROWS = None
@@ -300,7 +301,30 @@ def fused_interp_supported(dtype, D: int, T_m: int, rows: int = None) -> bool:
     return lanes in (8, 16) and D % vec == 0 and T_m % 32 == 0
 
 
+def keyrange_supported(dtype, D: int, T_m: int, T_src: Optional[int] = None, range_keys: Optional[int] = None) -> bool:
+    """Shapes the key-range form of `sea_sparse_attention` covers (path="keyrange"): 16-bit d = 64 / 128, fp32 d = 32 / 64,
+    T_m a multiple of 32 -- and, given the key axis and the range, a range of 1 .. 32767 keys that cuts it into at most 64."""
+    if not (D in ((32, 64) if dtype == torch.float32 else (64, 128)) and T_m % 32 == 0):
+        return False
+    if range_keys is None:
+        return True
+    return 1 <= range_keys <= 32767 and (T_src is None or -(-T_src // range_keys) <= KEYRANGE_MAX_RANGES)
+
+
+def keyrange_workspace_floats(N: int, H: int, T_dst: int, D: int, n_ranges: int) -> int:
+    """fp32 elements of the key-range form's workspace: per (n, h, range, t) the unnormalised accumulator (D) and the running
+    maximum and sum of the partial softmax (2)."""
+    return N * H * n_ranges * T_dst * (D + 2)
+
+
 _BWD_WS = {}
+_KEYRANGE_WS = {}
+
+
+def _keyrange_workspace(N: int, stride: int, device) -> torch.Tensor:
+    """(N, stride) fp32 partial states of the key-range form: one buffer per (device, stream), grown on demand, as the gather
+    backward's scratch is kept (`_bwd_workspace`: undefined between calls, not cached while a graph is being captured)."""
+    return _stream_workspace(_KEYRANGE_WS, N * stride * 4, device).view(torch.float32).view(N, stride)
 
 
 def _bwd_workspace(nbytes: int, device) -> torch.Tensor:
@@ -310,18 +334,24 @@ def _bwd_workspace(nbytes: int, device) -> torch.Tensor:
     stream as well: two backward passes on different streams (or threads) of one device never share scratch, so the caching
     allocator's stream ordering is not needed.  While a HIP graph is being captured the buffer is NOT cached (a block
     allocated then belongs to the graph's private pool: a global must not point into it) -- the capture gets its own."""
+    return _stream_workspace(_BWD_WS, nbytes, device)
+
+
+def _stream_workspace(cache: dict, nbytes: int, device) -> torch.Tensor:
     if torch.cuda.is_current_stream_capturing():
         return torch.empty((nbytes,), dtype=torch.uint8, device=device)
     key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _BWD_WS.get(key)
+    ws = cache.get(key)
     if ws is None or ws.numel() < nbytes:
-        _BWD_WS[key] = ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        cache[key] = ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
     return ws[:nbytes]
 
 
 def clear_bwd_workspace():
-    """Release the cached backward scratch (about 1 GB per device and stream at OPT-1.3B x 8); `clear_prep_cache()` calls it."""
+    """Release the cached backward scratch (about 1 GB per device and stream at OPT-1.3B x 8) and the key-range form's partial
+    states; `clear_prep_cache()` calls it."""
     _BWD_WS.clear()
+    _KEYRANGE_WS.clear()
 
 
 class _SparseAttentionFn(torch.autograd.Function):
@@ -417,7 +447,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
                      plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False,
-                     block_table: Optional[torch.Tensor] = None):
+                     block_table: Optional[torch.Tensor] = None, range_keys: Optional[int] = None):
     """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
@@ -426,6 +456,12 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     permuted view of an (N,T_dst,H*D) buffer to get the layout of attention.py:1279-1282 directly.
     Default output: fp32 (N,H,T_dst,D) (flat_csr_sdbmm.py:347 returns fp32).
     path: "auto" | "gather" (row-indexed gather kernels) | "tile" (MFMA tile kernel: 16-bit data, D in {64,80,128});
+    "keyrange" (with `range_keys`, 1 .. 32767): the key-range form for K / V beyond an XCD's L2 -- the key axis cut into ranges
+    of `range_keys` keys (64 at most), one launch for the partial softmax state of every (row, head, range), dispatched
+    range-major per head, and one that merges them.  It needs a handle whose columns are pending and leaves them pending
+    (`col` is neither read nor written); 16-bit d = 64 / 128 or fp32 d = 32 / 64, T_m % 32 == 0; no `want_probs`, no `plan`, no
+    decode or paged form, no gradients: ValueError otherwise.  Results agree with "gather" to fp32 rounding, not bit for bit
+    (another summation order), and are the same bits from run to run.
     row_tiles / key_window tune the tile kernel (0 = defaults).  The tile kernel (also inside "auto" with a plan) stages whole
     16-key tiles: every V row below T_src must be finite, kept or not (0 * Inf = NaN; include/sea_hip.h); the gather kernels
     read kept keys only.
@@ -442,6 +478,27 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
     lib = _lib.load()
     _lib.require_gpu(q, k, v, csr.crow, block_table)
+    keyrange = path == "keyrange"
+    if keyrange:
+        why = None
+        if range_keys is None or not 1 <= int(range_keys) <= 32767:
+            why = f"range_keys must be 1 .. 32767 (got {range_keys})"
+        elif not csr.col_is_pending:
+            why = "it takes a handle whose columns are pending (topk_to_csr / csr_from_selection with defer_emit=True)"
+        elif want_probs or plan is not None:
+            why = "the per-entry probabilities and a kernel-choice plan are not available in it"
+        elif csr.t_src_dev is not None or block_table is not None:
+            why = "it has no decode or paged form"
+        elif not keyrange_supported(q.dtype, q.shape[-1], csr._pending[0]):
+            why = f"16-bit d = 64 / 128 or fp32 d = 32 / 64 with T_m % 32 == 0 (got {q.dtype}, d = {q.shape[-1]}, T_m = {csr._pending[0]})"
+        elif -(-csr.T_src // int(range_keys)) > KEYRANGE_MAX_RANGES:
+            why = f"at most {KEYRANGE_MAX_RANGES} ranges ({csr.T_src} keys in ranges of {range_keys})"
+        elif torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, row_scale, avg, mix)):
+            why = "it is an inference form (no backward)"
+        if why is not None:
+            raise ValueError(f"sparse_attention(path=\"keyrange\"): {why}")
+    elif range_keys is not None:
+        raise ValueError("range_keys goes with path=\"keyrange\"")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, row_scale, avg, mix)):
         assert out is None and not want_probs, "the differentiable form returns a new fp32 tensor"
         return sparse_attention_autograd(q, k, v, csr, row_scale, avg, mix)
@@ -493,6 +550,14 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
             _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), csr.t_src_stride if t_src_dev is not None else 0,
             _p(block_table), table_stride, page_rows, _lib.stream_ptr())
 
+    if keyrange:                                              # the columns stay pending: nothing reads or writes `col`
+        T_m_, max_k_, causal_, _emit = csr._pending
+        n_ranges = -(-T_src // int(range_keys))
+        stride = (keyrange_workspace_floats(1, H, T_dst, D, n_ranges) + 3) & ~3      # batch items 16-byte aligned
+        ws = _keyrange_workspace(N, stride, q.device)
+        _lib.check(launch(csr._col, ws, None, _lib.SEA_ATTN_KEYRANGE | (int(range_keys) << 16), csr.bits, T_m_, int(causal_),
+                          max_k_, 0), "sea_sparse_attention")
+        return out
     if fused:
         T_m_, max_k_, causal_, _emit = csr._pending
         raw_col = csr._col
