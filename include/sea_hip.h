@@ -407,7 +407,9 @@ int sea_predictor_tail(const void* y, const float* z, int dtype, int64_t N, int6
  * a row's life in this issue-bound kernel -- becomes a 16-byte-per-lane copy into LDS.  C, y_strides, conv_w16 and Cp are
  * not read; everything else (and every bit of the result) as with y; a caller that wants the map later runs the z form of
  * sea_predictor_tail on the same z.  Exactly one of y and z is non-NULL, else SEA_EINVAL.
- * DECODE form, t_src_dev != NULL (y only; T_m = 256, W4 = 64, up = 4): the T rows are the LAST rows of sequences of
+ * DECODE form, t_src_dev != NULL (y only; 16-bit data; T_m = 256 with W4 = 64, up = 4 and H % 4 == 0 on the register-resident
+ * kernel, or any T_m < 256 this launch serves on the general-length kernel, which reads the row's width from t_src_dev like
+ * the first; anything else -- T_m = 256 with another H, T_m > 256 -- SEA_EUNSUPPORTED): the T rows are the LAST rows of sequences of
  * *t_src_dev tokens (device memory, for a step replayed as a HIP graph); `keep` is then the absolute table -- keep[i] = K of
  * the row that sees i+1 keys, for every position the session can reach (attention.py:849-866) -- and keep_stride_n / T_src
  * are not read.  crow_out (decode form only, T == 1; else NULL): (N, 2) int32 = [0, row total] per batch item, i.e. the
@@ -422,9 +424,11 @@ int sea_predictor_tail_select(const void* y, const float* z, int dtype, int64_t 
 
 /* The per-pixel constants of the tail -- for every output pixel the <= 3 taps of the area resize, gamma, beta: (W4, up, T_m,
  * gamma, beta) only, the same for every row -- computed ONCE into tab (3 * 256 uint32, 16-byte aligned) instead of by every
- * row's workgroup (round 5; T_m = 256).  The `consts_tab` argument of sea_predictor_tail_select (every form) and
- * sea_decode_cnn_tail_select takes it (NULL = each row computes the table itself, as before): -3.5 % of the launch at
- * OPT-1.3B x 8, -8 % at H = 12. */
+ * row's workgroup (round 5).  Any T_m <= 256 with W4 * up == T_m (else SEA_EUNSUPPORTED, checked before the pointers): the
+ * table is [3][64 E] words, E = ceil(T_m / 64) the pixels per lane of the kernel that reads it, so at most the 3 * 256 words
+ * `tab` always has; pixels past T_m hold no tap.  The `consts_tab` argument of sea_predictor_tail_select (read by its T_m = 256
+ * kernels; NULL = each row computes the table itself, as before: -3.5 % of the launch at OPT-1.3B x 8, -8 % at H = 12) and of
+ * sea_decode_cnn_tail_select takes it (there optional at T_m = 256, MANDATORY below). */
 int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, const void* gamma, const void* beta,
                               uint32_t* tab, sea_stream_t stream);
 
@@ -436,8 +440,8 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  *     launch has just written), conv2's new row from the ring of conv1's rows -- bit for bit the rows sea_causal_conv_c8 writes
  *     (same operand placement and k order; weights read straight from the packed images, w1_packed / w2_packed / bias as for
  *     sea_causal_conv_c8 with Cin = Cout = C, 3 x 3, `dilation`, pad_w = dilation);
- *   - runs the decode form of sea_predictor_tail_select on that row (T_m = 256, W4 = 64, up = 4; keep_table over
- *     absolute rows; outputs bits (N,1,W), row_nnz (N,1), head_off (N,1,H+1), crow_out (N,2), optional probs (N,H,1,256));
+ *   - runs the decode form of sea_predictor_tail_select on that row (T_m = 4 W4, up = 4; keep_table over
+ *     absolute rows; outputs bits (N,1,W), row_nnz (N,1), head_off (N,1,H+1), crow_out (N,2), optional probs (N,H,1,T_m));
  *   - files x_new and conv1's new row in their rings (slot = position % ring size: nothing is shifted) and, as the last
  *     workgroup to finish, advances counters = {rows seen (the new row's position), T_src of the step, T_src of the step JUST
  *     FINISHED}: counters[2] = counters[1], then counters[0] += 1, counters[1] += 1.  Launches behind this one in the same
@@ -446,8 +450,16 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  * `col` (optional, C <= 64): the step's CSR columns (N, col_stride_n) int32, ids = head * T_cap + key as the decode form of
  *   sea_csr_emit writes them, at most z_cap per item -- the emit of the one new row runs inside this launch too (one launch
  *   less per position); NULL = the caller runs that emit.
- * x_new (N, C/8, 64, 8); x_ring (N, ring_x, C/8, 64, 8); y1_ring (N, ring_y, C/8, 64, 8); y2 (N, C/8, 64, 8) scratch, all `dtype`
+ * x_new (N, C/8, W4, 8); x_ring (N, ring_x, C/8, W4, 8); y1_ring (N, ring_y, C/8, W4, 8); y2 (N, C/8, W4, 8) scratch, all `dtype`
  * (16-bit); ring sizes > 2 * dilation.  C = 2 H <= 80, H % 4 == 0.
+ * PREDICTOR LENGTH: T_m = 4 W4 with W4 % 8 == 0 and W4 <= 64 (a row is one pass of the row convolution), else SEA_EUNSUPPORTED.
+ *   W4 = 64 (T_m = 256) keeps the tail's row in registers, and `consts_tab` is optional (NULL: the workgroup computes it).  W4 =
+ *   16, 24, 32 (T_m = 64, 96, 128: the reference's grid) run the general-length tail -- E = ceil(T_m / 64) pixels per lane, the
+ *   rounded row through a flat 16-bit LDS image, bit for bit the general-length kernel of sea_predictor_tail_select -- and read
+ *   the per-pixel constants from `consts_tab` ONLY: the table of sea_predictor_tail_consts for this (W4, 4, T_m), 16-byte aligned,
+ *   is mandatory there (without it: SEA_EUNSUPPORTED).  Other W4 < 64 are not instantiated (SEA_EUNSUPPORTED), as is a row
+ *   whose z tile, flat image (2 H T_m bytes) and candidate list do not fit the LDS beside the kernel's static arrays (the weight
+ *   image, dead before the tail, is overlaid: H = 40 at T_m = 128 fits).
  * A counter triple PER SEQUENCE, counter_stride > 0 (0 = the batch's one triple): sequence n's {seen, T_src, T_src just
  * finished} at counters + n * counter_stride (counter_stride >= 3, else SEA_EINVAL).  Workgroup n reads its own triple (ring
  * slots, row widths, the in-launch emit); the last workgroup advances all N triples as above.
@@ -463,16 +475,16 @@ int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, co
  * per (sequence n, row j) serves position t = counters[n * counter_stride] + j:
  *   - conv1's rows t - 2 dil, t - dil, t: those at positions >= seen (new in this step) are recomputed from x rows -- x_new's
  *     row (q - seen) for a position q >= seen, the x ring's slot q % ring_x below it -- into the workgroup's own two rows of
- *     y1_scratch (N, rows, 2, C/8, 64, 8), row t into the y1 ring; older ones are read from the y1 ring;
- *   - conv2's row t into y2 (N, rows, C/8, 64, 8), then the tail + selection of that row (keep_table[t], width t + 1): bits
- *     (N, rows, W), row_nnz (N, rows), head_off (N, rows, H+1), optional probs (N, H, rows, 256).  No crow and no in-launch emit:
+ *     y1_scratch (N, rows, 2, C/8, W4, 8), row t into the y1 ring; older ones are read from the y1 ring;
+ *   - conv2's row t into y2 (N, rows, C/8, W4, 8), then the tail + selection of that row (keep_table[t], width t + 1): bits
+ *     (N, rows, W), row_nnz (N, rows), head_off (N, rows, H+1), optional probs (N, H, rows, T_m).  No crow and no in-launch emit:
  *     crow_out and col must be NULL, col_stride_n / z_cap / T_cap 0 (else SEA_EINVAL); run sea_csr_row_scan on row_nnz;
  *   - x_new's row j joins the x ring at slot t % ring_x.
  * No data passes between the workgroups of a launch: the ring slots read (positions seen - 2 dil .. seen - 1) and written
  * (seen .. seen + rows - 1) are disjoint, which needs ring_x, ring_y >= 2 * dilation + rows (else SEA_EINVAL).  A session
  * that may drop rows of a step again (rewind) needs more: x_ring >= LB + max rows (the window it exports), y1_ring >=
  * 2 * dilation + max rows.  The last of the N * rows workgroups advances every triple: counters[2] = counters[0] + rows,
- * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what the one-row form does).  x_new (N, rows, C/8, 64, 8) dense.
+ * counters[0] += rows, counters[1] = counters[0] + 1 (rows = 1: what the one-row form does).  x_new (N, rows, C/8, W4, 8) dense.
  * Everything else, and the other refusals, as for the one-row form; rows outside 1 .. 8: SEA_EINVAL.  Without y1_scratch
  * (the one-row form) rows must be 1, else SEA_EINVAL.
  * A sequence that sits out (negative triple): each of its `rows` workgroups writes an empty row (the row scan behind the launch

@@ -36,7 +36,7 @@ def main():
             cur[m.group(1).strip()] = int(m.group(2))
     for name, r in rows.items():
         if all(s in name for s in subs):
-            print(f"{name:110s} vgpr={r.get('VGPRs', -1):3d} agpr={r.get('AGPRs', 0):3d} spill={r.get('VGPRs Spill', 0):3d} "
+            print(f"{name:110s} vgpr={r.get('VGPRs', -1):3d} agpr={r.get('AGPRs', 0):3d} sgpr={r.get('TotalSGPRs', -1):3d} spill={r.get('VGPRs Spill', 0):3d} "
                   f"scratch={r.get('ScratchSize [bytes/lane]', 0):4d} occ={r.get('Occupancy [waves/SIMD]', -1)} "
                   f"lds={r.get('LDS Size [bytes/block]', 0)}")
 

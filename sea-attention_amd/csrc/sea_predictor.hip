@@ -590,18 +590,21 @@ extern "C" int sea_predictor_tail(const void* y, const float* z, int dtype, int6
 extern "C" int sea_predictor_tail_consts(int dtype, int64_t W4, int64_t up, int64_t T_m, const void* gamma, const void* beta,
                                          uint32_t* tab, sea_stream_t stream) {
   const char* nm = "sea_predictor_tail_consts";
-  SEA_REQUIRE(gamma && beta && tab, SEA_EINVAL, "%s: null pointer", nm);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16 || dtype == SEA_F32, SEA_EINVAL, "%s: bad dtype %d", nm, dtype);
-  SEA_REQUIRE(W4 > 0 && up > 0 && T_m == 256 && W4 * up == T_m && W4 + 1 < 1024, SEA_EUNSUPPORTED,
-              "%s: the table serves the T_m = 256 kernels (3 x 256 words)", nm);
+  SEA_REQUIRE(W4 > 0 && up > 0 && T_m <= 256 && W4 * up == T_m, SEA_EUNSUPPORTED,
+              "%s: the table serves the kernels up to T_m = 256 (3 x 64 E words, E = ceil(T_m / 64): at most 3 x 256), W4 * up == T_m", nm);
+  // [3][TMP] with TMP = 64 E, E the pixels per lane of the kernel that reads it (TailRow<T, E>::load_global); pixels past T_m
+  // hold count 0 / the unused tap
+  const int TMP = 64 * (int)((T_m + 63) / 64);
+  SEA_REQUIRE(gamma && beta && tab, SEA_EINVAL, "%s: null pointer", nm);
   TailParams p;
   p.y = nullptr; p.w4 = nullptr; p.b4 = nullptr; p.gamma = gamma; p.beta = beta; p.probs = nullptr; p.scores = nullptr; p.eps = 0.f;
   p.N = 1; p.C = 0; p.H = 1; p.T = 1; p.W4 = (int)W4; p.UP = (int)up; p.T_M = (int)T_m;
   p.ys_n = p.ys_c = p.ys_t = p.ys_w = p.ys_c8 = 0; p.w16 = nullptr; p.Cp = 0; p.z = nullptr; p.tab = nullptr;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == SEA_F16) hipLaunchKernelGGL((tail_consts_kernel<__half>), dim3(1), dim3(256), 0, s, p, tab, 256);
-  else if (dtype == SEA_F32) hipLaunchKernelGGL((tail_consts_kernel<float>), dim3(1), dim3(256), 0, s, p, tab, 256);
-  else hipLaunchKernelGGL((tail_consts_kernel<__hip_bfloat16>), dim3(1), dim3(256), 0, s, p, tab, 256);
+  if (dtype == SEA_F16) hipLaunchKernelGGL((tail_consts_kernel<__half>), dim3(1), dim3(256), 0, s, p, tab, TMP);
+  else if (dtype == SEA_F32) hipLaunchKernelGGL((tail_consts_kernel<float>), dim3(1), dim3(256), 0, s, p, tab, TMP);
+  else hipLaunchKernelGGL((tail_consts_kernel<__hip_bfloat16>), dim3(1), dim3(256), 0, s, p, tab, TMP);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

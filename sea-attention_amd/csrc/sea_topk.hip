@@ -754,6 +754,9 @@ __global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_f32_kernel(T
 // wv, wv + 4, ..., lane <-> E consecutive pixels); the rounded probabilities go through a flat 16-bit image of the row in
 // LDS ([head][pixel], 2 H T_m bytes) from which every thread takes the selection's layout (chunk c = 256 j + tid <-> flat
 // pixels 4c .. 4c+3) as packed keys.  Same arithmetic as predictor_tail_mfma_kernel + topk_select_kernel: bit-identical.
+// tail_select_row_gen below is this body as a device function for the fused decode kernels, and a decode session's rows are
+// bitwise this kernel's: the two CHANGE TOGETHER (the lane <-> pixel map, the batches of NBC heads, the rounding into the flat
+// image and the key order of select_body).
 template <typename T, int E, int EPT>
 __global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_gen_kernel(TailParams tp, TopkParams p) {
   constexpr int R = EPT / 4;
@@ -774,6 +777,57 @@ __global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_gen_kernel(T
   __syncthreads();
   TailRow<T, E> tr;
   tr.load(s_tab, lane);
+  const int mine = max(0, (tp.H - wv + 3) / 4);                   // heads wv, wv + 4, ... of this wave
+  for (int k0 = 0; k0 < mine; k0 += NBC) {
+    float a[NBC][E];
+    const int nb = min(NBC, mine - k0);
+    tr.heads(tp, lane, nb, [&](int b) { return s_z + (wv + 4 * (k0 + b)) * LDZ; },
+             [&](int b) { return (((int64_t)n * tp.H + (wv + 4 * (k0 + b))) * tp.T + t) * tp.T_M; }, a);
+#pragma unroll
+    for (int b = 0; b < NBC; ++b) {
+      if (b < nb) {
+        unsigned short* fr = s_flat + (wv + 4 * (k0 + b)) * tp.T_M + lane * E;
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+          if (lane * E + e < tp.T_M) fr[e] = __builtin_bit_cast(unsigned short, from_f<T>(a[b][e]));
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t key[EPT / 2];                                           // two 16-bit keys per register (select_body, K16)
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    const int c = j * TK_THREADS + tid;
+    uint2 v = make_uint2(0u, 0u);
+    if (c < p.nchunks) v = *reinterpret_cast<const uint2*>(s_flat + 4 * c);
+    key[2 * j] = v.x;
+    key[2 * j + 1] = v.y;
+  }
+  select_body<T, EPT, false, false, 64, true, true, false>(p, key, 0ull, n, t, row, (const T*)nullptr, reinterpret_cast<uint32_t*>(s_z));
+}
+
+// (the body of predictor_tail_select_gen_kernel above as a device function, for the fused decode kernels at W4 < 64: the
+// general-length twin of tail_select_row.  One difference: the per-pixel constants come from the table in global memory
+// (sea_predictor_tail_consts: [3][64 E] words) ONLY -- no fill path, no table in LDS; s_z: HP x (W4 + 3) | flat map (H T_m
+// 16-bit).  E = ceil(T_m / 64) pixels per lane and the batches of NBC heads fix the reduction order to the prefill kernel's at
+// the same T_m: the same bits.  The prefill kernel keeps its own copy, like predictor_tail_select_kernel: routed through this
+// function hipcc allocates it differently (E = 1: 66 -> 68 vector registers, E = 2: 107 -> 110, EPT 32: 93 -> 92).)
+template <typename T, int E, int EPT>
+__device__ __forceinline__ void tail_select_row_gen(const TailParams& tp, const TopkParams& p, float* s_z, int row) {
+  constexpr int R = EPT / 4;
+  constexpr int NBC = E >= 6 ? 4 : 8;                             // heads per batch of the tail stage (register budget)
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = row / tp.T, t = row - n * tp.T;
+  const int LDZ = tp.W4 + 3;
+  // the flat image sits behind the z tile, or behind the 8 KB the candidate list takes over from it if that is smaller
+  const int zt_words = ((tp.H + 15) / 16) * 16 * LDZ;
+  unsigned short* s_flat = reinterpret_cast<unsigned short*>(s_z + max(zt_words, 2 * TK_CAND_CAP));
+  TailRow<T, E> tr;
+  tr.load_global(tp.tab, lane);                                   // the table was computed once per weight set (launcher: not null)
+  tail_z_tile<T>(tp, s_z, n, t);
+  __syncthreads();
   const int mine = max(0, (tp.H - wv + 3) / 4);                   // heads wv, wv + 4, ... of this wave
   for (int k0 = 0; k0 < mine; k0 += NBC) {
     float a[NBC][E];
@@ -1031,7 +1085,8 @@ __global__ __launch_bounds__(TK_THREADS) void csr_emit_kernel(EmitParams p) {
 //   * computes the new row of conv1 from the rows t - 2 dil, t - dil (a ring of the MLP's previous outputs) and t (the row
 //     the MLP launch has just written), and the new row of conv2 from a ring of conv1's previous rows -- conv_row_c8, bit for
 //     bit the rows causal_conv_c8_kernel writes;
-//   * runs tail_select_row on that row, unchanged;
+//   * runs tail_select_row on that row, unchanged (T_m = 256; a shorter predictor length, W4 < 64: tail_select_row_gen with the
+//     constants table from global memory -- EG = ceil(T_m / 64) pixels per lane, 0 = the T_m = 256 form);
 //   * files the two new rows in their rings (no window to shift) and, as the LAST workgroup to finish (ticket), advances the
 //     session's device counters -- what the shift launch did.
 struct DecodeCnnParams {
@@ -1103,7 +1158,7 @@ __device__ __forceinline__ void decode_cnn_ticket(const DecodeCnnParams& dp, con
 
 // EMIT: the selection's one CSR row is expanded into its column ids here too (csr_emit_row: the decode-form sea_csr_emit launch that
 // followed); instantiated wherever the emit's 20 KB of LDS fit beside the weight image (all but the 80-channel form).
-template <typename T, int EPT, int NT, int KCH, bool EMIT>
+template <typename T, int EPT, int NT, int KCH, bool EMIT, int EG = 0>
 __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(DecodeCnnParams dp, TailParams tp, TopkParams p, EmitParams ep) {
   extern __shared__ __attribute__((aligned(16))) float s_z[];
   const int n = (int)blockIdx.x;
@@ -1153,7 +1208,10 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
   }
   __syncthreads();
   STAMP(12);  // decode: ring copy
-  tail_select_row<T, EPT, false>(tp, p, s_z, n);                   // T = 1: row n of the call is batch item n
+  // T = 1: row n of the call is batch item n.  The weight image is dead: the z tile, the flat image of the general-length form
+  // and the candidate list overlay it (launch_decode_cnn sizes the dynamic LDS for the larger of the two)
+  if constexpr (EG == 0) tail_select_row<T, EPT, false>(tp, p, s_z, n);
+  else tail_select_row_gen<T, EG, EPT>(tp, p, s_z, n);
   __syncthreads();
 #ifdef SEA_STAMP
   _tprev = __builtin_amdgcn_s_memtime();
@@ -1177,7 +1235,7 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_kernel(Deco
 // .. seen + rows - 1) are disjoint when a ring holds 2 dil + rows slots.  The selection runs as the decode form at T_src =
 // seen + rows over T_dst = rows rows; its crow comes from the row scan behind this launch.  The last workgroup of all N * rows
 // advances every triple: counters[2] = counters[0] + rows, counters[0] += rows, counters[1] = counters[0] + 1.
-template <typename T, int EPT, int NT, int KCH>
+template <typename T, int EPT, int NT, int KCH, int EG = 0>
 __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_rows_kernel(DecodeCnnParams dp, TailParams tp, TopkParams p,
                                                                                  void* y1_scratch) {
   extern __shared__ __attribute__((aligned(16))) float s_z[];
@@ -1235,7 +1293,8 @@ __global__ __launch_bounds__(TK_THREADS) void decode_cnn_tail_select_rows_kernel
   ps.t_src_dev = nullptr;
   ps.T_src = seen + rows;
   ps.keep = p.keep + seen;
-  tail_select_row<T, EPT, false>(tp, ps, s_z, b);                 // row b = n * rows + j of the call
+  if constexpr (EG == 0) tail_select_row<T, EPT, false>(tp, ps, s_z, b);      // row b = n * rows + j of the call
+  else tail_select_row_gen<T, EG, EPT>(tp, ps, s_z, b);
   __syncthreads();
   decode_cnn_ticket<true>(dp, dp.ctr_stride ? (int)gridDim.x / rows : 1, rows);
 }
@@ -1438,7 +1497,8 @@ static int launch_tail_select_gen(const TailParams& tp, const TopkParams& p, int
 
 // y (the activation, C8 / channels-last) or z (the 1x1 convolution's output (N, T, H, W4) fp32, as sea_causal_conv_c8's
 // epilogue writes it: the z tile of a row is then a copy into LDS instead of loads + MFMAs).  t_src_dev != NULL: the decode
-// form (see include/sea_hip.h): keep is the absolute table, keep_stride_n and T_src are not read.
+// form (see include/sea_hip.h): keep is the absolute table, keep_stride_n and T_src are not read; 16-bit data, any predictor
+// length the kernels serve (select_body reads the row's width from t_src_dev whichever kernel calls it).
 extern "C" int sea_predictor_tail_select(const void* y, const float* z, int dtype, int64_t N, int64_t C, int64_t H, int64_t T,
                                          int64_t W4, int64_t up, int64_t T_m, const int64_t* y_strides, const void* conv_b,
                                          const void* conv_w16, int64_t Cp, const void* gamma, const void* beta, float eps,
@@ -1463,7 +1523,9 @@ extern "C" int sea_predictor_tail_select(const void* y, const float* z, int dtyp
               "%s: fp32 data takes T_m = 256, H <= 32, H %% 4 == 0, a written map, no z / decode form", nm);
   SEA_REQUIRE(W4 * up == T_m && T_m % 4 == 0 && T_m <= 512 && H <= 64 && H * T_m <= 16384 && W4 + 1 < 1024 && W4 * up + 2 <= 2 * T_m,
               SEA_EUNSUPPORTED, "%s: needs W4 * up == T_m, T_m %% 4 == 0, T_m <= 512, H <= 64, H * T_m <= 16384", nm);
-  SEA_REQUIRE(tm256 || t_src_dev == nullptr, SEA_EUNSUPPORTED, "%s: the decode form takes T_m = 256 (W4 = 64, up = 4), H %% 4 == 0", nm);
+  // (T_m = 256 with H % 4 != 0 would go to the general-length kernel at four pixels per lane: no decode session runs that)
+  SEA_REQUIRE(t_src_dev == nullptr || tm256 || T_m < 256, SEA_EUNSUPPORTED,
+              "%s: the decode form takes T_m = 256 (W4 = 64, up = 4) with H %% 4 == 0, or T_m < 256", nm);
   if (z) {
     SEA_REQUIRE(W4 % 4 == 0 && (((uintptr_t)z | (uintptr_t)probs | (uintptr_t)scores) & 15) == 0, SEA_EUNSUPPORTED,
                 "%s: z rows must be whole 16-byte vectors, 16-byte aligned", nm);
@@ -1505,11 +1567,22 @@ template <typename T>
 static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, const TopkParams& p, const EmitParams& ep, void* scratch,
                              hipStream_t s) {
   const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
-  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
+  // eg: 0 = the register-resident T_m = 256 tail (tail_select_row); else the general-length tail (tail_select_row_gen) with
+  // eg = ceil(T_m / 64) pixels per lane, as the prefill kernel of the same T_m has them (same lane <-> pixel map: same bits)
+  const int eg = tp.W4 == 64 ? 0 : (tp.T_M + 63) / 64;
+  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float);
+  if (eg == 0) lds += (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);      // (general-length form: the table stays in global memory)
   if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
+  if (eg != 0) lds += ((size_t)p.M * 2 + 15) & ~(size_t)15;                // the flat 16-bit image of the row, behind z / the candidate list
   const int nt = (dp.C + 15) / 16, kch = (dp.C + 31) / 32;
   const size_t wimg = (size_t)(16 * nt) * 9 * kch * 64;                    // the weight image overlays the (later) z tile
   if (lds < wimg) lds = wimg;
+  // general-length form (eg = 1, 2: the entry point admits W4 <= 32 there): the plan is checked here against the kernels' STATIC
+  // LDS, which hipcc reports (scripts/kernel_resources.py sea_topk.hip decode_cnn_tail_select) as 10 576 bytes for every form
+  // without the in-launch emit (the selection's arrays) and 31 088 bytes with it -- allowed for as 12 KB and 12 + 21 KB.  A
+  // change to the static arrays of select_body or csr_emit_row moves those figures: measure again and keep the allowances above them.
+  constexpr size_t kStaticSelect = 12 * 1024, kStaticEmit = 21 * 1024, kLdsPerWorkgroup = 160 * 1024;
+  if (eg != 0 && lds + kStaticSelect + (!scratch && nt <= 4 ? kStaticEmit : 0) > kLdsPerWorkgroup) return SEA_EUNSUPPORTED;
   dim3 grid((unsigned)(tp.N * tp.T)), block(TK_THREADS);
 #define SEA_DCNN_GO(KERNEL, ...)                                                                                       \
   do {                                                                                                                 \
@@ -1517,12 +1590,19 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
     if (lds > 32 * 1024 && once.first()) SEA_MAX_LDS(KERNEL, lds);                                                     \
     hipLaunchKernelGGL(KERNEL, grid, block, lds, s, dp, tp, p, __VA_ARGS__);                                           \
   } while (0)
-#define SEA_DCNN(EE, NTV, KV)                                                                                          \
+#define SEA_DCNN_E(EE, NTV, KV, EGV)                                                                                   \
   do {                                                                                                                 \
     constexpr bool EM = (NTV) <= 4;                                                                                    \
-    if (scratch) SEA_DCNN_GO((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV>), scratch);                           \
+    if (scratch) SEA_DCNN_GO((decode_cnn_tail_select_rows_kernel<T, EE, NTV, KV, EGV>), scratch);                      \
     else if (!EM && ep.col != nullptr) return SEA_EUNSUPPORTED;                                                        \
-    else SEA_DCNN_GO((decode_cnn_tail_select_kernel<T, EE, NTV, KV, EM>), ep);                                         \
+    else SEA_DCNN_GO((decode_cnn_tail_select_kernel<T, EE, NTV, KV, EM, EGV>), ep);                                    \
+  } while (0)
+  // EE follows the channel tiling: wide enough for T_m = 256, so for every shorter row too (the key loads are guarded)
+#define SEA_DCNN(EE, NTV, KV)                                                                                          \
+  do {                                                                                                                 \
+    if (eg == 0) SEA_DCNN_E(EE, NTV, KV, 0);                                                                           \
+    else if (eg == 1) SEA_DCNN_E(EE, NTV, KV, 1);                                                                      \
+    else SEA_DCNN_E(EE, NTV, KV, 2);                                                                                   \
   } while (0)
   if (ept <= 8 && nt == 1 && kch == 1) { if (ept <= 4) SEA_DCNN(4, 1, 1); else SEA_DCNN(8, 1, 1); }
   else if (ept <= 16 && nt == 2 && kch == 1) SEA_DCNN(16, 2, 1);
@@ -1531,6 +1611,7 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
   else if (ept <= 40 && nt == 5 && kch == 3) SEA_DCNN(40, 5, 3);
   else return SEA_EUNSUPPORTED;
 #undef SEA_DCNN
+#undef SEA_DCNN_E
 #undef SEA_DCNN_GO
   return SEA_OK;
 }
@@ -1568,8 +1649,17 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
   SEA_REQUIRE(counter_stride >= 0 && counter_stride * N < (1ll << 31), SEA_EINVAL, "%s: bad counter stride %lld", nm,
               (long long)counter_stride);
   SEA_REQUIRE(dtype == SEA_F16 || dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: 16-bit data only (dtype %d)", nm, dtype);
-  SEA_REQUIRE(N > 0 && N * rows < (1 << 20) && H > 0 && H <= 64 && H % 4 == 0 && C == 2 * H && C % 8 == 0 && W4 == 64 && max_k > 0,
-              SEA_EUNSUPPORTED, "%s: needs T_m = 256 (W4 = 64), H %% 4 == 0, C = 2 H channels in whole blocks of 8", nm);
+  SEA_REQUIRE(N > 0 && N * rows < (1 << 20) && H > 0 && H <= 64 && H % 4 == 0 && C == 2 * H && C % 8 == 0 && max_k > 0,
+              SEA_EUNSUPPORTED, "%s: needs H %% 4 == 0, C = 2 H channels in whole blocks of 8", nm);
+  SEA_REQUIRE(W4 > 0 && W4 <= 64 && W4 % 8 == 0, SEA_EUNSUPPORTED,
+              "%s: rows of W4 = T_m / 4 pixels with W4 %% 8 == 0 and W4 <= 64 (one pass of the row convolution; got W4 = %lld)", nm,
+              (long long)W4);
+  SEA_REQUIRE(W4 == 64 || (consts_tab != nullptr && (((uintptr_t)consts_tab) & 15) == 0), SEA_EUNSUPPORTED,
+              "%s: without consts_tab: needs T_m = 256 (W4 = 64); a shorter predictor length (W4 = %lld) reads its per-pixel "
+              "constants from the table of sea_predictor_tail_consts, 16-byte aligned", nm, (long long)W4);
+  SEA_REQUIRE(W4 == 64 || (W4 >= 16 && W4 <= 32), SEA_EUNSUPPORTED,
+              "%s: below T_m = 256 (W4 = 64) the predictor lengths 64 .. 128 are instantiated (W4 = 16, 24, 32; got W4 = %lld)", nm,
+              (long long)W4);
   SEA_REQUIRE(CinP == (C + 31) / 32 * 32 && Cp % 32 == 0 && Cp >= C && dilation > 0 && 2 * pad_w == 2 * dilation, SEA_EUNSUPPORTED,
               "%s: 3 x 3 width-preserving convolutions with CinP = C rounded up to 32", nm);
   if (multi)
@@ -1582,33 +1672,35 @@ extern "C" int sea_decode_cnn_tail_select(const void* x_new, void* x_ring, void*
   SEA_REQUIRE((((uintptr_t)x_new | (uintptr_t)x_ring | (uintptr_t)y1_ring | (uintptr_t)y2 | (uintptr_t)y1_scratch |
                 (uintptr_t)w1_packed | (uintptr_t)w2_packed | (uintptr_t)conv_w16 | (uintptr_t)probs) & 15) == 0,
               SEA_EUNSUPPORTED, "%s: 16-byte alignment", nm);
+  const int64_t T_m = 4 * W4;
   DecodeCnnParams dp;
   dp.x_new = x_new; dp.x_ring = x_ring; dp.y1_ring = y1_ring; dp.y2 = y2; dp.w1 = w1_packed; dp.w2 = w2_packed; dp.b1 = bias1; dp.b2 = bias2;
   dp.counters = counters; dp.ctr_stride = (int)counter_stride; dp.ticket = ticket;
   dp.C = (int)C; dp.W = (int)W4; dp.RX = (int)ring_x; dp.RY = (int)ring_y; dp.dil = dilation; dp.pad_w = pad_w;
   TailParams tp;
   tp.y = y2; tp.w4 = nullptr; tp.b4 = conv_b; tp.gamma = gamma; tp.beta = beta; tp.probs = probs; tp.scores = nullptr; tp.eps = eps;
-  tp.N = (int)N; tp.C = (int)C; tp.H = (int)H; tp.T = (int)rows; tp.W4 = (int)W4; tp.UP = 4; tp.T_M = 256;
+  tp.N = (int)N; tp.C = (int)C; tp.H = (int)H; tp.T = (int)rows; tp.W4 = (int)W4; tp.UP = 4; tp.T_M = (int)T_m;
   // one C8 row per batch item (one-row form), per (item, row) (multi-row form)
   tp.ys_n = rows * C * W4; tp.ys_c = 1; tp.ys_t = multi ? C * W4 : 0; tp.ys_w = 8; tp.ys_c8 = W4 * 8;
   tp.w16 = conv_w16; tp.Cp = (int)Cp; tp.z = nullptr;
   tp.tab = (consts_tab != nullptr && (((uintptr_t)consts_tab) & 15) == 0) ? consts_tab : nullptr;
   TopkParams p;
-  p.src = nullptr; p.sn = H * 256; p.sh = 256; p.st = 256;
-  p.H = (int)H; p.T_dst = (int)rows; p.T_m = 256; p.T_src = (int)rows;          // (T_src: per workgroup, from its counters)
+  p.src = nullptr; p.sn = H * T_m; p.sh = T_m; p.st = T_m;
+  p.H = (int)H; p.T_dst = (int)rows; p.T_m = (int)T_m; p.T_src = (int)rows;     // (T_src: per workgroup, from its counters)
   p.is_causal = is_causal; p.max_k = max_k;
-  p.M = (int)(H * 256); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes(256);
+  p.M = (int)(H * T_m); p.nchunks = p.M / 4; p.W = (p.M + 31) / 32; p.G = group_lanes((int)T_m);
   p.keep = keep_table; p.keep_stride_n = 0;
   p.bits = bits; p.mask_out = nullptr; p.row_nnz = row_nnz; p.head_off = head_off; p.crow1 = crow_out;
   p.t_src_dev = multi ? nullptr : counters + 1; p.t_src_stride = multi ? 0 : (int)counter_stride;
   EmitParams ep;                                                                // (read by the one-row form alone)
-  ep.bits = bits; ep.crow = crow_out; ep.H = (int)H; ep.T_dst = 1; ep.T_m = 256; ep.T_src = 1; ep.is_causal = is_causal; ep.max_k = max_k;
+  ep.bits = bits; ep.crow = crow_out; ep.H = (int)H; ep.T_dst = 1; ep.T_m = (int)T_m; ep.T_src = 1; ep.is_causal = is_causal; ep.max_k = max_k;
   ep.W = p.W; ep.col = col; ep.col_stride_n = col_stride_n; ep.z_cap = z_cap; ep.values_out = nullptr; ep.T_enc = (int)T_cap;
   ep.t_src_dev = counters + 1; ep.t_src_stride = (int)counter_stride;
   hipStream_t s = (hipStream_t)stream;
   const int rc = dtype == SEA_F16 ? launch_decode_cnn<__half>(dp, tp, p, ep, y1_scratch, s)
                                   : launch_decode_cnn<__hip_bfloat16>(dp, tp, p, ep, y1_scratch, s);
-  SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation", nm);
+  SEA_REQUIRE(rc == SEA_OK, rc, "%s: this head / channel count has no fused decode instantiation (or, below T_m = 256, the row does "
+              "not fit its LDS plan)", nm);
   SEA_CHECK_LAUNCH(nm);
   return SEA_OK;
 }

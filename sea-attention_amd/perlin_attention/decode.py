@@ -128,6 +128,20 @@ def _fused_cnn_ok(convs, C, H, T_M, dt, LB) -> bool:
             and ops.decode_cnn_supported(C, H, T_M, dt) and LB >= 4 * convs[0].dilation)   # (the y1 ring's seed: 2 dil rows)
 
 
+def _predictor_length_error(T_M) -> Optional[str]:
+    """Why a session cannot run at predictor length T_M (None: it can).  Two kernels of a position set the limit: the fused
+    CNN launch convolves a row of W4 = T_M / 4 pixels in one pass (`ConvRowC8`: W4 <= 64), and the one-row decode attention
+    keeps a row's pixel bounds for T_m <= 256.  Below that the reference's grid is served (`ops.DECODE_PREDICTOR_LENGTHS`: the
+    lengths the fused CNN launch is instantiated and tested for)."""
+    if T_M > 256:
+        return (f"a decode session runs at predictor lengths T_M <= 256 (got T_M = {T_M}): W4 = T_M / 4 <= 64 in ConvRowC8 "
+                "(one pass per row), T_m <= 256 in the one-row decode attention")
+    if T_M not in ops.DECODE_PREDICTOR_LENGTHS:
+        return (f"a decode session runs at the predictor lengths {' / '.join(str(t) for t in ops.DECODE_PREDICTOR_LENGTHS)} "
+                f"(got T_M = {T_M})")
+    return None
+
+
 class PageAllocator:
     """Free list of a paged K / V pool's pages (host only; the device block table is the session's business).  Pages go out
     lowest index first at the start; pages given back are handed out again before any never-used one (most recently
@@ -321,7 +335,11 @@ class DecodeSession:
         self.k = int(pc.k)
         dev, dt = key_prefix.device, key_prefix.dtype
         assert dt in (torch.float16, torch.bfloat16)
-        assert ops.predictor_tail_select_supported(cs.rows_c8, H, self.T_M, decode=True), "fused tail + selection shape (T_M = 256, H <= 64)"
+        why = _predictor_length_error(self.T_M)
+        if why is not None:
+            raise ValueError(why)
+        assert ops.decode_tail_select_supported(cs.rows_c8, H, self.T_M), \
+            "fused tail + selection shape (the decode form: 16-bit data, H <= 64, a row that fits the kernel's LDS plan)"
         self.image = ps.image.clone()                                        # Performer sums, updated in place
         # CNN input rows: the window (last LB rows) and, behind it, the row of the current position -- ONE buffer, so that the
         # MLP writes the new row in place (no cat) and the window moves by an in-place shift at the end of the step
@@ -393,8 +411,9 @@ class DecodeSession:
         """A session over sequences of DIFFERENT lengths.  `sequences`: [(state, key_prefix, value_prefix), ...], each the
         output of an N = 1 cached forward, (1, H, L_i, D) with its own L_i.  Slot n of the batch is sequence n; `step` takes
         and returns (N, ...) rows as for a uniform session, and every row equals that sequence's own N = 1 session bit for
-        bit.  Defined where the fused CNN launch runs (`ops.decode_cnn_supported`: two-convolution body, T_M = 256, H <= 40,
-        16-bit data); anything else raises ValueError, as do mismatched H / D / dtype, a prefix shorter than the CNN's reach
+        bit.  Defined where the fused CNN launch runs (`ops.decode_cnn_supported`: two-convolution body, T_M in 64 / 96 / 128 /
+        256 -- the reference's grid up to the 256 the decode kernels take --, H <= 40, 16-bit data); anything else raises
+        ValueError, as do mismatched H / D / dtype, a prefix shorter than the CNN's reach
         and L_i >= capacity.
         `page_rows`: K / V in a pool of `pool_pages` pages of that many rows (default: enough for every slot at capacity; it
         may be far fewer), bitwise the contiguous session.  page_rows is a power of two and a multiple of the Performer chunk
@@ -423,13 +442,17 @@ class DecodeSession:
         if self.dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"a ragged session runs on 16-bit data (got {self.dtype})")
         self.T_M, self.k = int(pc.attention_predictor_length), int(pc.k)
+        why = _predictor_length_error(self.T_M)
+        if why is not None:
+            raise ValueError(why)
         self.LB = cnn_lookback(at.attention_predictor_cnn)
         convs = _cnn_convs(at)
         C = 2 * self.H                                                       # (the predictor's channel count: two per head)
         self.fused_cnn = _fused_cnn_ok(convs, C, self.H, self.T_M, self.dtype, self.LB)
         if not self.fused_cnn:
-            raise ValueError("a ragged session needs the fused CNN launch: a two-convolution predictor body, T_M = 256, "
-                             f"H <= 40 with H % 4 == 0, 16-bit data (got {len(convs)} convolutions, T_M = {self.T_M}, H = {self.H})")
+            raise ValueError("a ragged session needs the fused CNN launch: a two-convolution predictor body, T_M in "
+                             f"{' / '.join(str(t) for t in ops.DECODE_PREDICTOR_LENGTHS)}, H <= 40 with H % 4 == 0, 16-bit data "
+                             f"(got {len(convs)} convolutions, T_M = {self.T_M}, H = {self.H})")
         if not self.capacity <= at.v_eye_learned_causal.shape[2]:
             raise ValueError(f"capacity {self.capacity} beyond the value embedding ({at.v_eye_learned_causal.shape[2]} rows)")
         if max_step_rows is not None:

@@ -15,5 +15,5 @@ from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value
                         split_layernorm_c8, causal_conv_c8, causal_conv_c8_z, conv_z_supported, conv_c8_f32_supported, predictor_tail_z, pack_conv_weight, to_c8, from_c8,
                         predictor_mlp, predictor_mlp_supported, predictor_tail_select,
                         predictor_tail_select_supported, clear_prep_cache, prep_generation, pinned_prep, LazyTensor, realize,
-                        decode_stage, c8_window_shift, decode_fork, decode_fork_staging_bytes, decode_cnn_tail_select, decode_cnn_supported, decode_cnn_emits,
+                        decode_stage, c8_window_shift, decode_fork, decode_fork_staging_bytes, decode_cnn_tail_select, decode_cnn_supported, decode_cnn_emits, decode_tail_select_supported, DECODE_PREDICTOR_LENGTHS,
                         decode_gather_rows, decode_append_rows)

@@ -207,8 +207,9 @@ def _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, device):
 
 def _tail_consts(ln_w: torch.Tensor, ln_b: torch.Tensor, up: int, T_m: int, dt, device):
     """The tail's per-pixel constants (taps of the area resize, gamma, beta: `sea_predictor_tail_consts`) as a device table,
-    cached with the LayerNorm weights; None for shapes the table does not serve (T_m != 256, fp32 maps)."""
-    if T_m != 256 or dt not in (torch.float16, torch.bfloat16, torch.float32) or T_m % up:
+    cached with the LayerNorm weights: [3][64 E] words, E = ceil(T_m / 64) (at most 3 x 256); None for shapes the table does not
+    serve (T_m > 256)."""
+    if T_m > 256 or dt not in (torch.float16, torch.bfloat16, torch.float32) or T_m % up:
         return None
 
     def build():
@@ -241,8 +242,9 @@ def predictor_tail_z(z: torch.Tensor, conv_w: torch.Tensor, conv_b: torch.Tensor
 
 def predictor_tail_select_supported(y: torch.Tensor, H: int, T_m: int, decode: bool = False) -> bool:
     """Shapes csrc/sea_topk.hip: predictor_tail_select(_gen)_kernel take (see sea_predictor_tail_select in sea_hip.h):
-    any predictor length T_m % 4 == 0 up to 512 whose row fits the kernel's LDS plan; the decode form (`t_src_dev`) and the
-    register-resident kernel take T_m = 256 with H % 4 == 0."""
+    any predictor length T_m % 4 == 0 up to 512 whose row fits the kernel's LDS plan; the register-resident kernel takes
+    T_m = 256 with H % 4 == 0, and `decode=True` asks for that kernel's decode form (`t_src_dev`).  The decode form at any
+    length: `decode_tail_select_supported`."""
     if y.dtype == torch.float32:      # fp32 data (round 5): the T_m = 256 form on the fp32 MFMA, H <= 32, no decode form
         return (y.dim() == 5 or y.stride(1) == 1) and T_m == 256 and H % 4 == 0 and H <= 32 and not decode
     if not (y.dtype in (torch.float16, torch.bfloat16) and (y.dim() == 5 or y.stride(1) == 1)):
@@ -255,6 +257,15 @@ def predictor_tail_select_supported(y: torch.Tensor, H: int, T_m: int, decode: b
     E = E if E <= 4 else 6 if E <= 6 else 8
     zt = max((H + 15) // 16 * 16 * (W4 + 3) * 4 + 3 * 64 * E * 4, 8192)
     return zt + H * T_m * 2 + 12 * 1024 <= 160 * 1024
+
+
+def decode_tail_select_supported(y: torch.Tensor, H: int, T_m: int) -> bool:
+    """Shapes the decode form of `sea_predictor_tail_select` (`t_src_dev`) takes: 16-bit data; at T_m = 256 the
+    register-resident kernel (H % 4 == 0, as before), below it the general-length kernel wherever the row fits its LDS plan.
+    T_m = 256 with another H and T_m > 256 stay refused (no decode session runs there)."""
+    if y.dtype not in (torch.float16, torch.bfloat16):
+        return False
+    return predictor_tail_select_supported(y, H, T_m, decode=True) if T_m >= 256 else predictor_tail_select_supported(y, H, T_m)
 
 
 @_lib.device_guarded
@@ -271,7 +282,8 @@ def predictor_tail_select(y: Optional[torch.Tensor], conv_w: torch.Tensor, conv_
     `z` (with `y = None`, `map_dtype`): the 1x1 convolution's output (N, T, H, W4) fp32 from `causal_conv_c8_z`
     (the z form of `sea_predictor_tail_select`: the row's z tile is a copy instead of loads + MFMAs).
     Decode form (`sea_predictor_tail_select` with `t_src_dev`, a step replayed as a HIP graph): `t_src_dev` is a one-element int32
-    device tensor holding the sequence length (T_src is ignored) and `keep` a table over absolute row indices."""
+    device tensor holding the sequence length (T_src is ignored) and `keep` a table over absolute row indices; 16-bit data, any
+    served predictor length (`decode_tail_select_supported`)."""
     lib = _lib.load()
     H = conv_w.shape[0]
     if z is not None:
@@ -290,13 +302,14 @@ def predictor_tail_select(y: Optional[torch.Tensor], conv_w: torch.Tensor, conv_
             C = C8 * 8
         else:
             N, C, T, W4 = y.shape
-        assert conv_w.shape == (H, C) and W4 * up == T_m and predictor_tail_select_supported(y, H, T_m, decode=t_src_dev is not None)
+        assert conv_w.shape == (H, C) and W4 * up == T_m
+        assert decode_tail_select_supported(y, H, T_m) if t_src_dev is not None else predictor_tail_select_supported(y, H, T_m)
         dt, dev = y.dtype, y.device
     assert keep.dtype == torch.int32 and keep.is_contiguous() and (t_src_dev is not None or keep.shape in ((T,), (N, T)))
     _cw, cb, g, b, w16, Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, dev)
     if dt == torch.float32:           # fp32 data: the weights go in as the (C, Hpad) fp32 transposed copy, and the map is always written
         w16, Cp, lazy_probs = _cw, 0, False
-    tab = _tail_consts(ln_w, ln_b, up, T_m, dt, dev)
+    tab = _tail_consts(ln_w, ln_b, up, T_m, dt, dev) if T_m == 256 else None   # (the register-resident kernel reads it)
     if lazy_probs:
         assert t_src_dev is None
         if z is not None:
@@ -792,9 +805,16 @@ def decode_append_rows(slot: int, seen: int, rows: int, k_rows: Optional[torch.T
         c[0], c[1], c[2], _lib.stream_ptr()), "sea_decode_append_rows")
 
 
+DECODE_PREDICTOR_LENGTHS = (64, 96, 128, 256)
+
+
 def decode_cnn_supported(C: int, H: int, T_m: int, dtype) -> bool:
-    """Shapes `sea_decode_cnn_tail_select` is instantiated for (csrc/sea_topk.hip: launch_decode_cnn)."""
-    return (dtype in (torch.float16, torch.bfloat16) and T_m == 256 and H % 4 == 0 and 0 < H <= 40 and C == 2 * H and C % 8 == 0)
+    """Shapes `sea_decode_cnn_tail_select` is instantiated for (csrc/sea_topk.hip: launch_decode_cnn): the reference's grid of
+    predictor lengths up to 256 -- rows of W4 = T_m / 4 <= 64 pixels are one pass of the row convolution (`ConvRowC8`), and the
+    one-row decode attention takes T_m <= 256.  T_m = 256 keeps the row in registers; 64 / 96 / 128 pass it through a flat LDS
+    image (E = ceil(T_m / 64) = 1 or 2 pixels per lane), which fits beside the weight image for every H <= 40."""
+    return (dtype in (torch.float16, torch.bfloat16) and T_m in DECODE_PREDICTOR_LENGTHS and H % 4 == 0 and 0 < H <= 40
+            and C == 2 * H and C % 8 == 0)
 
 
 def decode_cnn_emits(C: int) -> bool:
@@ -811,12 +831,13 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
                            y1_scratch: Optional[torch.Tensor] = None):
     """One launch for a decoding step's predictor CNN (two 3 x 3 dilated causal convolutions, one new row each), tail,
     selection and the advance of the session's device counters (`sea_decode_cnn_tail_select`).  `conv1` / `conv2` are the
-    `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  x_new (N, s, C/8, 64, 8) and y2 of as many
-    elements, dense.  `counters` (3,) is the batch's one triple; an (N, 3) block holds one per sequence (`counter_stride` > 0:
+    `CausalConv2d` modules; rings and counters as include/sea_hip.h describes.  x_new (N, s, C/8, W4, 8) with W4 = T_m / 4 and
+    y2 of as many elements, dense; T_m in `DECODE_PREDICTOR_LENGTHS` (below 256 the kernel reads the per-pixel constants from
+    the `sea_predictor_tail_consts` table, which this wrapper always passes).  `counters` (3,) is the batch's one triple; an (N, 3) block holds one per sequence (`counter_stride` > 0:
     each workgroup reads its own sequence's, the launch advances all of them).
     One-row form (no `y1_scratch`; s = 1): `crow_out` (N, 2) receives the one-row CSR's crow; `col_out` (N, z_cap) int32 with
     `T_cap` (C <= 64, `decode_cnn_emits`): the CSR columns of the new row are written by this launch too.
-    Multi-row form (`y1_scratch` (N, s, 2, C/8, 64, 8) dense; 1 <= s <= 8, rings of at least 2 * dilation + s slots): a
+    Multi-row form (`y1_scratch` (N, s, 2, C/8, W4, 8) dense; 1 <= s <= 8, rings of at least 2 * dilation + s slots): a
     workgroup per (sequence, row); no crow and no columns (`crow_out` / `col_out` None): the caller runs the row scan
     (`csr_from_selection`).  Returns (probs (N,H,s,T_m) or None, (bits, row_nnz, head_off))."""
     lib = _lib.load()
@@ -844,6 +865,7 @@ def decode_cnn_tail_select(x_new: torch.Tensor, x_ring: torch.Tensor, y1_ring: t
     (w2p, _c), b2 = packs[1]
     _cw, cb, g, b, w16, Cp = _tail_pack(conv_w, conv_b, ln_w, ln_b, dt, dev)
     tab = _tail_consts(ln_w, ln_b, 4, T_m, dt, dev)
+    assert tab is not None
     probs = torch.empty((N, H, s, T_m), dtype=dt, device=dev) if want_probs else None
     Wb = (H * T_m + 31) // 32
     bits = torch.empty((N, s, Wb), dtype=torch.int32, device=dev)
