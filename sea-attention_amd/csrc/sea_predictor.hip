@@ -271,9 +271,10 @@ __global__ __launch_bounds__(256) void predictor_tail_mfma_kernel(TailParams p) 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int LDZ = p.W4 + 3;                     // z row: W4 pixels, [W4] = bias, [W4+1] = 0 (odd stride: no bank aliasing)
+  const TailLds L(p.H, p.W4, E);
+  const int LDZ = L.ldz;                        // z row: W4 pixels, [W4] = bias, [W4+1] = 0 (odd stride: no bank aliasing)
   float* s_z = reinterpret_cast<float*>(smem);  // HP x LDZ
-  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + ((p.H + 15) / 16) * 16 * LDZ);   // per-pixel constants [3][64 E]
+  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + L.tab);   // per-pixel constants [3][64 E]
   const int row = blockIdx.x;
   const int n = row / p.T, t = row - n * p.T;
   tail_z_tile<T>(p, s_z, n, t);
@@ -482,8 +483,7 @@ extern "C" int sea_split_layernorm(const void* x, int dtype, int64_t N, int64_t 
 template <typename T>
 static int launch_tail_mfma(const TailParams& p, dim3 grid, hipStream_t s) {
   const int E = (p.T_M + 63) / 64;
-  const int HP = ((p.H + 15) / 16) * 16;
-  const size_t lds = (size_t)HP * (p.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 64 * (E == 5 ? 6 : E == 7 ? 8 : E) * sizeof(uint32_t);
+  const size_t lds = TailLds(p.H, p.W4, E == 5 ? 6 : E == 7 ? 8 : E).zt_bytes();   // (no selection: no candidate list to make room for)
   if (lds > 64 * 1024 || p.W4 + 1 >= 1024 || p.W4 * p.UP + 2 > 2 * p.T_M) return SEA_EUNSUPPORTED;   // 10-bit taps, windows of <= 3 of them
 #define SEA_TAILM(EE) hipLaunchKernelGGL((predictor_tail_mfma_kernel<T, EE>), grid, dim3(256), lds, s, p)
   switch (E) {

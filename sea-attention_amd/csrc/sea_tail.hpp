@@ -357,4 +357,38 @@ struct TailRow {
   }
 };
 
+constexpr int TK_CAND_CAP = 1024;  // sea_topk.hip's select_body: threshold-bin keys resolved by direct ranking (more -> multi-pass fallback)
+
+// ---- the dynamic LDS of the tail kernels, laid out ONCE: every launcher sizes its launch and every kernel finds its pieces here --
+//   z tile, 16 ceil(H / 16) rows of W4 + 3 words | constants table [3][64 tab_e] words (tab_e = 0: read from global memory) |
+//   flat 16-bit image of the row's map, flat_bytes rounded up to 16 (0: the T_m = 256 forms keep the map in registers).
+// The fused tail + selection kernels lend z + table to select_body's candidate list (2 TK_CAND_CAP words) once the heads are
+// done, so there the flat image starts behind the larger of the two and `bytes` is never below the list; predictor_tail_mfma_kernel,
+// which selects nothing, takes zt_bytes().  Offsets in 4-byte words from the start of the dynamic LDS.
+struct TailLds {
+  int ldz, tab, zt, flat;   // z row stride; offset of the table = words of the z tile; z + table; offset of the flat image
+  size_t bytes;
+  // `tab` alone, for the T_m = 256 body, which needs nothing else at run time.  Written out a second time, and pinned to the
+  // constructor's below: taken from a constructed object there -- or with the constructor calling this -- hipcc moves one scalar
+  // instruction in the twelve decode_cnn_tail_select_rows_kernel<.., EG = 0>, which this way stay the code they were.
+  static __host__ __device__ constexpr int z_words(int H, int W4) { return ((H + 15) / 16) * 16 * (W4 + 3); }
+  __host__ __device__ constexpr TailLds(int H, int W4, int tab_e, size_t flat_bytes = 0)
+      : ldz(W4 + 3), tab(((H + 15) / 16) * 16 * (W4 + 3)), zt(tab + TAIL_TAB_ROWS * 64 * tab_e),
+        flat(zt > 2 * TK_CAND_CAP ? zt : 2 * TK_CAND_CAP),
+        bytes((size_t)flat * sizeof(uint32_t) + ((flat_bytes + 15) & ~(size_t)15)) {}
+  __host__ __device__ constexpr size_t zt_bytes() const { return (size_t)zt * sizeof(uint32_t); }
+};
+// (the formulas the launchers and kernels each carried, in bytes)
+static_assert(TailLds(32, 64, 4).tab == TailLds::z_words(32, 64) && TailLds(12, 16, 0).tab == TailLds::z_words(12, 16), "one z tile");
+static_assert(TailLds(32, 64, 4).tab * 4 == 8576 && TailLds(32, 64, 4).zt_bytes() == 8576 + 3072 && TailLds(32, 64, 4).bytes == 11648 &&
+              TailLds(32, 64, 4).ldz == 67, "T_m = 256, H = 32: z tile 8576 + table 3072");
+static_assert(TailLds(4, 64, 4).tab * 4 == 4288 && TailLds(4, 64, 4).zt_bytes() == 7360 && TailLds(4, 64, 4).bytes == 8192,
+              "T_m = 256, H = 4: z + table 7360 < the 8192 of the candidate list");
+static_assert(TailLds(12, 16, 1, 1536).tab * 4 == 1216 && TailLds(12, 16, 1, 1536).zt_bytes() == 1216 + 768 &&
+              TailLds(12, 16, 1, 1536).flat * 4 == 8192 && TailLds(12, 16, 1, 1536).bytes == 9728, "general form, H = 12, T_m = 64, E = 1");
+static_assert(TailLds(12, 16, 0, 1536).zt_bytes() == 1216 && TailLds(12, 16, 0, 1536).flat * 4 == 8192 &&
+              TailLds(12, 16, 0, 1536).bytes == 9728, "decode general form (table in global memory), H = 12, T_m = 64");
+static_assert(TailLds(64, 128, 8, 1).flat * 4 == 64 * 131 * 4 + 6144 && TailLds(64, 128, 8, 1).bytes == 64 * 131 * 4 + 6144 + 16,
+              "z + table above the candidate list: the flat image follows them, rounded up to 16 bytes");
+
 }  // namespace sea

@@ -99,8 +99,6 @@ __device__ inline int block_excl_scan(int v, int* s_wave /*[TK_WAVES]*/, int* to
   return base + incl - v;
 }
 
-constexpr int TK_CAND_CAP = 1024;  // threshold-bin keys resolved by direct ranking (more -> multi-pass fallback)
-
 // Slow path, rarely taken (massive ties / all-equal rows / overfull threshold bin): classic MSB radix passes
 // followed by an ordered tie scan.  It re-reads the row from memory in every pass instead of using the caller's
 // register-resident keys, so it adds nothing to the register budget of the hot path.
@@ -594,57 +592,26 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkParams p) {
 // moved into the dead z tile so that six workgroups' LDS fits) 412 us; with two 16-bit keys per register and the ragged form
 // (78 registers uncapped) capped at 72 (4 spills), 7 waves: 399 us.  64 registers: 40 spills, 574 us.  H <= 16: 76 -> 72,
 // 6 -> 7 waves, -5 %.  H = 40: 97-108 -> 90-96, 4 -> 5 waves, -7 %.
-// (the body of predictor_tail_select_kernel below as a device function, for the fused decode kernel.  The prefill kernel keeps
-// its own copy on purpose: routed through this function hipcc allocates it differently -- 9 spilled vector registers
-// instead of 3 at its 72-register cap, H = 32 -- and that kernel is 17 % of the headline step.)
+// ONE body, sea_tail_select_row.inc, for the prefill kernels (16-bit and fp32 data) and -- as the device function tail_select_row
+// -- for the fused decode kernels: a decode session's rows are bitwise the stateless forward's because both run that very text.
+// The text is stamped into the kernels rather than called from them, because hipcc allocates a kernel differently once its two
+// parameter structs reach the body through a function (kernel-resource-usage remarks of every kernel of this file against the
+// two written copies this replaces; no GPU needed):
+//   * by reference, predictor_tail_select_kernel<T, 32, false> -- 17 % of the headline step, 72 registers, 7 waves -- goes from
+//     1 spilled vector register / 8 bytes of scratch per lane to 7 / 28;
+//   * by value the vector registers, spills, scratch and occupancy of the twelve 16-bit kernels hold, but not their code: the
+//     spilled scalar registers move in seven of them (EPT 32: 62 -> 66, EPT 64: 198 -> 204) and in 23 of the 48 general-length
+//     kernels (E = 1, EPT 64: 184 -> 202), where <__half, 3, 8> and <__half, 3, 16> go from 73 to 72 vector registers;
+//   * the decode kernels keep the reference they always had: by value decode_cnn_tail_select_kernel<.., EG = 0> moves (EPT 4
+//     and 8: 111 vector + 4 accumulator registers, EPT 32 with NT = 3: 254 + 20).
+// The .inc expects T, EPT, FULL and tp, p, s_z, row in scope.
+// fp32 data (the reference's fp32 measurement protocol, benchmark_bert.py:196-239): the z tile runs on the fp32 MFMA
+// (tail_z_tile<float>), the map is fp32 and IS written, the keys are the 32-bit patterns of the probabilities (select_body's
+// unpacked form, whose slow path re-reads the row of the map this launch has just stored).  Bit-identical to
+// predictor_tail_mfma_kernel<float> followed by topk_select_kernel<float>: same device functions, same key layout.
 template <typename T, int EPT, bool FULL>
 __device__ __forceinline__ void tail_select_row(const TailParams& tp, const TopkParams& p, float* s_z, int row) {
-  constexpr int R = EPT / 4, E = 4;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = row / tp.T, t = row - n * tp.T;
-  constexpr int LDZ = 64 + 3;      // = W4 + 3 (sea_predictor_tail_select checks W4 == 64): z-row offsets become immediates
-#ifdef SEA_STAMP
-  unsigned long long _tprev = __builtin_amdgcn_s_memtime();
-#endif
-  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + ((tp.H + 15) / 16) * 16 * LDZ);   // per-pixel constants [3][64 E]
-  TailRow<T, E> tr;
-  if (tp.tab) tr.load_global(tp.tab, lane);                        // (block-uniform) the table was computed once per weight set
-  tail_z_tile<T>(tp, s_z, n, t);
-  if (!tp.tab) tail_consts_fill<T>(tp, s_tab, 64 * E);
-  __syncthreads();
-  if (!tp.tab) tr.load(s_tab, lane);
-  STAMP(8);   // z tile (MFMA) + per-pixel constants
-  uint32_t key[EPT / 2];                                           // two 16-bit keys per register (select_body, K16)
-  const int mine = FULL ? R : max(0, (tp.H - wv + 3) / 4);         // heads wv, wv + 4, ... of this wave (wave-uniform)
-  auto batch = [&](auto j0c, auto nbc) {                           // heads 4 (J0 + b) + wv, b < NBC, through one batch
-    constexpr int J0 = decltype(j0c)::value, NBC = decltype(nbc)::value;
-    float a[NBC][E];
-    const int nb = min(NBC, mine - J0);
-    if (nb > 0) {
-      // T_M == 256 == 64 E here (sea_predictor_tail_select checks): the full-row form, without its ragged twin in the kernel
-      tr.template heads_impl<true>(tp, lane, nb, [&](int b) { return s_z + (4 * (J0 + b) + wv) * LDZ; },
-                                   [&](int b) { return (((int64_t)n * tp.H + (4 * (J0 + b) + wv)) * tp.T + t) * (64 * E); }, a);
-    }
-#pragma unroll
-    for (int b = 0; b < NBC; ++b) {  // probabilities are >= +0: the 16-bit pattern the map stores orders like the number
-      key[2 * (J0 + b)] = (b < nb) ? pack2<T>(a[b][0], a[b][1]) : 0u;
-      key[2 * (J0 + b) + 1] = (b < nb) ? pack2<T>(a[b][2], a[b][3]) : 0u;
-    }
-  };
-  static_assert(R <= 16, "two batches of eight heads per wave");
-  if constexpr (R <= 8) {
-    batch(std::integral_constant<int, 0>{}, std::integral_constant<int, R>{});
-  } else {
-    batch(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{});
-    batch(std::integral_constant<int, 8>{}, std::integral_constant<int, R - 8>{});
-  }
-  STAMP(9);   // 8 heads per wave: resize + LayerNorm + softmax + store
-  // H <= 64: sea_predictor_tail_select checks.  The z tile and the constants table are dead once every wave has left the head
-  // loop, i.e. from select_body's first barrier on: the candidate list lives there (the launcher sizes the dynamic LDS for both).
-  // The packed-key selection never re-reads the map (its slow path works on the registers too): tp.probs may be null.
-  select_body<T, EPT, false, FULL, 64, true, true>(p, key, 0ull, n, t, row, (const T*)nullptr, reinterpret_cast<uint32_t*>(s_z));
+#include "sea_tail_select_row.inc"
 }
 
 template <typename T, int EPT, bool FULL>
@@ -655,98 +622,19 @@ template <typename T, int EPT, bool FULL>
 #define SEA_TSEL_OCC16 7
 #endif
 __global__ __launch_bounds__(TK_THREADS, EPT <= 16 ? SEA_TSEL_OCC16 : EPT == 32 ? SEA_TSEL_OCC32 : EPT == 40 ? 5 : 1) void predictor_tail_select_kernel(TailParams tp, TopkParams p) {
-  constexpr int R = EPT / 4, E = 4;
-  extern __shared__ __attribute__((aligned(16))) float s_z[];     // HP x (W4 + 3)
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  extern __shared__ __attribute__((aligned(16))) float s_z[];     // TailLds(H, 64, 4)
   const int row = blockIdx.x;
-  const int n = row / tp.T, t = row - n * tp.T;
-  constexpr int LDZ = 64 + 3;      // = W4 + 3 (sea_predictor_tail_select checks W4 == 64): z-row offsets become immediates
-#ifdef SEA_STAMP
-  unsigned long long _tprev = __builtin_amdgcn_s_memtime();
-#endif
-  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + ((tp.H + 15) / 16) * 16 * LDZ);   // per-pixel constants [3][64 E]
-  TailRow<T, E> tr;
-  if (tp.tab) tr.load_global(tp.tab, lane);                        // (block-uniform) the table was computed once per weight set
-  tail_z_tile<T>(tp, s_z, n, t);
-  if (!tp.tab) tail_consts_fill<T>(tp, s_tab, 64 * E);
-  __syncthreads();
-  if (!tp.tab) tr.load(s_tab, lane);
-  STAMP(8);   // z tile (MFMA) + per-pixel constants
-  uint32_t key[EPT / 2];                                           // two 16-bit keys per register (select_body, K16)
-  const int mine = FULL ? R : max(0, (tp.H - wv + 3) / 4);         // heads wv, wv + 4, ... of this wave (wave-uniform)
-  auto batch = [&](auto j0c, auto nbc) {                           // heads 4 (J0 + b) + wv, b < NBC, through one batch
-    constexpr int J0 = decltype(j0c)::value, NBC = decltype(nbc)::value;
-    float a[NBC][E];
-    const int nb = min(NBC, mine - J0);
-    if (nb > 0) {
-      // T_M == 256 == 64 E here (sea_predictor_tail_select checks): the full-row form, without its ragged twin in the kernel
-      tr.template heads_impl<true>(tp, lane, nb, [&](int b) { return s_z + (4 * (J0 + b) + wv) * LDZ; },
-                                   [&](int b) { return (((int64_t)n * tp.H + (4 * (J0 + b) + wv)) * tp.T + t) * (64 * E); }, a);
-    }
-#pragma unroll
-    for (int b = 0; b < NBC; ++b) {  // probabilities are >= +0: the 16-bit pattern the map stores orders like the number
-      key[2 * (J0 + b)] = (b < nb) ? pack2<T>(a[b][0], a[b][1]) : 0u;
-      key[2 * (J0 + b) + 1] = (b < nb) ? pack2<T>(a[b][2], a[b][3]) : 0u;
-    }
-  };
-  static_assert(R <= 16, "two batches of eight heads per wave");
-  if constexpr (R <= 8) {
-    batch(std::integral_constant<int, 0>{}, std::integral_constant<int, R>{});
-  } else {
-    batch(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{});
-    batch(std::integral_constant<int, 8>{}, std::integral_constant<int, R - 8>{});
-  }
-  STAMP(9);   // 8 heads per wave: resize + LayerNorm + softmax + store
-  // H <= 64: sea_predictor_tail_select checks.  The z tile and the constants table are dead once every wave has left the head
-  // loop, i.e. from select_body's first barrier on: the candidate list lives there (the launcher sizes the dynamic LDS for both).
-  // The packed-key selection never re-reads the map (its slow path works on the registers too): tp.probs may be null.
-  select_body<T, EPT, false, FULL, 64, true, true>(p, key, 0ull, n, t, row, (const T*)nullptr, reinterpret_cast<uint32_t*>(s_z));
+#include "sea_tail_select_row.inc"
 }
 
-// ---- fp32 DATA (round 5): the same fusion for the reference's fp32 measurement protocol (benchmark_bert.py:196-239) ----------
-// Same structure and layouts; the z tile runs on the fp32 MFMA (tail_z_tile<float>), the map is fp32 and IS written (nothing
-// lazy about the fp32 path), the keys are the 32-bit patterns of the probabilities (select_body's unpacked form, whose slow
-// path re-reads the row of the map this launch has just stored).  Bit-identical to predictor_tail_mfma_kernel<float> followed
-// by topk_select_kernel<float>: same device functions, same key layout (chunk 256 j + tid = head 4 j + wave, pixels 4 lane ..).
 template <int EPT>
 __global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_f32_kernel(TailParams tp, TopkParams p) {
   using T = float;
-  constexpr int R = EPT / 4, E = 4;
+  constexpr bool FULL = false;
+  static_assert(EPT <= 32, "one batch of eight heads per wave (H <= 32)");
   extern __shared__ __attribute__((aligned(16))) float s_z[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row = blockIdx.x;
-  const int n = row / tp.T, t = row - n * tp.T;
-  constexpr int LDZ = 64 + 3;
-  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + ((tp.H + 15) / 16) * 16 * LDZ);
-  TailRow<T, E> tr;
-  if (tp.tab) tr.load_global(tp.tab, lane);
-  tail_z_tile<T>(tp, s_z, n, t);
-  if (!tp.tab) tail_consts_fill<T>(tp, s_tab, 64 * E);
-  __syncthreads();
-  if (!tp.tab) tr.load(s_tab, lane);
-  uint32_t key[EPT];
-  const int mine = max(0, (tp.H - wv + 3) / 4);
-  auto batch = [&](auto j0c, auto nbc) {
-    constexpr int J0 = decltype(j0c)::value, NBC = decltype(nbc)::value;
-    float a[NBC][E];
-    const int nb = min(NBC, mine - J0);
-    if (nb > 0) {
-      tr.template heads_impl<true>(tp, lane, nb, [&](int b) { return s_z + (4 * (J0 + b) + wv) * LDZ; },
-                                   [&](int b) { return (((int64_t)n * tp.H + (4 * (J0 + b) + wv)) * tp.T + t) * (64 * E); }, a);
-    }
-#pragma unroll
-    for (int b = 0; b < NBC; ++b)
-#pragma unroll
-      for (int e = 0; e < E; ++e) key[4 * (J0 + b) + e] = (b < nb) ? f2key(a[b][e]) : 0u;
-  };
-  static_assert(R <= 8, "one batch of eight heads per wave (H <= 32)");
-  batch(std::integral_constant<int, 0>{}, std::integral_constant<int, R>{});
-  const T* base = reinterpret_cast<const T*>(tp.probs) + (int64_t)n * p.sn + (int64_t)t * p.st;
-  select_body<T, EPT, false, false, 64, true, false, false>(p, key, 0ull, n, t, row, base, reinterpret_cast<uint32_t*>(s_z));
+#include "sea_tail_select_row.inc"
 }
 
 // ---- the same fusion for ANY predictor length (T_m % 4 == 0, T_m <= 512; the reference's own grid runs 64 / 96 / 128 / 384:
@@ -754,107 +642,24 @@ __global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_f32_kernel(T
 // wv, wv + 4, ..., lane <-> E consecutive pixels); the rounded probabilities go through a flat 16-bit image of the row in
 // LDS ([head][pixel], 2 H T_m bytes) from which every thread takes the selection's layout (chunk c = 256 j + tid <-> flat
 // pixels 4c .. 4c+3) as packed keys.  Same arithmetic as predictor_tail_mfma_kernel + topk_select_kernel: bit-identical.
-// tail_select_row_gen below is this body as a device function for the fused decode kernels, and a decode session's rows are
-// bitwise this kernel's: the two CHANGE TOGETHER (the lane <-> pixel map, the batches of NBC heads, the rounding into the flat
-// image and the key order of select_body).
-template <typename T, int E, int EPT>
-__global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_gen_kernel(TailParams tp, TopkParams p) {
-  constexpr int R = EPT / 4;
-  constexpr int NBC = E >= 6 ? 4 : 8;                             // heads per batch of the tail stage (register budget)
-  extern __shared__ __attribute__((aligned(16))) float s_z[];     // HP x (W4 + 3) | constants [3][64 E] | flat map (H T_m 16-bit)
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int row = blockIdx.x;
-  const int n = row / tp.T, t = row - n * tp.T;
-  const int LDZ = tp.W4 + 3;
-  uint32_t* s_tab = reinterpret_cast<uint32_t*>(s_z + ((tp.H + 15) / 16) * 16 * LDZ);
-  // the flat image sits behind z + table, or behind the 8 KB the candidate list takes over from them if they are smaller
-  const int zt_words = ((tp.H + 15) / 16) * 16 * LDZ + TAIL_TAB_ROWS * 64 * E;
-  unsigned short* s_flat = reinterpret_cast<unsigned short*>(s_z + max(zt_words, 2 * TK_CAND_CAP));
-  tail_z_tile<T>(tp, s_z, n, t);
-  tail_consts_fill<T>(tp, s_tab, 64 * E);
-  __syncthreads();
-  TailRow<T, E> tr;
-  tr.load(s_tab, lane);
-  const int mine = max(0, (tp.H - wv + 3) / 4);                   // heads wv, wv + 4, ... of this wave
-  for (int k0 = 0; k0 < mine; k0 += NBC) {
-    float a[NBC][E];
-    const int nb = min(NBC, mine - k0);
-    tr.heads(tp, lane, nb, [&](int b) { return s_z + (wv + 4 * (k0 + b)) * LDZ; },
-             [&](int b) { return (((int64_t)n * tp.H + (wv + 4 * (k0 + b))) * tp.T + t) * tp.T_M; }, a);
-#pragma unroll
-    for (int b = 0; b < NBC; ++b) {
-      if (b < nb) {
-        unsigned short* fr = s_flat + (wv + 4 * (k0 + b)) * tp.T_M + lane * E;
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-          if (lane * E + e < tp.T_M) fr[e] = __builtin_bit_cast(unsigned short, from_f<T>(a[b][e]));
-      }
-    }
-  }
-  __syncthreads();
-  uint32_t key[EPT / 2];                                           // two 16-bit keys per register (select_body, K16)
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const int c = j * TK_THREADS + tid;
-    uint2 v = make_uint2(0u, 0u);
-    if (c < p.nchunks) v = *reinterpret_cast<const uint2*>(s_flat + 4 * c);
-    key[2 * j] = v.x;
-    key[2 * j + 1] = v.y;
-  }
-  select_body<T, EPT, false, false, 64, true, true, false>(p, key, 0ull, n, t, row, (const T*)nullptr, reinterpret_cast<uint32_t*>(s_z));
-}
-
-// (the body of predictor_tail_select_gen_kernel above as a device function, for the fused decode kernels at W4 < 64: the
-// general-length twin of tail_select_row.  One difference: the per-pixel constants come from the table in global memory
-// (sea_predictor_tail_consts: [3][64 E] words) ONLY -- no fill path, no table in LDS; s_z: HP x (W4 + 3) | flat map (H T_m
-// 16-bit).  E = ceil(T_m / 64) pixels per lane and the batches of NBC heads fix the reduction order to the prefill kernel's at
-// the same T_m: the same bits.  The prefill kernel keeps its own copy, like predictor_tail_select_kernel: routed through this
-// function hipcc allocates it differently (E = 1: 66 -> 68 vector registers, E = 2: 107 -> 110, EPT 32: 93 -> 92).)
+// ONE body again, sea_tail_select_row_gen.inc, stamped into the prefill kernel and into tail_select_row_gen for the fused decode
+// kernels at W4 < 64, for the reason given at tail_select_row (E = ceil(T_m / 64) pixels per lane and the batches of NBC heads
+// fix the reduction order: the same bits at the same T_m).  TAB_LDS: where the per-pixel constants come from -- the workgroup
+// fills the table in LDS (prefill), or a lane reads the table in global memory, computed once per weight set
+// (sea_predictor_tail_consts: [3][64 E] words; decode: no fill, no table in LDS).  The .inc expects T, E, EPT, TAB_LDS and tp, p,
+// s_z, row in scope.
 template <typename T, int E, int EPT>
 __device__ __forceinline__ void tail_select_row_gen(const TailParams& tp, const TopkParams& p, float* s_z, int row) {
-  constexpr int R = EPT / 4;
-  constexpr int NBC = E >= 6 ? 4 : 8;                             // heads per batch of the tail stage (register budget)
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = row / tp.T, t = row - n * tp.T;
-  const int LDZ = tp.W4 + 3;
-  // the flat image sits behind the z tile, or behind the 8 KB the candidate list takes over from it if that is smaller
-  const int zt_words = ((tp.H + 15) / 16) * 16 * LDZ;
-  unsigned short* s_flat = reinterpret_cast<unsigned short*>(s_z + max(zt_words, 2 * TK_CAND_CAP));
-  TailRow<T, E> tr;
-  tr.load_global(tp.tab, lane);                                   // the table was computed once per weight set (launcher: not null)
-  tail_z_tile<T>(tp, s_z, n, t);
-  __syncthreads();
-  const int mine = max(0, (tp.H - wv + 3) / 4);                   // heads wv, wv + 4, ... of this wave
-  for (int k0 = 0; k0 < mine; k0 += NBC) {
-    float a[NBC][E];
-    const int nb = min(NBC, mine - k0);
-    tr.heads(tp, lane, nb, [&](int b) { return s_z + (wv + 4 * (k0 + b)) * LDZ; },
-             [&](int b) { return (((int64_t)n * tp.H + (wv + 4 * (k0 + b))) * tp.T + t) * tp.T_M; }, a);
-#pragma unroll
-    for (int b = 0; b < NBC; ++b) {
-      if (b < nb) {
-        unsigned short* fr = s_flat + (wv + 4 * (k0 + b)) * tp.T_M + lane * E;
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-          if (lane * E + e < tp.T_M) fr[e] = __builtin_bit_cast(unsigned short, from_f<T>(a[b][e]));
-      }
-    }
-  }
-  __syncthreads();
-  uint32_t key[EPT / 2];                                           // two 16-bit keys per register (select_body, K16)
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const int c = j * TK_THREADS + tid;
-    uint2 v = make_uint2(0u, 0u);
-    if (c < p.nchunks) v = *reinterpret_cast<const uint2*>(s_flat + 4 * c);
-    key[2 * j] = v.x;
-    key[2 * j + 1] = v.y;
-  }
-  select_body<T, EPT, false, false, 64, true, true, false>(p, key, 0ull, n, t, row, (const T*)nullptr, reinterpret_cast<uint32_t*>(s_z));
+  constexpr bool TAB_LDS = false;
+#include "sea_tail_select_row_gen.inc"
+}
+
+template <typename T, int E, int EPT>
+__global__ __launch_bounds__(TK_THREADS) void predictor_tail_select_gen_kernel(TailParams tp, TopkParams p) {
+  constexpr bool TAB_LDS = true;
+  extern __shared__ __attribute__((aligned(16))) float s_z[];     // TailLds(H, W4, E, 2 H T_m)
+  const int row = blockIdx.x;
+#include "sea_tail_select_row_gen.inc"
 }
 
 // ---- crow = exclusive scan of row_nnz ------------------------------------------------------------
@@ -1431,8 +1236,7 @@ extern "C" int sea_mask_to_bits(const void* mask, int dtype, int64_t N, int64_t 
 template <typename T>
 static int launch_tail_select(const TailParams& tp, const TopkParams& p, int64_t rows, hipStream_t s) {
   const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
-  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
-  if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);     // the selection's candidate list re-uses it
+  const size_t lds = TailLds(tp.H, tp.W4, 4).bytes;
   dim3 grid((unsigned)rows), block(TK_THREADS);
 #define SEA_TSEL(EE)                                                                                              \
   do {                                                                                                            \
@@ -1453,8 +1257,7 @@ static int launch_tail_select(const TailParams& tp, const TopkParams& p, int64_t
 
 static int launch_tail_select_f32(const TailParams& tp, const TopkParams& p, int64_t rows, hipStream_t s) {
   const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
-  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);
-  if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
+  const size_t lds = TailLds(tp.H, tp.W4, 4).bytes;
   dim3 grid((unsigned)rows), block(TK_THREADS);
   if (ept <= 4) hipLaunchKernelGGL((predictor_tail_select_f32_kernel<4>), grid, block, lds, s, tp, p);
   else if (ept <= 8) hipLaunchKernelGGL((predictor_tail_select_f32_kernel<8>), grid, block, lds, s, tp, p);
@@ -1469,10 +1272,7 @@ static int launch_tail_select_gen(const TailParams& tp, const TopkParams& p, int
   const int ept = ((p.nchunks + TK_THREADS - 1) / TK_THREADS) * 4;
   const int E = (tp.T_M + 63) / 64;
   const int EE = E <= 4 ? E : E <= 6 ? 6 : 8;        // the widths launch_tail_mfma instantiates (same lane <-> pixel map: same bits)
-  // z tile + constants table (the candidate list of the selection re-uses them: at least its 8 KB), then the flat image
-  size_t zt = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float) + (size_t)TAIL_TAB_ROWS * 64 * EE * sizeof(uint32_t);
-  if (zt < 2 * TK_CAND_CAP * sizeof(uint32_t)) zt = 2 * TK_CAND_CAP * sizeof(uint32_t);
-  const size_t lds = zt + (((size_t)p.M * 2 + 15) & ~(size_t)15);
+  const size_t lds = TailLds(tp.H, tp.W4, EE, (size_t)p.M * 2).bytes;
   if (lds + 12 * 1024 > 160 * 1024) return SEA_EUNSUPPORTED;
   dim3 grid((unsigned)rows), block(TK_THREADS);
 #define SEA_TSG(EV, PV)                                                                                            \
@@ -1570,10 +1370,8 @@ static int launch_decode_cnn(const DecodeCnnParams& dp, const TailParams& tp, co
   // eg: 0 = the register-resident T_m = 256 tail (tail_select_row); else the general-length tail (tail_select_row_gen) with
   // eg = ceil(T_m / 64) pixels per lane, as the prefill kernel of the same T_m has them (same lane <-> pixel map: same bits)
   const int eg = tp.W4 == 64 ? 0 : (tp.T_M + 63) / 64;
-  size_t lds = (size_t)(((tp.H + 15) / 16) * 16) * (tp.W4 + 3) * sizeof(float);
-  if (eg == 0) lds += (size_t)TAIL_TAB_ROWS * 256 * sizeof(uint32_t);      // (general-length form: the table stays in global memory)
-  if (lds < 2 * TK_CAND_CAP * sizeof(uint32_t)) lds = 2 * TK_CAND_CAP * sizeof(uint32_t);
-  if (eg != 0) lds += ((size_t)p.M * 2 + 15) & ~(size_t)15;                // the flat 16-bit image of the row, behind z / the candidate list
+  // (general-length form: the table stays in global memory, and the row goes through its flat 16-bit image)
+  size_t lds = eg == 0 ? TailLds(tp.H, tp.W4, 4).bytes : TailLds(tp.H, tp.W4, 0, (size_t)p.M * 2).bytes;
   const int nt = (dp.C + 15) / 16, kch = (dp.C + 31) / 32;
   const size_t wimg = (size_t)(16 * nt) * 9 * kch * 64;                    // the weight image overlays the (later) z tile
   if (lds < wimg) lds = wimg;
