@@ -264,28 +264,34 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * Thinned pixels are stepped as the decode form of sea_csr_emit steps them (the key alone: the capacity changes no id;
  * H * T_src < 2^31).  The stateless fused form steps head * T_src + key like the reference and, like sea_csr_emit, refuses
  * H * T_src >= 2^24 (SEA_EUNSUPPORTED).
- * T_dst <= 8 new rows per sequence, no probs_out; 16-bit d = 64 / 80 / 128 or fp32 d = 32 / 64 (the fused forms), else
- * SEA_EUNSUPPORTED (run the decode form of sea_csr_emit + the plain form).  The lane groups of a workgroup that have no row
+ * T_dst <= 8 new rows per sequence; 16-bit d = 64 / 80 / 128 or fp32 d = 32 / 64 (the fused forms), else
+ * SEA_EUNSUPPORTED (run the decode form of sea_csr_emit + the plain form).
+ * probs_out is taken (every decode form: one length or one per sequence, paged or not, T_dst = 1 .. 8): entry e of a row
+ * receives rs * softmax_e at the slot `col` has for it -- or would have: with write_cols = 0 the values are written all the
+ * same -- with the plain form's expression, so the values are that form's bit for bit.  probs_stride_n >= col_stride_n
+ * (SEA_EINVAL otherwise).  Only the slots of real entries are written: an empty head, the slots behind a row and a sequence
+ * that sits out leave probs_out as it was (a caller that replays the launch keeps one buffer and never clears it).  The lane groups of a workgroup that have no row
  * touch the K / V rows of the expanded lists before the one group per row starts its dependent walk (what the unfused
  * kernel does from `col`).  Same arithmetic in the same order as sea_csr_emit + the plain form: the step stays bitwise
  * the stateless forward; the emit launch (or the emit phase of sea_decode_cnn_tail_select: pass col = NULL there) and the
  * crow -> col -> K / V load chain leave the position's critical path.
  *
  * A length PER SEQUENCE, t_src_stride > 0 (the decode form only; 0 = one length for the batch): sequence n's row widths follow
- * t_src_dev[n * t_src_stride]; T_src is the caches' capacity the ids are encoded with.  The gather path, no probs_out, no
- * plan; bits and t_src_dev are required (NULL: SEA_EINVAL, as is a negative stride).  Per workgroup the length is one scalar
+ * t_src_dev[n * t_src_stride]; T_src is the caches' capacity the ids are encoded with.  The gather path, no plan (probs_out
+ * as in the decode form above); bits and t_src_dev are required (NULL: SEA_EINVAL, as is a negative stride).  Per workgroup the length is one scalar
  * load: the same kernels, the same bits per sequence as the shared-length form at that sequence's length.
  *
  * PAGED K / V, block_table != NULL (the one-row decode form with a length per sequence: T_dst = 1, 16-bit data, D in {64, 80,
  * 128}, T_m <= 256).  k / v are the K / V halves of a page pool (P, H, page_rows, D) with element strides [page, head, row];
  * sequence n's key r lives in page block_table[n * table_stride + r / page_rows] (int32, on the device) at row r % page_rows.
- * Keys and column ids stay logical: ids are head * T_src + key as in the contiguous form, and the context rows are bitwise
- * that form's.  page_rows: a power of two and a multiple of the Performer chunk of D (sea_performer_chunk_rows);
+ * Keys and column ids stay logical: ids are head * T_src + key as in the contiguous form, and the context rows -- and, with
+ * probs_out, the per-entry values -- are bitwise that form's.  page_rows: a power of two and a multiple of the Performer chunk of D (sea_performer_chunk_rows);
  * table_stride >= ceil(T_src / page_rows), at most 4096 pages per table row; the page stride must stay below 4 GB and a page
  * below 2 GB.  Null pointers, t_src_stride = 0, a bad page size or table stride: SEA_EINVAL; other dtypes / D / shapes:
  * SEA_EUNSUPPORTED.  Without a table, page_rows and table_stride must be 0 (else SEA_EINVAL).
  * A sequence that sits out the step (per-sequence decode form: t_src_dev[n * t_src_stride] < 0, see sea_decode_cnn_tail_select):
- * its workgroups read no block table entry, K or V row and store ZEROS to its output rows (no row scale, no mix with avg) --
+ * its workgroups read no block table entry, K or V row, write nothing to probs_out and store ZEROS to its output rows (no row
+ * scale, no mix with avg) --
  * the one-row kernel in all its forms, the paged ones included, and the T_dst = 2 .. 8 lane-group forms.  The test is on the
  * length the workgroup loads anyway, at its first use: q, crow and head_off of the sequence (valid memory; crow / head_off as
  * the selection launch wrote its empty rows) may have been read by then.

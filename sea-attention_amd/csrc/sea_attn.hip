@@ -641,7 +641,11 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
 // PAGED: K / V in a page pool (AttnParams::table).  The sequence's block-table row is staged in LDS behind the V rows at kernel
 // start (its first ceil(T_src / page_rows) entries; dynamic LDS sized for the capacity's), and phase C translates each key to
 // (page, row) from there: the page term is a 64-bit product (page x page bytes overflows 32 bits), the row term stays 32-bit
-template <typename T, typename TO, int LPR, bool X80 = false, bool PAGED = false>
+// WP: also write the per-entry values rs * softmax to p.probs, at the slots `col` has (or would have: write_cols = 0).  Phase C's
+// sub == 0 lane leaves the raw score at the slot of every real entry -- the padded slots total .. padded-1 belong to the next head
+// -- and, once (m, l) are final, the same thread turns it into the probability with the expression of sparse_attn_rows_kernel's
+// WP pass (a thread sees its own stores: no fence).  An empty head and a sequence that sits out write nothing.
+template <typename T, typename TO, int LPR, bool X80 = false, bool PAGED = false, bool WP = false>
 __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) {
   constexpr int VEC = Elem<T>::VEC, NT = 256, NG = NT / LPR, XT = X80 ? 2 : 0, DL = LPR * (VEC + XT);
   static_assert(!X80 || LPR == 8, "d = 80: eight lanes per row");
@@ -767,6 +771,7 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
           vx[i] = *reinterpret_cast<const uint32_t*>(vb + (vo + off_x));
         }
       }
+      float dr[WP ? EPG : 1];                              // WP: the raw scores, for the stores below
 #pragma unroll
       for (int i = 0; i < EPG; ++i) {
         const int e = grp + i * NG;
@@ -775,8 +780,17 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
         d = group_sum<LPR>(d);
         if (e < nent) {
           if (sub == 0) s_sc[e] = c0 + e < total ? d : -INFINITY;
+          if constexpr (WP) dr[i] = d;
           *reinterpret_cast<uint4*>(s_v + (size_t)e * DL + sub * VEC) = vr[i];
           if constexpr (X80) *reinterpret_cast<uint32_t*>(s_v + (size_t)e * DL + DM + sub * 2) = vx[i];
+        }
+      }
+      if constexpr (WP) {                                  // real entries only: the padded slots are the next head's
+        if (sub == 0) {
+          float* pr = p.probs + n * p.probs_stride_n + beg + c0;
+#pragma unroll
+          for (int i = 0; i < EPG; ++i)
+            if (c0 + grp + i * NG < total) pr[grp + i * NG] = dr[i];
         }
       }
     }
@@ -838,6 +852,24 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
     __syncthreads();                                       // the chunk's LDS is free again
   }
 
+  if constexpr (WP) {                                      // m: the last chunk's carry; l: group 0's, through LDS (one barrier)
+    __shared__ float s_l;
+    if (tid == 0) s_l = l;
+    __syncthreads();
+    const float m = s_mcarry;
+    float c = (s_l > 0.f) ? (1.0f / s_l) : 0.f;
+    if (p.row_scale) c *= p.row_scale[(int64_t)n * p.H + h];
+    float* pr = p.probs + n * p.probs_stride_n + beg;
+    if (sub == 0) {                                        // the slots this thread stored in phase C
+      for (int c0 = 0; c0 < total; c0 += CH) {
+#pragma unroll
+        for (int i = 0; i < EPG; ++i) {
+          const int e = c0 + grp + i * NG;
+          if (e < total) pr[e] = __expf(pr[e] - m) * c;
+        }
+      }
+    }
+  }
   if (grp == 0 && dact) {                                  // sparse_attn_rows_kernel's epilogue (t = 0, T_dst = 1)
     const int64_t ridx = (int64_t)n * p.H + h;
     float sc_ = (l > 0.f) ? (1.0f / l) : 0.f;
@@ -990,32 +1022,32 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
   const int esz = (int)sizeof(T);
   const bool small = p.T_src < (1 << 24) && p.ks[2] * esz < (1 << 24) && p.vs[2] * esz < (1 << 24) &&
                      (int64_t)p.T_src * p.ks[2] * esz < (1ll << 31) && (int64_t)p.T_src * p.vs[2] * esz < (1ll << 31);
-  if constexpr (sizeof(T) == 2 && !WP) {
+  if constexpr (sizeof(T) == 2) {
     // one new row per sequence (a DecodeSession position): the whole workgroup serves the row (sparse_attn_decode1_kernel)
     if (p.bits && p.t_src_dev && p.T_dst == 1 && p.T_m <= 256 && small && (lpr == 8 || lpr == 16 || p.D == 80)) {
       if (p.table) {                                       // paged K / V: the PAGED forms, the table row behind the V rows
         const int tab = (int)((p.T_src + (1 << p.page_shift) - 1) >> p.page_shift) * (int)sizeof(int);
         if (p.D == 80) {
           constexpr int CH = 256, DL = 80;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
         } else if (lpr == 8) {
           constexpr int CH = 256, DL = 64;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
         } else {
           constexpr int CH = 128, DL = 128;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
+          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
         }
         return SEA_OK;
       }
       if (p.D == 80) {
         constexpr int CH = 256, DL = 80;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
+        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
       } else if (lpr == 8) {
         constexpr int CH = 256, DL = 64;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
+        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
       } else {
         constexpr int CH = 128, DL = 128;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
+        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
       }
       return SEA_OK;
     }
@@ -1027,8 +1059,7 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
       p.TB = (p.T_dst + rpb - 1) / rpb;
       const int64_t blocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
       if (p.bits && p.t_src_dev) {
-        if constexpr (WP) return SEA_EUNSUPPORTED;
-        else hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, false, 8, true, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
+        hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8, true, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
       } else if (p.bits) hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
       else hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8>), dim3((unsigned)blocks), dim3(512), 0, s, p);
       return SEA_OK;
@@ -1046,12 +1077,9 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
       if (lpr == 4) return SEA_EUNSUPPORTED;
       const int lds = p.fuse_cap * (int)sizeof(int);
       if (p.t_src_dev) {                                   // decode form
-        if constexpr (WP) return SEA_EUNSUPPORTED;
-        else {
-          if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, false, 8, true, true>), grid, block, lds, s, p);
-          else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, false, 8, true, true>), grid, block, lds, s, p);
-          return SEA_OK;
-        }
+        if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true, true>), grid, block, lds, s, p);
+        else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true, true>), grid, block, lds, s, p);
+        return SEA_OK;
       }
       if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true>), grid, block, lds, s, p);
       else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true>), grid, block, lds, s, p);
@@ -1239,8 +1267,12 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   p.t_src_stride = (int)t_src_stride;
   p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
   if (t_src_dev) {
-    SEA_REQUIRE(bits != nullptr && probs_out == nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
-                "%s: the decode form takes T_dst <= %d rows per sequence, no probs_out", nm, SEA_ATTN_WARM_ROWS);
+    SEA_REQUIRE(bits != nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
+                "%s: the decode form takes T_dst <= %d rows per sequence", nm, SEA_ATTN_WARM_ROWS);
+    // probs_out: one fp32 value per entry at the slot `col` has (or would have: write_cols = 0)
+    SEA_REQUIRE(probs_out == nullptr || probs_stride_n >= col_stride_n, SEA_EINVAL,
+                "%s: the decode form's probs_out needs probs_stride_n >= col_stride_n (%lld < %lld)", nm,
+                (long long)probs_stride_n, (long long)col_stride_n);
   }
   if (bits) {
     SEA_REQUIRE(path != SEA_ATTN_TILE && block_path == nullptr, SEA_EUNSUPPORTED, "%s: the fused interpolation runs on the gather kernels", nm);

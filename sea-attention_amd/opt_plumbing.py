@@ -143,6 +143,9 @@ class SeaOPTAttention(nn.Module):
         # opt-in fast generation: one-token calls that continue a cache run as a replayed HIP graph with room for this many
         # tokens per sequence (None: every call takes the regular cached forward)
         self.decode_graph_capacity: Optional[int] = None
+        # beside it: sessions are built with `attention_probs=True`, so that a one-token call with output_attentions=True stays
+        # on the graph path and returns the step's `session.attention_probs` (False: such a call takes the regular forward)
+        self.decode_graph_attentions: bool = False
         self._decode_session = None
 
     # the reference flips `benchmarking` on every attention module of the model to select the sparse path
@@ -165,16 +168,20 @@ class SeaOPTAttention(nn.Module):
         K / V and `PerlinAttentionState`; later calls must bring back the ticket the previous one returned.  Returns the
         forward's triple, or None when the call is not a step this path serves (the caller falls back)."""
         cap = self.decode_graph_capacity
-        if (not cap or len(past_key_value) < 3 or q.shape[2] != 1 or self.training or output_attentions
+        want = bool(output_attentions)
+        if (not cap or len(past_key_value) < 3 or q.shape[2] != 1 or self.training or (want and not self.decode_graph_attentions)
                 or not self.is_decoder or self.pconfig.lora_enabled or self.teacher_context_layer is not None):
             return None
         state, sess = past_key_value[2], self._decode_session
         if isinstance(state, SessionState):
             if not (state.session is sess and state.current):
                 return None                                   # a stale / foreign ticket: materialize() decides in the caller
+            if want and sess._probs_buf is None:
+                return None                                   # (a session built before `decode_graph_attentions` was set)
         else:
             try:
-                sess = self.perlin_self_attention.attention.decode_session(state, past_key_value[0], past_key_value[1], cap)
+                sess = self.perlin_self_attention.attention.decode_session(state, past_key_value[0], past_key_value[1], cap,
+                                                                           attention_probs=self.decode_graph_attentions)
             except AssertionError:                            # shapes / dtype / prefix the session does not cover
                 return None
             self._decode_session = sess
@@ -185,7 +192,7 @@ class SeaOPTAttention(nn.Module):
         dtype = self.q_proj.weight.dtype
         y = self.out_proj(ctx if ctx.dtype == dtype else ctx.to(dtype))
         self.last_loss = 0
-        return y, None, (sess.k_cache[:, :, :L], sess.v_cache[:, :, :L], SessionState(sess))
+        return y, (sess.attention_probs if want else None), (sess.k_cache[:, :, :L], sess.v_cache[:, :, :L], SessionState(sess))
 
     def forward(self, hidden_states: torch.Tensor, key_value_states=None,
                 past_key_value: Optional[Tuple[torch.Tensor, ...]] = None, attention_mask: Optional[torch.Tensor] = None,

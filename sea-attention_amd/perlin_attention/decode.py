@@ -103,6 +103,19 @@ table row into a per-session scratch (`sea_decode_gather_rows`, no host-built in
 of its cache.  Only rows >= L are written -- the open page and new pages, taken before anything is launched; table entries
 below the open index, the closed pages a fork shares, are untouched.  The parked-prompt flow, complete: `pause` the prompt,
 `fork` it as requests arrive, `extend` each copy by its request's rows, `resume` the copies, `release` them at EOS.
+
+The attention probabilities of a step (`attention_probs=True` at construction, off by default): the module's
+`partial_attention_probs` -- the per-entry row_scale * softmax values of the sparse attention, a `FlatCSR` with values -- from
+the replayed step itself.  The session owns one static fp32 buffer, (N, z_cap), or (N, S * z_cap) with `max_step_rows` S, and
+every attention launch of a step takes it as `probs_out` (`ops.sparse_attention`): the decode forms of `sea_sparse_attention`
+write each entry's value at the slot its column has -- or would have: the columns stay pending -- so the capture holds no
+extra launch and no fill node.  After every `step`, `session.attention_probs` is `session.csr.with_values(view of the buffer)`,
+a new handle per step over the step's own structure (a replay re-arms `session.csr`; a handle kept from an earlier step sees
+the buffer as later steps leave it).  Reading its `.col` / `.col_indices()` emits the columns exactly as `session.csr` does;
+`.values()`, `.col_indices()` and `.crow_indices()` are the cached forward's `partial_attention_probs` for that position, bit for
+bit (tests/test_gpu_decode_session_probs.py).  Slots that sit out have empty rows (their launch writes nothing).  The
+probabilities are an OUTPUT of the last step, not state: `rewind`, `fork`, `reorder`, `extend` and `admit` neither read nor
+change them.  Off (the default): no buffer, the same launches, the same `captures`, and `session.attention_probs` is None.
 """
 from collections import deque
 from typing import List, Optional
@@ -314,10 +327,14 @@ class DecodeSession:
     _empty = None
     _extend_kv = None            # (paged sessions: `extend`'s contiguous K / V scratch (2, H, capacity, D), allocated on first use)
     csr = None                   # (the CSR row of the last step; none while `from_sequences` seeds its slots)
+    attention_probs = None       # (attention_probs=True: the last step's per-entry probabilities, a FlatCSR with values)
+    _probs_buf = None            # (their static fp32 buffer, (N, z_cap) or (N, S * z_cap): `probs_out` of the attention launches)
+    _want_attention_probs = False
 
     def __init__(self, attention, state: PerlinAttentionState, key_prefix: torch.Tensor, value_prefix: torch.Tensor,
-                 capacity: int, use_graph: bool = True, fused_attention: bool = True):
+                 capacity: int, use_graph: bool = True, fused_attention: bool = True, attention_probs: bool = False):
         at = self.attention = attention
+        self._want_attention_probs = bool(attention_probs)
         pc = at.pconfig
         assert pc.causal and not at.training, "decoding is the causal inference path"
         N, H, L, D = key_prefix.shape
@@ -403,11 +420,14 @@ class DecodeSession:
         self._col_emit = None                                                # its pending-column state (graph replay re-arms it)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.probs = None                                                    # estimated attention probabilities of the last step
+        if self._want_attention_probs:                                       # (module docstring: written in place, never cleared)
+            self._probs_buf = torch.zeros((N, (self.max_step_rows or 1) * self.z_cap), dtype=torch.float32, device=dev)
         self._pinned, self._prep_generation = None, ops.prep_generation()
 
     @classmethod
     def from_sequences(cls, attention, sequences, capacity: int, use_graph: bool = True, fused_attention: bool = True,
-                       page_rows: Optional[int] = None, pool_pages: Optional[int] = None, max_step_rows: Optional[int] = None):
+                       page_rows: Optional[int] = None, pool_pages: Optional[int] = None, max_step_rows: Optional[int] = None,
+                       attention_probs: bool = False):
         """A session over sequences of DIFFERENT lengths.  `sequences`: [(state, key_prefix, value_prefix), ...], each the
         output of an N = 1 cached forward, (1, H, L_i, D) with its own L_i.  Slot n of the batch is sequence n; `step` takes
         and returns (N, ...) rows as for a uniform session, and every row equals that sequence's own N = 1 session bit for
@@ -423,9 +443,12 @@ class DecodeSession:
         (module docstring); contiguous K / V with the fused decode attention only (ValueError with `page_rows` or
         `fused_attention=False`).  None: one row per step, no rewind.
         An entry of `sequences` may be None: that slot starts EMPTY (as after `release`) and sits out until `admit`, `fork`
-        or `reorder` fills it; at least one entry is a real sequence."""
+        or `reorder` fills it; at least one entry is a real sequence.
+        `attention_probs`: every step also leaves the sparse attention's per-entry probabilities in `session.attention_probs`
+        (module docstring)."""
         self = cls.__new__(cls)
         at = self.attention = attention
+        self._want_attention_probs = bool(attention_probs)
         pc = at.pconfig
         seqs = list(sequences)
         if not (pc.causal and not at.training):
@@ -799,6 +822,12 @@ class DecodeSession:
         if col_emit is not None:
             csr._pending = col_emit
 
+    def _publish_attention_probs(self, s=1):
+        """After a step of s rows: the step's structure with the buffer's values, a new handle (no wire format of an earlier
+        step; pending columns follow `self.csr`, which the step has just re-armed)."""
+        if self._probs_buf is not None:
+            self.attention_probs = self.csr.with_values(self._probs_buf[:, :s * self.z_cap])
+
     def _conv1_seed(self, window):
         """What seeds the y1 ring behind a window of LB rows: conv1 over the window, and how many of its last rows are conv1's
         true values (all their taps lie inside the window)."""
@@ -987,7 +1016,8 @@ class DecodeSession:
             ops.sparse_attention(self.q_in, self.k_cache, self.v_cache, csr,
                                  row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
                                  avg=avg_rows, mix=avg_scale, out=self.ctx.view(self.N, 1, H, D).permute(0, 2, 1, 3),
-                                 path="gather", keep_columns_pending=True, block_table=self.block_table)
+                                 path="gather", keep_columns_pending=True, block_table=self.block_table,
+                                 probs_out=self._probs_buf)
             self.csr = csr                                                    # (the step's selection: columns on first read of .col)
             self._col_emit = csr._pending                                     # (None: a launch of the step writes the columns)
             return
@@ -1003,7 +1033,7 @@ class DecodeSession:
         ops.sparse_attention(self.q_in, self.k_cache, self.v_cache, csr,
                              row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
                              avg=avg_rows, mix=avg_scale, out=self.ctx.view(self.N, 1, H, D).permute(0, 2, 1, 3),
-                             path="gather")
+                             path="gather", probs_out=self._probs_buf)
         self.csr, self._col_emit = csr, None                                  # (the emit launch above wrote the columns)
         ops.c8_window_shift(self.xs, counters=self.ctr32[:2])                 # the window of the next position; counters += 1
 
@@ -1035,7 +1065,8 @@ class DecodeSession:
         ops.sparse_attention(q_in, self.k_cache, self.v_cache, csr,
                              row_scale=row_scale if at.pconfig.partial_attention_scaler else None,
                              avg=avg_rows, mix=avg_scale, out=ctx.view(N, s, H, D).permute(0, 2, 1, 3),
-                             path="gather", keep_columns_pending=True)
+                             path="gather", keep_columns_pending=True,
+                             probs_out=None if self._probs_buf is None else self._probs_buf[:, :s * self.z_cap])
         self.csr, self._col_emit = csr, csr._pending
 
     def _capture(self, s=None):
@@ -1119,6 +1150,7 @@ class DecodeSession:
             self._rearm(self.csr, self._col_emit)
         else:
             self._launch()
+        self._publish_attention_probs()
         if self.ragged:
             self._zero_sitting_rows(self.ctx)
             self.lengths = [L if out else L + 1 for L, out in zip(self.lengths, self._paused)]
@@ -1157,6 +1189,7 @@ class DecodeSession:
             self._rearm(self.csr, self._col_emit)                  # (as in `step`: the handle is every replay's)
         else:
             self._launch_rows(s)
+        self._publish_attention_probs(s)
         self._last_step = (s, list(self.lengths), crossed)
         self.lengths = [L if out else L + s for L, out in zip(self.lengths, self._paused)]
         ctx = self._rows_views(s)[4]

@@ -104,8 +104,15 @@ class FlatCSR:
         return sub
 
     def with_values(self, vals: torch.Tensor) -> "FlatCSR":
-        """Same structure (shared index tensors), other values."""
-        return FlatCSR(self.crow, self.col, self.head_off, self.H, self.T_src, self.bits, self.row_nnz, vals)
+        """Same structure (shared index tensors), other values.  While this handle's columns are pending the new one's are
+        too (the values of a fused decode launch that left them so): whoever reads its `.col` runs this handle's emit."""
+        if self._pending is None:
+            return FlatCSR(self.crow, self.col, self.head_off, self.H, self.T_src, self.bits, self.row_nnz, vals)
+        out = FlatCSR(self.crow, self._col, self.head_off, self.H, self.T_src, self.bits, self.row_nnz, vals)
+        out.t_src_dev = self.t_src_dev
+        T_m, k, causal, _emit = self._pending
+        out._pending = (T_m, k, causal, lambda: self.col)
+        return out
 
     def to_sparse_csr(self, values: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Materialise the reference's wire format: int64 indices, trimmed to Z = max nnz
@@ -447,7 +454,8 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
                      plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False,
-                     block_table: Optional[torch.Tensor] = None, range_keys: Optional[int] = None):
+                     block_table: Optional[torch.Tensor] = None, range_keys: Optional[int] = None,
+                     probs_out: Optional[torch.Tensor] = None):
     """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
@@ -469,7 +477,12 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     tile-favouring blocks decides on the device which one runs; the other exits at once); without it "auto" means the
     gather kernels.
     want_probs: also return the per-entry values rs * softmax (fp32, laid out like csr.col) -- what the reference
-    hands out as `partial_attention_probs` (attention.py:1162-1171); returns (out, probs).
+    hands out as `partial_attention_probs` (attention.py:1162-1171); returns (out, probs).  The decode forms (one row per
+    sequence, paged or not, and the few-row forms) write them from the fused launch, at the slots `col` has or -- with
+    keep_columns_pending -- would have.
+    probs_out: fp32 (N, >= csr.col.shape[1]), feature stride 1: the values are written there, in place, and returned (implies
+    want_probs).  Nothing else is touched: slots outside the rows keep what they held (without it: a fresh zero-filled tensor).
+    A captured decode step passes a static buffer and records no fill node.
     keep_columns_pending: with a handle whose columns are pending and the fused launch serving it, do NOT write the column
     array (the launch keeps the expanded columns in LDS): the handle stays pending and whoever reads `.col` later runs the
     emit launch -- for callers that return the CSR without anybody reading it (the layer's hot path).
@@ -477,6 +490,12 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     block_table[n, r // page_rows] (int32, (N, >= ceil(csr.T_src / page_rows))).  Only the one-row decode form reads pages: a
     pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
     lib = _lib.load()
+    want_probs = want_probs or probs_out is not None
+    if probs_out is not None:
+        _lib.require_gpu(probs_out)
+        assert (probs_out.dtype == torch.float32 and probs_out.dim() == 2 and probs_out.shape[0] == csr.N
+                and probs_out.shape[1] >= csr._col.shape[1] and probs_out.stride(1) == 1
+                and (csr.N == 1 or probs_out.stride(0) >= csr._col.stride(0))), "probs_out: fp32 (N, >= z_cap), feature stride 1"
     _lib.require_gpu(q, k, v, csr.crow, block_table)
     keyrange = path == "keyrange"
     if keyrange:
@@ -515,7 +534,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                          f"16-bit d = 64 / 80 / 128; got T_dst = {T_dst}, {q.dtype}, d = {D})")
     fused = paged or (csr.col_is_pending and fuse_emit and path != "tile" and not (path == "auto" and plan is not None)
                       and fused_interp_supported(q.dtype, D, csr._pending[0], None if decode_form else N * H * T_dst)
-                      and not (decode_form and (want_probs or T_dst > 8)))
+                      and not (decode_form and T_dst > 8))
     T_src = csr.T_src if paged else k.shape[2]
     table_stride, page_rows = 0, 0
     if paged:
@@ -561,7 +580,9 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     if fused:
         T_m_, max_k_, causal_, _emit = csr._pending
         raw_col = csr._col
-        probs = torch.zeros(raw_col.shape, dtype=torch.float32, device=q.device) if want_probs else None
+        probs = probs_out
+        if want_probs and probs is None:
+            probs = torch.zeros(raw_col.shape, dtype=torch.float32, device=q.device)
         rc = launch(raw_col, probs, None, _lib.SEA_ATTN_GATHER, csr.bits, T_m_, int(causal_), max_k_,
                     0 if keep_columns_pending else 1, csr.t_src_dev)
         if rc == 0:
@@ -571,7 +592,9 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         if rc != _lib.SEA_EUNSUPPORTED or paged:
             _lib.check(rc, "sea_sparse_attention")
         # a shape the fused form does not cover (nothing was launched): emit, then the plain operator below
-    probs = torch.zeros(csr.col.shape, dtype=torch.float32, device=q.device) if want_probs else None
+    probs = probs_out
+    if want_probs and probs is None:
+        probs = torch.zeros(csr.col.shape, dtype=torch.float32, device=q.device)
     flags = _PATHS[path] | ((int(row_tiles) & 0xf) << 8)
     if key_window:
         assert key_window & (key_window - 1) == 0, "key_window is a power of two"
