@@ -200,6 +200,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  *                    a kv-cache whose unused slots are uninitialised takes SEA_ATTN_GATHER (as DecodeSession does) or
  *                    zero-fills them;
  *   SEA_ATTN_KEYRANGE  the key-range form, for K + V per head beyond an XCD's L2 (see below); range_keys in bits 16..30;
+ *   bits 4..7 (SEA_ATTN_ROW_POOL_SHIFT): log2 of the row pool of the fused gather form (ROW-POOL form below; 0 = none);
  *   bits 8..11: row tiles per wave for the tile kernel (1 or 2; 0 = default for the head size);
  *   bits 12..15: log2 of its key window (6..12; 0 = default 2048).
  *
@@ -215,7 +216,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * sea_csr_emit's arithmetic bit for bit: fp32 scale = w_t / T_m, bounds round_half_away(b * scale), keys descending inside
  * a pixel, the reference's fp32 stepping for a pixel wider than max_k -- into a group-private list in LDS, writes the list
  * to `col` and walks it from LDS.  No separate sea_csr_emit launch, no column re-read from memory.  `flags` is not read
- * (the gather path), block_path must be NULL, probs_out is allowed.
+ * (the gather path) but for its row-pool field, block_path must be NULL without that field, probs_out is allowed.
  *   bits      (N, T_dst, ceil(H*T_m/32)) kept-pixel masks of sea_topk_select / sea_predictor_tail_select (T_m % 32 == 0);
  *             T_m, is_causal, max_k as for that launch.  With bits = NULL, T_m / is_causal / max_k / write_cols are not read;
  *   crow      from sea_csr_row_scan over that launch's row_nnz; head_off from the same launch;
@@ -257,6 +258,24 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * form.  bits == NULL, any other D (80 included), t_src_dev / block_table (no decode or paged form), write_cols != 0, more than
  * 64 ranges: SEA_EUNSUPPORTED, before anything is launched.
  *
+ * ROW-POOL form of the fused launch, bits != NULL and (flags >> SEA_ATTN_ROW_POOL_SHIFT) & 0xf = log2(POOL) != 0 (the one
+ * field of `flags` the fused gather form reads).  The gather kernels walk the rows of a wave in lockstep for as long as the
+ * wave's longest row lasts, so they deal rows to waves by length; without this field every workgroup ranks its own 64 (rows
+ * of 8 lanes, d = 80 included) or 32 (rows of 16 lanes) rows.  With it the entry issues two launches on `stream`, stream order
+ * being the only hand-off (graph-capturable): a pre-pass in which one workgroup per (n, h, pool of POOL consecutive query
+ * rows) counting-sorts the pool's rows by their entries, longest first, into the workspace, then the fused gather kernel
+ * whose wave w of the pool's block b (of nb = POOL / rows per workgroup) takes the sorted slots (w * nb + b) * rows_per_wave
+ * ...: a wave holds neighbours of the sorted order, a workgroup rows from the whole length range.  Which lane group walks a
+ * row changes no bit of the result: context rows and `col` are exactly those of the launch without the field.
+ *   block_path  the WORKSPACE (no plan exists in the fused form): 16-byte aligned uint16 base, probs_stride_n its elements per
+ *             batch item, >= H * ceil(T_dst / POOL) * POOL.  Caller-owned; after the launch it holds, per (n, h, pool), the
+ *             rows' offsets in the pool in the order they were dealt (a permutation of 0 .. POOL - 1, slots past T_dst last).
+ *             NULL, misaligned or too small: SEA_EINVAL (the message gives the elements needed);
+ *   POOL      a multiple of the form's rows per workgroup and at most 1024, else SEA_EUNSUPPORTED;
+ *   probs_out must be NULL; the decode and paged forms (t_src_dev / block_table), the key-range and tile paths and bits == NULL
+ *             are SEA_EUNSUPPORTED, before anything is launched.
+ * A launch of at most sea_attention_few_rows() rows (N * H * T_dst) ignores the field and reads no workspace.
+ *
  * DECODE form of the fused launch, bits and t_src_dev != NULL (round 5; SURVEY 8f-3, src/main/opt_generate.py:131,
  * PA/attention.py:410-426): a position of a graph-replayed decoding session has static kernel arguments, so the sequence
  * length the row widths follow is read from device memory (*t_src_dev, what the decode form of sea_csr_emit reads) while
@@ -297,6 +316,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * the selection launch wrote its empty rows) may have been read by then.
  */
 enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2, SEA_ATTN_KEYRANGE = 3 };
+enum { SEA_ATTN_ROW_POOL_SHIFT = 4 };
 int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
                          int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,

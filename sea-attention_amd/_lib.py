@@ -86,6 +86,7 @@ def library_path():
 
 
 SEA_ATTN_AUTO, SEA_ATTN_GATHER, SEA_ATTN_TILE, SEA_ATTN_KEYRANGE = 0, 1, 2, 3
+SEA_ATTN_ROW_POOL_SHIFT = 4                     # flags bits 4..7: log2 of the fused gather form's row pool (0 = none)
 SEA_OK, SEA_EINVAL, SEA_EUNSUPPORTED = 0, -1, -2
 
 

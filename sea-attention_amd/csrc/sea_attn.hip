@@ -148,6 +148,74 @@ __device__ inline int slot_length(const AttnParams& p, int n, int h, int tn) {
   return hon[h + 1] - hon[h];
 }
 
+// ---- rows dealt by length over POOLS of rows wider than a workgroup (SEA_ATTN_ROW_POOL) ---------------------------------
+// rows_by_length ranks the rows a workgroup owns, so the pool the sort draws from is tied to the workgroup size (0.89 of the
+// lane-steps carry an entry at 64 rows; 128 rows gave 0.93 but a 1024-thread workgroup lost more than that won).  Here the
+// ranking is a launch of its own in front of the attention launch: one workgroup counting-sorts the lengths of a pool of
+// `pool` consecutive rows of one (n, h), longest first -- an LDS histogram over min(len + 1, BINS - 1), a scan of it from the
+// top bin down, one LDS atomic per row for its slot; the rows of the top bin (BINS - 2 entries or more: a head that took
+// most of a row's budget) are ranked among themselves by comparison, so the order is non-increasing in the true length.
+// The order of rows of equal length is whatever the atomics give: one workgroup writes a pool's order and every reader reads
+// that.  order[(n, h, pool), slot] = the row's offset in its pool; the slots past T_dst (length -1) come last.
+constexpr int SEA_ATTN_ORDER_BINS = 512;
+__global__ __launch_bounds__(1024) void attn_row_order_kernel(AttnParams p) {
+  constexpr int BINS = SEA_ATTN_ORDER_BINS;
+  __shared__ int s_bin[BINS];                              // the histogram, then every bin's next slot
+  __shared__ int s_top[1024];                              // lengths of the rows in the top bin (by row), -1 elsewhere
+  const int tid = threadIdx.x, pool = p.pool_rows;
+  const int pl = (int)blockIdx.x % p.pools, pair = (int)blockIdx.x / p.pools;
+  const int n = pair / p.H, h = pair - n * p.H;
+  for (int b = tid; b < BINS; b += blockDim.x) s_bin[b] = 0;
+  const bool mine = tid < pool;                            // (a pool of 32 rows still runs one whole wave)
+  const int len = mine ? slot_length(p, n, h, pl * pool + tid) : -1;
+  const int bin = len + 1 < BINS - 1 ? len + 1 : BINS - 1;
+  if (mine) s_top[tid] = bin == BINS - 1 ? len : -1;
+  __syncthreads();
+  if (mine) atomicAdd(&s_bin[bin], 1);
+  __syncthreads();
+  if (tid < 64) {                                          // first slot of every bin, bins descending: lane L owns bins
+    constexpr int PER = BINS / 64;                         // BINS - 1 - PER * L down to BINS - PER * (L + 1)
+    int c[PER], sum = 0;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) { c[i] = s_bin[BINS - 1 - (tid * PER + i)]; sum += c[i]; }
+    int start = wave_incl_scan(sum) - sum;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) { s_bin[BINS - 1 - (tid * PER + i)] = start; start += c[i]; }
+  }
+  __syncthreads();
+  if (!mine) return;
+  int slot;
+  if (bin == BINS - 1) {                                   // the top bin starts at slot 0: rank by (length descending, row ascending)
+    slot = 0;
+    for (int r = 0; r < pool; ++r) {
+      const int o = s_top[r];
+      slot += (o > len || (o == len && r < tid)) ? 1 : 0;
+    }
+  } else {
+    slot = atomicAdd(&s_bin[bin], 1);
+  }
+  uint16_t* ord = const_cast<uint16_t*>(p.order) + n * p.order_stride_n + ((int64_t)h * p.pools + pl) * pool;
+  ord[slot] = (uint16_t)tid;
+}
+
+// the row this lane group walks when the rows are dealt from the pool's order: lane group (wave w, j) of the pool's block b
+// (of nb = pool_rows / RPB) takes slot (w * nb + b) * RPW + j -- every wave holds RPW neighbours of the sorted order, every
+// block octets spread over the whole length range (its longest rows in wave 0, its total near the mean).  Returns false for
+// a block all of whose slots lie past T_dst (block-uniform; the caller returns before any barrier).
+template <int LPR, int RPB>
+__device__ inline bool pooled_row(const AttnParams& p, int n, int h, int tb, int grp, int* t, bool* rowok) {
+  constexpr int RPW = 64 / LPR;
+  const int nb = p.pool_rows / RPB;
+  const int pl = tb / nb, b = tb - pl * nb;
+  const int rows = min(p.pool_rows, p.T_dst - pl * p.pool_rows);   // rows of this pool: they hold the first `rows` slots
+  if (b * RPW >= rows) return false;
+  const int slot = (((int)threadIdx.x >> 6) * nb + b) * RPW + grp;
+  const uint16_t* ord = p.order + n * p.order_stride_n + ((int64_t)h * p.pools + pl) * p.pool_rows;
+  *t = pl * p.pool_rows + (int)ord[slot];
+  *rowok = *t < p.T_dst;
+  return true;
+}
+
 // ---- steps I + J in one launch: the interpolation of ONE (row, head) by the lane group that walks it -----------------------
 // The lane group expands its row's kept pixels of head h to key columns -- the emit kernel's arithmetic, bit for bit
 // (interp_scale / interp_bound, keys descending inside a pixel, the reference's fp32 stepping for a thinned pixel) -- into
@@ -275,11 +343,13 @@ constexpr int SEA_ATTN_WARM_ROWS = 8;            // T_dst up to which the idle l
 // (offsets -> col -> K/V) load chains in flight instead of one, which is what the wave-per-row mapping lacks.
 // Workgroup = 4 waves = 256/LPR consecutive query rows of one (n, h).
 // DEC (with FUSE): the decode form -- row widths from *p.t_src_dev, the key lists warmed by the whole block (fused_warm).
-template <typename T, typename TO, int LPR, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false>
+// ORD (with FUSE, without DEC / WP): the rows come from the pool's order (pooled_row) instead of rows_by_length.
+template <typename T, typename TO, int LPR, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
 // the fused 16-bit inference forms are held to 64 registers (8 waves per SIMD; 4 - 8 spilled registers): measured 0.307 ms
 // against 0.328 ms at 88 registers for the 16-lane form (LLaMA-13B d = 128), and the same direction for the 8-lane form
 __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ? 8 : 1) void sparse_attn_rows_kernel(AttnParams p) {
   static_assert(!DEC || FUSE, "the decode form is a fused form");
+  static_assert(!ORD || (FUSE && !DEC && !WP), "rows are dealt from pools in the fused inference form only");
   constexpr int VEC = Elem<T>::VEC;
   constexpr int RPW = 64 / LPR;       // rows per wave
   constexpr int RPB = NWB * RPW;      // rows per workgroup
@@ -293,7 +363,12 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   const int grp = lane / LPR, sub = lane - grp * LPR;
   const int gi = (int)(threadIdx.x >> 6) * RPW + grp;      // lane group index inside the block
   bool rowok;
-  const int t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
+  int t;
+  if constexpr (ORD) {
+    if (!pooled_row<LPR, RPB>(p, n, h, tb, grp, &t, &rowok)) return;
+  } else {
+    t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
+  }
   const bool dact = sub * VEC < p.D;
   const int tt = t < p.T_dst ? t : p.T_dst - 1;
   const int sube = dact ? sub : 0;    // lanes beyond D re-read fragment 0 (their q fragment is zero)
@@ -488,11 +563,12 @@ template <> __device__ inline void unpack2<__half>(uint32_t r, float* f) {
 template <typename TO> __device__ inline void store2(TO* dst, float a, float b) { *reinterpret_cast<uint32_t*>(dst) = pack2<TO>(a, b); }
 template <> __device__ inline void store2<float>(float* dst, float a, float b) { *reinterpret_cast<float2*>(dst) = make_float2(a, b); }
 
-template <typename T, typename TO, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false>
+template <typename T, typename TO, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
 // (no wave floor here: capping this kernel at 80 / 64 registers for 6 / 8 waves per SIMD measured 0.427 / 0.489 ms against
 // 0.418 ms as compiled, OPT-2.7B T = 8192 -- DESIGN.md section 9)
 __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams p) {
   static_assert(!DEC || FUSE, "the decode form is a fused form");
+  static_assert(!ORD || (FUSE && !DEC && !WP), "rows are dealt from pools in the fused inference form only");
   constexpr int LPR = 8, VEC = 8, XT = 2, DM = LPR * VEC;     // DM = 64 elements in the 16-byte fragments
   constexpr int RPW = 64 / LPR, RPB = NWB * RPW;
   int pair, tb;
@@ -503,7 +579,12 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
   const int grp = lane / LPR, sub = lane - grp * LPR;
   const int gi = (int)(threadIdx.x >> 6) * RPW + grp;
   bool rowok;
-  const int t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
+  int t;
+  if constexpr (ORD) {
+    if (!pooled_row<LPR, RPB>(p, n, h, tb, grp, &t, &rowok)) return;
+  } else {
+    t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
+  }
   const int tt = t < p.T_dst ? t : p.T_dst - 1;
 
   const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1]);
@@ -1057,6 +1138,16 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
     if (p.D == 80 && small) {                          // d = 80: 8 lanes x (8 + 2) elements per row
       const int rpb = 8 * 8;                               // 8 waves x 8 rows, sorted by length
       p.TB = (p.T_dst + rpb - 1) / rpb;
+      if constexpr (!WP) {
+        if (p.order) {                                     // rows dealt from pools (the entry has checked the form)
+          if (p.pool_rows % rpb) return SEA_EINVAL;
+          p.TB = p.pools * (p.pool_rows / rpb);
+          const int64_t pblocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
+          hipLaunchKernelGGL(attn_row_order_kernel, dim3((unsigned)(NH * p.pools)), dim3(p.pool_rows < 64 ? 64 : p.pool_rows), 0, s, p);
+          hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, false, 8, true, false, true>), dim3((unsigned)pblocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
+          return SEA_OK;
+        }
+      }
       const int64_t blocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
       if (p.bits && p.t_src_dev) {
         hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8, true, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
@@ -1080,6 +1171,17 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
         if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true, true>), grid, block, lds, s, p);
         else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true, true>), grid, block, lds, s, p);
         return SEA_OK;
+      }
+      if constexpr (!WP) {
+        if (p.order) {                                     // rows dealt from pools (the entry has checked the form)
+          if (p.pool_rows % rpb) return SEA_EINVAL;
+          p.TB = p.pools * (p.pool_rows / rpb);
+          const dim3 pgrid((unsigned)((int64_t)8 * ((NH + 7) / 8) * p.TB));
+          hipLaunchKernelGGL(attn_row_order_kernel, dim3((unsigned)(NH * p.pools)), dim3(p.pool_rows < 64 ? 64 : p.pool_rows), 0, s, p);
+          if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, false, 8, true, false, true>), pgrid, block, lds, s, p);
+          else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, false, 8, true, false, true>), pgrid, block, lds, s, p);
+          return SEA_OK;
+        }
       }
       if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true>), grid, block, lds, s, p);
       else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true>), grid, block, lds, s, p);
@@ -1171,6 +1273,43 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
                                     int64_t table_stride, int64_t page_rows, sea_stream_t stream) {
   const char* nm = "sea_sparse_attention";
   // SEA_ATTN_KEYRANGE: range_keys in bits 16..30 of flags, the workspace in probs_out / probs_stride_n (sea_hip.h)
+  // SEA_ATTN_ROW_POOL: log2 of the pool in bits 4..7 of flags, the order workspace in block_path / probs_stride_n (sea_hip.h)
+  int pool_log2 = (flags >> SEA_ATTN_ROW_POOL_SHIFT) & 0xf;
+  flags &= ~(0xf << SEA_ATTN_ROW_POOL_SHIFT);
+  const uint16_t* order = nullptr;
+  int64_t order_stride_n = 0;
+  if (pool_log2) {
+    const char* rp = "the row-pool form";
+    SEA_REQUIRE((flags & 0xff) != SEA_ATTN_KEYRANGE && (flags & 0xff) != SEA_ATTN_TILE, SEA_EUNSUPPORTED,
+                "%s: %s deals the rows of the fused gather kernels: the key-range and tile paths have none (path %d)", nm, rp, flags & 0xff);
+    SEA_REQUIRE(bits != nullptr, SEA_EUNSUPPORTED, "%s: %s is a fused form (bits is NULL)", nm, rp);
+    SEA_REQUIRE(t_src_dev == nullptr && block_table == nullptr && t_src_stride == 0, SEA_EUNSUPPORTED,
+                "%s: %s has no decode or paged form (t_src_dev / block_table)", nm, rp);
+    SEA_REQUIRE(probs_out == nullptr, SEA_EUNSUPPORTED, "%s: %s writes no per-entry probabilities (probs_out must be NULL)", nm, rp);
+    SEA_REQUIRE(N > 0 && H > 0 && T_dst > 0 && T_src > 0 && D > 0, SEA_EINVAL, "%s: bad shape", nm);
+    if (N * H * T_dst <= SEA_ATTN_FEW_ROWS) {              // a launch of few rows: the field is ignored, the workspace not read
+      pool_log2 = 0;
+      block_path = nullptr;
+      probs_stride_n = 0;
+    }
+  }
+  if (pool_log2) {
+    const char* rp = "the row-pool form";
+    const int64_t pool = 1ll << pool_log2;
+    SEA_REQUIRE(pool <= 1024, SEA_EUNSUPPORTED, "%s: %s takes pools of at most 1024 rows (got %lld)", nm, rp, (long long)pool);
+    // rows per workgroup of the fused gather kernels (launch_attn_wp): 64 for rows of 8 lanes (d = 80 included), 32 for rows of 16
+    const int64_t rpb = (dtype == SEA_F32 ? D > 32 : (D > 64 && D != 80)) ? 32 : 64;
+    SEA_REQUIRE(pool % rpb == 0, SEA_EUNSUPPORTED, "%s: %s needs a pool that is a multiple of the %lld rows of a workgroup (got %lld)",
+                nm, rp, (long long)rpb, (long long)pool);
+    const int64_t pools = (T_dst + pool - 1) / pool, need = H * pools * pool;
+    SEA_REQUIRE(block_path != nullptr && aligned16(block_path) && probs_stride_n >= need, SEA_EINVAL,
+                "%s: %s needs a 16-byte aligned uint16 workspace in block_path with probs_stride_n >= %lld elements per batch "
+                "item (got %lld)", nm, rp, (long long)need, (long long)probs_stride_n);
+    order = reinterpret_cast<const uint16_t*>(block_path);
+    order_stride_n = probs_stride_n;
+    block_path = nullptr;                                  // (no plan in the fused form)
+    probs_stride_n = 0;
+  }
   const bool keyrange = (flags & 0xff) == SEA_ATTN_KEYRANGE;
   KeyRangeParams kr = {nullptr, 0, 0, 0};
   if (keyrange) {
@@ -1266,6 +1405,8 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
               (long long)t_src_stride);
   p.t_src_stride = (int)t_src_stride;
   p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
+  p.order = order; p.order_stride_n = order_stride_n;
+  p.pool_rows = order ? 1 << pool_log2 : 0; p.pools = order ? (int)((T_dst + p.pool_rows - 1) / p.pool_rows) : 0;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
                 "%s: the decode form takes T_dst <= %d rows per sequence", nm, SEA_ATTN_WARM_ROWS);

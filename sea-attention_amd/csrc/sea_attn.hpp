@@ -49,6 +49,12 @@ struct AttnParams {
   // r & (page_rows - 1).  Keys and column ids stay logical (head * T_src + key): only the K / V loads translate
   const int32_t* table;
   int table_stride, page_shift;
+  // rows dealt by length over pools of `pool_rows` query rows (SEA_ATTN_ROW_POOL; the ORD forms of the fused gather kernels):
+  // order (N, H, pools * pool_rows) from attn_row_order_kernel -- per pool its rows' offsets, longest row first, the slots
+  // past T_dst last.  NULL: every workgroup ranks its own rows (rows_by_length)
+  const uint16_t* order;
+  int64_t order_stride_n;
+  int pool_rows, pools;
 };
 
 template <typename TO, int VEC> __device__ inline void store_frag(TO* dst, const float* f);

@@ -38,6 +38,12 @@ from . import ops
 timer = lambda name: get_bench().region(name)
 mem = lambda name: get_bench().mem_region(name)
 _C8_DECLINED = set()      # (dtype, Cin, Cout, k) of predictor convolutions the hand-written kernels declined: warned about once each
+# what a new PerlinAttention's `attention_row_pool` starts as: the smallest pool whose attention launch AND step separated from
+# the parent's in both interleaved rounds at the headline (profiles/r07a_ab_attn_row_pool.log).  The layer uses it
+# for the forms that were measured to gain -- 16-bit d = 64 and d = 128; d = 80 (touching ranges at 512) and fp32 data (not
+# measured) keep the in-block ranking
+ATTENTION_ROW_POOL: Optional[int] = 512
+ATTENTION_ROW_POOL_HEAD_SIZES = (64, 128)
 
 
 def _safe_to(t, d):
@@ -157,6 +163,10 @@ class PerlinAttention(nn.Module):
         # K / V rows in flight fit an XCD's L2) wherever it exists -- pending CSR columns, no probabilities wanted, 16-bit d = 64 /
         # 128 or fp32 d = 32 / 64, at most 64 ranges, `lazy_csr_columns` (the form writes no columns) -- and the keys exceed one range; None = never (DESIGN 5.4h has the measurements)
         self.key_range: Optional[int] = None
+        # sparse mode: an integer = the fused attention launch deals its rows to waves by length over pools of that many query
+        # rows (`ops.sparse_attention(row_pool=...)`: a sorting pre-pass in front of the gather kernel; the same bits) wherever
+        # that form exists and the head size takes the pool; None = every workgroup ranks its own rows
+        self.attention_row_pool: Optional[int] = ATTENTION_ROW_POOL
         # HIP Performer: None = the library's plan for the shape (it cuts ONE long sequence into segments so that all CUs
         # work: another fp32 summation order than the one-pass kernel a full batch takes), 1 = always the one-pass kernel
         # (bench.py's self-check runs a batch item alone with it, so that the item reproduces its batched rows bit for bit)
@@ -1013,10 +1023,15 @@ class PerlinAttention(nn.Module):
                                                    mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
                                                    path="keyrange", range_keys=int(self.key_range))
                     else:
+                        row_pool = self.attention_row_pool
+                        if row_pool is not None and not (qs.dtype != torch.float32 and HID in ATTENTION_ROW_POOL_HEAD_SIZES
+                                                         and ops.row_pool_supported(qs.dtype, HID, int(row_pool))):
+                            row_pool = None
                         res = ops.sparse_attention(qs, ks, vs, csr, row_scale=row_scale, avg=average_context_layer,
                                                    mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
                                                    want_probs=want_probs, path="gather" if want_probs else self.sparse_kernel,
-                                                   plan=plan, keep_columns_pending=self.lazy_csr_columns and not want_probs)
+                                                   plan=plan, keep_columns_pending=self.lazy_csr_columns and not want_probs,
+                                                   row_pool=row_pool)
                     if want_probs:
                         probs_csr = csr.with_values(res[1])
         if probs_csr is not None:

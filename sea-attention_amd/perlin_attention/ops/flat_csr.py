@@ -324,8 +324,34 @@ def keyrange_workspace_floats(N: int, H: int, T_dst: int, D: int, n_ranges: int)
     return N * H * n_ranges * T_dst * (D + 2)
 
 
+ROW_POOL_MAX = 1024
+
+
+def row_pool_supported(dtype, D: int, row_pool: int) -> bool:
+    """Pools the row-pool form of the fused launch takes (`sparse_attention(row_pool=...)`): a power of two, at most 1024 rows
+    and a multiple of the rows a workgroup of the form walks -- 64 for rows of 8 lanes (16-bit d = 64 / 80, fp32 d = 32), 32
+    for rows of 16 lanes (16-bit d = 128, fp32 d = 64)."""
+    vec = 4 if dtype == torch.float32 else 8
+    rpb = 64 if (D == 80 and vec == 8) or D <= 8 * vec else 32
+    return row_pool >= rpb and row_pool <= ROW_POOL_MAX and row_pool & (row_pool - 1) == 0
+
+
+def row_pool_workspace_elems(N: int, H: int, T_dst: int, row_pool: int) -> int:
+    """int16 elements of the row-pool form's order workspace: one per (n, h, slot of a pool), whole pools."""
+    return N * H * -(-T_dst // row_pool) * row_pool
+
+
 _BWD_WS = {}
 _KEYRANGE_WS = {}
+_ROW_POOL_WS = {}
+
+
+def row_pool_workspace(N: int, H: int, T_dst: int, row_pool: int, device) -> torch.Tensor:
+    """(N, H, pools * row_pool) int16 order of the row-pool form -- per (n, h, pool) the rows' offsets in the pool, longest row
+    first, written by the launch's pre-pass and read by its gather kernel: one buffer per (device, stream), kept like the
+    key-range form's workspace (undefined between calls; a graph capture gets its own, like any temporary)."""
+    per = row_pool_workspace_elems(1, H, T_dst, row_pool)
+    return _stream_workspace(_ROW_POOL_WS, N * per * 2, device).view(torch.int16).view(N, H, per // H)
 
 
 def _keyrange_workspace(N: int, stride: int, device) -> torch.Tensor:
@@ -355,10 +381,11 @@ def _stream_workspace(cache: dict, nbytes: int, device) -> torch.Tensor:
 
 
 def clear_bwd_workspace():
-    """Release the cached backward scratch (about 1 GB per device and stream at OPT-1.3B x 8) and the key-range form's partial
-    states; `clear_prep_cache()` calls it."""
+    """Release the cached backward scratch (about 1 GB per device and stream at OPT-1.3B x 8), the key-range form's partial
+    states and the row-pool form's order; `clear_prep_cache()` calls it."""
     _BWD_WS.clear()
     _KEYRANGE_WS.clear()
+    _ROW_POOL_WS.clear()
 
 
 class _SparseAttentionFn(torch.autograd.Function):
@@ -455,7 +482,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
                      plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False,
                      block_table: Optional[torch.Tensor] = None, range_keys: Optional[int] = None,
-                     probs_out: Optional[torch.Tensor] = None):
+                     row_pool: Optional[int] = None, probs_out: Optional[torch.Tensor] = None):
     """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
@@ -488,8 +515,16 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     emit launch -- for callers that return the CSR without anybody reading it (the layer's hot path).
     block_table: paged K / V: k / v are the K / V halves of a page pool (P, H, page_rows, D), sequence n's key r in page
     block_table[n, r // page_rows] (int32, (N, >= ceil(csr.T_src / page_rows))).  Only the one-row decode form reads pages: a
-    pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises."""
+    pending per-sequence decode handle, T_dst = 1, 16-bit d = 64 / 80 / 128; anything else raises.
+    row_pool: deal the fused launch's rows to its waves by length over pools of that many query rows (a pre-pass sorts every
+    pool; `row_pool_supported`: a power of two up to 1024, a multiple of the form's rows per workgroup, ValueError otherwise)
+    instead of the 64 / 32 rows a workgroup ranks by itself.  The same bits, another schedule.  It applies where the fused
+    inference launch serves the call (no probabilities, no decode or paged form, more than `attention_few_rows()` rows) and is
+    ignored elsewhere; the order it dealt by is left in `row_pool_workspace(N, H, T_dst, row_pool, device)`."""
     lib = _lib.load()
+    if row_pool is not None and not row_pool_supported(q.dtype, q.shape[-1], int(row_pool)):
+        raise ValueError(f"sparse_attention(row_pool={row_pool}): a power of two up to {ROW_POOL_MAX} and a multiple of the rows a "
+                         f"workgroup walks (64 for rows of 8 lanes, 32 for rows of 16; got {q.dtype}, d = {q.shape[-1]})")
     want_probs = want_probs or probs_out is not None
     if probs_out is not None:
         _lib.require_gpu(probs_out)
@@ -558,14 +593,18 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         nb_ = N * H * ((T_dst + 15) // 16)
         assert plan.dtype == torch.uint8 and plan.numel() == ((nb_ + 3) & ~3) + 4 and plan.is_contiguous()
 
-    def launch(col, probs, block_path, flags, bits=None, T_m=0, is_causal=0, max_k=0, write_cols=1, t_src_dev=None):
+    def launch(col, probs, block_path, flags, bits=None, T_m=0, is_causal=0, max_k=0, write_cols=1, t_src_dev=None, order=None):
+        if order is not None:                                 # the row-pool form: its workspace in block_path / probs_stride_n
+            block_path, ws_stride = order, order.stride(0)
+        else:
+            ws_stride = probs.stride(0) if probs is not None else 0
         return lib.sea_sparse_attention(
             _p(q), _p(k), _p(v), _lib.dtype_code(q.dtype), N, H, T_dst, T_src, D,
             _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
             _p(csr.crow), _p(col), col.stride(0), _p(csr.head_off),
             _p(row_scale), _p(avg), _lib.strides3(avg) if avg is not None else None, _p(mix),
             _p(out), _lib.dtype_code(out.dtype), _lib.strides3(out),
-            _p(probs), probs.stride(0) if probs is not None else 0, _p(block_path), flags,
+            _p(probs), ws_stride, _p(block_path), flags,
             _p(bits), T_m, is_causal, max_k, write_cols, _p(t_src_dev), csr.t_src_stride if t_src_dev is not None else 0,
             _p(block_table), table_stride, page_rows, _lib.stream_ptr())
 
@@ -583,8 +622,12 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         probs = probs_out
         if want_probs and probs is None:
             probs = torch.zeros(raw_col.shape, dtype=torch.float32, device=q.device)
-        rc = launch(raw_col, probs, None, _lib.SEA_ATTN_GATHER, csr.bits, T_m_, int(causal_), max_k_,
-                    0 if keep_columns_pending else 1, csr.t_src_dev)
+        flags, order = _lib.SEA_ATTN_GATHER, None
+        if row_pool is not None and not (decode_form or paged or want_probs):
+            flags |= (int(row_pool).bit_length() - 1) << _lib.SEA_ATTN_ROW_POOL_SHIFT
+            order = row_pool_workspace(N, H, T_dst, int(row_pool), q.device)
+        rc = launch(raw_col, probs, None, flags, csr.bits, T_m_, int(causal_), max_k_,
+                    0 if keep_columns_pending else 1, csr.t_src_dev, order)
         if rc == 0:
             if not keep_columns_pending:
                 csr._pending = None                         # the launch has written the columns
