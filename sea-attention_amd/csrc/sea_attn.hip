@@ -1064,7 +1064,8 @@ __global__ __launch_bounds__(256) void csr_spmm_kernel(SpmmParams p) {
     const int64_t key = ok ? ((int64_t)col[e] - hcol) : 0;
     const float pv = ok ? vals[e] : 0.f;
     uint4 vr = make_uint4(0, 0, 0, 0);
-    if (dact) vr = *reinterpret_cast<const uint4*>(vb + key * p.vs[2]);
+    // groups past the list's end load no V row: 0 * V[0] is NaN when row 0 is not finite, and nobody need have kept it
+    if (dact && ok) vr = *reinterpret_cast<const uint4*>(vb + key * p.vs[2]);
     float vf[VEC];
     unpack16<T>(vr, vf);
 #pragma unroll

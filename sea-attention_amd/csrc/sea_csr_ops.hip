@@ -29,13 +29,15 @@ __device__ inline float fkey_inv(uint32_t k) {
 
 // One 256-thread workgroup per (n, t) row.  Per-head running max / sum live in LDS; lanes that hold
 // entries of the same head are combined inside the wave before touching LDS (entries of a row are
-// grouped by head, so a wave sees 1-3 distinct heads).
+// grouped by head, so a wave sees 1-3 distinct heads).  Every wave sums into a slot of its own, in program
+// order, and the four slots are added in a fixed order: float atomics from several waves made the sum of
+// a head of more than two wave-chunks depend on their arrival order (other bits from run to run).
 template <typename I>
 __global__ __launch_bounds__(256) void csr_softmax_kernel(const float* in_all, float* out_all, int H, int T_dst, int T_src,
                                                          const I* crow_all, const I* col_all, int64_t col_stride_n) {
   __shared__ uint32_t s_max[1024];
-  __shared__ float s_sum[1024];
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ float s_sum[4][1024];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int row = blockIdx.x;
   const int n = row / T_dst, t = row - n * T_dst;
   const I* crow = crow_all + (int64_t)n * (T_dst + 1);
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(256) void csr_softmax_kernel(const float* in_all, f
   float* out = out_all + n * col_stride_n;
   const int64_t beg = crow[t], end = crow[t + 1];
   if (beg == end) return;
-  for (int i = tid; i < H; i += 256) { s_max[i] = 0u; s_sum[i] = 0.f; }
+  for (int i = tid; i < H; i += 256) { s_max[i] = 0u; s_sum[0][i] = s_sum[1][i] = s_sum[2][i] = s_sum[3][i] = 0.f; }
   __syncthreads();
   // pass 1: per-head max
   for (int64_t e0 = beg; e0 < end; e0 += 256) {
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void csr_softmax_kernel(const float* in_all, f
       const int h0 = __shfl(h, src);
       const bool mine = h == h0;
       const float sm = wave_sum(mine ? ex : 0.f);
-      if (lane == src) atomicAdd(&s_sum[h0], sm);
+      if (lane == src) s_sum[wv][h0] += sm;
       active &= ~__ballot(mine);
     }
   }
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void csr_softmax_kernel(const float* in_all, f
   // pass 3: normalise
   for (int64_t e = beg + tid; e < end; e += 256) {
     const int h = (int)(col[e] / T_src);
-    out[e] = __expf(in[e] - fkey_inv(s_max[h])) / s_sum[h];
+    out[e] = __expf(in[e] - fkey_inv(s_max[h])) / (((s_sum[0][h] + s_sum[1][h]) + s_sum[2][h]) + s_sum[3][h]);
   }
 }
 
