@@ -114,31 +114,13 @@ __global__ __launch_bounds__(256) void sparse_attn_kernel(AttnParams p) {
     m = M;
   }
 
+  const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
   if (WP && sub == 0) {                                    // every group: the entries it scored in pass 1
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float c = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) c *= p.row_scale[ridx];
+    const float c = attn_row_factor(p, ridx, l);
     float* pr = p.probs + n * p.probs_stride_n;
     for (int e = beg + grp; e < end; e += KPI) pr[e] = __expf(pr[e] - m) * c;
   }
-  if (grp == 0 && dact) {
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float scale = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) scale *= p.row_scale[ridx];
-    float o[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) o[j] = (l > 0.f) ? acc[j] * scale : 0.f;   // empty row: 0 even if the clamped key's V is not finite
-    if (p.mix) {
-      const float a = p.mix[ridx];
-      const T* ap = reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1] + t * p.as[2] + sub * VEC;
-      float af[VEC];
-      unpack16<T>(*reinterpret_cast<const uint4*>(ap), af);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
-    }
-    TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + t * p.os[2] + sub * VEC;
-    store_frag<TO, VEC>(op, o);
-  }
+  if (grp == 0 && dact) attn_epilogue<T, TO, false>(p, ridx, n, h, t, sub, l, acc);
 }
 
 // natural-order length of slot gi's row for rows_by_length (sea_attn.hpp): -1 for slots past T_dst
@@ -308,6 +290,13 @@ __device__ inline void fused_expand(const AttnParams& p, int n, int h, int tt, b
 // Decode form (DEC kernels, T_dst of a few rows): the block's key lists are complete in LDS (or, not fitting, in `col`); before
 // the one lane group per row starts its dependent walk, EVERY lane group of the block touches the K / V rows of the lists --
 // what the unfused kernel's warming pass does from `col` (see there).  Every thread of the block calls (two barriers).
+// one warming touch: the lane's 16-byte fragments of key_c's K and V rows; the caller sinks the returned word
+__device__ inline uint32_t touch_kv(const char* kbase, const char* vbase, uint32_t key_c, uint32_t kst, uint32_t vst, uint32_t lane_off) {
+  const uint4 a = *reinterpret_cast<const uint4*>(kbase + (__umul24(key_c, kst) + lane_off));
+  const uint4 b = *reinterpret_cast<const uint4*>(vbase + (__umul24(key_c, vst) + lane_off));
+  return a.x ^ b.x;
+}
+
 template <int LPR, int NG>
 __device__ inline void fused_warm(const int* s_keys, int total, bool fits, int hcol, const char* kbase, const char* vbase,
                                   uint32_t kst, uint32_t vst, uint32_t lane_off) {
@@ -315,12 +304,7 @@ __device__ inline void fused_warm(const int* s_keys, int total, bool fits, int h
   if (fits) {                                              // (block-uniform)
     const int g = (int)threadIdx.x / LPR;
     uint32_t sink = 0;
-    for (int e = g; e < total; e += NG) {
-      const uint32_t key_c = (uint32_t)(s_keys[e] - hcol);
-      const uint4 a = *reinterpret_cast<const uint4*>(kbase + (__umul24(key_c, kst) + lane_off));
-      const uint4 b = *reinterpret_cast<const uint4*>(vbase + (__umul24(key_c, vst) + lane_off));
-      sink ^= a.x ^ b.x;
-    }
+    for (int e = g; e < total; e += NG) sink ^= touch_kv(kbase, vbase, (uint32_t)(s_keys[e] - hcol), kst, vst, lane_off);
     asm volatile("" ::"v"(sink));                          // the loads must complete; their values are not used
   }
   __syncthreads();
@@ -344,13 +328,16 @@ constexpr int SEA_ATTN_WARM_ROWS = 8;            // T_dst up to which the idle l
 // Workgroup = 4 waves = 256/LPR consecutive query rows of one (n, h).
 // DEC (with FUSE): the decode form -- row widths from *p.t_src_dev, the key lists warmed by the whole block (fused_warm).
 // ORD (with FUSE, without DEC / WP): the rows come from the pool's order (pooled_row) instead of rows_by_length.
-template <typename T, typename TO, int LPR, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
-// the fused 16-bit inference forms are held to 64 registers (8 waves per SIMD; 4 - 8 spilled registers): measured 0.307 ms
-// against 0.328 ms at 88 registers for the 16-lane form (LLaMA-13B d = 128), and the same direction for the 8-lane form
-__global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ? 8 : 1) void sparse_attn_rows_kernel(AttnParams p) {
+// X80: the row fragment is RowFrag's d = 80 map (8 lanes of 8 + 2 elements).  ONE body, written on the fragment type, under
+// two entry points: sparse_attn_rows_kernel (rows of 4 / 8 / 16 lanes) and sparse_attn_rows80_kernel, which differ in their
+// launch bounds only (see there).
+template <typename T, typename TO, int LPR, int U, bool WP, int NWB, bool FUSE, bool DEC, bool ORD, bool X80>
+__device__ __forceinline__ void attn_rows_body(const AttnParams& p) {
   static_assert(!DEC || FUSE, "the decode form is a fused form");
   static_assert(!ORD || (FUSE && !DEC && !WP), "rows are dealt from pools in the fused inference form only");
-  constexpr int VEC = Elem<T>::VEC;
+  static_assert(!X80 || LPR == 8, "d = 80: eight lanes per row");
+  using F = RowFrag<T, X80>;
+  constexpr int VEC = F::VEC, NF = F::NF;
   constexpr int RPW = 64 / LPR;       // rows per wave
   constexpr int RPB = NWB * RPW;      // rows per workgroup
   int pair, tb;
@@ -369,7 +356,7 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   } else {
     t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
   }
-  const bool dact = sub * VEC < p.D;
+  const bool dact = X80 || sub * VEC < p.D;
   const int tt = t < p.T_dst ? t : p.T_dst - 1;
   const int sube = dact ? sub : 0;    // lanes beyond D re-read fragment 0 (their q fragment is zero)
 
@@ -377,11 +364,11 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1]);
   const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1]);
   const uint32_t kst = (uint32_t)p.ks[2] * (uint32_t)sizeof(T), vst = (uint32_t)p.vs[2] * (uint32_t)sizeof(T);
-  const uint32_t lane_off = (uint32_t)(sube * VEC) * (uint32_t)sizeof(T);
+  const typename F::Lane ln = F::lane(sube);
 
-  uint4 qraw = make_uint4(0, 0, 0, 0);
-  if (dact) qraw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] +
-                                                  (int64_t)tt * p.qs[2] + sub * VEC);
+  F qf;
+  qf.clear();
+  if (dact) qf.load(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + (int64_t)tt * p.qs[2], sub);
   const int row_beg = p.crow[(int64_t)n * (p.T_dst + 1) + tt];
   const int32_t* ho = p.head_off + ((int64_t)n * p.T_dst + tt) * (p.H + 1);
   const int beg = row_beg + ho[h];
@@ -399,24 +386,21 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
     t_src = p.t_src_dev[n * p.t_src_stride];               // the sequence's length (block-uniform; the one load of it)
     if (t_src < 0) {                                       // the sequence sits out this step (DecodeSession.pause / release): no
       const int t0 = tb * RPB + gi;                        // K or V access (its CSR rows are empty), its context rows are zeros
-      if (t0 < p.T_dst && dact) {
-        float o[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) o[j] = 0.f;
-        store_frag<TO, VEC>(reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t0 * p.os[2] + sub * VEC, o);
-      }
+      if (t0 < p.T_dst && dact) attn_zero_row<T, TO, X80>(p, n, h, t0, sub);
       return;
     }
   }
   if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, t_src, s_keys, &lbase, &fits, &ltotal);
-  if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, lane_off);
+  // (d = 80: the 16-byte fragments of the lists' K / V rows: 128 of a row's 160 bytes, i.e. both of its cache lines)
+  if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, ln.m);
 
   // ---- a decoding step: T_dst of one or a few rows, so all but a few of the block's lane groups have no row -- and the one
   // that has walks its ~k entries down ONE dependent chain (column indices -> four K / V rows -> the next four ...: three
   // memory round trips per 8 entries, 40 us for an OPT-1.3B x 8 step whose K / V lines come cold from HBM).  The idle groups
   // first touch every K / V row the block's rows will gather, all at once: the walk below then finds them in this CU's L1 /
   // the L2.  Arithmetic untouched: the step stays bitwise the stateless forward.
-  if constexpr (!FUSE) {
+  // (not for d = 80: the pass was written into the power-of-two kernel only -- DESIGN.md section 8)
+  if constexpr (!FUSE && !X80) {
     if (p.T_dst <= SEA_ATTN_WARM_ROWS) {                   // (grid-uniform)
       constexpr int NG = NWB * RPW;
       const int g = (int)threadIdx.x / LPR;
@@ -425,12 +409,7 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
         const int rb2 = p.crow[(int64_t)n * (p.T_dst + 1) + r];
         const int32_t* ho2 = p.head_off + ((int64_t)n * p.T_dst + r) * (p.H + 1);
         const int b2 = rb2 + ho2[h], e2 = rb2 + ho2[h + 1];
-        for (int e = b2 + g; e < e2; e += NG) {
-          const uint32_t key_c = (uint32_t)(col[e] - hcol);
-          const uint4 a = *reinterpret_cast<const uint4*>(kbase + (__umul24(key_c, kst) + lane_off));
-          const uint4 b = *reinterpret_cast<const uint4*>(vbase + (__umul24(key_c, vst) + lane_off));
-          sink ^= a.x ^ b.x;
-        }
+        for (int e = b2 + g; e < e2; e += NG) sink ^= touch_kv(kbase, vbase, (uint32_t)(col[e] - hcol), kst, vst, ln.m);
       }
       asm volatile("" ::"v"(sink));                        // the loads must complete; their values are not used
       __syncthreads();
@@ -438,9 +417,9 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
   }
 
   float m = -INFINITY, l = 0.f;
-  float acc[VEC];
+  float acc[NF];
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+  for (int j = 0; j < NF; ++j) acc[j] = 0.f;
 
   // longest row of the wave bounds the loop (rows of a wave are neighbours: similar lengths)
   int zmax = end - beg;
@@ -462,68 +441,49 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
     for (int u0 = 0; u0 < LPR; u0 += U) {
       if (i0 + u0 < zmax) {                                // wave-uniform
         bool ok[U];
-        uint4 kr[U], vr[U];
+        F kr[U], vr[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           ok[u] = beg + i0 + u0 + u < end;
           const uint32_t key_c = (uint32_t)__builtin_amdgcn_ds_bpermute(grp_lane0 + ((u0 + u) << 2), cidx);
-          kr[u] = *reinterpret_cast<const uint4*>(kbase + (__umul24(key_c, kst) + lane_off));
-          vr[u] = *reinterpret_cast<const uint4*>(vbase + (__umul24(key_c, vst) + lane_off));
+          kr[u].load(kbase, __umul24(key_c, kst), ln);
+          vr[u].load(vbase, __umul24(key_c, vst), ln);
         }
         float s[U];
         float mnew = m;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          float d = frag_dot<T>(qraw, kr[u]);
-          d = group_sum<LPR>(d);
+          const float d = group_sum<LPR>(qf.dot(kr[u]));
           s[u] = ok[u] ? d : -INFINITY;
           mnew = fmaxf(mnew, s[u]);
           if (WP && ok[u] && sub == u0 + u) p.probs[n * p.probs_stride_n + beg + i0 + u0 + u] = d;   // entry j by lane j % LPR
         }
-        const float msafe = (mnew == -INFINITY) ? 0.f : mnew;     // rows that have seen nothing yet: exp(-inf - 0) = 0
-        const float alpha = __expf(m - msafe);
-        l *= alpha;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[j] *= alpha;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const float pu = __expf(s[u] - msafe);
-          float vf[VEC];
-          unpack16<T>(vr[u], vf);
-          l += pu;
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(pu, vf[j], acc[j]);
-        }
-        m = mnew;
+        softmax_step<U>(s, mnew, vr, m, l, acc);
       }
     }
   }
 
+  const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
   if (WP && rowok) {
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float c = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) c *= p.row_scale[ridx];
+    const float c = attn_row_factor(p, ridx, l);
     float* pr = p.probs + n * p.probs_stride_n;
     for (int e = beg + sub; e < end; e += LPR) pr[e] = __expf(pr[e] - m) * c;
   }
-  if (rowok && dact) {
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float scale = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) scale *= p.row_scale[ridx];
-    float o[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) o[j] = (l > 0.f) ? acc[j] * scale : 0.f;   // empty row: 0 even if the clamped key's V is not finite
-    if (p.mix) {
-      const float a = p.mix[ridx];
-      const T* ap = reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1] + (int64_t)t * p.as[2] + sub * VEC;
-      float af[VEC];
-      unpack16<T>(*reinterpret_cast<const uint4*>(ap), af);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
-    }
-    TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t * p.os[2] + sub * VEC;
-    store_frag<TO, VEC>(op, o);
-  }
+  if (rowok && dact) attn_epilogue<T, TO, X80>(p, ridx, n, h, t, sub, l, acc);
+}
+
+template <typename T, typename TO, int LPR, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
+// the fused 16-bit inference forms are held to 64 registers (8 waves per SIMD; 4 - 8 spilled registers): measured 0.307 ms
+// against 0.328 ms at 88 registers for the 16-lane form (LLaMA-13B d = 128), and the same direction for the 8-lane form
+__global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ? 8 : 1) void sparse_attn_rows_kernel(AttnParams p) {
+  attn_rows_body<T, TO, LPR, U, WP, NWB, FUSE, DEC, ORD, false>(p);
+}
+
+template <typename T, typename TO, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
+// (no wave floor here: capping this kernel at 80 / 64 registers for 6 / 8 waves per SIMD measured 0.427 / 0.489 ms against
+// 0.418 ms as compiled, OPT-2.7B T = 8192 -- DESIGN.md section 9)
+__global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams p) {
+  attn_rows_body<T, TO, 8, U, WP, NWB, FUSE, DEC, ORD, true>(p);
 }
 
 // ---- a decoding step of ONE new row per sequence (T_dst = 1): the whole workgroup serves the row (round 5) ----------------
@@ -541,184 +501,7 @@ __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ?
 //      the row's end included (probability exp(-inf) = 0 times the last entry's V row) -- the step stays bitwise the stateless
 //      forward (tests/test_decode_session.py, test_kv_cache.py).
 // Rows longer than CH entries pass through in chunks (state carried).  16-bit data, rows of 8 or 16 lanes, T_m <= 256.
-// ---- d = 80 (OPT-2.7B heads), 16-bit data: 8 lanes per row, each with 8 + 2 elements -------------------------
-// The power-of-two mapping above gives a d = 80 row 16 lanes of which 10 carry data (4 rows per wave).  Here a row
-// takes 8 lanes: lane j holds elements 8j..8j+7 (one 16-byte load) plus the pair 64+2j, 65+2j (one 4-byte load), so a
-// wave advances 8 rows with every lane busy.  Same walk, same online softmax, same epilogue as sparse_attn_rows_kernel.
-template <typename T> __device__ inline float tail_dot(uint32_t q, uint32_t k, float d);
-template <> __device__ inline float tail_dot<__hip_bfloat16>(uint32_t q, uint32_t k, float d) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q), __builtin_bit_cast(sea_bf2, k), d, false);
-}
-template <> __device__ inline float tail_dot<__half>(uint32_t q, uint32_t k, float d) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q), __builtin_bit_cast(sea_h2, k), d, false);
-}
-template <typename T> __device__ inline void unpack2(uint32_t r, float* f);
-template <> __device__ inline void unpack2<__hip_bfloat16>(uint32_t r, float* f) {
-  f[0] = __uint_as_float(r << 16); f[1] = __uint_as_float(r & 0xffff0000u);
-}
-template <> __device__ inline void unpack2<__half>(uint32_t r, float* f) {
-  const float2 t = __half22float2(__builtin_bit_cast(__half2, r));
-  f[0] = t.x; f[1] = t.y;
-}
-template <typename TO> __device__ inline void store2(TO* dst, float a, float b) { *reinterpret_cast<uint32_t*>(dst) = pack2<TO>(a, b); }
-template <> __device__ inline void store2<float>(float* dst, float a, float b) { *reinterpret_cast<float2*>(dst) = make_float2(a, b); }
-
-template <typename T, typename TO, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
-// (no wave floor here: capping this kernel at 80 / 64 registers for 6 / 8 waves per SIMD measured 0.427 / 0.489 ms against
-// 0.418 ms as compiled, OPT-2.7B T = 8192 -- DESIGN.md section 9)
-__global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams p) {
-  static_assert(!DEC || FUSE, "the decode form is a fused form");
-  static_assert(!ORD || (FUSE && !DEC && !WP), "rows are dealt from pools in the fused inference form only");
-  constexpr int LPR = 8, VEC = 8, XT = 2, DM = LPR * VEC;     // DM = 64 elements in the 16-byte fragments
-  constexpr int RPW = 64 / LPR, RPB = NWB * RPW;
-  int pair, tb;
-  if (kernel_is_idle(p) || !map_block(p.N * p.H, p.TB, &pair, &tb)) return;
-  const int n = pair / p.H;
-  const int h = (pair - n * p.H + n) % p.H;                // heads rotated over the XCDs per item (see sparse_attn_rows_kernel)
-  const int lane = threadIdx.x & 63;
-  const int grp = lane / LPR, sub = lane - grp * LPR;
-  const int gi = (int)(threadIdx.x >> 6) * RPW + grp;
-  bool rowok;
-  int t;
-  if constexpr (ORD) {
-    if (!pooled_row<LPR, RPB>(p, n, h, tb, grp, &t, &rowok)) return;
-  } else {
-    t = tb * RPB + rows_by_length<LPR, RPB>(slot_length(p, n, h, tb * RPB + gi), gi, sub, &rowok);
-  }
-  const int tt = t < p.T_dst ? t : p.T_dst - 1;
-
-  const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1]);
-  const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1]);
-  const uint32_t kst = (uint32_t)p.ks[2] * (uint32_t)sizeof(T), vst = (uint32_t)p.vs[2] * (uint32_t)sizeof(T);
-  const uint32_t off_m = (uint32_t)(sub * VEC) * (uint32_t)sizeof(T);              // 16-byte fragment
-  const uint32_t off_x = (uint32_t)(DM + sub * XT) * (uint32_t)sizeof(T);          // 4-byte pair
-
-  const T* qrow = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + (int64_t)tt * p.qs[2];
-  const uint4 qraw = *reinterpret_cast<const uint4*>(qrow + sub * VEC);
-  const uint32_t qx = *reinterpret_cast<const uint32_t*>(qrow + DM + sub * XT);
-  const int row_beg = p.crow[(int64_t)n * (p.T_dst + 1) + tt];
-  const int32_t* ho = p.head_off + ((int64_t)n * p.T_dst + tt) * (p.H + 1);
-  const int beg = row_beg + ho[h];
-  const int end = rowok ? row_beg + ho[h + 1] : beg;
-  const int32_t* col = p.col + n * p.col_stride_n;
-  const int hcol = h * p.T_src;
-  extern __shared__ int s_keys[];                          // fused interpolation: see fused_expand
-  int lbase = 0;
-  bool fits = false;
-  int ltotal = 0;
-  int t_src = p.T_src;
-  if constexpr (DEC) {
-    t_src = p.t_src_dev[n * p.t_src_stride];               // the sequence's length (block-uniform; the one load of it)
-    if (t_src < 0) {                                       // the sequence sits out this step: zeros, as in sparse_attn_rows_kernel
-      const int t0 = tb * RPB + gi;
-      if (t0 < p.T_dst) {
-        float o[VEC + XT];
-#pragma unroll
-        for (int j = 0; j < VEC + XT; ++j) o[j] = 0.f;
-        TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t0 * p.os[2];
-        store_frag<TO, VEC>(op + sub * VEC, o);
-        store2<TO>(op + DM + sub * XT, o[VEC], o[VEC + 1]);
-      }
-      return;
-    }
-  }
-  if constexpr (FUSE) fused_expand<LPR, RPB, DEC>(p, n, h, tt, rowok, gi, sub, beg, end, hcol, t_src, s_keys, &lbase, &fits, &ltotal);
-  // (the 16-byte fragments of the lists' K / V rows: 128 of a row's 160 bytes, i.e. both of its cache lines)
-  if constexpr (DEC) fused_warm<LPR, NWB * RPW>(s_keys, ltotal, fits, hcol, kbase, vbase, kst, vst, off_m);
-
-  float m = -INFINITY, l = 0.f;
-  float acc[VEC + XT];
-#pragma unroll
-  for (int j = 0; j < VEC + XT; ++j) acc[j] = 0.f;
-
-  int zmax = end - beg;
-#pragma unroll
-  for (int o = LPR; o < 64; o <<= 1) zmax = max(zmax, __shfl_xor(zmax, o));
-  const int last = end - 1;
-  const int grp_lane0 = (lane - sub) << 2;
-  for (int i0 = 0; i0 < zmax; i0 += LPR) {
-    int cidx;
-    {
-      const int e = beg + i0 + sub;
-      const int ec = e < end ? e : (last >= beg ? last : 0);
-      cidx = (end > beg) ? (entry_column<FUSE>(p, col, n, ec, beg, s_keys, lbase, fits) - hcol) : 0;
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < LPR; u0 += U) {
-      if (i0 + u0 < zmax) {                                // wave-uniform
-        bool ok[U];
-        uint4 kr[U], vr[U];
-        uint32_t kx[U], vx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          ok[u] = beg + i0 + u0 + u < end;
-          const uint32_t key_c = (uint32_t)__builtin_amdgcn_ds_bpermute(grp_lane0 + ((u0 + u) << 2), cidx);
-          const uint32_t ko = __umul24(key_c, kst), vo = __umul24(key_c, vst);
-          kr[u] = *reinterpret_cast<const uint4*>(kbase + (ko + off_m));
-          kx[u] = *reinterpret_cast<const uint32_t*>(kbase + (ko + off_x));
-          vr[u] = *reinterpret_cast<const uint4*>(vbase + (vo + off_m));
-          vx[u] = *reinterpret_cast<const uint32_t*>(vbase + (vo + off_x));
-        }
-        float s[U];
-        float mnew = m;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          float d = tail_dot<T>(qx, kx[u], frag_dot<T>(qraw, kr[u]));
-          d = group_sum<LPR>(d);
-          s[u] = ok[u] ? d : -INFINITY;
-          mnew = fmaxf(mnew, s[u]);
-          if (WP && ok[u] && sub == u0 + u) p.probs[n * p.probs_stride_n + beg + i0 + u0 + u] = d;
-        }
-        const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
-        const float alpha = __expf(m - msafe);
-        l *= alpha;
-#pragma unroll
-        for (int j = 0; j < VEC + XT; ++j) acc[j] *= alpha;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const float pu = __expf(s[u] - msafe);
-          float vf[VEC + XT];
-          unpack16<T>(vr[u], vf);
-          unpack2<T>(vx[u], vf + VEC);
-          l += pu;
-#pragma unroll
-          for (int j = 0; j < VEC + XT; ++j) acc[j] = fmaf(pu, vf[j], acc[j]);
-        }
-        m = mnew;
-      }
-    }
-  }
-
-  if (WP && rowok) {
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float c = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) c *= p.row_scale[ridx];
-    float* pr = p.probs + n * p.probs_stride_n;
-    for (int e = beg + sub; e < end; e += LPR) pr[e] = __expf(pr[e] - m) * c;
-  }
-  if (rowok) {
-    const int64_t ridx = ((int64_t)n * p.H + h) * p.T_dst + t;
-    float scale = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) scale *= p.row_scale[ridx];
-    float o[VEC + XT];
-#pragma unroll
-    for (int j = 0; j < VEC + XT; ++j) o[j] = (l > 0.f) ? acc[j] * scale : 0.f;
-    if (p.mix) {
-      const float a = p.mix[ridx];
-      const T* ap = reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1] + (int64_t)t * p.as[2];
-      float af[VEC + XT];
-      unpack16<T>(*reinterpret_cast<const uint4*>(ap + sub * VEC), af);
-      unpack2<T>(*reinterpret_cast<const uint32_t*>(ap + DM + sub * XT), af + VEC);
-#pragma unroll
-      for (int j = 0; j < VEC + XT; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
-    }
-    TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t * p.os[2];
-    store_frag<TO, VEC>(op + sub * VEC, o);
-    store2<TO>(op + DM + sub * XT, o[VEC], o[VEC + 1]);
-  }
-}
-
-// X80: d = 80 on 8 lanes per row -- lane j holds elements 8j .. 8j+7 plus the pair 64+2j, 65+2j (sparse_attn_rows80_kernel's map)
+// X80: d = 80 on 8 lanes per row -- lane j holds elements 8j .. 8j+7 plus the pair 64+2j, 65+2j (RowFrag's d = 80 map)
 // PAGED: K / V in a page pool (AttnParams::table).  The sequence's block-table row is staged in LDS behind the V rows at kernel
 // start (its first ceil(T_src / page_rows) entries; dynamic LDS sized for the capacity's), and phase C translates each key to
 // (page, row) from there: the page term is a 64-bit product (page x page bytes overflows 32 bits), the row term stays 32-bit
@@ -726,11 +509,20 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_rows80_kernel(AttnParams
 // sub == 0 lane leaves the raw score at the slot of every real entry -- the padded slots total .. padded-1 belong to the next head
 // -- and, once (m, l) are final, the same thread turns it into the probability with the expression of sparse_attn_rows_kernel's
 // WP pass (a thread sees its own stores: no fence).  An empty head and a sequence that sits out write nothing.
+// the kernel's chunk and its dynamic LDS (16-bit rows; PAGED: the table row comes behind these bytes)
+template <int LPR, bool X80>
+struct Decode1Lds {
+  static constexpr int CH = LPR == 8 ? 256 : 128;          // entries per chunk: CH / 4 steps fit one wave, CH / NG = 8 per lane group
+  static constexpr int DL = LPR * (8 + (X80 ? 2 : 0));     // elements of a staged V row
+  static constexpr int bytes = CH * 8 + CH + CH * DL * 2;  // s_keys and s_sc [CH], s_al [CH / 4], s_v [CH][DL]
+};
+
 template <typename T, typename TO, int LPR, bool X80 = false, bool PAGED = false, bool WP = false>
 __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) {
-  constexpr int VEC = Elem<T>::VEC, NT = 256, NG = NT / LPR, XT = X80 ? 2 : 0, DL = LPR * (VEC + XT);
+  using F = RowFrag<T, X80>;
+  constexpr int VEC = F::VEC, NF = F::NF, NT = 256, NG = NT / LPR;
   static_assert(!X80 || LPR == 8, "d = 80: eight lanes per row");
-  constexpr int CH = LPR == 8 ? 256 : 128;                 // entries per chunk: CH / 4 steps fit one wave, CH / NG = 8 per lane group
+  constexpr int CH = Decode1Lds<LPR, X80>::CH, DL = Decode1Lds<LPR, X80>::DL;
   constexpr int EPG = CH / NG;
   static_assert(VEC == 8 && CH / 4 <= 64 && CH % NG == 0, "16-bit rows; one lane per step in phase D");
   extern __shared__ __attribute__((aligned(16))) char dsm[];
@@ -755,27 +547,17 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
     const int32_t* trow = p.table + (int64_t)n * p.table_stride;
     for (int i = tid; i < npg; i += NT) s_tab[i] = trow[i];            // (read after phase B's barrier; none when t_src < 0)
   }
-  const uint32_t lane_off = (uint32_t)(sube * VEC) * (uint32_t)sizeof(T);
-  uint4 qraw = make_uint4(0, 0, 0, 0);
-  if (dact) qraw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + sub * VEC);
-  constexpr int DM = LPR * VEC;                            // X80: elements in the 16-byte fragments; the pairs sit behind them
-  const uint32_t off_x = (uint32_t)(DM + sub * 2) * (uint32_t)sizeof(T);
-  uint32_t qx = 0;
-  if constexpr (X80) qx = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + DM + sub * 2);
+  const typename F::Lane ln = F::lane(sube);
+  F qf;
+  qf.clear();
+  if (dact) qf.load(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1], sub);
   const int beg = p.crow[(int64_t)n * 2] + p.head_off[(int64_t)n * (p.H + 1) + h];
   const int hcol = h * p.T_src;
 
   // the sequence sits out this step (DecodeSession.pause / release; block-uniform, at the first use of the length so that the
   // loads above do not wait for it): no table, K or V access, its context row is zeros
   if (t_src < 0) {
-    if (grp == 0 && dact) {
-      float o[VEC + 2];
-#pragma unroll
-      for (int j = 0; j < VEC + 2; ++j) o[j] = 0.f;
-      TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1];
-      store_frag<TO, VEC>(op + sub * VEC, o);
-      if constexpr (X80) store2<TO>(op + DM + sub * 2, o[VEC], o[VEC + 1]);
-    }
+    if (grp == 0 && dact) attn_zero_row<T, TO, X80>(p, n, h, 0, sub);
     return;
   }
 
@@ -799,9 +581,9 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
   int32_t* gcol = p.col_w + n * p.col_stride_n;
 
   float l = 0.f;
-  float acc[VEC + XT];
+  float acc[NF];
 #pragma unroll
-  for (int j = 0; j < VEC + XT; ++j) acc[j] = 0.f;
+  for (int j = 0; j < NF; ++j) acc[j] = 0.f;
 
   for (int c0 = 0; c0 < padded; c0 += CH) {                // (block-uniform)
     // this thread's pixel: its entries that fall into the chunk
@@ -828,8 +610,7 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
 
     // ---- C: one lane group per entry, EPG entries each, every load in flight at once ------------------------------------
     {
-      uint4 kr[EPG], vr[EPG];
-      uint32_t kx[EPG], vx[EPG];
+      F kr[EPG], vr[EPG];
 #pragma unroll
       for (int i = 0; i < EPG; ++i) {
         const int e = grp + i * NG;
@@ -845,25 +626,18 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
         } else {
           ko = __umul24(key_c, kst); vo = __umul24(key_c, vst);
         }
-        kr[i] = *reinterpret_cast<const uint4*>(kb + (ko + lane_off));
-        vr[i] = *reinterpret_cast<const uint4*>(vb + (vo + lane_off));
-        if constexpr (X80) {
-          kx[i] = *reinterpret_cast<const uint32_t*>(kb + (ko + off_x));
-          vx[i] = *reinterpret_cast<const uint32_t*>(vb + (vo + off_x));
-        }
+        kr[i].load(kb, ko, ln);
+        vr[i].load(vb, vo, ln);
       }
       float dr[WP ? EPG : 1];                              // WP: the raw scores, for the stores below
 #pragma unroll
       for (int i = 0; i < EPG; ++i) {
         const int e = grp + i * NG;
-        float d = frag_dot<T>(qraw, kr[i]);
-        if constexpr (X80) d = tail_dot<T>(qx, kx[i], d);
-        d = group_sum<LPR>(d);
+        const float d = group_sum<LPR>(qf.dot(kr[i]));
         if (e < nent) {
           if (sub == 0) s_sc[e] = c0 + e < total ? d : -INFINITY;
           if constexpr (WP) dr[i] = d;
-          *reinterpret_cast<uint4*>(s_v + (size_t)e * DL + sub * VEC) = vr[i];
-          if constexpr (X80) *reinterpret_cast<uint32_t*>(s_v + (size_t)e * DL + DM + sub * 2) = vx[i];
+          vr[i].put(s_v + (size_t)e * DL, sub);
         }
       }
       if constexpr (WP) {                                  // real entries only: the padded slots are the next head's
@@ -909,24 +683,19 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
         const float alpha = s_al[st];
         const float4 pu4 = *reinterpret_cast<const float4*>(s_sc + 4 * st);
         const float pu[4] = {pu4.x, pu4.y, pu4.z, pu4.w};
-        uint4 vr[4];
-        uint32_t vx[4];
+        F vr[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          vr[u] = *reinterpret_cast<const uint4*>(s_v + (size_t)(4 * st + u) * DL + sub * VEC);
-          if constexpr (X80) vx[u] = *reinterpret_cast<const uint32_t*>(s_v + (size_t)(4 * st + u) * DL + DM + sub * 2);
-        }
+        for (int u = 0; u < 4; ++u) vr[u].load(s_v + (size_t)(4 * st + u) * DL, sub);
         l *= alpha;
 #pragma unroll
-        for (int j = 0; j < VEC + XT; ++j) acc[j] *= alpha;
+        for (int j = 0; j < NF; ++j) acc[j] *= alpha;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          float vf[VEC + 2];
-          unpack16<T>(vr[u], vf);
-          if constexpr (X80) unpack2<T>(vx[u], vf + VEC);
+          float vf[NF];
+          vr[u].unpack(vf);
           l += pu[u];
 #pragma unroll
-          for (int j = 0; j < VEC + XT; ++j) acc[j] = fmaf(pu[u], vf[j], acc[j]);
+          for (int j = 0; j < NF; ++j) acc[j] = fmaf(pu[u], vf[j], acc[j]);
         }
       }
     }
@@ -938,8 +707,7 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
     if (tid == 0) s_l = l;
     __syncthreads();
     const float m = s_mcarry;
-    float c = (s_l > 0.f) ? (1.0f / s_l) : 0.f;
-    if (p.row_scale) c *= p.row_scale[(int64_t)n * p.H + h];
+    const float c = attn_row_factor(p, (int64_t)n * p.H + h, s_l);
     float* pr = p.probs + n * p.probs_stride_n + beg;
     if (sub == 0) {                                        // the slots this thread stored in phase C
       for (int c0 = 0; c0 < total; c0 += CH) {
@@ -951,26 +719,7 @@ __global__ __launch_bounds__(256) void sparse_attn_decode1_kernel(AttnParams p) 
       }
     }
   }
-  if (grp == 0 && dact) {                                  // sparse_attn_rows_kernel's epilogue (t = 0, T_dst = 1)
-    const int64_t ridx = (int64_t)n * p.H + h;
-    float sc_ = (l > 0.f) ? (1.0f / l) : 0.f;
-    if (p.row_scale) sc_ *= p.row_scale[ridx];
-    float o[VEC + 2];
-#pragma unroll
-    for (int j = 0; j < VEC + XT; ++j) o[j] = (l > 0.f) ? acc[j] * sc_ : 0.f;
-    if (p.mix) {
-      const float a = p.mix[ridx];
-      const T* ap = reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1];
-      float af[VEC + 2];
-      unpack16<T>(*reinterpret_cast<const uint4*>(ap + sub * VEC), af);
-      if constexpr (X80) unpack2<T>(*reinterpret_cast<const uint32_t*>(ap + DM + sub * 2), af + VEC);
-#pragma unroll
-      for (int j = 0; j < VEC + XT; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
-    }
-    TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1];
-    store_frag<TO, VEC>(op + sub * VEC, o);
-    if constexpr (X80) store2<TO>(op + DM + sub * 2, o[VEC], o[VEC + 1]);
-  }
+  if (grp == 0 && dact) attn_epilogue<T, TO, X80>(p, (int64_t)n * p.H + h, n, h, 0, sub, l, acc);   // (t = 0, T_dst = 1)
 }
 
 // ---- unfused SDDMM: one wave per (n, t) row, all heads -----------------------------------------------
@@ -1096,6 +845,61 @@ static bool strides_ok(const int64_t* s, int vec) { return s[0] % vec == 0 && s[
 // A decoding step (T_dst of a few rows per (n, h)): the fused form has nothing to win there (one row per workgroup), and the
 // plain lane-group kernel warms the row's K / V lines with its idle lane groups first (below).  sea_attention_few_rows().
 constexpr int64_t SEA_ATTN_FEW_ROWS = 2048;
+
+// one new row per sequence (sparse_attn_decode1_kernel): contiguous K / V, or (p.table) the PAGED form, the table row behind the V rows
+template <typename T, typename TO, int LPR, bool X80, bool WP>
+static void launch_decode1(const AttnParams& p, hipStream_t s) {
+  constexpr int lds = Decode1Lds<LPR, X80>::bytes;
+  const dim3 grid((unsigned)(p.N * p.H)), block(256);
+  if (p.table) {
+    const int tab = (int)((p.T_src + (1 << p.page_shift) - 1) >> p.page_shift) * (int)sizeof(int);
+    hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, LPR, X80, true, WP>), grid, block, lds + tab, s, p);
+  } else {
+    hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, LPR, X80, false, WP>), grid, block, lds, s, p);
+  }
+}
+
+// the lane-group kernel's entry point for a row fragment: d = 80 has its own (they differ in their launch bounds)
+template <typename T, typename TO, int LPR, bool WP, int NWB, bool FUSE, bool DEC, bool ORD, bool X80>
+static constexpr auto rows_entry() {
+  if constexpr (X80) return &sparse_attn_rows80_kernel<T, TO, 4, WP, NWB, FUSE, DEC, ORD>;
+  else return &sparse_attn_rows_kernel<T, TO, LPR, 4, WP, NWB, FUSE, DEC, ORD>;
+}
+
+// the lane-group kernels over rows of LPR lanes (X80: d = 80, 8 lanes x (8 + 2) elements per row): the plain form, or with
+// p.bits one of the fused forms -- decode, rows dealt from pools, fused inference
+template <typename T, typename TO, int LPR, bool WP, bool X80>
+static int launch_rows(AttnParams p, hipStream_t s) {
+  // rows per workgroup (sorted by length inside the kernel): 64 for rows of 4 or 8 lanes, 32 for rows of 16 lanes.
+  // Measured at the headline shape (layer's own selection, bf16 d = 64): 32 / 64 / 128 rows per block 0.99 / 0.96 / 1.00 ms.
+  constexpr int NWB = LPR == 4 ? 4 : 8, RPB = NWB * (64 / LPR);
+  const int NH = p.N * p.H;
+  p.TB = (p.T_dst + RPB - 1) / RPB;
+  void (*kern)(AttnParams) = rows_entry<T, TO, LPR, WP, NWB, false, false, false, X80>();
+  int lds = 0;
+  if (p.bits) {                                            // fused interpolation: group-private key lists in LDS
+    if constexpr (LPR == 4) {
+      return SEA_EUNSUPPORTED;
+    } else {
+      lds = p.fuse_cap * (int)sizeof(int);
+      kern = rows_entry<T, TO, LPR, WP, NWB, true, false, false, X80>();
+      if (p.t_src_dev) {                                   // decode form
+        kern = rows_entry<T, TO, LPR, WP, NWB, true, true, false, X80>();
+      } else if constexpr (!WP) {
+        if (p.order) {                                     // rows dealt from pools (the entry has checked the form)
+          if (p.pool_rows % RPB) return SEA_EINVAL;
+          p.TB = p.pools * (p.pool_rows / RPB);
+          hipLaunchKernelGGL(attn_row_order_kernel, dim3((unsigned)(NH * p.pools)), dim3(p.pool_rows < 64 ? 64 : p.pool_rows), 0, s, p);
+          kern = rows_entry<T, TO, LPR, false, NWB, true, false, true, X80>();
+        }
+      }
+    }
+  }
+  const dim3 grid((unsigned)((int64_t)8 * ((NH + 7) / 8) * p.TB)), block(NWB * 64);
+  hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+  return SEA_OK;
+}
+
 template <typename T, typename TO, bool WP>
 static int launch_attn_wp(AttnParams p, hipStream_t s) {
   constexpr int VEC = Elem<T>::VEC;
@@ -1107,93 +911,22 @@ static int launch_attn_wp(AttnParams p, hipStream_t s) {
   if constexpr (sizeof(T) == 2) {
     // one new row per sequence (a DecodeSession position): the whole workgroup serves the row (sparse_attn_decode1_kernel)
     if (p.bits && p.t_src_dev && p.T_dst == 1 && p.T_m <= 256 && small && (lpr == 8 || lpr == 16 || p.D == 80)) {
-      if (p.table) {                                       // paged K / V: the PAGED forms, the table row behind the V rows
-        const int tab = (int)((p.T_src + (1 << p.page_shift) - 1) >> p.page_shift) * (int)sizeof(int);
-        if (p.D == 80) {
-          constexpr int CH = 256, DL = 80;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
-        } else if (lpr == 8) {
-          constexpr int CH = 256, DL = 64;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
-        } else {
-          constexpr int CH = 128, DL = 128;
-          hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, true, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2 + tab, s, p);
-        }
-        return SEA_OK;
-      }
-      if (p.D == 80) {
-        constexpr int CH = 256, DL = 80;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, true, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
-      } else if (lpr == 8) {
-        constexpr int CH = 256, DL = 64;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 8, false, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
-      } else {
-        constexpr int CH = 128, DL = 128;
-        hipLaunchKernelGGL((sparse_attn_decode1_kernel<T, TO, 16, false, false, WP>), dim3((unsigned)NH), dim3(256), CH * 8 + CH + CH * DL * 2, s, p);
-      }
+      if (p.D == 80) launch_decode1<T, TO, 8, true, WP>(p, s);
+      else if (lpr == 8) launch_decode1<T, TO, 8, false, WP>(p, s);
+      else launch_decode1<T, TO, 16, false, WP>(p, s);
       return SEA_OK;
     }
   }
   if (p.table) return SEA_EUNSUPPORTED;                    // (only the one-row decode kernel reads a page pool)
   if constexpr (sizeof(T) == 2) {
-    if (p.D == 80 && small) {                          // d = 80: 8 lanes x (8 + 2) elements per row
-      const int rpb = 8 * 8;                               // 8 waves x 8 rows, sorted by length
-      p.TB = (p.T_dst + rpb - 1) / rpb;
-      if constexpr (!WP) {
-        if (p.order) {                                     // rows dealt from pools (the entry has checked the form)
-          if (p.pool_rows % rpb) return SEA_EINVAL;
-          p.TB = p.pools * (p.pool_rows / rpb);
-          const int64_t pblocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
-          hipLaunchKernelGGL(attn_row_order_kernel, dim3((unsigned)(NH * p.pools)), dim3(p.pool_rows < 64 ? 64 : p.pool_rows), 0, s, p);
-          hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, false, 8, true, false, true>), dim3((unsigned)pblocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
-          return SEA_OK;
-        }
-      }
-      const int64_t blocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
-      if (p.bits && p.t_src_dev) {
-        hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8, true, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
-      } else if (p.bits) hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8, true>), dim3((unsigned)blocks), dim3(512), p.fuse_cap * (int)sizeof(int), s, p);
-      else hipLaunchKernelGGL((sparse_attn_rows80_kernel<T, TO, 4, WP, 8>), dim3((unsigned)blocks), dim3(512), 0, s, p);
-      return SEA_OK;
-    }
+    if (p.D == 80 && small) return launch_rows<T, TO, 8, WP, true>(p, s);
   }
   if (lpr <= 16 && small) {
-    // rows per workgroup (sorted by length inside the kernel): 64 for rows of 4 or 8 lanes, 32 for rows of 16 lanes.
-    // Measured at the headline shape (layer's own selection, bf16 d = 64): 32 / 64 / 128 rows per block 0.99 / 0.96 / 1.00 ms.
-    const int nwb = lpr == 4 ? 4 : 8;
-    const int rpb = nwb * (64 / lpr);
-    p.TB = (p.T_dst + rpb - 1) / rpb;
-    const int64_t blocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;
-    dim3 grid((unsigned)blocks), block(nwb * 64);
-    if (p.bits) {                                          // fused interpolation: group-private key lists in LDS
-      if (lpr == 4) return SEA_EUNSUPPORTED;
-      const int lds = p.fuse_cap * (int)sizeof(int);
-      if (p.t_src_dev) {                                   // decode form
-        if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true, true>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true, true>), grid, block, lds, s, p);
-        return SEA_OK;
-      }
-      if constexpr (!WP) {
-        if (p.order) {                                     // rows dealt from pools (the entry has checked the form)
-          if (p.pool_rows % rpb) return SEA_EINVAL;
-          p.TB = p.pools * (p.pool_rows / rpb);
-          const dim3 pgrid((unsigned)((int64_t)8 * ((NH + 7) / 8) * p.TB));
-          hipLaunchKernelGGL(attn_row_order_kernel, dim3((unsigned)(NH * p.pools)), dim3(p.pool_rows < 64 ? 64 : p.pool_rows), 0, s, p);
-          if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, false, 8, true, false, true>), pgrid, block, lds, s, p);
-          else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, false, 8, true, false, true>), pgrid, block, lds, s, p);
-          return SEA_OK;
-        }
-      }
-      if (lpr == 8) hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8, true>), grid, block, lds, s, p);
-      else hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8, true>), grid, block, lds, s, p);
-      return SEA_OK;
-    }
     switch (lpr) {
-      case 4: hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 4, 4, WP, 4>), grid, block, 0, s, p); break;
-      case 8: hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 8, 4, WP, 8>), grid, block, 0, s, p); break;
-      default: hipLaunchKernelGGL((sparse_attn_rows_kernel<T, TO, 16, 4, WP, 8>), grid, block, 0, s, p); break;
+      case 4: return launch_rows<T, TO, 4, WP, false>(p, s);
+      case 8: return launch_rows<T, TO, 8, WP, false>(p, s);
+      default: return launch_rows<T, TO, 16, WP, false>(p, s);
     }
-    return SEA_OK;
   }
   if (p.bits) return SEA_EUNSUPPORTED;                      // (the wave-per-row kernel below has no fused form)
   const int64_t blocks = (int64_t)8 * ((NH + 7) / 8) * p.TB;

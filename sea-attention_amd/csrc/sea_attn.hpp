@@ -154,6 +154,150 @@ template <> __device__ inline float frag_dot<__half>(const uint4& q, const uint4
   return __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q.w), __builtin_bit_cast(sea_h2, k.w), d, false);
 }
 
+// ---- d = 80 (OPT-2.7B heads), 16-bit data: 8 lanes per row, each with 8 + 2 elements -------------------------
+// The power-of-two mapping gives a d = 80 row 16 lanes of which 10 carry data (4 rows per wave).  Here a row
+// takes 8 lanes: lane j holds elements 8j..8j+7 (one 16-byte load) plus the pair 64+2j, 65+2j (one 4-byte load), so a
+// wave advances 8 rows with every lane busy.
+template <typename T> __device__ inline float tail_dot(uint32_t q, uint32_t k, float d);
+template <> __device__ inline float tail_dot<__hip_bfloat16>(uint32_t q, uint32_t k, float d) {
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sea_bf2, q), __builtin_bit_cast(sea_bf2, k), d, false);
+}
+template <> __device__ inline float tail_dot<__half>(uint32_t q, uint32_t k, float d) {
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(sea_h2, q), __builtin_bit_cast(sea_h2, k), d, false);
+}
+template <typename T> __device__ inline void unpack2(uint32_t r, float* f);
+template <> __device__ inline void unpack2<__hip_bfloat16>(uint32_t r, float* f) {
+  f[0] = __uint_as_float(r << 16); f[1] = __uint_as_float(r & 0xffff0000u);
+}
+template <> __device__ inline void unpack2<__half>(uint32_t r, float* f) {
+  const float2 t = __half22float2(__builtin_bit_cast(__half2, r));
+  f[0] = t.x; f[1] = t.y;
+}
+template <typename TO> __device__ inline void store2(TO* dst, float a, float b) { *reinterpret_cast<uint32_t*>(dst) = pack2<TO>(a, b); }
+template <> __device__ inline void store2<float>(float* dst, float a, float b) { *reinterpret_cast<float2*>(dst) = make_float2(a, b); }
+
+// ---- what ONE LANE holds of a q / K / V / avg / out row of the gather kernels --------------------------------------------
+// Lane `sub` of a row's lane group holds the 16-byte fragment `sub` (VEC elements); X80 (the d = 80 map above): also the pair
+// behind the DM = 64 elements of the fragments.  NF = the lane's elements as floats.  The power-of-two form never touches `x`:
+// every use of it sits under `if constexpr (X80)`, so it costs no register and no load.  Which lanes are active is the
+// kernels' business (dact = sub * VEC < D, lanes beyond D re-read fragment 0; every lane is active for d = 80).
+template <typename T, bool X80 = false>
+struct RowFrag {
+  static constexpr int VEC = Elem<T>::VEC, XT = X80 ? 2 : 0, NF = VEC + XT;
+  static constexpr int DM = 8 * VEC;                       // X80: elements in the 16-byte fragments; the pairs sit behind them
+  static_assert(!X80 || sizeof(T) == 2, "d = 80: 16-bit data, eight lanes per row");
+  uint4 r;
+  uint32_t x;
+
+  // byte offsets of lane `sub`'s parts inside a row of T
+  struct Lane { uint32_t m, x; };
+  __device__ static inline Lane lane(int sub) {
+    return {(uint32_t)(sub * VEC) * (uint32_t)sizeof(T), (uint32_t)(DM + sub * XT) * (uint32_t)sizeof(T)};
+  }
+  // (the loads and clear() fill the fragment in place: a fragment returned by value and copied into an array element cost
+  // sparse_attn_decode1_kernel 22 registers)
+  __device__ inline void clear() {
+    r = make_uint4(0, 0, 0, 0);
+    if constexpr (X80) x = 0;
+  }
+  // a gathered row: wave-uniform 64-bit base + 32-bit byte offset of the row + the lane's
+  __device__ inline void load(const char* base, uint32_t row_off, Lane ln) {
+    r = *reinterpret_cast<const uint4*>(base + (row_off + ln.m));
+    if constexpr (X80) x = *reinterpret_cast<const uint32_t*>(base + (row_off + ln.x));
+  }
+  // a row by its pointer (q, avg; the rows staged in LDS)
+  __device__ inline void load(const T* row, int sub) {
+    r = *reinterpret_cast<const uint4*>(row + sub * VEC);
+    if constexpr (X80) x = *reinterpret_cast<const uint32_t*>(row + DM + sub * XT);
+  }
+  __device__ inline void put(T* row, int sub) const {     // as loaded (staging in LDS)
+    *reinterpret_cast<uint4*>(row + sub * VEC) = r;
+    if constexpr (X80) *reinterpret_cast<uint32_t*>(row + DM + sub * XT) = x;
+  }
+  // this lane's part of q . k (exact products, fp32 accumulation; group_sum adds the lanes)
+  __device__ inline float dot(const RowFrag& k) const {
+    float d = frag_dot<T>(r, k.r);
+    if constexpr (X80) d = tail_dot<T>(x, k.x, d);
+    return d;
+  }
+  __device__ inline void unpack(float* f) const {
+    unpack16<T>(r, f);
+    if constexpr (X80) unpack2<T>(x, f + VEC);
+  }
+  template <typename TO> __device__ static inline void store(TO* row, int sub, const float* f) {
+    store_frag<TO, VEC>(row + sub * VEC, f);
+    if constexpr (X80) store2<TO>(row + DM + sub * XT, f[VEC], f[VEC + 1]);
+  }
+  template <typename TO> __device__ static inline void store_zero(TO* row, int sub) {
+    float o[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) o[j] = 0.f;
+    store<TO>(row, sub, o);
+  }
+};
+
+// ---- one step of the online softmax: U scored entries into a lane group's state (m, l, acc[NF]) -------------------------
+// s[u]: the group's score of entry u (group_sum of the lanes' dots), -INFINITY where the entry does not exist; mnew: the
+// maximum of m and the s[u], which the caller's scoring loop tracks (found inside this function instead, the key-range
+// kernel took one register more and lost a wave of occupancy); v[u]: the entry's V fragment, already loaded (a masked
+// entry's is whatever the caller loaded for it: its probability is exp(-inf) = 0).  The gather kernels' walk
+// (attn_rows_body) and the key-range walk take this step; sparse_attn_decode1_kernel's phases D + E repeat its operations
+// in its order.
+template <int U, typename F>
+__device__ __forceinline__ void softmax_step(const float* s, float mnew, const F* v, float& m, float& l, float* acc) {
+  const float msafe = (mnew == -INFINITY) ? 0.f : mnew;     // rows that have seen nothing yet: exp(-inf - 0) = 0
+  const float alpha = __expf(m - msafe);
+  l *= alpha;
+#pragma unroll
+  for (int j = 0; j < F::NF; ++j) acc[j] *= alpha;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float pu = __expf(s[u] - msafe);
+    float vf[F::NF];
+    v[u].unpack(vf);
+    l += pu;
+#pragma unroll
+    for (int j = 0; j < F::NF; ++j) acc[j] = fmaf(pu, vf[j], acc[j]);
+  }
+  m = mnew;
+}
+
+// ---- the gather kernels' epilogue -------------------------------------------------------------------------------------
+// what a row's sum l turns into the factor of its accumulators (and, times exp(s - m), of its per-entry probabilities)
+__device__ inline float attn_row_factor(const AttnParams& p, int64_t ridx, float l) {
+  float scale = (l > 0.f) ? (1.0f / l) : 0.f;
+  if (p.row_scale) scale *= p.row_scale[ridx];
+  return scale;
+}
+template <typename TO> __device__ inline TO* attn_out_row(const AttnParams& p, int n, int h, int t) {
+  return reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t * p.os[2];
+}
+// row (n, h, t) = ridx of the (N, H, T_dst) rows, by the lane `sub` that holds (l, acc): acc / l * row_scale, the blend with
+// avg, the store in out_dtype.  The caller has picked the lanes (its row exists, the lane is active)
+template <typename T, typename TO, bool X80>
+__device__ __forceinline__ void attn_epilogue(const AttnParams& p, int64_t ridx, int n, int h, int t, int sub, float l, const float* acc) {
+  using F = RowFrag<T, X80>;
+  const float scale = attn_row_factor(p, ridx, l);
+  float o[F::NF];
+#pragma unroll
+  for (int j = 0; j < F::NF; ++j) o[j] = (l > 0.f) ? acc[j] * scale : 0.f;   // empty row: 0 even if the clamped key's V is not finite
+  if (p.mix) {
+    const float a = p.mix[ridx];
+    F avg;
+    avg.load(reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1] + (int64_t)t * p.as[2], sub);
+    float af[F::NF];
+    avg.unpack(af);
+#pragma unroll
+    for (int j = 0; j < F::NF; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
+  }
+  F::template store<TO>(attn_out_row<TO>(p, n, h, t), sub, o);
+}
+// the context row of a sequence that sits out a decode step (DecodeSession.pause / release): zeros
+template <typename T, typename TO, bool X80>
+__device__ inline void attn_zero_row(const AttnParams& p, int n, int h, int t, int sub) {
+  RowFrag<T, X80>::template store_zero<TO>(attn_out_row<TO>(p, n, h, t), sub);
+}
+
 // true when the plan hands this launch to the OTHER kernel (uniform over the whole grid: every workgroup returns at once)
 __device__ inline bool kernel_is_idle(const AttnParams& p) {
   if (p.sel == nullptr) return false;

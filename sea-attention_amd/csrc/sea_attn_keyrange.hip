@@ -87,7 +87,8 @@ __device__ inline bool range_reaches_row(const AttnParams& p, int t, int k0) {
 
 template <typename T, int LPR, int U, int NWB>
 __global__ __launch_bounds__(NWB * 64) void attn_keyrange_partial_kernel(AttnParams p, KeyRangeParams kr) {
-  constexpr int VEC = Elem<T>::VEC;
+  using F = RowFrag<T>;
+  constexpr int VEC = F::VEC;
   constexpr int RPW = 64 / LPR;       // rows per wave
   constexpr int RPB = NWB * RPW;      // rows per workgroup
   constexpr int Q = SEA_KEYRANGE_LIST / RPB;               // entries of a row's list held in LDS at a time
@@ -132,11 +133,11 @@ __global__ __launch_bounds__(NWB * 64) void attn_keyrange_partial_kernel(AttnPar
   const char* kbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + h * p.ks[1]);
   const char* vbase = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + h * p.vs[1]);
   const uint32_t kst = (uint32_t)p.ks[2] * (uint32_t)sizeof(T), vst = (uint32_t)p.vs[2] * (uint32_t)sizeof(T);
-  const uint32_t lane_off = (uint32_t)(sube * VEC) * (uint32_t)sizeof(T);
+  const typename F::Lane ln = F::lane(sube);
 
-  uint4 qraw = make_uint4(0, 0, 0, 0);
-  if (dact) qraw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] +
-                                                  (int64_t)tt * p.qs[2] + sub * VEC);
+  F qf;
+  qf.clear();
+  if (dact) qf.load(reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + (int64_t)tt * p.qs[2], sub);
   const float scale = interp_scale(row_width(tt, p.T_dst, p.T_src, p.is_causal), p.T_m);
   const uint32_t* brow = p.bits + ((int64_t)n * p.T_dst + tt) * p.W + h * WPH;
   int* slice = s_keys + gi * Q;                            // written and read by this lane group alone: no workgroup barrier
@@ -174,42 +175,27 @@ __global__ __launch_bounds__(NWB * 64) void attn_keyrange_partial_kernel(AttnPar
       for (int u0 = 0; u0 < LPR; u0 += U) {
         if (i0 + u0 < zmax) {                              // wave-uniform
           bool ok[U];
-          uint4 kf[U], vr[U];
+          F kf[U], vr[U];
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             ok[u] = i0 + u0 + u < pn;
             const uint32_t key_c = (uint32_t)__builtin_amdgcn_ds_bpermute(grp_lane0 + ((u0 + u) << 2), cidx);
-            kf[u] = make_uint4(0, 0, 0, 0);
-            vr[u] = make_uint4(0, 0, 0, 0);
+            kf[u].clear();
+            vr[u].clear();
             if (has) {
-              kf[u] = *reinterpret_cast<const uint4*>(kbase + (__umul24(key_c, kst) + lane_off));
-              vr[u] = *reinterpret_cast<const uint4*>(vbase + (__umul24(key_c, vst) + lane_off));
+              kf[u].load(kbase, __umul24(key_c, kst), ln);
+              vr[u].load(vbase, __umul24(key_c, vst), ln);
             }
           }
           float s[U];
           float mnew = m;
 #pragma unroll
           for (int u = 0; u < U; ++u) {
-            float d = frag_dot<T>(qraw, kf[u]);
-            d = group_sum<LPR>(d);
+            const float d = group_sum<LPR>(qf.dot(kf[u]));
             s[u] = ok[u] ? d : -INFINITY;
             mnew = fmaxf(mnew, s[u]);
           }
-          const float msafe = (mnew == -INFINITY) ? 0.f : mnew;     // rows that have seen nothing yet: exp(-inf - 0) = 0
-          const float alpha = __expf(m - msafe);
-          l *= alpha;
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] *= alpha;
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const float pu = __expf(s[u] - msafe);
-            float vf[VEC];
-            unpack16<T>(vr[u], vf);
-            l += pu;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) acc[j] = fmaf(pu, vf[j], acc[j]);
-          }
-          m = mnew;
+          softmax_step<U>(s, mnew, vr, m, l, acc);
         }
       }
     }
@@ -262,21 +248,7 @@ __global__ __launch_bounds__(256) void attn_keyrange_combine_kernel(AttnParams p
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[j] = fmaf(af[j], w, acc[j]);
   }
-  float scale = (l > 0.f) ? (1.0f / l) : 0.f;
-  if (p.row_scale) scale *= p.row_scale[ridx];
-  float o[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) o[j] = (l > 0.f) ? acc[j] * scale : 0.f;
-  if (p.mix) {
-    const float a = p.mix[ridx];
-    const T* ap = reinterpret_cast<const T*>(p.avg) + n * p.as[0] + h * p.as[1] + (int64_t)t * p.as[2] + sub * VEC;
-    float af[VEC];
-    unpack16<T>(*reinterpret_cast<const uint4*>(ap), af);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) o[j] = o[j] * a + (1.0f - a) * af[j];
-  }
-  TO* op = reinterpret_cast<TO*>(p.out) + n * p.os[0] + h * p.os[1] + (int64_t)t * p.os[2] + sub * VEC;
-  store_frag<TO, VEC>(op, o);
+  attn_epilogue<T, TO, false>(p, ridx, n, h, t, sub, l, acc);
 }
 
 template <typename T, typename TO>
