@@ -18,7 +18,7 @@
 // it is both the C operand of the update S += phi(K_c)^T V_c and -- register r of a 16x16 tile being row
 // 4g+r of lane group g -- the B operand of the carry term phi(Q_c) S, with the k index of that product
 // permuted accordingly on the A side.  All products run on v_mfma_f32_16x16x4_f32 (exact fp32).
-#include "sea_common.hpp"
+#include "sea_performer16.hpp"
 #include <cstdlib>
 
 #ifdef SEA_STAMP
@@ -39,95 +39,20 @@ __device__ unsigned long long sea_dbg_wg[2048];   // [start, end] (s_memrealtime
 
 namespace sea {
 
-using f4 = __attribute__((ext_vector_type(4))) float;
 #define SEA_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-struct PerfParams {
-  const void *q, *k, *v;   // (N,H,T,D)
-  const void* pos;         // (>=T, D) learned causal value embedding
-  const float* W;          // (nb, D) fp32
-  void* out;               // (N,H,T,3D)
-  void* avg;               // optional (N,H,T,D): cumulative average of v (bf16 kernel only)
-  int64_t qs[3], ks[3], vs[3];
-  int64_t pos_stride;
-  int N, H, T, nb;
-  // sequence-parallel form (few (n,h) pairs): the T rows are cut into nseg segments of seg_len rows (a multiple of the
-  // chunk size).  Pass 1 (STATE_ONLY kernels, grid.y = nseg-1) leaves every segment's state increment in `carry`,
-  // pass 2 (grid.y = nseg) starts each segment from the sum of the increments before it.  nseg = 1: one pass.
-  float* carry;
-  int nseg, seg_len;
-  // stateful form (kv-cache decoding): the rows handed in continue a sequence.  state_in / state_out are per-(n,h)
-  // images in the carry format (state registers, k-sum, column sum of v); t_base = rows the state has already seen
-  // (only the cumulative average needs the absolute row index).  Either may be null.
-  const float* state_in;
-  float* state_out;
-  int t_base;
-  // device-resident form of t_base (a captured decode step replayed as a HIP graph: the position lives in memory).  When
-  // set, `pos` is the BASE of the embedding table and the kernel reads its rows from row *t_base_dev on.
-  const int32_t* t_base_dev;
-  // per-sequence positions (t_base_stride > 0, the SEQ instantiations of the 16-bit kernels): sequence n has seen
-  // t_base_dev[n * t_base_stride] rows.  0: the one position above
-  int t_base_stride;
-  // chunk-aligned step (the 16-bit MFMA kernels): the state image is the state at the last CHUNK BOUNDARY c0 =
-  // floor(t_base / C) * C, and the open chunk's rows c0 .. t_base-1 are walked again (k, v, pos from the caller's kv-cache,
-  // no q, no output), so that every new row is computed by the very instruction sequence the stateless pass runs for it --
-  // bitwise the stateless result for any split of the sequence into calls.  k / v / pos then point at row c0 (with
-  // t_base_dev: at row 0 of the caches / the table, the kernel adds c0); q / out / avg at the first new row.
-  int aligned;
-  // paged K / V (a block table, the PAGED instantiations of the SEQ forms): k / v are the K / V halves of a page pool,
-  // strides [page, head, row]; sequence n's chunk c0 lives in page table[n * table_stride + c0 / page_rows] at row
-  // c0 % page_rows (page_rows = 1 << page_shift, a multiple of C: the open chunk and the new row lie in that one page)
-  const int32_t* table;
-  int table_stride, page_shift;
-};
-
-typedef __attribute__((ext_vector_type(8))) __bf16 pbf8;
-typedef __attribute__((ext_vector_type(8))) _Float16 ph8;
-typedef __attribute__((ext_vector_type(4))) short ps4;
-
-// 16-bit storage type of the split operands: bf16 data splits into bf16 terms (2 x 8 significand bits), fp16 data into
-// fp16 terms (2 x 11 bits; the state S and the products stay well inside fp16's range for T up to tens of thousands)
-template <typename T> struct S16;
-template <> struct S16<__hip_bfloat16> {
-  static constexpr unsigned short ONE = 0x3F80;
-  __device__ static inline unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, __float2bfloat16(x)); }
-  __device__ static inline float val(unsigned short b) { return __uint_as_float((uint32_t)b << 16); }
-  __device__ static inline f4 mfma(const uint4& a, const uint4& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pbf8, a), __builtin_bit_cast(pbf8, b), c, 0, 0, 0);
-  }
-};
-template <> struct S16<__half> {
-  static constexpr unsigned short ONE = 0x3C00;
-  __device__ static inline unsigned short bits(float x) { return __builtin_bit_cast(unsigned short, __float2half(x)); }
-  __device__ static inline float val(unsigned short b) { return __half2float(__builtin_bit_cast(__half, b)); }
-  __device__ static inline f4 mfma(const uint4& a, const uint4& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph8, a), __builtin_bit_cast(ph8, b), c, 0, 0, 0);
-  }
-};
 
 // fp32 data.  NW = 8 waves per workgroup: two per SIMD, so one wave's LDS/MFMA latency hides behind the other's issue
 template <int D, int NBT, int C, bool STATE_ONLY>
 __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
-  constexpr int NW = 8, NTH = NW * 64;
+  using P = PerfF32Plan<D, NBT, C>;          // the constants, the LDS images and the carry size (sea_performer16.hpp)
+  constexpr int NW = P::NW, NTH = P::NTH, NBP = P::NBP, RB = P::RB, EB = P::EB, JB = P::JB;
+  constexpr int LDQ = P::LDQ, LDV = P::LDV, LDP = P::LDP, LDA = P::LDA, LDW = P::LDW, DSL = P::DSL;
   constexpr int VEC = Elem<float>::VEC;
-  constexpr int E = 2 * D, NBP = NBT * 16;
-  constexpr int RB = C / 16;                  // row blocks per chunk
-  constexpr int EB = E / 16;                  // column blocks of V / S / O
-  constexpr int JB = (EB + NW - 1) / NW;      // column blocks owned by one wave
-  constexpr int LDQ = D + 2, LDV = E + 16, LDP = NBP + 2, LDA = C + 2, LDW = D + 2;
-  static_assert(LDA <= LDQ, "the A tile is overlaid on the Q tile");
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sW = smem;               // NBP x LDW   W (rows >= nb are zero)
-  float* sQ = sW + NBP * LDW;     // C x LDQ     Q chunk, later the masked A tile (C x LDA)
-  float* sK = sQ + C * LDQ;       // C x LDQ
-  float* sV = sK + C * LDQ;       // C x LDV     [pos | v]
-  float* sQp = sV + C * LDV;      // C x LDP     phi(Q)
-  float* sKp = sQp + C * LDP;     // C x LDP     phi(K)
-  float* sKsum = sKp + C * LDP;   // NBP         running sum of phi(k)
-  float* sDen = sKsum + NBP;      // C           denominators of the current chunk
-  constexpr int DSL = RB + NW * 64 / C;       // partial-denominator slots per row: RB key blocks + carry parts
-  float* sDenP = sDen + C;        // C x DSL     partials, summed in a fixed order (bitwise reproducible)
-  float* sA = sQ;
+  float *sW = smem + P::oW, *sQ = smem + P::oQ, *sK = smem + P::oK, *sV = smem + P::oV, *sQp = smem + P::oQp, *sKp = smem + P::oKp;
+  float *sKsum = smem + P::oKsum, *sDen = smem + P::oDen, *sDenP = smem + P::oDenP;
+  float* sA = sQ;                 // the masked A tile overlays the Q chunk
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -151,7 +76,7 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
   }
 
   // state = sum of the increments of the segments before this one (fixed order); raw per-thread register images
-  constexpr int CARRY = JB * NBT * 4 * NTH + NBP;
+  constexpr int CARRY = (int)P::carry_floats;
   f4 S[JB][NBT];
 #pragma unroll
   for (int a = 0; a < JB; ++a)
@@ -167,7 +92,7 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
         for (int b = 0; b < NBT; ++b)
 #pragma unroll
           for (int r = 0; r < 4; ++r) S[a][b][r] = cr[((a * NBT + b) * 4 + r) * NTH + tid];
-      if (tid < NBP) ks0 = cr[JB * NBT * 4 * NTH + tid];
+      if (tid < NBP) ks0 = cr[P::ksum_at + tid];
     }
     if (!STATE_ONLY) {
       for (int s2 = 0; s2 < seg; ++s2) {
@@ -178,7 +103,7 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
           for (int b = 0; b < NBT; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r) S[a][b][r] += cr[((a * NBT + b) * 4 + r) * NTH + tid];
-        if (tid < NBP) ks0 += cr[JB * NBT * 4 * NTH + tid];
+        if (tid < NBP) ks0 += cr[P::ksum_at + tid];
       }
     }
     if (tid < NBP) sKsum[tid] = ks0;
@@ -391,7 +316,7 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
       for (int b = 0; b < NBT; ++b)
 #pragma unroll
         for (int r = 0; r < 4; ++r) cw[((a * NBT + b) * 4 + r) * NTH + tid] = S[a][b][r];
-    if (tid < NBP) cw[JB * NBT * 4 * NTH + tid] = sKsum[tid];
+    if (tid < NBP) cw[P::ksum_at + tid] = sKsum[tid];
   } else if (p.state_out && seg == p.nseg - 1) {           // the block that walked the last rows holds the final state
     float* cw = p.state_out + (int64_t)nh * CARRY;
 #pragma unroll
@@ -400,7 +325,7 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
       for (int b = 0; b < NBT; ++b)
 #pragma unroll
         for (int r = 0; r < 4; ++r) cw[((a * NBT + b) * 4 + r) * NTH + tid] = S[a][b][r];
-    if (tid < NBP) cw[JB * NBT * 4 * NTH + tid] = sKsum[tid];
+    if (tid < NBP) cw[P::ksum_at + tid] = sKsum[tid];
   }
 }
 
@@ -425,160 +350,50 @@ __global__ __launch_bounds__(512) void performer_kernel(PerfParams p) {
 //     row-major in LDS and are fetched with the transposing read ds_read_b64_tr_b16.
 //   * S is, as in the fp32 kernel, the B operand of phi(Q).S straight from the accumulator registers; element j
 //     of lane group g is feature 16*(2kk + j/4) + 4g + j%4, and the phi(Q) fragment is gathered in that order.
+//
+// The plan (Perf16Plan), the workgroup prologue, the carry image and the phases of a chunk are in sea_performer16.hpp, shared
+// with the wide-head kernel below; here: the staging and the chunk walk.
 // ======================================================================================================
-// x -> (hi, lo) 16-bit patterns with hi + lo ~ x to twice the type's significand bits
-template <typename T> __device__ inline void split16(float x, unsigned short& hi, unsigned short& lo) {
-  hi = S16<T>::bits(x);
-  lo = S16<T>::bits(x - S16<T>::val(hi));
-}
-__device__ inline uint2 pack4(const unsigned short (&v)[4]) {
-  return make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16));
-}
-__device__ inline uint4 cat8(uint2 a, uint2 b) { return make_uint4(a.x, a.y, b.x, b.y); }
-__device__ inline uint2 lds_tr(const unsigned short* p) {      // ds_read_b64_tr_b16
-  const ps4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ps4 __attribute__((address_space(3)))*)(p));
-  return __builtin_bit_cast(uint2, v);
-}
-
 template <typename T, int NBT, bool STATE_ONLY, bool SEQ = false, bool PAGED = false>
 __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
-  constexpr int D = 64, C = 64, NW = 8, NTH = 512, E = 2 * D;
-  constexpr int NBP = NBT * 16;
-  constexpr int KF = (NBT + 1) / 2;            // 32-wide k-steps over the (padded) features
-  constexpr int FP = KF * 32;                  // padded feature count
-  constexpr int RB = C / 16, EB = E / 16;
-  static_assert(EB == NW, "one 16-column block of [pos | v] per wave");
-  // LDS row strides picked with a bank model of the two access patterns (64 banks x 4 B; b128 row reads are served in
-  // 4 lane groups of 16, transposing b64 reads in 2 of 32): 160 / 224 B rows make the operand row reads conflict-free
-  // (4 cycles per wave instruction; the first version's 144 B rows: 8), 192 B rows halve the conflicts of the
-  // transposing reads of phi(K) (4 cycles; 144 B: 8; the conflict-free 2 needs a swizzle); rows stay 16-byte multiples
-  constexpr int LDQ2 = FP + 16;                // phi(Q) rows (elements): row reads only
-  constexpr int LDK2 = (FP == 64) ? 96 : FP + 8; // phi(K) rows (16-byte multiples): transposing reads + a few row reads
-  constexpr int LDA = C + 16;                  // A rows: row reads only
-  constexpr int DSL = RB + NTH / C;            // denominator partial slots per row
+  using P = Perf16Plan<64, 64, NBT>;
+  constexpr int D = P::D, C = P::C, E = P::E, NSET = P::NSET;
+  static_assert(P::EB == P::NW, "one 16-column block of [pos | v] per wave");
   extern __shared__ __attribute__((aligned(16))) char smem_b[];
-  unsigned short* sW = reinterpret_cast<unsigned short*>(smem_b);   // [D/8][NBP][8]   projection, k-chunked
-  unsigned short* sQ = sW + (D / 8) * NBP * 8;                      // [D/8][C][8]
-  unsigned short* sK = sQ + (D / 8) * C * 8;                        // [D/8][C][8]
-  unsigned short* sV = sK + (D / 8) * C * 8;                        // [C][E] 256-byte rows, chunk-swizzled
-  unsigned short* sQh = sV + C * E;                                 // [2][ [C][LDQ2] x 2, [C][LDK2] x 2 ]: the phi images of two
-  unsigned short* sQl = sQh + C * LDQ2;                             //   chunks in flight (set stride PHI below)
-  unsigned short* sKh = sQl + C * LDQ2;                             // [C][LDK2]
-  unsigned short* sKl = sKh + C * LDK2;
-  // two sets where they fit (FP = 64: 152 KB in all); with FP = 96 one set, and (b) of the next chunk waits for a fourth barrier
-  constexpr int NSET = (FP == 64) ? 2 : 1;
-  unsigned short* sAh = sKl + C * LDK2 + (NSET - 1) * (2 * C * LDQ2 + 2 * C * LDK2);   // [C][LDA]   (behind the last set)
-  unsigned short* sAl = sAh + C * LDA;
-  float* sKsum = reinterpret_cast<float*>(sAl + C * LDA);           // [FP]
-  float* sDenP = sKsum + FP;                                        // [C][DSL]
-  float* sKsP = sDenP + C * DSL;                                    // [NW][FP]   per-wave k-sum increments
+  const Perf16Lds<P> L(smem_b);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int nh = blockIdx.x;
-  const int n = nh / p.H, h = nh - n * p.H;
-  const int seg = blockIdx.y;                              // sequence-parallel form, see PerfParams
-  const int tb = SEQ ? p.t_base_dev[n * p.t_base_stride] : p.t_base_dev ? *p.t_base_dev : p.t_base;   // rows seen (block-uniform)
-  // (SEQ: per-sequence positions; a form of its own, so that the shared-position step's counter load does not wait for n)
-  // chunk-aligned step: local row 0 is the chunk boundary at or below tb; the `lead` rows up to tb are the open chunk's old
-  // rows (k, v, pos only).  Otherwise lead = 0 and local row 0 is row tb.
-  const int lead = p.aligned ? tb % C : 0;
-  const int row_base = tb - lead;                          // absolute index of local row 0
-  const int TL = p.T + lead;                               // local rows of this call
-  const int t_begin = seg * p.seg_len, t_end = min(TL, t_begin + p.seg_len);
-  const T* qb = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] - (int64_t)lead * p.qs[2];   // rows < lead are never read
-  int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;            // k / v given as cache bases: start at the boundary
-  int64_t kv_n = n;
-  if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
-    static_assert(SEQ, "the paged step has a position per sequence");
-    kv_n = p.table[(int64_t)n * p.table_stride + (max(row_base, 0) >> p.page_shift)];   // (tb < 0, a sequence sitting out: entry 0, unused)
-    cache_row = row_base & ((1 << p.page_shift) - 1);
-  }
-  const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
-  const T* vb = reinterpret_cast<const T*>(p.v) + kv_n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
-  const T* pb = reinterpret_cast<const T*>(p.pos) + (p.t_base_dev ? (int64_t)row_base * p.pos_stride : 0);
-  T* ob = reinterpret_cast<T*>(p.out) + (int64_t)nh * p.T * (3 * D) - (int64_t)lead * (3 * D);           // rows < lead are never stored
+  const Perf16Wg<T, D, C, SEQ, PAGED> wg(p);
   const float cnorm = powf((float)D, -0.25f);
 
-  // projection (its values are bf16-exact: the reference casts the buffer to the data dtype), zero padded rows
-  for (int i = tid; i < (D / 8) * NBP * 8; i += NTH) {
-    const int j = i & 7, f = (i >> 3) % NBP, kc = (i >> 3) / NBP;
-    sW[i] = f < p.nb ? S16<T>::bits(p.W[f * D + kc * 8 + j]) : (unsigned short)0;
-  }
-  // phi and A images: padded features / upper-triangular tiles are written once (zero) and never again
-  for (int i = tid; i < NSET * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA; i += NTH) sQh[i] = 0;
-  for (int i = tid; i < C * DSL; i += NTH) sDenP[i] = 0.f;   // slots of key blocks above the diagonal stay zero
-
-  // carry image of one (n, h, segment): per-thread state registers, the k-sum, the per-thread column sum of v
-  constexpr int CARRY = NBT * 4 * NTH + FP + NTH;
-  f4 S[NBT];
-#pragma unroll
-  for (int b = 0; b < NBT; ++b) S[b] = f4{0.f, 0.f, 0.f, 0.f};
-  // running column sums of v (cumulative-average output): in the transposed accumulator layout of (d) a lane owns the four
-  // columns e0 + 4 lg + r of its wave; the 16 lanes of a lane group carry the same four.  Image slot of column r: lane
-  // (lg, li = r) of the wave, i.e. (tid & ~15) + r.
-  float csum[4] = {0.f, 0.f, 0.f, 0.f};
-  const int cslot = (tid & ~15);
-  {
-    float ks0 = 0.f;
-    if (!STATE_ONLY && p.state_in) {                       // increments of pass 1 do not include the incoming state
-      const float* cr = p.state_in + (int64_t)nh * CARRY;
-#pragma unroll
-      for (int b = 0; b < NBT; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S[b][r] = cr[(b * 4 + r) * NTH + tid];
-      if (tid < FP) ks0 = cr[NBT * 4 * NTH + tid];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) csum[r] = cr[NBT * 4 * NTH + FP + cslot + r];
-    }
-    if (!STATE_ONLY) {
-      for (int s2 = 0; s2 < seg; ++s2) {                   // fixed order: bitwise reproducible
-        const float* cr = p.carry + ((int64_t)nh * (p.nseg - 1) + s2) * CARRY;
-#pragma unroll
-        for (int b = 0; b < NBT; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) S[b][r] += cr[(b * 4 + r) * NTH + tid];
-        if (tid < FP) ks0 += cr[NBT * 4 * NTH + tid];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) csum[r] += cr[NBT * 4 * NTH + FP + cslot + r];
-      }
-    }
-    if (tid < FP) sKsum[tid] = ks0;
-  }
+  perf16_lds_init<T, P>(L, p.W, p.nb, tid);
+  f4 S[1][NBT];
+  float csum[1][4];
+  perf16_state_init<P, STATE_ONLY>(p, wg.nh, wg.seg, tid, S, csum, L.sKsum);
 
   // a sequence that sits out this step (DecodeSession.pause / release: its counter row is negative, tb < 0) does nothing: no
   // K / V / q read, state image and output rows untouched (a paged one has read entry 0 of its table row and uses it for
   // nothing).  Block-uniform; here, at the position's first use, so that the staging above does not wait for the counter
-  if constexpr (SEQ) { if (tb < 0) return; }
+  if constexpr (SEQ) { if (wg.tb < 0) return; }
+  const Perf16Bufs B = wg.buffers(p);
+  const int t_begin = wg.t_begin, t_end = wg.t_end, lead = wg.lead;
   // one 16-byte piece of each tensor per thread and chunk; prefetched one chunk ahead
   const int sr = tid >> 3, sc = tid & 7;        // staging row, 8-element column chunk
-  // All global traffic goes through buffer instructions with hardware range checking: a row beyond T reads zeros /
-  // drops its store WITHOUT a branch.  (Branches around loads and stores make the compiler's vmcnt bookkeeping
-  // pessimistic: the wait for the prefetched chunk then also waits for every output store of the previous one.)
-  constexpr unsigned OOB = 0x7FFFFF00u;
-  auto mk = [&](const T* base, int64_t row_stride) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)(((int64_t)(TL - 1) * row_stride + D) * 2), 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rq = mk(qb, p.qs[2]), rk = mk(kb, p.ks[2]), rv = mk(vb, p.vs[2]), rp = mk(pb, p.pos_stride);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (int)((int64_t)TL * 3 * D * 2), 0x00020000);
-  typedef __attribute__((ext_vector_type(4))) unsigned int bu4;
-  const bool want_avg = p.avg != nullptr;                  // block-uniform
-  T* gb = reinterpret_cast<T*>(p.avg) + (want_avg ? (int64_t)nh * p.T * D - (int64_t)lead * D : 0);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(gb, 0, want_avg ? (int)((int64_t)TL * D * 2) : 0, 0x00020000);
   bu4 pq, pk, pv, pp;
   auto issue_qk = [&](int t0n) {
     const int t = t0n + sr;
     const bool ok = t < t_end;
-    pq = __builtin_amdgcn_raw_buffer_load_b128(rq, (ok && !STATE_ONLY && t >= lead) ? (int)((t * p.qs[2] + sc * 8) * 2) : (int)OOB, 0, 0);
-    pk = __builtin_amdgcn_raw_buffer_load_b128(rk, ok ? (int)((t * p.ks[2] + sc * 8) * 2) : (int)OOB, 0, 0);
+    pq = __builtin_amdgcn_raw_buffer_load_b128(B.rq, (ok && !STATE_ONLY && t >= lead) ? (int)((t * p.qs[2] + sc * 8) * 2) : PERF16_OOB, 0, 0);
+    pk = __builtin_amdgcn_raw_buffer_load_b128(B.rk, ok ? (int)((t * p.ks[2] + sc * 8) * 2) : PERF16_OOB, 0, 0);
   };
   auto issue_v = [&](int t0n) {
     const int t = t0n + sr;
     const bool ok = t < t_end;
-    pv = __builtin_amdgcn_raw_buffer_load_b128(rv, ok ? (int)((t * p.vs[2] + sc * 8) * 2) : (int)OOB, 0, 0);
-    pp = __builtin_amdgcn_raw_buffer_load_b128(rp, ok ? (int)((t * p.pos_stride + sc * 8) * 2) : (int)OOB, 0, 0);
+    pv = __builtin_amdgcn_raw_buffer_load_b128(B.rv, ok ? (int)((t * p.vs[2] + sc * 8) * 2) : PERF16_OOB, 0, 0);
+    pp = __builtin_amdgcn_raw_buffer_load_b128(B.rp, ok ? (int)((t * p.pos_stride + sc * 8) * 2) : PERF16_OOB, 0, 0);
   };
 #ifdef SEA_STAMP
   unsigned long long _tprev = __builtin_amdgcn_s_memtime();
@@ -586,35 +401,8 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
 #endif
   issue_qk(t_begin);
   issue_v(t_begin);
-  // swizzled chunk position inside a 256-byte row of the V image (conflict-free transposing reads)
-  auto vchunk = [](int row, int ch) { return ch ^ (((row & 3) << 2) | ((row >> 2) & 3)); };
-
-  // cumulative average of v (step K's input) on the waves that own the v columns: prefix sum over the chunk rows =
-  // tril(ones) . V on the matrix cores (1.0 and v are exact in bf16, fp32 accumulation) + the running column sum
-  auto tril_frag = [&](int ib, int ks) {
-    unsigned short o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (ks * 32 + lg * 8 + j <= ib * 16 + li) ? S16<T>::ONE : (unsigned short)0;
-    const unsigned short (&o0)[4] = *reinterpret_cast<const unsigned short (*)[4]>(&o[0]);
-    const unsigned short (&o1)[4] = *reinterpret_cast<const unsigned short (*)[4]>(&o[4]);
-    return cat8(pack4(o0), pack4(o1));
-  };
-
-  uint4 tril[RB][C / 32];                                  // loop-invariant A operands of the prefix-sum product
-#pragma unroll
-  for (int ib = 0; ib < RB; ++ib)
-#pragma unroll
-    for (int ks = 0; ks < C / 32; ++ks) tril[ib][ks] = tril_frag(ib, ks);
-
-  auto write_state = [&]() {                               // this thread's part of the (n, h) image
-    float* cw = p.state_out + (int64_t)nh * CARRY;
-#pragma unroll
-    for (int b = 0; b < NBT; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) cw[(b * 4 + r) * NTH + tid] = S[b][r];
-    if (tid < FP) cw[NBT * 4 * NTH + tid] = sKsum[tid];
-    cw[NBT * 4 * NTH + FP + tid] = li == 0 ? csum[0] : li == 1 ? csum[1] : li == 2 ? csum[2] : li == 3 ? csum[3] : 0.f;
-  };
+  uint4 tril[P::RB][C / 32];
+  perf16_tril_table<T, P>(tril, li, lg);
 
   // ---- the chunk walk, software-pipelined over THREE barriers per chunk (the first version ran a chunk's five phases one after
   // the other behind five barriers; at two waves per SIMD every phase is a dependent chain -- LDS read -> MFMA -> vector ->
@@ -625,290 +413,22 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
   //   P2  (c_{j+1}): A tiles and partials of chunk j+1;  [pos | v] of chunk j+1 and q, k of chunk j+2 go from the prefetch
   //       registers to LDS (their old images were last read in P1), the loads of chunks j+2 / j+3 are issued;
   //   (until round 4 a third phase P3 -- denominators, 1 / row index and the k-sum of chunk j+1 on a few threads, behind its own
-  //   barrier; now the first lines of (d), see there: TWO barriers per chunk).
-  // Results leave straight from the accumulators (8-byte pieces: phase (d) holds four consecutive columns of a row per lane).
-  auto rows_of = [&](int t0) { return min(C, t_end - t0); };
-  // aligned step, open chunk (always the call's last): its rows produce output but do NOT enter the state -- S, the k-sum
-  // and the column sums stay the state AT THE BOUNDARY, which is the image the next call continues from (it walks this
-  // chunk's rows again).  Block-uniform.
-  auto upd_of = [&](int t0) { return !(p.aligned && rows_of(t0) < C); };
+  //   barrier; now the first lines of (d), see perf16_denoms: TWO barriers per chunk).
   auto stage_qk = [&]() {
-    // row slot XOR 2 * chunk: the 16 lanes of a b128 store (2 rows x 8 chunks; chunk images are 1 KB = 0 mod 64 banks apart)
-    // land in 16 different 4-bank groups instead of 2 (8-way conflicts); the reads of (b) permute inside their 16-row runs
-    *reinterpret_cast<bu4*>(sQ + (sc * C + (sr ^ (2 * sc))) * 8) = pq;
-    *reinterpret_cast<bu4*>(sK + (sc * C + (sr ^ (2 * sc))) * 8) = pk;
+    *reinterpret_cast<bu4*>(L.sQ + (sc * C + P::qk_slot(sr, sc)) * 8) = pq;
+    *reinterpret_cast<bu4*>(L.sK + (sc * C + P::qk_slot(sr, sc)) * 8) = pk;
   };
   auto stage_v = [&](int t0) {                               // chunk t0's [pos | v] rows; v also is the third block of the output
-    const int rows = rows_of(t0);
-    if (!STATE_ONLY) __builtin_amdgcn_raw_buffer_store_b128(pv, ro, (sr < rows && t0 + sr >= lead) ? ((t0 + sr) * (3 * D) + 2 * D + sc * 8) * 2 : (int)OOB, 0, 0);
-    *reinterpret_cast<bu4*>(sV + sr * E + vchunk(sr, sc) * 8) = pp;
-    *reinterpret_cast<bu4*>(sV + sr * E + vchunk(sr, D / 8 + sc) * 8) = pv;
+    const int rows = wg.rows_of(t0);
+    if (!STATE_ONLY) __builtin_amdgcn_raw_buffer_store_b128(pv, B.ro, (sr < rows && t0 + sr >= lead) ? ((t0 + sr) * (3 * D) + 2 * D + sc * 8) * 2 : PERF16_OOB, 0, 0);
+    *reinterpret_cast<bu4*>(L.sV + sr * E + P::vchunk(sr, sc) * 8) = pp;
+    *reinterpret_cast<bu4*>(L.sV + sr * E + P::vchunk(sr, D / 8 + sc) * 8) = pv;
   };
-  // ---- (b) feature maps, transposed: X^T[f][t] = sum_d W[f][d] x[t][d]; wave = (Q | K, row block) ----------
-  auto phase_b = [&](int rows, unsigned short* sQh, unsigned short* sQl, unsigned short* sKh, unsigned short* sKl) {
-    if (!STATE_ONLY || wv >= RB) {                           // the state-only pass needs phi(K) alone (wave-uniform)
-      const int which = wv / RB, rb = wv - which * RB;
-      const unsigned short* src = which ? sK : sQ;
-      f4 acc[NBT];
-#pragma unroll
-      for (int fb = 0; fb < NBT; ++fb) acc[fb] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < D / 32; ++ks) {
-        const uint4 bx = *reinterpret_cast<const uint4*>(src + ((4 * ks + lg) * C + ((rb * 16 + li) ^ (2 * (4 * ks + lg)))) * 8);
-#pragma unroll
-        for (int fb = 0; fb < NBT; ++fb) {
-          const uint4 aw = *reinterpret_cast<const uint4*>(sW + ((4 * ks + lg) * NBP + fb * 16 + li) * 8);
-          acc[fb] = S16<T>::mfma(aw, bx, acc[fb]);
-        }
-      }
-      unsigned short* dh = which ? sKh : sQh;
-      unsigned short* dl = which ? sKl : sQl;
-      const int row = rb * 16 + li;                          // lane: 4 consecutive features of one row
-#pragma unroll
-      for (int fb = 0; fb < NBT; ++fb) {
-        unsigned short hh[4], ll[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int f = fb * 16 + lg * 4 + r;
-          float val = fmaxf(cnorm * acc[fb][r], 0.f) + 1e-3f;
-          if (f >= p.nb || row >= rows) val = 0.f;           // padded features / rows beyond T contribute nothing
-          split16<T>(val, hh[r], ll[r]);
-        }
-        // feature 32kk + 16a + 4g + j is stored at position 32kk + 8g + 4a + j: the 8 features lane group g needs of
-        // a 32-wide k-step in (d) (4 of tile 2kk, 4 of tile 2kk+1) are then one 16-byte piece
-        const int pos = (fb >> 1) * 32 + lg * 8 + (fb & 1) * 4;
-        const int ldx = which ? LDK2 : LDQ2;
-        *reinterpret_cast<uint2*>(dh + row * ldx + pos) = pack4(hh);
-        *reinterpret_cast<uint2*>(dl + row * ldx + pos) = pack4(ll);
-      }
-    }
-  };
-  // ---- (c) A^T tiles (lower triangle), denominator and k-sum partials ------------------------------------
-  auto phase_c = [&](const unsigned short* sQh, const unsigned short* sQl, const unsigned short* sKh, const unsigned short* sKl) {
-    if constexpr (!STATE_ONLY)
-    for (int tile = wv; tile < RB * (RB + 1) / 2; tile += NW) {
-      int ib = 0, rem = tile;
-      while (rem > ib) { rem -= ib + 1; ++ib; }              // tile -> (query block ib, key block jb <= ib)
-      const int jb = rem;
-      f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KF; ++ks) {
-        const int ko = ks * 32 + lg * 8;
-        const uint4 kh = *reinterpret_cast<const uint4*>(sKh + (jb * 16 + li) * LDK2 + ko);
-        const uint4 kl = *reinterpret_cast<const uint4*>(sKl + (jb * 16 + li) * LDK2 + ko);
-        const uint4 qh = *reinterpret_cast<const uint4*>(sQh + (ib * 16 + li) * LDQ2 + ko);
-        const uint4 ql = *reinterpret_cast<const uint4*>(sQl + (ib * 16 + li) * LDQ2 + ko);
-        acc = S16<T>::mfma(kh, qh, acc);
-        acc = S16<T>::mfma(kh, ql, acc);
-        acc = S16<T>::mfma(kl, qh, acc);
-      }
-      const int trow = ib * 16 + li;                         // lane: A[trow][s0 .. s0+3]
-      const int s0 = jb * 16 + lg * 4;
-      unsigned short hh[4], ll[4];
-      float rs = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float val = (s0 + r <= trow) ? acc[r] : 0.f;   // causal mask inside the diagonal tiles
-        rs += val;
-        split16<T>(val, hh[r], ll[r]);
-      }
-      *reinterpret_cast<uint2*>(sAh + trow * LDA + s0) = pack4(hh);
-      *reinterpret_cast<uint2*>(sAl + trow * LDA + s0) = pack4(ll);
-      rs = xor32_sum(xor16_sum(rs));
-      if (lg == 0) sDenP[trow * DSL + jb] = rs;              // one writer per (row, key block)
-    }
-    {
-      // carry part of the denominators: phi(q_t) . (ksum + eps) over the (permuted) feature positions
-      const int row = tid & (C - 1), part = tid / C;         // 8 parts x (FP/8) positions
-      constexpr int PER = FP / (NTH / C);
-      float s = 0.f;
-      if constexpr (!STATE_ONLY)
-#pragma unroll
-      for (int g4 = 0; g4 < PER / 4; ++g4) {
-        const int f = part * PER + g4 * 4;
-        const uint2 qh = *reinterpret_cast<const uint2*>(sQh + row * LDQ2 + f);
-        const uint2 ql = *reinterpret_cast<const uint2*>(sQl + row * LDQ2 + f);
-        const float4 ks = *reinterpret_cast<const float4*>(sKsum + f);
-        s = fmaf(S16<T>::val((unsigned short)(qh.x & 0xffff)) + S16<T>::val((unsigned short)(ql.x & 0xffff)), ks.x + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.x >> 16)) + S16<T>::val((unsigned short)(ql.x >> 16)), ks.y + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.y & 0xffff)) + S16<T>::val((unsigned short)(ql.y & 0xffff)), ks.z + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.y >> 16)) + S16<T>::val((unsigned short)(ql.y >> 16)), ks.w + 1e-6f, s);
-      }
-      sDenP[row * DSL + RB + part] = s;
-      // k-sum increment: wave w owns rows 8w .. 8w+7; lane = (4-position group fc, row lane rr)
-      constexpr int FG = FP / 4, RRN = 64 / FG, RPL = (C / NW) / RRN;
-      const int fc = lane % FG, rr = lane / FG;
-      float k4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (rr < RRN) {
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) {
-          const int r2 = wv * (C / NW) + rr * RPL + j;
-          const uint2 kh = *reinterpret_cast<const uint2*>(sKh + r2 * LDK2 + fc * 4);
-          const uint2 kl = *reinterpret_cast<const uint2*>(sKl + r2 * LDK2 + fc * 4);
-          k4[0] += S16<T>::val((unsigned short)(kh.x & 0xffff)) + S16<T>::val((unsigned short)(kl.x & 0xffff));
-          k4[1] += S16<T>::val((unsigned short)(kh.x >> 16)) + S16<T>::val((unsigned short)(kl.x >> 16));
-          k4[2] += S16<T>::val((unsigned short)(kh.y & 0xffff)) + S16<T>::val((unsigned short)(kl.y & 0xffff));
-          k4[3] += S16<T>::val((unsigned short)(kh.y >> 16)) + S16<T>::val((unsigned short)(kl.y >> 16));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (FG == 16) {
-          k4[j] = xor16_sum(xor32_sum(k4[j]));                   // (l, l+32) then (+16): same association as the shuffle form
-        } else {
-#pragma unroll
-          for (int o = FG * (RRN / 2); o >= FG; o >>= 1) k4[j] += __shfl_down(k4[j], o);   // fixed order
-        }
-      }
-      if (lane < FG) *reinterpret_cast<float4*>(sKsP + wv * FP + fc * 4) = make_float4(k4[0], k4[1], k4[2], k4[3]);
-    }
-  };
-  // ---- (d) O = A V + phi(Q) S over this wave's 16 columns; (e) S += phi(K)^T V ------------------------------
-  auto phase_de = [&](int t0, int rows, bool upd, const unsigned short* sQh, const unsigned short* sQl, const unsigned short* sKh,
-                      const unsigned short* sKl) {
-    // what a phase of its own (and its barrier) did until round 4: the k-sum takes this chunk's increments (the partials of (c)
-    // read it before, the next chunk's (c) runs behind the next barrier), and every lane sums the denominator partials of ITS
-    // rows -- the same additions in the same order in every lane that holds the row, so nothing changes in the results
-    if (tid < FP) {
-      float s = sKsum[tid];
-#pragma unroll
-      for (int i = 0; i < NW; ++i) s += sKsP[i * FP + tid];       // fixed order: bitwise reproducible
-      if (upd) sKsum[tid] = s;
-    }
-    // (a lane sums ONE row -- lane group g the rows of block g % RB -- and the reciprocals travel by lane permutes: four rows and
-    // eight divisions per lane made the phase VALU-bound, 2.5 % slower than the barrier it replaces at 256 workgroups)
-    float dn[RB], ri1 = 0.f;
-    if constexpr (!STATE_ONLY) {
-      const int myrow = (lg % RB) * 16 + li;
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < DSL; ++i) s += sDenP[myrow * DSL + i];
-      const float d1 = 1.0f / s;
-      ri1 = 1.0f / (float)(row_base + t0 + myrow + 1);
-#pragma unroll
-      for (int ib = 0; ib < RB; ++ib) dn[ib] = __shfl(d1, ib * 16 + li);
-    }
-    {
-      const int jb = wv, e0 = jb * 16;
-      // V fragments (B operand, k = chunk row): rows 32ks + 8lg + {0..3 | 4..7}, columns e0 .. e0+15
-      uint4 vf[C / 32];
-      {
-        const int q = li >> 2, pp_ = li & 3;
-#pragma unroll
-        for (int ks = 0; ks < C / 32; ++ks) {
-          const int r0 = ks * 32 + lg * 8;
-          const uint2 a = lds_tr(sV + (r0 + q) * E + vchunk(r0 + q, 2 * jb + (pp_ >> 1)) * 8 + 4 * (pp_ & 1));
-          const uint2 b = lds_tr(sV + (r0 + 4 + q) * E + vchunk(r0 + 4 + q, 2 * jb + (pp_ >> 1)) * 8 + 4 * (pp_ & 1));
-          vf[ks] = cat8(a, b);
-        }
-      }
-      if constexpr (STATE_ONLY) {
-        if (want_avg && jb >= EB / 2) {                    // column total of the chunk = the last row's prefix
-          f4 cum = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks <= (RB - 1) / 2; ++ks) cum = S16<T>::mfma(vf[ks], tril[RB - 1][ks], cum);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) csum[r] += __shfl(cum[r], (lane & 48) | 15);
-        }
-      } else {
-      f4 o[RB];
-#pragma unroll
-      for (int ib = 0; ib < RB; ++ib) o[ib] = f4{0.f, 0.f, 0.f, 0.f};
-      // A V: key k-step ks covers key blocks 2ks, 2ks+1; query block ib needs k-steps <= ib/2
-#pragma unroll
-      for (int ib = 0; ib < RB; ++ib) {
-#pragma unroll
-        for (int ks = 0; ks <= ib / 2; ++ks) {
-          const uint4 ah = *reinterpret_cast<const uint4*>(sAh + (ib * 16 + li) * LDA + ks * 32 + lg * 8);
-          const uint4 al = *reinterpret_cast<const uint4*>(sAl + (ib * 16 + li) * LDA + ks * 32 + lg * 8);
-          o[ib] = S16<T>::mfma(vf[ks], ah, o[ib]);
-          o[ib] = S16<T>::mfma(vf[ks], al, o[ib]);
-        }
-      }
-      // phi(Q) S: the state tiles, split, are the B operand; k-step kk pairs feature blocks 2kk and 2kk+1
-#pragma unroll
-      for (int kk = 0; kk < KF; ++kk) {
-        unsigned short h0[4], h1[4], l0[4], l1[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          split16<T>(S[2 * kk][r], h0[r], l0[r]);
-          if (2 * kk + 1 < NBT) split16<T>(S[(2 * kk + 1 < NBT) ? 2 * kk + 1 : 0][r], h1[r], l1[r]);
-          else h1[r] = l1[r] = 0;
-        }
-        const uint4 bh = cat8(pack4(h0), pack4(h1)), bl = cat8(pack4(l0), pack4(l1));
-#pragma unroll
-        for (int ib = 0; ib < RB; ++ib) {
-          const uint4 ah = *reinterpret_cast<const uint4*>(sQh + (ib * 16 + li) * LDQ2 + kk * 32 + lg * 8);
-          const uint4 al = *reinterpret_cast<const uint4*>(sQl + (ib * 16 + li) * LDQ2 + kk * 32 + lg * 8);
-          o[ib] = S16<T>::mfma(bh, ah, o[ib]);
-          o[ib] = S16<T>::mfma(bl, ah, o[ib]);
-          o[ib] = S16<T>::mfma(bh, al, o[ib]);
-        }
-      }
-      // Every product above has its operands SWAPPED (O^T = V^T A^T + S^T phi(Q)^T; the A and B fragment layouts are mirror
-      // images, so the same registers serve): the accumulator of query block ib then holds, per lane, row ib*16 + li and the
-      // FOUR CONSECUTIVE COLUMNS e0 + 4 lg + r -- one 8-byte LDS store and one denominator read per block instead of four
-      // 2-byte stores (two lanes per bank word) and four reads.
-      const int col = e0 + 4 * lg;
-#pragma unroll
-      for (int ib = 0; ib < RB; ++ib) {
-        const int row = ib * 16 + li;
-        unsigned short ob[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ob[r] = S16<T>::bits(o[ib][r] * dn[ib]);
-        const uint2 w2 = pack4(ob);
-        typedef __attribute__((ext_vector_type(2))) unsigned int bu2;
-        __builtin_amdgcn_raw_buffer_store_b64(bu2{w2.x, w2.y}, ro, (row < rows && t0 + row >= lead) ? ((t0 + row) * (3 * D) + col) * 2 : (int)OOB, 0, 0);
-      }
-      if (want_avg && jb >= EB / 2) {                      // wave-uniform: this wave's 16 columns are v features
-        f4 cum[RB];
-#pragma unroll
-        for (int ib = 0; ib < RB; ++ib) {
-          cum[ib] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks <= ib / 2; ++ks) cum[ib] = S16<T>::mfma(vf[ks], tril[ib][ks], cum[ib]);
-        }
-        const int gcol = col - D;
-#pragma unroll
-        for (int ib = 0; ib < RB; ++ib) {
-          const int row = ib * 16 + li;
-          const float ri = __shfl(ri1, ib * 16 + li);
-          unsigned short gb4[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) gb4[r] = S16<T>::bits((cum[ib][r] + csum[r]) * ri);
-          const uint2 w2 = pack4(gb4);
-          typedef __attribute__((ext_vector_type(2))) unsigned int bu2;
-          __builtin_amdgcn_raw_buffer_store_b64(bu2{w2.x, w2.y}, rg, (row < rows && t0 + row >= lead) ? ((t0 + row) * D + gcol) * 2 : (int)OOB, 0, 0);
-        }
-        if (upd) {                                         // column totals of the chunk = its last row's prefix (lane li = 15)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) csum[r] += __shfl(cum[RB - 1][r], (lane & 48) | 15);
-        }
-      }
-      }
-      // (e) S[f][e] += sum_s phi(k_s)[f] V[s][e]: A operand = phi(K)^T by transposing reads of the row-major images
-      if (upd) {
-        const int q = li >> 2, pp_ = li & 3;
-#pragma unroll
-        for (int rb = 0; rb < NBT; ++rb) {
-#pragma unroll
-          for (int ks = 0; ks < C / 32; ++ks) {
-            const int r0 = ks * 32 + lg * 8;
-            const int co = (rb >> 1) * 32 + 8 * pp_ + (rb & 1) * 4;      // positions of features 16rb + 4p .. +3
-            const uint4 kh = cat8(lds_tr(sKh + (r0 + q) * LDK2 + co), lds_tr(sKh + (r0 + 4 + q) * LDK2 + co));
-            const uint4 kl = cat8(lds_tr(sKl + (r0 + q) * LDK2 + co), lds_tr(sKl + (r0 + 4 + q) * LDK2 + co));
-            S[rb] = S16<T>::mfma(kh, vf[ks], S[rb]);
-            S[rb] = S16<T>::mfma(kl, vf[ks], S[rb]);
-          }
-        }
-      }
-    }
-  };
-  constexpr int PHI = 2 * C * LDQ2 + 2 * C * LDK2;          // elements of one phi image set (Qh, Ql, Kh, Kl)
-  auto run_b = [&](int t0, int buf) { phase_b(rows_of(t0), sQh + buf * PHI, sQl + buf * PHI, sKh + buf * PHI, sKl + buf * PHI); };
-  auto run_c = [&](int buf) { phase_c(sQh + buf * PHI, sQl + buf * PHI, sKh + buf * PHI, sKl + buf * PHI); };
+  auto run_b = [&](int t0, int buf) { perf16_phase_b<T, P, STATE_ONLY>(L, L.set(buf), wg.rows_of(t0), p.nb, cnorm, wv, li, lg); };
+  auto run_c = [&](int buf) { perf16_phase_c<T, P, STATE_ONLY>(L, L.set(buf), tid, wv, lane, li, lg); };
   auto run_de = [&](int t0, int buf) {
-    phase_de(t0, rows_of(t0), upd_of(t0), sQh + buf * PHI, sQl + buf * PHI, sKh + buf * PHI, sKl + buf * PHI);
+    perf16_phase_de<T, P, STATE_ONLY>(L, L.set(buf), B, t0, wg.rows_of(t0), wg.row_base, lead, wg.upd_of(t0), wg.want_avg, S, csum, tril,
+                                      tid, wv, lane, li, lg);
   };
   if (t_begin < t_end) {
     // prologue: chunk 0 through (b), (c); chunk 1's q, k staged; loads of chunk 1 ([pos | v]) and chunk 2 (q, k) in flight
@@ -944,24 +464,10 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
       PSTAMP(1);
     }
   }
-  if constexpr (STATE_ONLY) {
-    float* cw = p.carry + ((int64_t)nh * (p.nseg - 1) + seg) * CARRY;
-#pragma unroll
-    for (int b = 0; b < NBT; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) cw[(b * 4 + r) * NTH + tid] = S[b][r];
-    if (tid < FP) cw[NBT * 4 * NTH + tid] = sKsum[tid];
-    cw[NBT * 4 * NTH + FP + tid] = li == 0 ? csum[0] : li == 1 ? csum[1] : li == 2 ? csum[2] : li == 3 ? csum[3] : 0.f;
-  } else {
-    // the block that walked the last rows holds the final state (aligned step: the state at the last chunk boundary).  A step
-    // that closed no chunk leaves the image as it found it: updated in place (a DecodeSession) there is nothing to write --
-    // 25 KB of stores per (n, h) whose drain was the end of the launch on 63 of 64 positions
-    const bool unchanged = p.aligned && p.state_in == p.state_out && t_end - t_begin <= C && !upd_of(t_begin);
-    if (p.state_out && seg == p.nseg - 1 && !unchanged) write_state();
+  perf16_state_finish<P, STATE_ONLY>(p, wg.nh, wg.seg, tid, li, t_end - t_begin <= C && !wg.upd_of(t_begin), S, csum, L.sKsum);
 #ifdef SEA_STAMP
-    if (threadIdx.x == 0) { const int _w = blockIdx.y * gridDim.x + blockIdx.x; if (_w < 1024) { sea_dbg_wg[2 * _w] = _rstart64; sea_dbg_wg[2 * _w + 1] = __builtin_amdgcn_s_memrealtime(); } }
+  if (!STATE_ONLY && threadIdx.x == 0) { const int _w = blockIdx.y * gridDim.x + blockIdx.x; if (_w < 1024) { sea_dbg_wg[2 * _w] = _rstart64; sea_dbg_wg[2 * _w + 1] = __builtin_amdgcn_s_memrealtime(); } }
 #endif
-  }
 }
 
 // ---- wide heads (D = 80, 128): the same algorithm with the chunk cut to C = 32 rows so that the LDS images fit (the
@@ -975,25 +481,22 @@ __global__ __launch_bounds__(512) void performer_bf16_kernel(PerfParams p) {
 // The 25 KB of result tiles the first version flushed one chunk later paid for the second image set (d = 128: 120 KB).
 template <typename T, int D, int C, int NBT, bool STATE_ONLY, bool SEQ = false, bool PAGED = false>
 __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
-  constexpr int NW = 8, NTH = 512, E = 2 * D, CPR = D / 8;
-  constexpr int DP = (D + 31) / 32 * 32, KC = DP / 8;    // head dimension padded to whole k-steps, its 8-element chunks
-  constexpr int EL = 256;                                // elements per row of the V image (512 bytes: room for the swizzle)
+  using P = Perf16Plan<D, C, NBT>;
+  constexpr int NW = P::NW, NTH = P::NTH, CPR = P::CPR, KC = P::KC, EL = P::EL, NBP = P::NBP, KF = P::KF, FP = P::FP;
+  constexpr int RB = P::RB, EB = P::EB, JB = P::JB;
+  constexpr int LDQ2 = P::LDQ2, LDK2 = P::LDK2, LDA = P::LDA, DSL = P::DSL, PHI = P::PHI;
   constexpr int STG = C * CPR;                           // threads that stage one 16-byte piece of each tensor
-  static_assert(STG <= NTH && D % 16 == 0 && E <= EL && C % 16 == 0 && C <= 32, "staging pieces fit the block, whole column blocks");
-  constexpr int NBP = NBT * 16;
-  constexpr int KF = (NBT + 1) / 2;            // 32-wide k-steps over the (padded) features
-  constexpr int FP = KF * 32;                  // padded feature count
-  constexpr int RB = C / 16, EB = E / 16, JB = (EB + NW - 1) / NW, NPART = 8;
-  // (b) runs on all eight waves: a (Q | K, row block) pair is shared by BW waves, each taking FBP of the feature blocks
-  constexpr int BW = NW / (2 * RB), FBP = (NBT + BW - 1) / BW;
-  static_assert(2 * RB * BW == NW, "feature-map product: whole waves per (tensor, row block)");
-  // LDS row strides: see the D = 64 kernel (bank model of the b128 row reads and the transposing b64 reads)
-  constexpr int LDQ2 = FP + 16;                // phi(Q) rows (elements): row reads only
-  constexpr int LDK2 = (FP == 64) ? 96 : FP + 8; // phi(K) rows (16-byte multiples): transposing reads + a few row reads
-  constexpr int LDA = C + 16;                  // A rows: row reads only
-  constexpr int DSL = RB + NPART;              // denominator partial slots per row
-  constexpr int PHI = 2 * C * LDQ2 + 2 * C * LDK2;          // elements of one phi image set (Qh, Ql, Kh, Kl)
+  static_assert(P::WIDE && P::NSET == 2 && C <= 32, "two phi image sets, two chunks per state-pass iteration");
   extern __shared__ __attribute__((aligned(16))) char smem_b[];
+  const Perf16Lds<P> L(smem_b);                          // for the shared phases (b), (c)
+  // This kernel keeps its own pointer chain, its (d)(e) and tril / vchunk lambdas: taken from the shared header (Perf16Lds,
+  // perf16_phase_de, perf16_state_update) the same source compiles to another register allocation and schedule -- D = 80 output
+  // forms 217 -> 170 VGPRs, D = 128 254 -> 236 -- and measured 1.5 - 4.5 % slower.  The chain is the plan's:
+  static_assert(KC * NBP * 8 == P::oQ && KC * C * 8 == P::oK - P::oQ && KC * C * 8 == P::oV - P::oK && C * EL == P::oPhi - P::oV &&
+                    2 * PHI == P::oA - P::oPhi && P::n16 == P::oA + 2 * C * LDA && FP == P::oDenP && C * DSL == P::oKsP - P::oDenP &&
+                    NW * FP == P::oKsP2 - P::oKsP && P::oV2_bytes == 2 * (size_t)P::n16 + sizeof(float) * (P::oKsP2 + NW * FP) &&
+                    P::lds_bytes == P::oV2_bytes + 2 * C * EL,
+                "the pointer chain below and the plan's offsets are one layout");
   unsigned short* sW = reinterpret_cast<unsigned short*>(smem_b);   // [KC][NBP][8]  projection, k-chunked (zero padded)
   unsigned short* sQ = sW + KC * NBP * 8;                           // [KC][C][8]    (chunks >= D / 8: zero)
   unsigned short* sK = sQ + KC * C * 8;                             // [KC][C][8]
@@ -1011,29 +514,8 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int nh = blockIdx.x;
-  const int n = nh / p.H, h = nh - n * p.H;
-  const int seg = blockIdx.y;                              // sequence-parallel form, see PerfParams
-  const int tb = SEQ ? p.t_base_dev[n * p.t_base_stride] : p.t_base_dev ? *p.t_base_dev : p.t_base;   // rows seen (block-uniform)
-  // (SEQ: per-sequence positions; a form of its own, so that the shared-position step's counter load does not wait for n)
-  // chunk-aligned step: local row 0 is the chunk boundary at or below tb; the `lead` rows up to tb are the open chunk's old
-  // rows (k, v, pos only).  Otherwise lead = 0 and local row 0 is row tb.
-  const int lead = p.aligned ? tb % C : 0;
-  const int row_base = tb - lead;                          // absolute index of local row 0
-  const int TL = p.T + lead;                               // local rows of this call
-  const int t_begin = seg * p.seg_len, t_end = min(TL, t_begin + p.seg_len);
-  const T* qb = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] - (int64_t)lead * p.qs[2];   // rows < lead are never read
-  int64_t cache_row = (p.aligned && p.t_base_dev) ? row_base : 0;            // k / v given as cache bases: start at the boundary
-  int64_t kv_n = n;
-  if constexpr (PAGED) {                                   // one table lookup per workgroup: the chunk's page
-    static_assert(SEQ, "the paged step has a position per sequence");
-    kv_n = p.table[(int64_t)n * p.table_stride + (max(row_base, 0) >> p.page_shift)];   // (tb < 0, a sequence sitting out: entry 0, unused)
-    cache_row = row_base & ((1 << p.page_shift) - 1);
-  }
-  const T* kb = reinterpret_cast<const T*>(p.k) + kv_n * p.ks[0] + h * p.ks[1] + cache_row * p.ks[2];
-  const T* vb = reinterpret_cast<const T*>(p.v) + kv_n * p.vs[0] + h * p.vs[1] + cache_row * p.vs[2];
-  const T* pb = reinterpret_cast<const T*>(p.pos) + (p.t_base_dev ? (int64_t)row_base * p.pos_stride : 0);
-  T* ob = reinterpret_cast<T*>(p.out) + (int64_t)nh * p.T * (3 * D) - (int64_t)lead * (3 * D);           // rows < lead are never stored
+  const Perf16Wg<T, D, C, SEQ, PAGED> wg(p);
+  const int nh = wg.nh, seg = wg.seg, tb = wg.tb, lead = wg.lead, row_base = wg.row_base, t_begin = wg.t_begin, t_end = wg.t_end;
   const float cnorm = powf((float)D, -0.25f);
 
   // projection (its values are bf16-exact: the reference casts the buffer to the data dtype), zero padded rows
@@ -1047,52 +529,10 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   for (int i = tid; i < 2 * PHI + 2 * C * LDA; i += NTH) sPhi[i] = 0;
   for (int i = tid; i < C * DSL; i += NTH) sDenP[i] = 0.f;   // slots of key blocks above the diagonal stay zero
 
-  // carry image of one (n, h, segment): per-thread state registers, the k-sum, the column sums of v
-  constexpr int CARRY = JB * NBT * 4 * NTH + FP + JB * NTH;
+  constexpr int CARRY = (int)P::carry_floats;
   f4 S[JB][NBT];
-  // running column sums of v (cumulative-average output): in the transposed accumulator layout of (d) a lane owns the four
-  // columns e0 + 4 lg + r of each of its wave's blocks; image slot of column r of block jq: jq * NTH + (tid & ~15) + r
   float csum[JB][4];
-  const int cslot = (tid & ~15);
-#pragma unroll
-  for (int jq = 0; jq < JB; ++jq) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) csum[jq][r] = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBT; ++b) S[jq][b] = f4{0.f, 0.f, 0.f, 0.f};
-  }
-  {
-    float ks0 = 0.f;
-    if (!STATE_ONLY && p.state_in) {                       // increments of pass 1 do not include the incoming state
-      const float* cr = p.state_in + (int64_t)nh * CARRY;
-#pragma unroll
-      for (int jq = 0; jq < JB; ++jq) {
-#pragma unroll
-        for (int b = 0; b < NBT; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) S[jq][b][r] = cr[((jq * NBT + b) * 4 + r) * NTH + tid];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) csum[jq][r] = cr[JB * NBT * 4 * NTH + FP + jq * NTH + cslot + r];
-      }
-      if (tid < FP) ks0 = cr[JB * NBT * 4 * NTH + tid];
-    }
-    if (!STATE_ONLY) {
-      for (int s2 = 0; s2 < seg; ++s2) {                   // fixed order: bitwise reproducible
-        const float* cr = p.carry + ((int64_t)nh * (p.nseg - 1) + s2) * CARRY;
-#pragma unroll
-        for (int jq = 0; jq < JB; ++jq) {
-#pragma unroll
-          for (int b = 0; b < NBT; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[jq][b][r] += cr[((jq * NBT + b) * 4 + r) * NTH + tid];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) csum[jq][r] += cr[JB * NBT * 4 * NTH + FP + jq * NTH + cslot + r];
-        }
-        if (tid < FP) ks0 += cr[JB * NBT * 4 * NTH + tid];
-      }
-    }
-    if (tid < FP) sKsum[tid] = ks0;
-  }
+  perf16_state_init<P, STATE_ONLY>(p, nh, seg, tid, S, csum, sKsum);
 
   // a sequence that sits out this step (DecodeSession.pause / release: its counter row is negative, tb < 0) does nothing: no
   // K / V / q read, state image and output rows untouched (a paged one has read entry 0 of its table row and uses it for
@@ -1107,16 +547,9 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
   // drops its store WITHOUT a branch.  (Branches around loads and stores make the compiler's vmcnt bookkeeping
   // pessimistic: the wait for the prefetched chunk then also waits for every output store of the previous one.)
   constexpr unsigned OOB = 0x7FFFFF00u;
-  auto mk = [&](const T* base, int64_t row_stride) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)(((int64_t)(TL - 1) * row_stride + D) * 2), 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rq = mk(qb, p.qs[2]), rk = mk(kb, p.ks[2]), rv = mk(vb, p.vs[2]), rp = mk(pb, p.pos_stride);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (int)((int64_t)TL * 3 * D * 2), 0x00020000);
-  typedef __attribute__((ext_vector_type(4))) unsigned int bu4;
-  typedef __attribute__((ext_vector_type(2))) unsigned int bu2;
-  const bool want_avg = p.avg != nullptr;                  // block-uniform
-  T* gb = reinterpret_cast<T*>(p.avg) + (want_avg ? (int64_t)nh * p.T * D - (int64_t)lead * D : 0);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(gb, 0, want_avg ? (int)((int64_t)TL * D * 2) : 0, 0x00020000);
+  const Perf16Bufs B = wg.buffers(p);
+  const __amdgpu_buffer_rsrc_t rq = B.rq, rk = B.rk, rv = B.rv, rp = B.rp, ro = B.ro, rg = B.rg;
+  const bool want_avg = wg.want_avg;
   // two sets of prefetch registers: every load has two chunk times between issue and use (d = 128: 202.7 -> 199.9 us; halves the lag
   // of the last segment's workgroups in the pipelined walk)
   struct Pre { bu4 q, k, v, p; };
@@ -1157,21 +590,7 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
 #pragma unroll
     for (int ks = 0; ks < C / 32; ++ks) tril[ib][ks] = tril_frag(ib, ks);
 
-  auto write_image = [&](float* cw) {                      // this thread's part of an (n, h[, segment]) image
-#pragma unroll
-    for (int jq = 0; jq < JB; ++jq) {
-#pragma unroll
-      for (int b = 0; b < NBT; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cw[((jq * NBT + b) * 4 + r) * NTH + tid] = S[jq][b][r];
-      float* cs = cw + JB * NBT * 4 * NTH + FP + jq * NTH + tid;    // lane li = 0 writes the group's four sums, lanes >= 4 zeros
-      if (li == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cs[r] = csum[jq][r];
-      } else if (li >= 4) cs[0] = 0.f;
-    }
-    if (tid < FP) cw[JB * NBT * 4 * NTH + tid] = sKsum[tid];
-  };
+  auto write_image = [&](float* cw) { perf16_carry_write<P>(cw, tid, li, S, csum, sKsum); };
 
   // ---- the chunk walk: the D = 64 kernel's three-barrier pipeline (P1 = (d)(e) of chunk j + (b) of chunk j+1 into the other
   // image set; P2 = (c) of chunk j+1, staging of [pos | v] of chunk j+1 and q, k of chunk j+2, loads issued; P3 = denominators
@@ -1195,139 +614,9 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
     }
   };
   // ---- (b) feature maps, transposed: X^T[f][t] = sum_d W[f][d] x[t][d]; wave = (Q | K, row block, part of the feature blocks) ----
-  auto phase_b = [&](int rows, unsigned short* set) {
-    const int which = wv / (NW / 2);
-    if (!STATE_ONLY || which == 1) {                         // the state-only pass needs phi(K) alone (wave-uniform)
-      // D = 80: waves 0 and 1 (SIMDs 0, 1) own a second column block in (d)(e), so the larger share of the feature blocks goes
-      // to the waves of SIMDs 2 and 3
-      const int rb = wv & (RB - 1), part = (BW - 1) - ((wv % (NW / 2)) / RB);
-      const unsigned short* src = which ? sK : sQ;
-      f4 acc[FBP];
-#pragma unroll
-      for (int fb = 0; fb < FBP; ++fb) acc[fb] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < DP / 32; ++ks) {
-        const uint4 bx = *reinterpret_cast<const uint4*>(src + ((4 * ks + lg) * C + ((rb * 16 + li) ^ ((4 * ks + lg) & 15))) * 8);
-#pragma unroll
-        for (int fb = 0; fb < FBP; ++fb) {
-          const int fbg = part * FBP + fb;                   // (wave-uniform)
-          if (fbg < NBT) {
-            const uint4 aw = *reinterpret_cast<const uint4*>(sW + ((4 * ks + lg) * NBP + fbg * 16 + li) * 8);
-            acc[fb] = S16<T>::mfma(aw, bx, acc[fb]);
-          }
-        }
-      }
-      const int ldx = which ? LDK2 : LDQ2;
-      unsigned short* dh = set + (which ? 2 * C * LDQ2 : 0);
-      unsigned short* dl = dh + C * ldx;
-      const int row = rb * 16 + li;                          // lane: 4 consecutive features of one row
-#pragma unroll
-      for (int fb = 0; fb < FBP; ++fb) {
-        const int fbg = part * FBP + fb;
-        if (fbg < NBT) {
-          unsigned short hh[4], ll[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int f = fbg * 16 + lg * 4 + r;
-            float val = fmaxf(cnorm * acc[fb][r], 0.f) + 1e-3f;
-            if (f >= p.nb || row >= rows) val = 0.f;           // padded features / rows beyond T contribute nothing
-            split16<T>(val, hh[r], ll[r]);
-          }
-          // feature 32kk + 16a + 4g + j is stored at position 32kk + 8g + 4a + j: the 8 features lane group g needs of
-          // a 32-wide k-step in (d) (4 of tile 2kk, 4 of tile 2kk+1) are then one 16-byte piece
-          const int pos = (fbg >> 1) * 32 + lg * 8 + (fbg & 1) * 4;
-          *reinterpret_cast<uint2*>(dh + row * ldx + pos) = pack4(hh);
-          *reinterpret_cast<uint2*>(dl + row * ldx + pos) = pack4(ll);
-        }
-      }
-    }
-  };
+  auto phase_b = [&](int rows, unsigned short* set) { perf16_phase_b<T, P, STATE_ONLY>(L, set, rows, p.nb, cnorm, wv, li, lg); };
   // ---- (c) A^T tiles (lower triangle), denominator and k-sum partials ------------------------------------
-  auto phase_c = [&](const unsigned short* set) {
-    const unsigned short* sQh = set;
-    const unsigned short* sQl = sQh + C * LDQ2;
-    const unsigned short* sKh = sQl + C * LDQ2;
-    const unsigned short* sKl = sKh + C * LDK2;
-    if constexpr (!STATE_ONLY)
-    for (int tile = wv; tile < RB * (RB + 1) / 2; tile += NW) {   // (the first waves: they stage nothing at D = 80)
-      int ib = 0, rem = tile;
-      while (rem > ib) { rem -= ib + 1; ++ib; }              // tile -> (query block ib, key block jb <= ib)
-      const int jb = rem;
-      f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KF; ++ks) {
-        const int ko = ks * 32 + lg * 8;
-        const uint4 kh = *reinterpret_cast<const uint4*>(sKh + (jb * 16 + li) * LDK2 + ko);
-        const uint4 kl = *reinterpret_cast<const uint4*>(sKl + (jb * 16 + li) * LDK2 + ko);
-        const uint4 qh = *reinterpret_cast<const uint4*>(sQh + (ib * 16 + li) * LDQ2 + ko);
-        const uint4 ql = *reinterpret_cast<const uint4*>(sQl + (ib * 16 + li) * LDQ2 + ko);
-        acc = S16<T>::mfma(kh, qh, acc);
-        acc = S16<T>::mfma(kh, ql, acc);
-        acc = S16<T>::mfma(kl, qh, acc);
-      }
-      const int trow = ib * 16 + li;                         // lane: A[trow][s0 .. s0+3]
-      const int s0 = jb * 16 + lg * 4;
-      unsigned short hh[4], ll[4];
-      float rs = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float val = (s0 + r <= trow) ? acc[r] : 0.f;   // causal mask inside the diagonal tiles
-        rs += val;
-        split16<T>(val, hh[r], ll[r]);
-      }
-      *reinterpret_cast<uint2*>(sAh + trow * LDA + s0) = pack4(hh);
-      *reinterpret_cast<uint2*>(sAl + trow * LDA + s0) = pack4(ll);
-      rs = xor32_sum(xor16_sum(rs));
-      if (lg == 0) sDenP[trow * DSL + jb] = rs;              // one writer per (row, key block)
-    }
-    {
-      // carry part of the denominators: phi(q_t) . (ksum + eps) over the (permuted) feature positions
-      const int row = tid & (C - 1), part = tid / C;         // NPART parts x (FP / NPART) positions
-      constexpr int PER = FP / NPART;
-      static_assert(PER % 4 == 0, "four positions per step");
-      float s = 0.f;
-      if constexpr (!STATE_ONLY)
-      if (part < NPART)
-#pragma unroll
-      for (int g4 = 0; g4 < PER / 4; ++g4) {
-        const int f = part * PER + g4 * 4;
-        const uint2 qh = *reinterpret_cast<const uint2*>(sQh + row * LDQ2 + f);
-        const uint2 ql = *reinterpret_cast<const uint2*>(sQl + row * LDQ2 + f);
-        const float4 ks = *reinterpret_cast<const float4*>(sKsum + f);
-        s = fmaf(S16<T>::val((unsigned short)(qh.x & 0xffff)) + S16<T>::val((unsigned short)(ql.x & 0xffff)), ks.x + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.x >> 16)) + S16<T>::val((unsigned short)(ql.x >> 16)), ks.y + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.y & 0xffff)) + S16<T>::val((unsigned short)(ql.y & 0xffff)), ks.z + 1e-6f, s);
-        s = fmaf(S16<T>::val((unsigned short)(qh.y >> 16)) + S16<T>::val((unsigned short)(ql.y >> 16)), ks.w + 1e-6f, s);
-      }
-      if (part < NPART) sDenP[row * DSL + RB + part] = s;
-      // k-sum increment: wave w owns rows 4w .. 4w+3; lane = (4-position group fc, row lane rr)
-      constexpr int FG = FP / 4, RRN = 64 / FG, RPL = (C / NW) / RRN;
-      const int fc = lane % FG, rr = lane / FG;
-      float k4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (rr < RRN) {
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) {
-          const int r2 = wv * (C / NW) + rr * RPL + j;
-          const uint2 kh = *reinterpret_cast<const uint2*>(sKh + r2 * LDK2 + fc * 4);
-          const uint2 kl = *reinterpret_cast<const uint2*>(sKl + r2 * LDK2 + fc * 4);
-          k4[0] += S16<T>::val((unsigned short)(kh.x & 0xffff)) + S16<T>::val((unsigned short)(kl.x & 0xffff));
-          k4[1] += S16<T>::val((unsigned short)(kh.x >> 16)) + S16<T>::val((unsigned short)(kl.x >> 16));
-          k4[2] += S16<T>::val((unsigned short)(kh.y & 0xffff)) + S16<T>::val((unsigned short)(kl.y & 0xffff));
-          k4[3] += S16<T>::val((unsigned short)(kh.y >> 16)) + S16<T>::val((unsigned short)(kl.y >> 16));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (FG == 16) {
-          k4[j] = xor16_sum(xor32_sum(k4[j]));                   // (l, l+32) then (+16): same association as the shuffle form
-        } else {
-#pragma unroll
-          for (int o = FG * (RRN / 2); o >= FG; o >>= 1) k4[j] += __shfl_down(k4[j], o);   // fixed order
-        }
-      }
-      if (lane < FG) *reinterpret_cast<float4*>(sKsP + wv * FP + fc * 4) = make_float4(k4[0], k4[1], k4[2], k4[3]);
-    }
-  };
+  auto phase_c = [&](const unsigned short* set) { perf16_phase_c<T, P, STATE_ONLY>(L, set, tid, wv, lane, li, lg); };
   // ---- (d) O = A V + phi(Q) S over this wave's column blocks; (e) S += phi(K)^T V ------------------------------
   auto phase_de = [&](int t0, int rows, bool upd, const unsigned short* set) {
     const unsigned short* sQh = set;
@@ -1493,80 +782,10 @@ __global__ __launch_bounds__(512) void performer_bf16w_kernel(PerfParams p) {
       return __builtin_amdgcn_raw_buffer_load_b128(rk, (t < t_end && stager) ? (int)((t * p.ks[2] + sc * 8) * 2) : (int)OOB, 0, 0);
     };
     // phi(K) of one chunk by HALF the workgroup (the waves whose `which` selects it): src = staged k rows, dh = hi image
-    auto phase_bk = [&](int rows, const unsigned short* src, unsigned short* dh) {
-      const int rb = wv & (RB - 1), part = (BW - 1) - ((wv % (NW / 2)) / RB);
-      f4 acc[FBP];
-#pragma unroll
-      for (int fb = 0; fb < FBP; ++fb) acc[fb] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < DP / 32; ++ks) {
-        const uint4 bx = *reinterpret_cast<const uint4*>(src + ((4 * ks + lg) * C + ((rb * 16 + li) ^ ((4 * ks + lg) & 15))) * 8);
-#pragma unroll
-        for (int fb = 0; fb < FBP; ++fb) {
-          const int fbg = part * FBP + fb;                   // (wave-uniform)
-          if (fbg < NBT) {
-            const uint4 aw = *reinterpret_cast<const uint4*>(sW + ((4 * ks + lg) * NBP + fbg * 16 + li) * 8);
-            acc[fb] = S16<T>::mfma(aw, bx, acc[fb]);
-          }
-        }
-      }
-      unsigned short* dl = dh + C * LDK2;
-      const int row = rb * 16 + li;
-#pragma unroll
-      for (int fb = 0; fb < FBP; ++fb) {
-        const int fbg = part * FBP + fb;
-        if (fbg < NBT) {
-          unsigned short hh[4], ll[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int f = fbg * 16 + lg * 4 + r;
-            float val = fmaxf(cnorm * acc[fb][r], 0.f) + 1e-3f;
-            if (f >= p.nb || row >= rows) val = 0.f;
-            split16<T>(val, hh[r], ll[r]);
-          }
-          const int pos = (fbg >> 1) * 32 + lg * 8 + (fbg & 1) * 4;
-          *reinterpret_cast<uint2*>(dh + row * LDK2 + pos) = pack4(hh);
-          *reinterpret_cast<uint2*>(dl + row * LDK2 + pos) = pack4(ll);
-        }
-      }
-    };
+    auto phase_bk = [&](int rows, const unsigned short* src, unsigned short* dh) { perf16_feature_map<T, P>(src, L.sW, dh, P::LDK2, rows, p.nb, cnorm, wv, li, lg); };
     // per-wave k-sum increments of one chunk (phase (c)'s code) into `dst` [NW][FP]
-    auto ksum_partial = [&](const unsigned short* sKh, float* dst) {
-      const unsigned short* sKl = sKh + C * LDK2;
-      constexpr int FG = FP / 4, RRN = 64 / FG, RPL = (C / NW) / RRN;
-      const int fc = lane % FG, rr = lane / FG;
-      float k4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (rr < RRN) {
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) {
-          const int r2 = wv * (C / NW) + rr * RPL + j;
-          const uint2 kh = *reinterpret_cast<const uint2*>(sKh + r2 * LDK2 + fc * 4);
-          const uint2 kl = *reinterpret_cast<const uint2*>(sKl + r2 * LDK2 + fc * 4);
-          k4[0] += S16<T>::val((unsigned short)(kh.x & 0xffff)) + S16<T>::val((unsigned short)(kl.x & 0xffff));
-          k4[1] += S16<T>::val((unsigned short)(kh.x >> 16)) + S16<T>::val((unsigned short)(kl.x >> 16));
-          k4[2] += S16<T>::val((unsigned short)(kh.y & 0xffff)) + S16<T>::val((unsigned short)(kl.y & 0xffff));
-          k4[3] += S16<T>::val((unsigned short)(kh.y >> 16)) + S16<T>::val((unsigned short)(kl.y >> 16));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (FG == 16) {
-          k4[j] = xor16_sum(xor32_sum(k4[j]));
-        } else {
-#pragma unroll
-          for (int o = FG * (RRN / 2); o >= FG; o >>= 1) k4[j] += __shfl_down(k4[j], o);
-        }
-      }
-      if (lane < FG) *reinterpret_cast<float4*>(dst + wv * FP + fc * 4) = make_float4(k4[0], k4[1], k4[2], k4[3]);
-    };
-    auto ksum_fold = [&](const float* src) {                 // fixed order: bitwise reproducible
-      if (tid < FP) {
-        float s_ = sKsum[tid];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) s_ += src[i * FP + tid];
-        sKsum[tid] = s_;
-      }
-    };
+    auto ksum_partial = [&](const unsigned short* sKh, float* dst) { perf16_ksum_partial<T, P>(sKh, dst, wv, lane); };
+    auto ksum_fold = [&](const float* src) { perf16_ksum_fold<P>(sKsum, src, tid, true); };
     // column totals of v and S += phi(K)^T [pos | v] for one chunk: phase (d)(e)'s STATE_ONLY code
     auto phase_e = [&](const unsigned short* sVi, const unsigned short* sKh) {
       const unsigned short* sKl = sKh + C * LDK2;
@@ -1774,57 +993,32 @@ struct PerfForm {
   bool mfma16 = false;
 };
 
-// fp32 kernel: LDS images and carry floats (the per-thread state registers + the k-sum)
-template <int D, int NBT, int C>
-constexpr size_t perf_lds() {
-  constexpr int E = 2 * D, NBP = NBT * 16;
-  return sizeof(float) * (NBP * (D + 2) + 2 * C * (D + 2) + C * (E + 16) + 2 * C * (NBP + 2) + NBP + C + C * (C / 16 + 512 / C));
-}
-template <int D, int NBT>
-constexpr int64_t perf_carry_floats() { return (int64_t)(((2 * D / 16) + 7) / 8) * NBT * 4 * 512 + NBT * 16; }
+// Every form's LDS bytes and carry floats come from its plan (PerfF32Plan / Perf16Plan), which the kernel carves its images from.
 template <int D, int NBT, int C>
 static PerfForm perf_f32_form() {
+  using P = PerfF32Plan<D, NBT, C>;
   return {launch_perf<performer_kernel<D, NBT, C, true>, performer_kernel<D, NBT, C, false>, performer_kernel<D, NBT, C, false>,
-                      nullptr, C, perf_lds<D, NBT, C>()>, C,
-          perf_carry_floats<D, NBT>(), false};
+                      nullptr, C, P::lds_bytes>, C, P::carry_floats, false};
 }
 
 // 16-bit kernel, D = 64
-template <int NBT>
-constexpr size_t perf_bf16_lds() {
-  constexpr int D = 64, C = 64, NTH = 512, E = 2 * D, NBP = NBT * 16, FP = ((NBT + 1) / 2) * 32, LDQ2 = FP + 16, LDK2 = (FP == 64) ? 96 : FP + 8, LDA = C + 16;
-  constexpr int NSET = (FP == 64) ? 2 : 1;                   // phi image sets (performer_bf16_kernel)
-  return 2 * ((D / 8) * NBP * 8 + 2 * (D / 8) * C * 8 + C * E + NSET * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
-         sizeof(float) * (FP + C * (C / 16 + NTH / C) + 8 * FP);
-}
-template <int NBT>
-constexpr int64_t perf_bf16_carry_floats() { return (int64_t)NBT * 4 * 512 + ((NBT + 1) / 2) * 32 + 512; }
 template <typename T, int NBT>
 static PerfForm perf_bf16_form() {
-  static_assert(perf_bf16_lds<NBT>() > 64 * 1024, "the attribute is set above 64 KB");
+  using P = Perf16Plan<64, 64, NBT>;
+  static_assert(P::lds_bytes > 64 * 1024, "the attribute is set above 64 KB");
   return {launch_perf<performer_bf16_kernel<T, NBT, true>, performer_bf16_kernel<T, NBT, false>,
-                      performer_bf16_kernel<T, NBT, false, true>, performer_bf16_kernel<T, NBT, false, true, true>, 64,
-                      perf_bf16_lds<NBT>()>, 64,
-          perf_bf16_carry_floats<NBT>(), true};
+                      performer_bf16_kernel<T, NBT, false, true>, performer_bf16_kernel<T, NBT, false, true, true>, P::C,
+                      P::lds_bytes>, P::C, P::carry_floats, true};
 }
 
 // the wide-head form of the 16-bit kernel (d = 80 / 128: 32-row chunks, up to two column blocks per wave)
-template <int D, int C, int NBT>
-constexpr size_t perf_bf16w_lds() {
-  constexpr int NBP = NBT * 16, FP = ((NBT + 1) / 2) * 32, LDQ2 = FP + 16, LDK2 = (FP == 64) ? 96 : FP + 8, LDA = C + 16;
-  constexpr int KC = (D + 31) / 32 * 4, EL = 256;
-  return 2 * (KC * NBP * 8 + 2 * KC * C * 8 + C * EL + 2 * (2 * C * LDQ2 + 2 * C * LDK2) + 2 * C * LDA) +
-         sizeof(float) * (FP + C * (C / 16 + 8) + 8 * FP) +
-         sizeof(float) * 8 * FP + 2 * C * EL;     // the state pass's second k-sum partials and second [pos | v] image
-}
-template <int D, int NBT>
-constexpr int64_t perf_bf16w_carry_floats() { return (int64_t)((2 * D / 16 + 7) / 8) * NBT * 4 * 512 + ((NBT + 1) / 2) * 32 + ((2 * D / 16 + 7) / 8) * 512; }
 template <typename T, int D, int NBT>
 static PerfForm perf_bf16w_form() {
-  static_assert(perf_bf16w_lds<D, 32, NBT>() > 64 * 1024, "the attribute is set above 64 KB");
+  using P = Perf16Plan<D, 32, NBT>;
+  static_assert(P::lds_bytes > 64 * 1024, "the attribute is set above 64 KB");
   return {launch_perf<performer_bf16w_kernel<T, D, 32, NBT, true>, performer_bf16w_kernel<T, D, 32, NBT, false>,
                       performer_bf16w_kernel<T, D, 32, NBT, false, true>, performer_bf16w_kernel<T, D, 32, NBT, false, true, true>,
-                      32, perf_bf16w_lds<D, 32, NBT>()>, 32, perf_bf16w_carry_floats<D, NBT>(), true};
+                      P::C, P::lds_bytes>, P::C, P::carry_floats, true};
 }
 
 template <typename T>

@@ -132,6 +132,12 @@ def test_host_side_planning_entries():
     assert b"D=96" in lib.sea_last_error()
     sb = lib.sea_performer_state_bytes(2, 4, 64, 33, BF16)
     assert sb > 0 and sb % (2 * 4) == 0 and lib.sea_performer_state_bytes(2, 4, 96, 33, BF16) == 0
+    # the state image is ABI (decode sessions hold it across steps): its exact size per (n, h), every kernel form
+    for D, nb, floats16, floats32 in ((64, 33, 6720, 6192), (64, 66, 10848, 10320), (80, 43, 13376, 12336), (80, 58, 21600, 20560),
+                                      (128, 77, 21600, 20560)):
+        for dtype in (torch.bfloat16, torch.float16):
+            assert lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(dtype)) == 4 * floats16, (D, nb, dtype)
+        assert lib.sea_performer_state_bytes(1, 1, D, nb, _lib.dtype_code(torch.float32)) == 4 * floats32, (D, nb)
     # every Performer query answers from one table of kernel forms: across each form's edges they agree with each other
     from sea_attention_amd.perlin_attention import ops
     for dtype in (torch.float32, torch.float16, torch.bfloat16):
