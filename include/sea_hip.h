@@ -202,7 +202,17 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  *   SEA_ATTN_KEYRANGE  the key-range form, for K + V per head beyond an XCD's L2 (see below); range_keys in bits 16..30;
  *   bits 4..7 (SEA_ATTN_ROW_POOL_SHIFT): log2 of the row pool of the fused gather form (ROW-POOL form below; 0 = none);
  *   bits 8..11: row tiles per wave for the tile kernel (1 or 2; 0 = default for the head size);
- *   bits 12..15: log2 of its key window (6..12; 0 = default 2048).
+ *   bits 12..15: log2 of its key window (6..12; 0 = default 2048);
+ *   bits 16..17 (SEA_ATTN_GRID_ORDER_SHIFT; every path but SEA_ATTN_KEYRANGE, the fused forms included): the order in which
+ *                    the workgroups of an XCD take the row blocks of its (n, h) pairs -- a causal row block's work grows with
+ *                    t.  0: pair after pair, t ascending; 1: pair after pair, t descending (the heaviest block first); 2: the
+ *                    XCD's pairs G at a time, their row blocks interleaved, t descending, G = 1 << bits 18..19
+ *                    (SEA_ATTN_GRID_GROUP_SHIFT; 1, 2 or 4: G pairs' K + V share the XCD's L2).  Another value: SEA_EINVAL.
+ *                    Rows are independent: every output bit is that of order 0.  The forward prefill launches read the
+ *                    field: the fused gather forms (bits != NULL) with and without pools, the wave-per-row kernel (rows
+ *                    wider than 16 lanes) and the tile kernel.  The decode forms (t_src_dev), a launch of at most
+ *                    sea_attention_few_rows() rows and the unfused lane-group form (bits == NULL, rows of up to 16 lanes)
+ *                    keep order 0 whatever the field says.  A library without the field ignores the bits.
  *
  * probs_out (optional): fp32, laid out like `col` (row n at probs_out + n*probs_stride_n): entry e receives
  *   rs * softmax_e -- the values of `partial_attention_probs` after flat_csr_softmax + flat_csr_elmul
@@ -316,7 +326,7 @@ int sea_csr_spmm(const float* values, const void* v, int dtype,
  * the selection launch wrote its empty rows) may have been read by then.
  */
 enum sea_attn_path { SEA_ATTN_AUTO = 0, SEA_ATTN_GATHER = 1, SEA_ATTN_TILE = 2, SEA_ATTN_KEYRANGE = 3 };
-enum { SEA_ATTN_ROW_POOL_SHIFT = 4 };
+enum { SEA_ATTN_ROW_POOL_SHIFT = 4, SEA_ATTN_GRID_ORDER_SHIFT = 16, SEA_ATTN_GRID_GROUP_SHIFT = 18 };
 int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
                          int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
                          const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,

@@ -87,6 +87,9 @@ def library_path():
 
 SEA_ATTN_AUTO, SEA_ATTN_GATHER, SEA_ATTN_TILE, SEA_ATTN_KEYRANGE = 0, 1, 2, 3
 SEA_ATTN_ROW_POOL_SHIFT = 4                     # flags bits 4..7: log2 of the fused gather form's row pool (0 = none)
+# flags bits 16..17 / 18..19 (every path but the key-range form, whose range_keys sit there): the order the attention grid's
+# workgroups take their row blocks in (0 = ascending) and log2 of the pairs the grouped order interleaves
+SEA_ATTN_GRID_ORDER_SHIFT, SEA_ATTN_GRID_GROUP_SHIFT = 16, 18
 SEA_OK, SEA_EINVAL, SEA_EUNSUPPORTED = 0, -1, -2
 
 

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void sparse_attn_kernel(AttnParams p) {
   constexpr int VEC = Elem<T>::VEC;
   constexpr int KPI = 64 / LPR;  // keys per wave-instruction
   int pair, tb;
-  if (!map_block(p.N * p.H, p.TB, &pair, &tb)) return;
+  if (!map_block((int)blockIdx.x, p.N * p.H, p.TB, p.grid_order, p.grid_group, &pair, &tb)) return;
   const int n = pair / p.H, h = pair - n * p.H;
   const int t = tb * 4 + (threadIdx.x >> 6);
   if (t >= p.T_dst) return;
@@ -341,7 +341,14 @@ __device__ __forceinline__ void attn_rows_body(const AttnParams& p) {
   constexpr int RPW = 64 / LPR;       // rows per wave
   constexpr int RPB = NWB * RPW;      // rows per workgroup
   int pair, tb;
-  if (kernel_is_idle(p) || !map_block(p.N * p.H, p.TB, &pair, &tb)) return;      // (grid / workgroup uniform: before any barrier)
+  // (grid / workgroup uniform: before any barrier.)  The fused prefill forms take the launch's grid order.  The decode forms
+  // keep the ascending one (their rows are one position's), and so does the unfused form -- decode steps of few rows and
+  // handles whose columns are written, no prefill hot path: with the orders' code in it the compiler gave it 93 registers for
+  // 78 (d = 80: 85 for 72) and a wave less per SIMD
+  constexpr bool ORDERED = FUSE && !DEC;
+  if (kernel_is_idle(p) ||
+      !map_block((int)blockIdx.x, p.N * p.H, p.TB, ORDERED ? p.grid_order : (int)SEA_GRID_ASCENDING, ORDERED ? p.grid_group : 1, &pair, &tb))
+    return;
   const int n = pair / p.H;
   // heads rotated over the XCDs per batch item: the pair index is congruent to the XCD label (map_block), so without the
   // rotation an XCD would serve the same residue class of heads for every item and a heavy head would load one XCD only
@@ -472,11 +479,35 @@ __device__ __forceinline__ void attn_rows_body(const AttnParams& p) {
   if (rowok && dact) attn_epilogue<T, TO, X80>(p, ridx, n, h, t, sub, l, acc);
 }
 
+// -DSEA_STAMP (a diagnostic build, never the shipped library; scripts/stamp_attn_grid.py): lane 0 of wave 0 of every workgroup
+// of the lane-group kernels leaves the 100 MHz clock at its entry and at its exit, and the XCC it ran on, in a buffer of its
+// own -- when the workgroups of a launch are resident, per XCD.  No output depends on the stamps.
+#ifdef SEA_STAMP
+constexpr int SEA_ATTN_STAMP_BLOCKS = 1 << 16;             // workgroups of a launch that have a slot (the headline: 16 384)
+__device__ unsigned long long sea_attn_grid_stamps[3 * SEA_ATTN_STAMP_BLOCKS];
+#define ATTN_GRID_STAMP(i)                                                                                     \
+  do {                                                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < (unsigned)SEA_ATTN_STAMP_BLOCKS)                                      \
+      sea_attn_grid_stamps[3 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime();                           \
+  } while (0)
+#define ATTN_GRID_STAMP_XCC()                                                                                  \
+  do {                                                                                                         \
+    if (threadIdx.x == 0 && blockIdx.x < (unsigned)SEA_ATTN_STAMP_BLOCKS)                                      \
+      sea_attn_grid_stamps[3 * blockIdx.x + 2] = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 0xf; /* XCC_ID[3:0] */ \
+  } while (0)
+#else
+#define ATTN_GRID_STAMP(i) do {} while (0)
+#define ATTN_GRID_STAMP_XCC() do {} while (0)
+#endif
+
 template <typename T, typename TO, int LPR, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
 // the fused 16-bit inference forms are held to 64 registers (8 waves per SIMD; 4 - 8 spilled registers): measured 0.307 ms
 // against 0.328 ms at 88 registers for the 16-lane form (LLaMA-13B d = 128), and the same direction for the 8-lane form
 __global__ __launch_bounds__(NWB * 64, (FUSE && !DEC && sizeof(T) == 2 && !WP) ? 8 : 1) void sparse_attn_rows_kernel(AttnParams p) {
+  ATTN_GRID_STAMP(0);
+  ATTN_GRID_STAMP_XCC();
   attn_rows_body<T, TO, LPR, U, WP, NWB, FUSE, DEC, ORD, false>(p);
+  ATTN_GRID_STAMP(1);
 }
 
 template <typename T, typename TO, int U, bool WP, int NWB = 4, bool FUSE = false, bool DEC = false, bool ORD = false>
@@ -1045,6 +1076,15 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
     probs_stride_n = 0;
   }
   const bool keyrange = (flags & 0xff) == SEA_ATTN_KEYRANGE;
+  // bits 16..17 / 18..19 (every path but the key-range form, whose range_keys sit there): the grid order and log2 of its group
+  int grid_order = SEA_GRID_ASCENDING, grid_group = 1;
+  if (!keyrange) {
+    grid_order = (flags >> SEA_ATTN_GRID_ORDER_SHIFT) & 3;
+    grid_group = 1 << ((flags >> SEA_ATTN_GRID_GROUP_SHIFT) & 3);
+    flags &= 0xffff;
+    SEA_REQUIRE(grid_order <= SEA_GRID_GROUPED && grid_group <= 4, SEA_EINVAL,
+                "%s: grid order %d with groups of %d pairs: orders 0 .. 2, groups of 1, 2 or 4", nm, grid_order, grid_group);
+  }
   KeyRangeParams kr = {nullptr, 0, 0, 0};
   if (keyrange) {
     SEA_REQUIRE(bits != nullptr, SEA_EUNSUPPORTED, "%s: the key-range form is a fused form (bits is NULL)", nm);
@@ -1141,6 +1181,10 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
   p.table = block_table; p.table_stride = (int)table_stride; p.page_shift = block_table ? __builtin_ctzll(page_rows) : 0;
   p.order = order; p.order_stride_n = order_stride_n;
   p.pool_rows = order ? 1 << pool_log2 : 0; p.pools = order ? (int)((T_dst + p.pool_rows - 1) / p.pool_rows) : 0;
+  // the forward prefill launches take the caller's grid order; a decoding step (t_src_dev, or few rows) keeps the ascending one
+  const bool prefill = t_src_dev == nullptr && N * H * T_dst > SEA_ATTN_FEW_ROWS;
+  p.grid_order = prefill ? grid_order : (int)SEA_GRID_ASCENDING;
+  p.grid_group = prefill ? grid_group : 1;
   if (t_src_dev) {
     SEA_REQUIRE(bits != nullptr && T_dst <= SEA_ATTN_WARM_ROWS, SEA_EUNSUPPORTED,
                 "%s: the decode form takes T_dst <= %d rows per sequence", nm, SEA_ATTN_WARM_ROWS);
@@ -1194,6 +1238,37 @@ extern "C" int sea_sparse_attention(const void* q, const void* k, const void* v,
 }
 
 extern "C" int64_t sea_attention_few_rows(void) { return SEA_ATTN_FEW_ROWS; }
+
+// The kernels' block map on the host (exported beside the ABI of sea_hip.h, not part of it: a test and diagnostic hook): for
+// every workgroup index of a launch of NH pairs x TB row blocks, what map_block makes of it.  Returns the grid's size, or a
+// negative error code.
+extern "C" int64_t sea_attention_grid_map(int64_t NH, int64_t TB, int order, int group, int32_t* pair, int32_t* tb, int32_t* has_work) {
+  const char* nm = "sea_attention_grid_map";
+  SEA_REQUIRE(pair && tb && has_work, SEA_EINVAL, "%s: null pointer", nm);
+  SEA_REQUIRE(NH > 0 && TB > 0 && 8 * ((NH + 7) / 8) * TB < (1ll << 31), SEA_EINVAL, "%s: bad grid %lld x %lld", nm, (long long)NH, (long long)TB);
+  SEA_REQUIRE(order >= 0 && order <= SEA_GRID_GROUPED && (group == 1 || group == 2 || group == 4), SEA_EINVAL,
+              "%s: grid order %d with groups of %d pairs: orders 0 .. 2, groups of 1, 2 or 4", nm, order, group);
+  const int64_t blocks = 8 * ((NH + 7) / 8) * TB;
+  for (int64_t b = 0; b < blocks; ++b) {
+    int pr = -1, rb = -1;
+    has_work[b] = map_block((int)b, (int)NH, (int)TB, order, group, &pr, &rb) ? 1 : 0;
+    pair[b] = pr;
+    tb[b] = rb;
+  }
+  return blocks;
+}
+
+#ifdef SEA_STAMP
+// the stamps of the last lane-group launch: per workgroup (entry, exit, XCC) -- and cleared for the next one
+extern "C" int sea_debug_attn_grid_stamps(unsigned long long* host, int64_t blocks) {
+  if (blocks > SEA_ATTN_STAMP_BLOCKS) return SEA_EINVAL;
+  const size_t bytes = sizeof(unsigned long long) * 3 * (size_t)blocks;
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(sea_attn_grid_stamps), bytes) != hipSuccess) return SEA_ELAUNCH;
+  void* dev = nullptr;
+  if (hipGetSymbolAddress(&dev, HIP_SYMBOL(sea_attn_grid_stamps)) != hipSuccess || hipMemset(dev, 0, bytes) != hipSuccess) return SEA_ELAUNCH;
+  return SEA_OK;
+}
+#endif
 
 extern "C" int sea_attention_plan(const uint32_t* bits, int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t T_m,
                                   int is_causal, float entries_per_tile, uint8_t* block_path, sea_stream_t stream) {

@@ -55,6 +55,9 @@ struct AttnParams {
   const uint16_t* order;
   int64_t order_stride_n;
   int pool_rows, pools;
+  // the order in which the grid's workgroups take their XCD's row blocks (map_block below: SEA_GRID_*, pairs per group);
+  // read by the forward prefill kernels, ascending for every other launch
+  int grid_order, grid_group;
 };
 
 template <typename TO, int VEC> __device__ inline void store_frag(TO* dst, const float* f);
@@ -90,28 +93,48 @@ template <> __device__ inline void store_frag<__half, 4>(__half* dst, const floa
   *reinterpret_cast<uint2*>(dst) = r.u;
 }
 
-// (n, h, row-block) from blockIdx, XCD-aware: blocks b and b+8 share an XCD (observed dispatch
-// order; only affects L2 locality).  Returns false if this block has no work.
-__device__ inline bool map_block(int NH, int TB, int* pair, int* tb) {
-  const int bid = blockIdx.x;
+// (n, h, row-block) from the workgroup index `bid`, XCD-aware: blocks b and b+8 share an XCD (observed dispatch order; only
+// affects L2 locality).  Returns false if this block has no work.  The grid is 8 * ceil(NH / 8) * TB workgroups, dispatched
+// in index order, so `slot` = bid >> 3 is the position of a workgroup in ITS XCD's queue and the map decides in which order
+// an XCD takes the row blocks of its NH / 8 pairs (one function for the kernels and for the host,
+// sea_attention_grid_map):
+//   SEA_GRID_ASCENDING    pair after pair, tb ascending -- with causal rows the lightest block of a pair first, the heaviest last;
+//   SEA_GRID_HEAVY_FIRST  pair after pair, tb descending (= SEA_GRID_GROUPED with G = 1);
+//   SEA_GRID_GROUPED      the XCD's pairs G at a time: the blocks of the G pairs interleaved (pair 0's block TB - 1, pair 1's
+//                         block TB - 1, ..., pair 0's block TB - 2, ...), tb descending; the last group holds what is left.
+enum { SEA_GRID_ASCENDING = 0, SEA_GRID_HEAVY_FIRST = 1, SEA_GRID_GROUPED = 2 };
+__host__ __device__ inline bool map_block(int bid, int NH, int TB, int order, int G, int* pair, int* tb) {
   const int xcd = bid & 7, slot = bid >> 3;
-  const int pl = slot / TB;
   const int full = NH >> 3;                      // groups of 8 pairs: pair 8 pl + x lives on XCD x (its K / V stay in that L2)
-  if (pl < full) {
-    *tb = slot - pl * TB;
-    *pair = pl * 8 + xcd;
+  const bool desc = order != SEA_GRID_ASCENDING;
+  if (slot < full * TB) {
+    if (order != SEA_GRID_GROUPED || G == 1) {             // pair after pair (one division, as before there were orders)
+      const int pl = slot / TB, rb = slot - pl * TB;
+      *tb = desc ? TB - 1 - rb : rb;
+      *pair = pl * 8 + xcd;
+      return true;
+    }
+    const int grp = slot / (G * TB), w = slot - grp * (G * TB);      // group of G pairs; position inside it
+    const int left = full - grp * G, cnt = left < G ? left : G;      // pairs of this group (the last one may hold fewer)
+    const int rb = w / cnt;
+    *tb = TB - 1 - rb;
+    *pair = (grp * G + (w - rb * cnt)) * 8 + xcd;
     return true;
   }
   // the last, partial group (NH % 8 = r pairs; round 5): its r TB row blocks are dealt round-robin to ALL eight XCDs instead
   // of TB blocks to each of r XCDs while 8 - r sit idle -- 12 pairs (OPT-125m, one sequence: the long-context and grid legs)
   // were 2 + 2 + 2 + 2 + 1 + 1 + 1 + 1 pairs per XCD, i.e. the launch lasted as long as 16 pairs
   const int r = NH - full * 8;
-  const int item = (slot - pl * TB) * 8 + xcd;
-  if (pl > full || item >= r * TB) return false;
-  const int pr = item / TB;
-  *tb = item - pr * TB;
+  const int item = (slot - full * TB) * 8 + xcd;
+  if (item >= r * TB) return false;              // (slot < (full + 1) * TB: the grid ends there)
+  const int pr = item / TB, rb = item - pr * TB;
+  *tb = desc ? TB - 1 - rb : rb;
   *pair = full * 8 + pr;
   return true;
+}
+// the ascending order from blockIdx: the decode forms, the key-range pair, the backward passes, the unfused CSR operators
+__device__ inline bool map_block(int NH, int TB, int* pair, int* tb) {
+  return map_block((int)blockIdx.x, NH, TB, SEA_GRID_ASCENDING, 1, pair, tb);
 }
 
 // ---- the gather kernels' score: q . k over a lane group (sea_attn.hip, sea_attn_keyrange.hip) -----------------------------

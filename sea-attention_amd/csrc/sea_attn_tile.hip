@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NW * 64) void sparse_attn_tile_kernel(AttnParams p,
   constexpr float LOG2E = 1.4426950408889634f;
   extern __shared__ __attribute__((aligned(16))) char at_smem[];
   int pair, tb;
-  if (kernel_is_idle(p) || !map_block(p.N * p.H, p.TB, &pair, &tb)) return;
+  if (kernel_is_idle(p) || !map_block((int)blockIdx.x, p.N * p.H, p.TB, p.grid_order, p.grid_group, &pair, &tb)) return;
   const int n = pair / p.H, h = pair - n * p.H;
   const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));

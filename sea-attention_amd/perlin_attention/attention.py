@@ -44,6 +44,9 @@ _C8_DECLINED = set()      # (dtype, Cin, Cout, k) of predictor convolutions the 
 # measured) keep the in-block ranking
 ATTENTION_ROW_POOL: Optional[int] = 512
 ATTENTION_ROW_POOL_HEAD_SIZES = (64, 128)
+# what a new PerlinAttention's `attention_grid_order` starts as: "auto" = per launch the order measured to pay for its data
+# (`ops.grid_order_default`: 16-bit K + V of 1 .. 4 MiB a pair; DESIGN 6.4, profiles/r08a_*), ascending everywhere else
+ATTENTION_GRID_ORDER = "auto"
 
 
 def _safe_to(t, d):
@@ -167,6 +170,11 @@ class PerlinAttention(nn.Module):
         # rows (`ops.sparse_attention(row_pool=...)`: a sorting pre-pass in front of the gather kernel; the same bits) wherever
         # that form exists and the head size takes the pool; None = every workgroup ranks its own rows
         self.attention_row_pool: Optional[int] = ATTENTION_ROW_POOL
+        # sparse mode: the order in which the prefill attention launch's workgroups take the row blocks of their XCD's (n, h)
+        # pairs (`ops.sparse_attention(grid_order=...)`: "ascending", "heavy-first", "grouped" or ("grouped", G); the same bits)
+        # "auto" = `ops.grid_order_default` of the launch's data (the shapes measured to gain; ascending elsewhere); None =
+        # ascending everywhere
+        self.attention_grid_order = ATTENTION_GRID_ORDER
         # HIP Performer: None = the library's plan for the shape (it cuts ONE long sequence into segments so that all CUs
         # work: another fp32 summation order than the one-pass kernel a full batch takes), 1 = always the one-pass kernel
         # (bench.py's self-check runs a batch item alone with it, so that the item reproduces its batched rows bit for bit)
@@ -1027,11 +1035,14 @@ class PerlinAttention(nn.Module):
                         if row_pool is not None and not (qs.dtype != torch.float32 and HID in ATTENTION_ROW_POOL_HEAD_SIZES
                                                          and ops.row_pool_supported(qs.dtype, HID, int(row_pool))):
                             row_pool = None
+                        grid_order = self.attention_grid_order
+                        if grid_order == "auto":
+                            grid_order = ops.grid_order_default(qs.dtype, HID, T_SRC)
                         res = ops.sparse_attention(qs, ks, vs, csr, row_scale=row_scale, avg=average_context_layer,
                                                    mix=average_scale, out=ctx.view(N, T, H, HID).permute(0, 2, 1, 3),
                                                    want_probs=want_probs, path="gather" if want_probs else self.sparse_kernel,
                                                    plan=plan, keep_columns_pending=self.lazy_csr_columns and not want_probs,
-                                                   row_pool=row_pool)
+                                                   row_pool=row_pool, grid_order=grid_order)
                     if want_probs:
                         probs_csr = csr.with_values(res[1])
         if probs_csr is not None:

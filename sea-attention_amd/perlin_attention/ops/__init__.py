@@ -9,7 +9,7 @@ from .flat_csr import flat_csr_to_dense
 # fused MI355X entry points (not in the reference)
 from .flat_csr import (FlatCSR, fused_interp_supported, attention_few_rows, topk_to_csr, topk_mask, sparse_attention, sparse_attention_bytes, attention_plan, plan_blocks, make_plan,
                        sparse_attention_autograd, keyrange_supported, keyrange_workspace_floats,
-                       row_pool_supported, row_pool_workspace, row_pool_workspace_elems,
+                       row_pool_supported, row_pool_workspace, row_pool_workspace_elems, GRID_ORDERS, GRID_GROUPS, grid_group_rule, grid_order_default, attention_grid_map,
                        keep_table_causal, keep_table_kernel_test, z_capacity, csr_from_selection)
 from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value, performer_supported, performer_avg_supported,
                         performer_step, performer_plan, performer_chunk_rows,

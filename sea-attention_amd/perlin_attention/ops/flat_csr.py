@@ -11,6 +11,7 @@ when a torch CSR tensor is asked for.
 
 Every operator here launches HIP kernels through the C ABI; CPU tensors are rejected.
 """
+import ctypes
 import math
 from ctypes import c_void_p, c_int64
 from typing import Optional
@@ -341,6 +342,61 @@ def row_pool_workspace_elems(N: int, H: int, T_dst: int, row_pool: int) -> int:
     return N * H * -(-T_dst // row_pool) * row_pool
 
 
+GRID_ORDERS = ("ascending", "heavy-first", "grouped")
+GRID_GROUPS = (1, 2, 4)
+GRID_GROUP_L2_BYTES = 2 << 20
+
+
+def grid_group_rule(dtype, D: int, T_src: int) -> int:
+    """How many (n, h) pairs the "grouped" grid order interleaves on an XCD when the caller names none: the largest of 1, 2, 4
+    whose K + V (2 * T_src * D elements a pair) fit in 2 MiB, half an XCD's L2."""
+    pair_bytes = 2 * T_src * D * (4 if dtype == torch.float32 else 2)
+    return max([g for g in GRID_GROUPS if g * pair_bytes <= GRID_GROUP_L2_BYTES], default=1)
+
+
+def grid_order_default(dtype, D: int, T_src: int):
+    """The grid order measured to pay for a prefill launch of this data (None = ascending, where none did): 16-bit
+    data whose K + V per (n, h) pair take 1 .. 4 MiB -- ("grouped", 2) where two pairs fit in half an XCD's L2 (OPT-1.3B:
+    1 MiB a pair), "heavy-first" beyond (d = 128 at 4096 keys: 2 MiB, d = 80 at 8192: 2.6 MiB).  Shorter key axes (2048 keys
+    of d = 64), fp32 data and pairs beyond the L2 (32 768 keys) measured no gain and keep the ascending order."""
+    if dtype == torch.float32:
+        return None
+    pair_bytes = 2 * T_src * D * 2
+    if pair_bytes < (1 << 20) or pair_bytes > (4 << 20):
+        return None
+    return ("grouped", 2) if 2 * pair_bytes <= GRID_GROUP_L2_BYTES else "heavy-first"
+
+
+def _grid_order_flags(grid_order, dtype, D: int, T_src: int) -> int:
+    """`flags` bits 16..19 of sea_sparse_attention for a `grid_order` of sparse_attention (0 for None: today's order)."""
+    if grid_order is None:
+        return 0
+    name, group = grid_order if isinstance(grid_order, tuple) else (grid_order, None)
+    if name not in GRID_ORDERS or (group is not None and (name != "grouped" or group not in GRID_GROUPS)):
+        raise ValueError(f"sparse_attention(grid_order={grid_order!r}): one of {GRID_ORDERS}, or (\"grouped\", G) with G in {GRID_GROUPS}")
+    if name == "grouped" and group is None:
+        group = grid_group_rule(dtype, D, T_src)
+    return (GRID_ORDERS.index(name) << _lib.SEA_ATTN_GRID_ORDER_SHIFT) | \
+        ((int(group or 1).bit_length() - 1) << _lib.SEA_ATTN_GRID_GROUP_SHIFT)
+
+
+def attention_grid_map(NH: int, TB: int, grid_order="ascending", group: int = 1):
+    """What the attention kernels' workgroups make of their index (`sea_attention_grid_map`, the kernels' own function run on
+    the host; no GPU): int32 arrays (pair, tb, has_work) over the 8 * ceil(NH / 8) * TB workgroups of a launch of NH (n, h)
+    pairs with TB row blocks each."""
+    import numpy as np
+    lib = _lib.load()
+    fn = lib.sea_attention_grid_map
+    fn.argtypes, fn.restype = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_void_p], ctypes.c_int64
+    blocks = 8 * ((NH + 7) // 8) * TB
+    pair, tb, work = (np.empty(blocks, dtype=np.int32) for _ in range(3))
+    got = fn(NH, TB, GRID_ORDERS.index(grid_order), group, pair.ctypes.data, tb.ctypes.data, work.ctypes.data)
+    if got != blocks:
+        raise RuntimeError(f"sea_attention_grid_map({NH}, {TB}, {grid_order}, {group}) = {got}: {lib.sea_last_error().decode()}")
+    return pair, tb, work
+
+
 _BWD_WS = {}
 _KEYRANGE_WS = {}
 _ROW_POOL_WS = {}
@@ -482,7 +538,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
                      path: str = "auto", want_probs: bool = False, row_tiles: int = 0, key_window: int = 0,
                      plan: Optional[torch.Tensor] = None, fuse_emit: bool = True, keep_columns_pending: bool = False,
                      block_table: Optional[torch.Tensor] = None, range_keys: Optional[int] = None,
-                     row_pool: Optional[int] = None, probs_out: Optional[torch.Tensor] = None):
+                     row_pool: Optional[int] = None, grid_order=None, probs_out: Optional[torch.Tensor] = None):
     """Fused SDDMM + per-(row,head) softmax + row scale + SpMM (+ mix) over the flat CSR (`sea_sparse_attention`).
 
     q (N,H,T_dst,D), k/v (N,H,T_src,D), any [n,h,t] strides, feature stride 1.
@@ -520,8 +576,16 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     pool; `row_pool_supported`: a power of two up to 1024, a multiple of the form's rows per workgroup, ValueError otherwise)
     instead of the 64 / 32 rows a workgroup ranks by itself.  The same bits, another schedule.  It applies where the fused
     inference launch serves the call (no probabilities, no decode or paged form, more than `attention_few_rows()` rows) and is
-    ignored elsewhere; the order it dealt by is left in `row_pool_workspace(N, H, T_dst, row_pool, device)`."""
+    ignored elsewhere; the order it dealt by is left in `row_pool_workspace(N, H, T_dst, row_pool, device)`.
+    grid_order: the order in which the launch's workgroups take the row blocks of the (n, h) pairs of their XCD (a causal row
+    block's work grows with t): None or "ascending" (t ascending, pair after pair), "heavy-first" (t descending inside a pair),
+    "grouped" (the XCD's pairs G at a time, their blocks interleaved, t descending; G by `grid_group_rule`) or ("grouped", G)
+    with G in 1, 2, 4.  The same bits, another schedule.  The prefill launches take it -- the fused gather forms
+    with or without pools, the wave-per-row kernel (rows wider than 16 lanes) and the tile kernel; the decode forms, launches
+    of at most `attention_few_rows()` rows, the key-range form and the unfused lane-group form (a handle whose columns are
+    written, rows of up to 16 lanes) keep the ascending order."""
     lib = _lib.load()
+    order_flags = _grid_order_flags(grid_order, q.dtype, q.shape[-1], csr.T_src)
     if row_pool is not None and not row_pool_supported(q.dtype, q.shape[-1], int(row_pool)):
         raise ValueError(f"sparse_attention(row_pool={row_pool}): a power of two up to {ROW_POOL_MAX} and a multiple of the rows a "
                          f"workgroup walks (64 for rows of 8 lanes, 32 for rows of 16; got {q.dtype}, d = {q.shape[-1]})")
@@ -622,7 +686,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
         probs = probs_out
         if want_probs and probs is None:
             probs = torch.zeros(raw_col.shape, dtype=torch.float32, device=q.device)
-        flags, order = _lib.SEA_ATTN_GATHER, None
+        flags, order = _lib.SEA_ATTN_GATHER | (0 if decode_form or paged else order_flags), None
         if row_pool is not None and not (decode_form or paged or want_probs):
             flags |= (int(row_pool).bit_length() - 1) << _lib.SEA_ATTN_ROW_POOL_SHIFT
             order = row_pool_workspace(N, H, T_dst, int(row_pool), q.device)
@@ -638,7 +702,7 @@ def sparse_attention(q, k, v, csr: FlatCSR, row_scale: Optional[torch.Tensor] = 
     probs = probs_out
     if want_probs and probs is None:
         probs = torch.zeros(csr.col.shape, dtype=torch.float32, device=q.device)
-    flags = _PATHS[path] | ((int(row_tiles) & 0xf) << 8)
+    flags = _PATHS[path] | ((int(row_tiles) & 0xf) << 8) | (0 if decode_form else order_flags)
     if key_window:
         assert key_window & (key_window - 1) == 0, "key_window is a power of two"
         flags |= (int(key_window).bit_length() - 1) << 12
