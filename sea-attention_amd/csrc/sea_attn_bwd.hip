@@ -278,11 +278,15 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_bwd_rows_kernel(BwdGathe
 #pragma unroll
   for (int o = LPR; o < 64; o <<= 1) zmax = max(zmax, __shfl_xor(zmax, o));
   const int grp_lane0 = (lane - sub) << 2;
+  // a row without entries walks along with its wave's longest row: it must not load key 0 of its head, which no query may keep
+  // and which may then hold anything -- ds = 0 does not stop a NaN there (fmaf(0, NaN, dq) is NaN).  Its K / V fragments stay 0
+  const bool loads = dact && end > beg;
   for (int i0 = 0; i0 < zmax; i0 += LPR) {
     // lane `sub` owns entry i0 + sub of the row: its column, its probability, and -- after the walk -- its ds
     const int e_mine = beg + i0 + sub;
     const bool mine = e_mine < end;
-    // lanes past the row's end re-read the row's own last entry with p = 0 (a kept key: finite rows), empty rows key 0
+    // lanes past the row's end re-read the row's own last entry with p = 0 (a kept key: finite rows); a row without entries
+    // names key 0 and loads nothing (`loads`)
     const int c_mine = mine ? col[e_mine] : (end > beg ? col[end - 1] : hcol);   // head * T_src + key
     const float p_mine = mine ? pr[e_mine] : 0.f;
     float ds_mine = 0.f;
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(NWB * 64) void sparse_attn_bwd_rows_kernel(BwdGathe
           pu[u] = __int_as_float(__builtin_amdgcn_ds_bpermute(grp_lane0 + ((u0 + u) << 2), __float_as_int(p_mine)));
           kr[u] = make_uint4(0, 0, 0, 0);
           vr[u] = make_uint4(0, 0, 0, 0);
-          if (dact) {
+          if (loads) {
             kr[u] = *reinterpret_cast<const uint4*>(kb + (int64_t)key * p.ks[2]);
             vr[u] = *reinterpret_cast<const uint4*>(vb + (int64_t)key * p.vs[2]);
           }

@@ -1,7 +1,8 @@
 """-m gpu: backward of the sparse attention against torch autograd through the DENSE masked formulation of
 the same operator (the reference's dense branch, attention.py:1061-1133: softmax(q k^T + mask) v with the mask the CSR
 densifies to).  fp32: gradients to 1e-4 relative; 16-bit inputs: against the fp32 evaluation of the same rounded
-inputs (the kernels accumulate in fp32), bar = one rounding step of the 16-bit gradient they are cast to."""
+inputs (the kernels accumulate in fp32), bar = one rounding step of the 16-bit gradient they are cast to.
+The error itself is bounded per element, against fp64, in tests/test_gpu_backward_reference.py."""
 import pytest
 import torch
 
