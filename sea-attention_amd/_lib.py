@@ -80,6 +80,14 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/sea_hip_train.h: the training-side entries, additive beside the inference ABI above and versioned on their own
+TRAIN_ABI_VERSION = 1      # SEA_TRAIN_ABI_VERSION
+_TRAIN_SIGNATURES = {
+    "sea_train_version": ([], c_int),
+    "sea_kd_estimator_loss": ([ptr, c_int, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
+    "sea_kd_estimator_loss_bwd": ([ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -119,6 +127,13 @@ def load(build_if_missing=True):
     if lib.sea_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.sea_version()}, this binding speaks {ABI_VERSION} (include/sea_hip.h: "
                            "SEA_ABI_VERSION lists what changed) -- rebuild the library from this tree's csrc/")
+    for name, (argtypes, restype) in _TRAIN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_train_version() != TRAIN_ABI_VERSION:
+        raise RuntimeError(f"{path}: training entries of version {lib.sea_train_version()}, this binding speaks "
+                           f"{TRAIN_ABI_VERSION} (include/sea_hip_train.h) -- rebuild the library from this tree's csrc/")
     _lib = lib
     return lib
 

@@ -17,6 +17,13 @@ Two modes, as in the reference:
   with no host synchronisation between them.  There is no fallback: without the library or on a CPU
   tensor this mode raises.
 
+Distillation loss (`output.loss`).  Dense mode adds three terms, as the reference does: the estimator term
+(`_kl_and_mse` of the stretched score map against `attention_scores_truth`), the student-score term (the same of
+q k^T) and the context MSE.  Sparse mode returns `loss = 0` -- unless `fused_kd_loss` is set: then both modes take
+the estimator term from `ops.kd_estimator_loss` (csrc/sea_kd_loss.hip: no T x T tensor, no rank jitter, unpadded
+batches inside `ops.kd_estimator_loss_supported`), and sparse mode's loss is that term plus the context MSE.  The
+student-score term needs q k^T over ALL keys, which sparse mode exists to avoid: it stays out of sparse mode's loss.
+
 Scope of this round: the causal configuration (`pconfig.causal=True`, `k_flatten_dim='causal_batch'`,
 the only one the OPT/LLaMA path constructs -- perlin_opt.py:224-239) without kv-cache.
 """
@@ -186,7 +193,16 @@ class PerlinAttention(nn.Module):
         # an integer = that many heads at a time: same context and same loss (the KD terms are means over heads, summed
         # chunk by chunk), the T x T tensors live for one chunk only and the three T x T OUTPUT fields are None
         self.dense_head_chunk = None
-        self._fused_gates = None            # (row_scale, average_scale) when the fused predictor MLP produced them
+        # training, both modes: True = the estimator's KD term (0.1 KL + MSE of the stretched score map against
+        # `attention_scores_truth`) comes from `ops.kd_estimator_loss` (csrc/sea_kd_loss.hip) instead of `_kl_and_mse` over the
+        # (N,H,T,T) resize, wherever the batch is unpadded and `ops.kd_estimator_loss_supported` holds; elsewhere nothing
+        # changes.  With it, SPARSE mode also returns a loss (the estimator term + the context term; `forward` has the details).
+        # Stated deviation under this opt-in: the fused term never applies the reference's 10 % rank jitter
+        # (resize_m_to_t.py:39-45) and draws no `random.random()` for it.  False = the reference's torch expression in dense
+        # mode and `loss == 0` in sparse mode
+        self.fused_kd_loss = False
+        self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
+        self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
         self._avg_ahead = None              # cumulative average of v when the Performer launch produced it
 
@@ -480,7 +496,7 @@ class PerlinAttention(nn.Module):
         fused_mlp = self._fused_mlp_ok(performer_value)
         if fused_mlp:
             with timer("predictor"):
-                want_scores = get_bench().activate_temp_buffers or (not self.benchmarking)
+                want_scores = get_bench().activate_temp_buffers or (not self.benchmarking) or self._kd_wants_scores
                 with timer("predictor.mlp"):   # enc + dec_row + lnorm1 (+ the two gates) in one launch
                     x, t_attention_predictor, row_scale, avg_scale = ops.predictor_mlp(
                         performer_value, self.attention_predictor_enc[0], self.attention_predictor_enc[1],
@@ -519,7 +535,7 @@ class PerlinAttention(nn.Module):
             # HIP fast path for the bandwidth-bound estimator pieces: device tensors, no autograd, and the
             # standard causal predictor layout (ChannelSplit+LN, ..., upsample x4, 1x1 conv pad 1, LN, softmax)
             use_hip = self._hip_estimator_ok(t_attention_predictor)
-            want_scores = get_bench().activate_temp_buffers or (not self.benchmarking)
+            want_scores = get_bench().activate_temp_buffers or (not self.benchmarking) or self._kd_wants_scores
             if use_hip:
                 cnn = self.attention_predictor_cnn
                 ln1, keepres, ln2 = cnn[0].module, cnn[1].module, cnn[2].module
@@ -596,6 +612,7 @@ class PerlinAttention(nn.Module):
         assert self.pconfig.k_flatten and self.pconfig.k_flatten_dim == 'causal_batch', \
             f"causal SEA selects per row over the pooled heads (k_flatten=True, k_flatten_dim='causal_batch'); got " \
             f"k_flatten={self.pconfig.k_flatten}, k_flatten_dim={self.pconfig.k_flatten_dim!r}"
+        self._kd_wants_scores = False
         if self.pconfig.use_cache or last_state is not None:
             assert self.pconfig.attention_predictor_method != 'comp', "the compressed predictor has no cached form (attention.py:650)"
             return self._forward_cached(q, k, v, q_for_atten, k_for_atten, v_for_atten, q_for_score, k_for_score,
@@ -634,6 +651,8 @@ class PerlinAttention(nn.Module):
         bench.register_temp_buffer('v', v)
         bench.register_temp_buffer('attention_mask', attention_mask)
 
+        self._kd_wants_scores = bool(self.fused_kd_loss and attention_scores_truth is not None and not_padded)
+
         with timer("perlin"):
             N, H, T, HID = q.shape
             v, t_attention_predictor, estimated_attention_score, estimated_attention_probs = self._estimate(
@@ -650,7 +669,17 @@ class PerlinAttention(nn.Module):
             loss = 0
             estimated_attention_probs_resized = None
             head_chunk = None if self.benchmarking else self.dense_head_chunk
-            if not self.benchmarking and attention_scores_truth is not None:
+            # `fused_kd_loss`: the estimator's KD term on the HIP kernels, no (N,H,T,T) resize and no rank jitter for it.  In
+            # sparse mode this term and the context term are the whole loss: the student-score term (`_kl_and_mse` of q k^T
+            # over ALL keys against the truth, `_forward_dense`) needs the dense scores sparse mode exists to avoid and stays out
+            fused_kd = (self._kd_wants_scores and estimated_attention_score is not None
+                        and ops.kd_estimator_loss_supported(estimated_attention_score, attention_scores_truth))
+            if fused_kd:
+                loss = loss + ops.kd_estimator_loss(estimated_attention_score, attention_scores_truth)
+                if not self.benchmarking and not head_chunk:          # the unchunked dense form returns the stretched estimate
+                    estimated_attention_probs_resized = resize_dense(estimated_attention_probs, 0, False)
+                    bench.register_temp_buffer('estimated_attention_probs_resized', estimated_attention_probs_resized)
+            elif not self.benchmarking and attention_scores_truth is not None:
                 if head_chunk:
                     # KD loss of the estimator (:741-763) a few heads at a time: both terms are means over (n, h, t[, s]),
                     # so the chunks' values weighted by their share of the heads add up to the unchunked loss
@@ -690,7 +719,7 @@ class PerlinAttention(nn.Module):
             if self.pconfig.context_output_method != 'mix':
                 raise Exception("only context_output_method='mix' is live in the reference (:1286-1314)")
 
-            if not self.benchmarking and context_layer_truth is not None:
+            if (not self.benchmarking or fused_kd) and context_layer_truth is not None:
                 loss = loss + F.mse_loss(context_layer_truth, partial_context_layer)
 
             # (head-chunked dense mode never forms the resized T x T estimate: it hands out the T_M-wide map, like sparse mode)

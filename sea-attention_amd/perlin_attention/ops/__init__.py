@@ -18,3 +18,5 @@ from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value
                         predictor_tail_select_supported, clear_prep_cache, prep_generation, pinned_prep, LazyTensor, realize,
                         decode_stage, c8_window_shift, decode_fork, decode_fork_staging_bytes, decode_cnn_tail_select, decode_cnn_supported, decode_cnn_emits, decode_tail_select_supported, DECODE_PREDICTOR_LENGTHS,
                         decode_gather_rows, decode_append_rows)
+# training-side entry points (include/sea_hip_train.h)
+from .kd_loss import kd_estimator_loss, kd_estimator_loss_supported, kd_estimator_loss_parts
