@@ -16,7 +16,9 @@ extern "C" {
 #endif
 
 /* Version of the entries in this header, returned by sea_train_version().
- *   1  sea_kd_estimator_loss, sea_kd_estimator_loss_bwd */
+ *   1  sea_kd_estimator_loss, sea_kd_estimator_loss_bwd
+ *      sea_kd_score_loss, sea_kd_score_loss_bwd: added later WITHOUT a bump -- they are additive, the suite pins this number
+ *      at 1, and a binding that needs them finds out by looking the symbols up (a library without them fails to load there) */
 #define SEA_TRAIN_ABI_VERSION 1
 
 int sea_train_version(void);
@@ -57,6 +59,48 @@ int sea_kd_estimator_loss_bwd(const void* est, int est_dtype, const int64_t* est
                               const float* pix_tgt, const float* row_stats, const float* grad_loss,
                               int64_t N, int64_t H, int64_t T, int64_t T_m,
                               void* d_est, sea_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * t3  distillation loss of the student's own scores, causal and unpadded, T_dst == T_src == T (row t sees keys 0 .. t).
+ * Replaces, for the student-score term: PerlinAttention's  _kl_and_mse(q_for_score @ k_for_score^T, truth)  -- the (N,H,T,T)
+ * score tensor, two masked fills, log_softmax, two softmaxes, kl_div and mse_loss.
+ *
+ * Per (n,h) and row t, over the keys s <= t, with S_ts = q_t . k_s accumulated in fp32 from the 16-bit inputs (the torch form
+ * rounds q k^T to the data type first: the kernels keep the fp32 accumulator) and x_ts the teacher's score as fp32:
+ *   p_s = softmax over s <= t of S_ts,   tgt_s = softmax over s <= t of x_ts
+ *   row_kl[n,h,t]  = sum_s tgt_s (log tgt_s - log p_s)            (a key with tgt_s == 0 adds 0)
+ *   row_mse[n,h,t] = sum_s (p_s - tgt_s)^2                         (key by key, never the expanded form)
+ *   row_q[n,h,t]   = sum_s p_s (p_s - tgt_s)
+ *   row_stats[n,h,t] = { max_s S_ts, log sum_s exp(S_ts - max), max_s x_ts, log sum_s exp(x_ts - max) }
+ * The loss is  0.1 * sum(row_kl) / R + sum(row_mse) / (R * T),  R = N*H*T; the caller reduces the row values.
+ *
+ * q, k (N,H,T,D): fp16 or bf16, both of `qk_dtype`.  truth (N,H,T,T): fp32 / fp16 / bf16 independently.  Each with strides[3] =
+ * {n, h, t} in elements, innermost stride 1, rows 16-byte aligned (base pointer and every stride; SEA_EINVAL otherwise).
+ * Only keys s <= t of truth are read, apart from the rest of a 16-byte chunk that holds such a key where that chunk lies inside
+ * the row's T elements; nothing read past t reaches a result.  Columns of q / k past D are never read (D = 80: the last k-step
+ * of the matrix instruction is padded with zero fragments).  The four outputs are fp32 and contiguous, row_stats 16-byte
+ * aligned.  No atomics, one summation order: the same inputs give the same bits.
+ * Limits: D in {64, 80, 128}, 1 <= T <= 16384, 16-bit q / k (SEA_EUNSUPPORTED otherwise -- fp32 q / k and unknown dtype codes
+ * included -- before any launch).
+ */
+int sea_kd_score_loss(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                      const void* truth, int truth_dtype, const int64_t* truth_strides,
+                      int64_t N, int64_t H, int64_t T, int64_t D,
+                      float* row_kl, float* row_mse, float* row_q, float* row_stats,
+                      sea_stream_t stream);
+
+/* t4  its gradient with respect to q and k: two launches (a pass over the query blocks for d_q, one over the key blocks for
+ * d_k), both computing S again and reading the causal half of truth again, as t3 reads it.  With p_s and tgt_s from row_stats:
+ *   dS_ts = g * ( 0.1 / R * (p_s - tgt_s) + 2 / (R * T) * (p_s (p_s - tgt_s) - p_s row_q[t]) ),   0 for s > t
+ *   d_q[n,h,t,:] = sum over s <= t of dS_ts k_s,      d_k[n,h,s,:] = sum over t >= s of dS_ts q_t
+ * g = *grad_loss, the upstream gradient of the scalar loss: a DEVICE fp32 (no host synchronisation).  dS enters the matrix
+ * instructions as a 16-bit hi + lo pair, the sums are fp32.  d_q and d_k are contiguous (N,H,T,D) in q's dtype, 8-byte aligned,
+ * every element written.  Same limits and refusals as t3. */
+int sea_kd_score_loss_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                          const void* truth, int truth_dtype, const int64_t* truth_strides,
+                          const float* row_q, const float* row_stats, const float* grad_loss,
+                          int64_t N, int64_t H, int64_t T, int64_t D,
+                          void* d_q, void* d_k, sea_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
 LIB_PATH = os.path.join(PKG_DIR, "libsea_hip.so")
 SOURCES = ["sea_topk.hip", "sea_attn.hip", "sea_attn_tile.hip", "sea_attn_keyrange.hip", "sea_attn_bwd.hip", "sea_csr_ops.hip",
-           "sea_predictor.hip", "sea_performer.hip", "sea_conv.hip", "sea_mlp.hip", "sea_decode.hip", "sea_kd_loss.hip"]
+           "sea_predictor.hip", "sea_performer.hip", "sea_conv.hip", "sea_mlp.hip", "sea_decode.hip", "sea_kd_loss.hip",
+           "sea_kd_score_loss.hip"]
 HEADERS = [os.path.join(CSRC, "sea_common.hpp"), os.path.join(CSRC, "sea_attn.hpp"), os.path.join(CSRC, "sea_tail.hpp"),
            os.path.join(CSRC, "sea_convfrag.hpp"), os.path.join(CSRC, "sea_performer16.hpp"),
            os.path.join(CSRC, "sea_tail_select_row.inc"),

@@ -86,6 +86,10 @@ _TRAIN_SIGNATURES = {
     "sea_train_version": ([], c_int),
     "sea_kd_estimator_loss": ([ptr, c_int, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_kd_estimator_loss_bwd": ([ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr], c_int),
+    # (added without a bump of the version above: include/sea_hip_train.h says why)
+    "sea_kd_score_loss": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
+    "sea_kd_score_loss_bwd": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr, ptr],
+                              c_int),
 }
 
 

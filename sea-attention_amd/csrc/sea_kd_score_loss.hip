@@ -1,0 +1,480 @@
+// Distillation loss of the student's own scores (include/sea_hip_train.h, t3 / t4): 0.1 KL + MSE between the softmax of q k^T
+// over the causal keys of each row and the softmax of the teacher's scores, without a T x T tensor.  gfx950 only.
+//
+// Replaces, for the student-score term of PerlinAttention (`_forward_dense`, `_dense_attention_by_head_chunks`):
+//   torch.matmul(q_for_score, k_for_score^T)     the (N,H,T,T) scores, rounded to 16 bits
+//   attention.py  _kl_and_mse                    two masked fills, log_softmax, two softmaxes, kl_div, mse_loss (fp32 copies)
+//
+// One tile body serves the three kernels.  A wave OWNS 16 indices (queries in the forward and in the backward's row pass, keys
+// in its column pass) and SWEEPS the other side in tiles of 64 staged in LDS for the four waves of the workgroup.  The score
+// tile is  (swept x own) = swept_tile . own^T  on v_mfma_f32_16x16x32: the accumulator has the own index on the lane (lane & 15)
+// and the swept index in the registers.  Which swept index a row of the A operand stands for is free, so row i of sub-tile c is
+// swept index 16 (i >> 2) + 4 c + (i & 3): lane l then holds the SIXTEEN CONSECUTIVE swept indices 16 (l >> 4) .. + 15 of its own
+// index.  In the forward and the row pass those are consecutive keys of one query: the teacher's scores come straight from
+// global memory in 16-byte chunks, already in the accumulator's lane map, and never pass through LDS.  The same sixteen values
+// are, eight at a time, the B operand of the gradient's MFMA (k = 8 (l >> 4) + j stands for swept index 16 (l >> 4) + 8 u + j in
+// k-step u; the A operand is read from a transposed LDS image with the same numbering), so dS never leaves registers either.
+#include "sea_common.hpp"
+#include "../../include/sea_hip_train.h"
+
+namespace sea {
+
+constexpr int KS_MAX_T = 16384;
+constexpr int KS_TILE = 64;                        // swept indices per tile; also own indices per workgroup (4 waves x 16)
+constexpr int KS_THREADS = 256;
+
+typedef __attribute__((ext_vector_type(8))) __bf16 ks_bf8;
+typedef __attribute__((ext_vector_type(8))) _Float16 ks_h8;
+typedef __attribute__((ext_vector_type(4))) float ks_f4;
+
+template <typename T> struct KsX;
+template <> struct KsX<__hip_bfloat16> {
+  static constexpr float DS_SCALE = 1.0f;
+  __device__ static inline ks_f4 mfma(const uint4& a, const uint4& b, ks_f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ks_bf8, a), __builtin_bit_cast(ks_bf8, b), c, 0, 0, 0);
+  }
+};
+template <> struct KsX<__half> {
+  // dS is at most 0.1 + 4 / T in magnitude and falls with the row length; times 2^12 its hi + lo halves stay clear of fp16's
+  // subnormals (a power of two: taken out again exactly with the upstream gradient)
+  static constexpr float DS_SCALE = 4096.0f;
+  __device__ static inline ks_f4 mfma(const uint4& a, const uint4& b, ks_f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ks_h8, a), __builtin_bit_cast(ks_h8, b), c, 0, 0, 0);
+  }
+};
+
+template <int D> struct KsGeo {
+  static constexpr int KK = (D + 31) / 32;         // k-steps of the score MFMA; at D = 80 half of the third is zero fragments
+  static constexpr int DT = D / 16;                // 16-wide column tiles of dQ / dK
+  static constexpr int CH = D / 8;                 // 16-byte chunks per row
+  static constexpr int RST = D + 8;                // row image: elements per row (16 bytes of padding)
+  static constexpr int TST = KS_TILE + 8;          // transposed image: elements per column of the tile
+};
+
+__device__ inline float ks_xor16_max(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ inline float ks_xor32_max(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+// over the four lanes l & 15 + {0, 16, 32, 48} that share an own index; every one of them ends with the same bits
+__device__ inline float ks_own_max(float v) { return ks_xor32_max(ks_xor16_max(v)); }
+__device__ inline float ks_own_sum(float v) { return xor32_sum(xor16_sum(v)); }
+
+struct KsParams {
+  const void* q;
+  const void* k;
+  const void* truth;
+  int64_t qsn, qsh, qst, ksn, ksh, kst, xsn, xsh, xst;
+  int N, H, T;
+  float* row_kl;
+  float* row_mse;
+  float* row_q;
+  float* row_stats;
+  const float* grad_loss;
+  void* d_q;
+  void* d_k;
+};
+
+// Rows i0 .. i0 + 63 of `src` (stride `st` elements) into LDS: the row image and, for the gradient's A operand, the transposed
+// one.  Rows at or past T are zero and are not loaded.  Consecutive lanes take consecutive rows.
+template <typename T, int D, bool TR>
+__device__ inline void ks_stage(const T* src, int64_t st, int i0, int Tn, unsigned short* s_row, unsigned short* s_tr) {
+  using G = KsGeo<D>;
+#pragma unroll
+  for (int ch = threadIdx.x; ch < KS_TILE * G::CH; ch += KS_THREADS) {
+    const int row = ch & (KS_TILE - 1), cc = ch >> 6;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i0 + row < Tn) v = *reinterpret_cast<const uint4*>(src + (int64_t)(i0 + row) * st + cc * 8);
+    *reinterpret_cast<uint4*>(s_row + row * G::RST + cc * 8) = v;
+    if constexpr (TR) {
+      const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s_tr[(cc * 8 + j) * G::TST + row] = (unsigned short)(d[j >> 1] >> (16 * (j & 1)));
+    }
+  }
+}
+
+// the lane's own fragments (B operand of the score MFMA): row `idx` of `src`, columns 32 kk + 8 (l >> 4) .. + 7; zero past D
+// (the padded k-step at 80) and for an index at or past T -- neither is read
+template <typename T, int D>
+__device__ inline void ks_own_frags(const T* src, int64_t st, int idx, int Tn, int lane, uint4 (&own)[KsGeo<D>::KK]) {
+#pragma unroll
+  for (int kk = 0; kk < KsGeo<D>::KK; ++kk) {
+    const int col = kk * 32 + 8 * (lane >> 4);
+    own[kk] = make_uint4(0u, 0u, 0u, 0u);
+    if (idx < Tn && col < D) own[kk] = *reinterpret_cast<const uint4*>(src + (int64_t)idx * st + col);
+  }
+}
+
+// score tile: s[e], e = 0 .. 15, is  swept(16 (l >> 4) + e) . own(l & 15)
+template <typename T, int D>
+__device__ inline void ks_scores(const unsigned short* s_row, const uint4 (&own)[KsGeo<D>::KK], int lane, float (&s)[16]) {
+  using G = KsGeo<D>;
+  const int li = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int row = 16 * (li >> 2) + 4 * c + (li & 3);
+    ks_f4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < G::KK; ++kk) {
+      const int col = kk * 32 + 8 * g;
+      uint4 f = make_uint4(0u, 0u, 0u, 0u);
+      if (D % 32 == 0 || col < D) f = *reinterpret_cast<const uint4*>(s_row + row * G::RST + col);
+      a = KsX<T>::mfma(f, own[kk], a);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[4 * c + r] = a[r];
+  }
+}
+
+// The teacher's scores of query t (row pointer `xrow`), keys s0 .. s0 + 15, as fp32.  Only chunks with a key <= t are touched;
+// a chunk is loaded whole only where it lies inside the row's T elements (what it holds past t is dropped by the caller's
+// mask), the rest goes element by element up to t.  t < 0: nothing is read.
+template <typename TX>
+__device__ inline void ks_truth_keys(const TX* xrow, int t, int Tn, int s0, float (&x)[16]) {
+  constexpr int VEC = Elem<TX>::VEC;
+#pragma unroll
+  for (int c = 0; c < 16 / VEC; ++c) {
+    const int s = s0 + c * VEC;
+    float f[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) f[j] = 0.f;
+    if (s <= t) {
+      if (s + VEC <= Tn) {
+        const uint4 raw = *reinterpret_cast<const uint4*>(xrow + s);
+        unpack16<TX>(raw, f);
+      } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          if (s + j <= t) f[j] = Elem<TX>::to_f(xrow[s + j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) x[c * VEC + j] = f[j];
+  }
+}
+
+// block -> (index of the 64-block of own indices, (n, h)).  All (n, h) of one block index are neighbours in the grid, and the
+// grid starts with the longest sweeps (the causal triangle: block b of the queries sweeps b + 1 key tiles, block b of the keys
+// sweeps NB - b query tiles), so the launch ends on the short ones.
+template <bool COL> __device__ inline void ks_block(const KsParams& p, int& ob, int& n, int& h) {
+  const int NH = p.N * p.H, NB = (p.T + KS_TILE - 1) / KS_TILE;
+  const int i = blockIdx.x / NH, nh = blockIdx.x - i * NH;
+  ob = COL ? i : NB - 1 - i;
+  n = nh / p.H;
+  h = nh - n * p.H;
+}
+
+// ---- forward -----------------------------------------------------------------------------------------------------------------
+template <typename T, typename TX, int D>
+__global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
+  using G = KsGeo<D>;
+  __shared__ __align__(16) unsigned short s_row[KS_TILE * G::RST];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  int rb, n, h;
+  ks_block<false>(p, rb, n, h);
+  const T* q = reinterpret_cast<const T*>(p.q) + n * p.qsn + h * p.qsh;
+  const T* k = reinterpret_cast<const T*>(p.k) + n * p.ksn + h * p.ksh;
+  const int t = rb * KS_TILE + 16 * w + li;
+  const bool own_ok = t < p.T;
+  const int tv = own_ok ? t : -1;                  // no key is <= -1: a query past T reads and adds nothing
+  const TX* xrow = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh + (int64_t)(own_ok ? t : 0) * p.xst;
+  uint4 own[G::KK];
+  ks_own_frags<T, D>(q, p.qst, t, p.T, lane, own);
+
+  // sweep 1: running maximum and sum of both softmaxes, per lane over its keys
+  float ms = -INFINITY, ls = 0.f, mx = -INFINITY, lx = 0.f;
+  for (int tile = 0; tile <= rb; ++tile) {
+    const int s0 = tile * KS_TILE + 16 * g;
+    __syncthreads();
+    ks_stage<T, D, false>(k, p.kst, tile * KS_TILE, p.T, s_row, nullptr);
+    float xv[16], sv[16];
+    ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
+    __syncthreads();
+    ks_scores<T, D>(s_row, own, lane, sv);
+    float ts = -INFINITY, tx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const bool ok = s0 + e <= tv;
+      sv[e] = ok ? sv[e] : -INFINITY;
+      xv[e] = ok ? xv[e] : -INFINITY;
+      ts = fmaxf(ts, sv[e]);
+      tx = fmaxf(tx, xv[e]);
+    }
+    const float ns = fmaxf(ms, ts), nx = fmaxf(mx, tx);
+    if (ns > -INFINITY) {                          // (the lane has met a key <= t: both maxima are finite from here on)
+      float a = 0.f, b = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        a += expf(sv[e] - ns);
+        b += expf(xv[e] - nx);
+      }
+      ls = ls * expf(ms - ns) + a;
+      lx = lx * expf(mx - nx) + b;
+      ms = ns;
+      mx = nx;
+    }
+  }
+  const float M = ks_own_max(ms), MX = ks_own_max(mx);
+  const float L = ks_own_sum(ms > -INFINITY ? ls * expf(ms - M) : 0.f);
+  const float LX = ks_own_sum(mx > -INFINITY ? lx * expf(mx - MX) : 0.f);
+  const float inv_l = 1.0f / L, log_l = logf(L), inv_lx = 1.0f / LX, log_lx = logf(LX);
+
+  // sweep 2: the scores again, both probabilities, the three row sums key by key
+  float kl = 0.f, mse = 0.f, rq = 0.f;
+  for (int tile = 0; tile <= rb; ++tile) {
+    const int s0 = tile * KS_TILE + 16 * g;
+    __syncthreads();
+    ks_stage<T, D, false>(k, p.kst, tile * KS_TILE, p.T, s_row, nullptr);
+    float xv[16], sv[16];
+    ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
+    __syncthreads();
+    ks_scores<T, D>(s_row, own, lane, sv);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      if (s0 + e <= tv) {
+        const float ds = sv[e] - M, dx = xv[e] - MX;
+        const float pe = expf(ds) * inv_l, tg = expf(dx) * inv_lx;
+        kl += tg > 0.f ? tg * ((dx - log_lx) - (ds - log_l)) : 0.f;
+        const float df = pe - tg;
+        mse += df * df;
+        rq += pe * df;
+      }
+    }
+  }
+  kl = ks_own_sum(kl);
+  mse = ks_own_sum(mse);
+  rq = ks_own_sum(rq);
+  if (own_ok && g == 0) {
+    const int64_t r = ((int64_t)n * p.H + h) * p.T + t;
+    p.row_kl[r] = kl;
+    p.row_mse[r] = mse;
+    p.row_q[r] = rq;
+    *reinterpret_cast<float4*>(p.row_stats + 4 * r) = make_float4(M, log_l, MX, log_lx);
+  }
+}
+
+// ---- backward ----------------------------------------------------------------------------------------------------------------
+// COL = false, the row pass: own = queries, sweeps the key tiles 0 .. rb, dQ^T += K^T . dS^T.
+// COL = true, the column pass: own = keys, sweeps the query tiles kb .. NB - 1, dK^T += Q^T . dS.
+// Both: the score tile again, p and tgt from row_stats, dS (without g / R, times DS_SCALE) as hi + lo 16-bit halves.
+template <typename T, typename TX, int D, bool COL>
+__global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
+  using G = KsGeo<D>;
+  using X = KsX<T>;
+  __shared__ __align__(16) unsigned short s_row[KS_TILE * G::RST];
+  __shared__ __align__(16) unsigned short s_tr[D * G::TST];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  int ob, n, h;
+  ks_block<COL>(p, ob, n, h);
+  const int NB = (p.T + KS_TILE - 1) / KS_TILE;
+  const T* q = reinterpret_cast<const T*>(p.q) + n * p.qsn + h * p.qsh;
+  const T* k = reinterpret_cast<const T*>(p.k) + n * p.ksn + h * p.ksh;
+  const TX* x = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh;
+  const int64_t r0 = ((int64_t)n * p.H + h) * p.T;
+  const int o = ob * KS_TILE + 16 * w + li;        // the lane's own index
+  const bool own_ok = o < p.T;
+  uint4 own[G::KK];
+  ks_own_frags<T, D>(COL ? k : q, COL ? p.kst : p.qst, o, p.T, lane, own);
+  const float k_kl = 0.1f * X::DS_SCALE, k_mse = 2.0f / (float)p.T * X::DS_SCALE;
+
+  float4 st_own = make_float4(0.f, 0.f, 0.f, 0.f);
+  float rq_own = 0.f;
+  if (!COL && own_ok) {
+    st_own = *reinterpret_cast<const float4*>(p.row_stats + 4 * (r0 + o));
+    rq_own = p.row_q[r0 + o];
+  }
+  const TX* xrow = x + (int64_t)(own_ok ? o : 0) * p.xst;     // row pass only
+
+  ks_f4 out[G::DT];
+#pragma unroll
+  for (int dt = 0; dt < G::DT; ++dt) out[dt] = ks_f4{0.f, 0.f, 0.f, 0.f};
+
+  const int tile_lo = COL ? ob : 0, tile_hi = COL ? NB - 1 : ob;
+  for (int tile = tile_lo; tile <= tile_hi; ++tile) {
+    const int i0 = tile * KS_TILE + 16 * g;        // the lane's first swept index
+    __syncthreads();
+    ks_stage<T, D, true>(COL ? q : k, COL ? p.qst : p.kst, tile * KS_TILE, p.T, s_row, s_tr);
+    float xv[16], sv[16], u[16];
+    bool ok[16];
+    if constexpr (!COL) {
+      ks_truth_keys<TX>(xrow, own_ok ? o : -1, p.T, i0, xv);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) ok[e] = own_ok && i0 + e <= o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int t = i0 + e;
+        ok[e] = t < p.T && o <= t;                 // (o <= t < T: the key is inside too)
+        xv[e] = ok[e] ? Elem<TX>::to_f(x[(int64_t)t * p.xst + o]) : 0.f;
+      }
+    }
+    __syncthreads();
+    ks_scores<T, D>(s_row, own, lane, sv);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      float4 st = st_own;
+      float rq = rq_own;
+      if constexpr (COL) {
+        if (ok[e]) {
+          st = *reinterpret_cast<const float4*>(p.row_stats + 4 * (r0 + i0 + e));
+          rq = p.row_q[r0 + i0 + e];
+        }
+      }
+      float v = 0.f;
+      if (ok[e]) {
+        const float pe = expf((sv[e] - st.x) - st.y), tg = expf((xv[e] - st.z) - st.w);
+        const float df = pe - tg;
+        v = k_kl * df + k_mse * (pe * df - pe * rq);
+      }
+      u[e] = v;
+    }
+    // dS as the B operand: element j of k-step uu is swept index 16 g + 8 uu + j, the numbering of the transposed image
+    uint4 bh[2], bl[2];
+#pragma unroll
+    for (int uu = 0; uu < 2; ++uu) {
+      uint32_t hi[4], lo[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float a = u[8 * uu + 2 * j], b = u[8 * uu + 2 * j + 1];
+        const T ah = from_f<T>(a), bhh = from_f<T>(b);
+        hi[j] = (uint32_t)__builtin_bit_cast(unsigned short, ah) | ((uint32_t)__builtin_bit_cast(unsigned short, bhh) << 16);
+        lo[j] = pack2<T>(a - Elem<T>::to_f(ah), b - Elem<T>::to_f(bhh));
+      }
+      bh[uu] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+      bl[uu] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    }
+#pragma unroll
+    for (int dt = 0; dt < G::DT; ++dt) {
+#pragma unroll
+      for (int uu = 0; uu < 2; ++uu) {
+        const uint4 a = *reinterpret_cast<const uint4*>(s_tr + (16 * dt + li) * G::TST + 16 * g + 8 * uu);
+        out[dt] = X::mfma(a, bh[uu], out[dt]);
+        out[dt] = X::mfma(a, bl[uu], out[dt]);
+      }
+    }
+  }
+  // out[dt][r] = d(own = l & 15, column 16 dt + 4 (l >> 4) + r): four 16-bit values, one 8-byte store
+  if (own_ok) {
+    const int64_t R = (int64_t)p.N * p.H * p.T;
+    const float scale = *p.grad_loss * (float)(1.0 / ((double)R * (double)X::DS_SCALE));
+    T* dst = reinterpret_cast<T*>(COL ? p.d_k : p.d_q) + (r0 + o) * D + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < G::DT; ++dt) {
+      const uint2 pk = make_uint2(pack2<T>(out[dt][0] * scale, out[dt][1] * scale), pack2<T>(out[dt][2] * scale, out[dt][3] * scale));
+      *reinterpret_cast<uint2*>(dst + 16 * dt) = pk;
+    }
+  }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+static int ks_check(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                    const void* truth, int truth_dtype, const int64_t* truth_strides, int64_t N, int64_t H, int64_t T, int64_t D) {
+  SEA_REQUIRE(q, SEA_EINVAL, "%s: q is null", nm);
+  SEA_REQUIRE(k, SEA_EINVAL, "%s: k is null", nm);
+  SEA_REQUIRE(q_strides, SEA_EINVAL, "%s: q_strides is null", nm);
+  SEA_REQUIRE(k_strides, SEA_EINVAL, "%s: k_strides is null", nm);
+  SEA_REQUIRE(truth, SEA_EINVAL, "%s: truth is null", nm);
+  SEA_REQUIRE(truth_strides, SEA_EINVAL, "%s: truth_strides is null", nm);
+  SEA_REQUIRE(qk_dtype != SEA_F32, SEA_EUNSUPPORTED, "%s: fp32 q / k (qk_dtype) is outside the kernels: 16-bit data only", nm);
+  SEA_REQUIRE(qk_dtype == SEA_F16 || qk_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown qk_dtype %d", nm, qk_dtype);
+  SEA_REQUIRE(truth_dtype == SEA_F32 || truth_dtype == SEA_F16 || truth_dtype == SEA_BF16, SEA_EUNSUPPORTED,
+              "%s: unknown truth_dtype %d", nm, truth_dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0, SEA_EINVAL, "%s: bad shape N=%lld H=%lld T=%lld D=%lld", nm, (long long)N,
+              (long long)H, (long long)T, (long long)D);
+  SEA_REQUIRE(D == 64 || D == 80 || D == 128, SEA_EUNSUPPORTED, "%s: D=%lld (needs D in {64, 80, 128})", nm, (long long)D);
+  SEA_REQUIRE(T <= KS_MAX_T, SEA_EUNSUPPORTED, "%s: T=%lld (needs T <= %d)", nm, (long long)T, KS_MAX_T);
+  SEA_REQUIRE(N * H * ((T + KS_TILE - 1) / KS_TILE) < (1ll << 31), SEA_EUNSUPPORTED, "%s: grid too large", nm);
+  const struct { const char* name; const void* ptr; const int64_t* s; int64_t row; int vec; } a[3] = {
+      {"q", q, q_strides, D, 8}, {"k", k, k_strides, D, 8}, {"truth", truth, truth_strides, T, truth_dtype == SEA_F32 ? 4 : 8}};
+  for (const auto& t : a) {
+    SEA_REQUIRE(t.s[0] >= 0 && t.s[1] >= 0 && t.s[2] >= t.row, SEA_EINVAL, "%s: bad %s strides {%lld, %lld, %lld} for rows of %lld",
+                nm, t.name, (long long)t.s[0], (long long)t.s[1], (long long)t.s[2], (long long)t.row);
+    SEA_REQUIRE(((uintptr_t)t.ptr & 15) == 0 && t.s[0] % t.vec == 0 && t.s[1] % t.vec == 0 && t.s[2] % t.vec == 0, SEA_EINVAL,
+                "%s: %s rows must be 16-byte aligned (base pointer and every stride)", nm, t.name);
+  }
+  return SEA_OK;
+}
+
+static KsParams ks_params(const void* q, const void* k, const int64_t* qs, const int64_t* ks, const void* truth, const int64_t* xs,
+                          int64_t N, int64_t H, int64_t T) {
+  KsParams p = {};
+  p.q = q; p.k = k; p.truth = truth;
+  p.qsn = qs[0]; p.qsh = qs[1]; p.qst = qs[2];
+  p.ksn = ks[0]; p.ksh = ks[1]; p.kst = ks[2];
+  p.xsn = xs[0]; p.xsh = xs[1]; p.xst = xs[2];
+  p.N = (int)N; p.H = (int)H; p.T = (int)T;
+  return p;
+}
+
+static inline unsigned ks_grid(const KsParams& p) { return (unsigned)((int64_t)p.N * p.H * ((p.T + KS_TILE - 1) / KS_TILE)); }
+
+template <typename T, typename TX, int D> static int ks_launch(const char* nm, bool bwd, const KsParams& p, hipStream_t s) {
+  if (!bwd) {
+    hipLaunchKernelGGL((ks_fwd_kernel<T, TX, D>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    SEA_CHECK_LAUNCH(nm);
+  } else {
+    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, false>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    SEA_CHECK_LAUNCH(nm);
+    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, true>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    SEA_CHECK_LAUNCH(nm);
+  }
+  return SEA_OK;
+}
+template <typename T, typename TX> static int ks_launch_d(const char* nm, bool bwd, int64_t D, const KsParams& p, hipStream_t s) {
+  if (D == 64) return ks_launch<T, TX, 64>(nm, bwd, p, s);
+  if (D == 80) return ks_launch<T, TX, 80>(nm, bwd, p, s);
+  return ks_launch<T, TX, 128>(nm, bwd, p, s);
+}
+template <typename T> static int ks_launch_x(const char* nm, bool bwd, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
+  if (truth_dtype == SEA_F32) return ks_launch_d<T, float>(nm, bwd, D, p, s);
+  if (truth_dtype == SEA_F16) return ks_launch_d<T, __half>(nm, bwd, D, p, s);
+  return ks_launch_d<T, __hip_bfloat16>(nm, bwd, D, p, s);
+}
+static int ks_dispatch(const char* nm, bool bwd, int qk_dtype, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
+  if (qk_dtype == SEA_F16) return ks_launch_x<__half>(nm, bwd, truth_dtype, D, p, s);
+  return ks_launch_x<__hip_bfloat16>(nm, bwd, truth_dtype, D, p, s);
+}
+
+}  // namespace sea
+
+using namespace sea;
+
+extern "C" int sea_kd_score_loss(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                                 const void* truth, int truth_dtype, const int64_t* truth_strides, int64_t N, int64_t H, int64_t T,
+                                 int64_t D, float* row_kl, float* row_mse, float* row_q, float* row_stats, sea_stream_t stream) {
+  const char* nm = "sea_kd_score_loss";
+  const int rc = ks_check(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, N, H, T, D);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
+  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
+  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
+  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
+  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0, SEA_EINVAL, "%s: row_stats must be 16-byte aligned", nm);
+  KsParams p = ks_params(q, k, q_strides, k_strides, truth, truth_strides, N, H, T);
+  p.row_kl = row_kl; p.row_mse = row_mse; p.row_q = row_q; p.row_stats = row_stats;
+  return ks_dispatch(nm, false, qk_dtype, truth_dtype, D, p, (hipStream_t)stream);
+}
+
+extern "C" int sea_kd_score_loss_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                                     const void* truth, int truth_dtype, const int64_t* truth_strides, const float* row_q,
+                                     const float* row_stats, const float* grad_loss, int64_t N, int64_t H, int64_t T, int64_t D,
+                                     void* d_q, void* d_k, sea_stream_t stream) {
+  const char* nm = "sea_kd_score_loss_bwd";
+  const int rc = ks_check(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, N, H, T, D);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
+  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
+  SEA_REQUIRE(grad_loss, SEA_EINVAL, "%s: grad_loss is null", nm);
+  SEA_REQUIRE(d_q, SEA_EINVAL, "%s: d_q is null", nm);
+  SEA_REQUIRE(d_k, SEA_EINVAL, "%s: d_k is null", nm);
+  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0 && ((uintptr_t)d_q & 7) == 0 && ((uintptr_t)d_k & 7) == 0, SEA_EINVAL,
+              "%s: row_stats must be 16-byte aligned, d_q and d_k 8-byte aligned", nm);
+  KsParams p = ks_params(q, k, q_strides, k_strides, truth, truth_strides, N, H, T);
+  p.row_q = const_cast<float*>(row_q); p.row_stats = const_cast<float*>(row_stats);
+  p.grad_loss = grad_loss; p.d_q = d_q; p.d_k = d_k;
+  return ks_dispatch(nm, true, qk_dtype, truth_dtype, D, p, (hipStream_t)stream);
+}

@@ -22,7 +22,11 @@ Distillation loss (`output.loss`).  Dense mode adds three terms, as the referenc
 q k^T) and the context MSE.  Sparse mode returns `loss = 0` -- unless `fused_kd_loss` is set: then both modes take
 the estimator term from `ops.kd_estimator_loss` (csrc/sea_kd_loss.hip: no T x T tensor, no rank jitter, unpadded
 batches inside `ops.kd_estimator_loss_supported`), and sparse mode's loss is that term plus the context MSE.  The
-student-score term needs q k^T over ALL keys, which sparse mode exists to avoid: it stays out of sparse mode's loss.
+student-score term needs q k^T over ALL keys, which sparse mode exists to avoid: it stays out of sparse mode's loss --
+unless `fused_kd_score_loss` is set: then both modes take it from `ops.kd_score_loss` (csrc/sea_kd_score_loss.hip: q k^T
+recomputed tile by tile against the truth, no T x T tensor, scores kept in fp32; unpadded 16-bit batches inside
+`ops.kd_score_loss_supported`), and sparse mode adds it and the context MSE.  With both switches on, sparse mode's loss
+has every term of dense mode's.
 
 Scope of this round: the causal configuration (`pconfig.causal=True`, `k_flatten_dim='causal_batch'`,
 the only one the OPT/LLaMA path constructs -- perlin_opt.py:224-239) without kv-cache.
@@ -201,6 +205,14 @@ class PerlinAttention(nn.Module):
         # (resize_m_to_t.py:39-45) and draws no `random.random()` for it.  False = the reference's torch expression in dense
         # mode and `loss == 0` in sparse mode
         self.fused_kd_loss = False
+        # training, both modes, independent of `fused_kd_loss`: True = the student-score KD term (0.1 KL + MSE of
+        # q_for_score k_for_score^T against `attention_scores_truth`) comes from `ops.kd_score_loss`
+        # (csrc/sea_kd_score_loss.hip) instead of `_kl_and_mse` over the (N,H,T,T) scores, wherever the batch is unpadded and
+        # `ops.kd_score_loss_supported` holds (16-bit data, head size 64 / 80 / 128, T <= 16384); elsewhere nothing changes.
+        # With it, SPARSE mode's loss gains this term (and the context term); with both switches sparse mode's loss has every
+        # term dense mode's has.  Stated deviation under this opt-in: the kernels keep q k^T in its fp32 accumulator, the torch
+        # form rounds it to the data type before the softmaxes
+        self.fused_kd_score_loss = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -672,6 +684,7 @@ class PerlinAttention(nn.Module):
             # `fused_kd_loss`: the estimator's KD term on the HIP kernels, no (N,H,T,T) resize and no rank jitter for it.  In
             # sparse mode this term and the context term are the whole loss: the student-score term (`_kl_and_mse` of q k^T
             # over ALL keys against the truth, `_forward_dense`) needs the dense scores sparse mode exists to avoid and stays out
+            # (`fused_kd_score_loss`, below, brings it in without them)
             fused_kd = (self._kd_wants_scores and estimated_attention_score is not None
                         and ops.kd_estimator_loss_supported(estimated_attention_score, attention_scores_truth))
             if fused_kd:
@@ -697,6 +710,14 @@ class PerlinAttention(nn.Module):
                     bench.register_temp_buffer('estimated_attention_probs_resized', estimated_attention_probs_resized)
                     bench.register_temp_buffer('estimated_attention_score_resized', estimated_attention_score_resized)
 
+            # `fused_kd_score_loss`: the student-score term (`_kl_and_mse` of q k^T against the truth) on the HIP kernels, no
+            # (N,H,T,T) score tensor for it.  Dense mode takes the term from here instead of `_forward_dense` (which is handed no
+            # truth: it uses it for nothing else); sparse mode gains the term, and the context term with it
+            fused_score = bool(self.fused_kd_score_loss and attention_scores_truth is not None and not_padded
+                               and ops.kd_score_loss_supported(q_for_score, k_for_score, attention_scores_truth))
+            if fused_score:
+                loss = loss + ops.kd_score_loss(q_for_score, k_for_score, attention_scores_truth)
+
             if not not_padded:
                 estimated_attention_probs = estimated_attention_probs * (dst_attention_mask > -1)
             bench.register_temp_buffer('masked_estimated_attention_probs', estimated_attention_probs)
@@ -709,7 +730,8 @@ class PerlinAttention(nn.Module):
             else:
                 out = self._forward_dense(q, v, q_for_score, k_for_score, t_attention_predictor,
                                           estimated_attention_probs, causal_attention_mask, dst_attention_mask,
-                                          attention_scores_truth, FP_MIN, T_SRC, T_M, resize_dense, head_chunk=head_chunk)
+                                          None if fused_score else attention_scores_truth, FP_MIN, T_SRC, T_M, resize_dense,
+                                          head_chunk=head_chunk)
                 partial_context_layer, partial_attention_probs, partial_attention_mask, attention_probs_dense, l2 = out
                 loss = loss + l2
 
@@ -719,7 +741,7 @@ class PerlinAttention(nn.Module):
             if self.pconfig.context_output_method != 'mix':
                 raise Exception("only context_output_method='mix' is live in the reference (:1286-1314)")
 
-            if (not self.benchmarking or fused_kd) and context_layer_truth is not None:
+            if (not self.benchmarking or fused_kd or fused_score) and context_layer_truth is not None:
                 loss = loss + F.mse_loss(context_layer_truth, partial_context_layer)
 
             # (head-chunked dense mode never forms the resized T x T estimate: it hands out the T_M-wide map, like sparse mode)
