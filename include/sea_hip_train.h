@@ -18,7 +18,10 @@ extern "C" {
 /* Version of the entries in this header, returned by sea_train_version().
  *   1  sea_kd_estimator_loss, sea_kd_estimator_loss_bwd
  *      sea_kd_score_loss, sea_kd_score_loss_bwd: added later WITHOUT a bump -- they are additive, the suite pins this number
- *      at 1, and a binding that needs them finds out by looking the symbols up (a library without them fails to load there) */
+ *      at 1, and a binding that needs them finds out by looking the symbols up (a library without them fails to load there)
+ *      sea_kd_estimator_loss_qk, sea_kd_score_loss_qk, sea_kd_score_loss_qk_bwd (t5 - t7, the teacher as q_t, k_t in place of
+ *      its score tensor): added the same way, WITHOUT a bump, for the same reasons.  t1, t3 and t4 keep their signatures; folding
+ *      each pair into one entry is for the next bump */
 #define SEA_TRAIN_ABI_VERSION 1
 
 int sea_train_version(void);
@@ -101,6 +104,50 @@ int sea_kd_score_loss_bwd(const void* q, const void* k, int qk_dtype, const int6
                           const float* row_q, const float* row_stats, const float* grad_loss,
                           int64_t N, int64_t H, int64_t T, int64_t D,
                           void* d_q, void* d_k, sea_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * t5 - t7  the same losses with the teacher FACTORED: teacher_q, teacher_k (N,H,T,D) in place of truth (N,H,T,T), which is
+ * nothing but their product (teacher_q already carries the teacher's scaling).  With these entries no T x T tensor exists in a
+ * training step, neither in the library nor in its caller.
+ *
+ * x_ts = teacher_q_t . teacher_k_s is accumulated in fp32 from the 16-bit inputs, tile by tile on the matrix instructions, and
+ * is NOT rounded to the data type -- the decision t3 states for the student's scores.  A caller that used to hand over the
+ * teacher's own bmm result (rounded to 16 bits) therefore gets other row values than from t1 / t3, by far more than the
+ * kernels' error; against the unrounded product the forms and the accuracy are those of t1 - t4.
+ *
+ * teacher_q, teacher_k: fp16 or bf16, both of `teacher_dtype`, each with strides[3] = {n, h, t} in elements, innermost stride
+ * 1, rows 16-byte aligned (base pointer and every stride).  Columns past D are never read (D = 80: the padded k-step).
+ * Limits: D in {64, 80, 128}, 1 <= T <= 16384.  Null pointers, bad strides and misalignment are SEA_EINVAL; everything else
+ * (D, T, fp32 or unknown dtype codes, a teacher of another type than the student) is SEA_EUNSUPPORTED; all before any launch,
+ * sea_last_error() names the argument.  No atomics, one summation order: the same inputs give the same bits.
+ *
+ * t5  the estimator's term, forward.  Outputs exactly t1's (row_kl, row_mse, pix_tgt -- exactly 0 on empty pixels --,
+ * row_stats = { m_e, log S }), so t2 is its backward as it is: t2 never read the teacher.  est as in t1 (fp32 / fp16 / bf16,
+ * independent of the teacher's type); T_m % 4 == 0, T_m <= 512.  pix_tgt is cleared on `stream` before the launch.  The sums
+ * S and G_b are taken in another order than t1's, so t5 and t1 on the same scores agree to rounding, not bit for bit. */
+int sea_kd_estimator_loss_qk(const void* est, int est_dtype, const int64_t* est_strides,
+                             const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                             const int64_t* teacher_q_strides, const int64_t* teacher_k_strides,
+                             int64_t N, int64_t H, int64_t T, int64_t T_m, int64_t D,
+                             float* row_kl, float* row_mse, float* pix_tgt, float* row_stats,
+                             sea_stream_t stream);
+
+/* t6  the student-score term, forward: t3 with the factored teacher.  teacher_dtype must be qk_dtype (one tile body serves
+ * both products: a teacher holding the student's bits gives row_kl = row_mse = row_q = 0 exactly). */
+int sea_kd_score_loss_qk(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                         const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                         const int64_t* teacher_q_strides, const int64_t* teacher_k_strides,
+                         int64_t N, int64_t H, int64_t T, int64_t D,
+                         float* row_kl, float* row_mse, float* row_q, float* row_stats,
+                         sea_stream_t stream);
+
+/* t7  its gradient with respect to q and k: t4 with the factored teacher (the teacher's tile is recomputed in both passes). */
+int sea_kd_score_loss_qk_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                             const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                             const int64_t* teacher_q_strides, const int64_t* teacher_k_strides,
+                             const float* row_q, const float* row_stats, const float* grad_loss,
+                             int64_t N, int64_t H, int64_t T, int64_t D,
+                             void* d_q, void* d_k, sea_stream_t stream);
 
 #ifdef __cplusplus
 }

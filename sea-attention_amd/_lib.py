@@ -90,6 +90,13 @@ _TRAIN_SIGNATURES = {
     "sea_kd_score_loss": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_kd_score_loss_bwd": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr, ptr],
                               c_int),
+    # t5 - t7, the same entries with the teacher as q_t, k_t instead of the score tensor (also without a bump)
+    "sea_kd_estimator_loss_qk": ([ptr, c_int, _i64p, ptr, ptr, c_int, _i64p, _i64p, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr],
+                                 c_int),
+    "sea_kd_score_loss_qk": ([ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, c_int, _i64p, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr,
+                              ptr], c_int),
+    "sea_kd_score_loss_qk_bwd": ([ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, ptr, i64, i64, i64, i64,
+                                  ptr, ptr, ptr], c_int),
 }
 
 

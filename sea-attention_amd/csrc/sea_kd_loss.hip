@@ -9,31 +9,12 @@
 // needs the key counts c_b, the teacher's probability mass per pixel G_b and a few scalars: the forward reads the causal half
 // of the teacher's scores once, the backward is T_M wide.
 #include "sea_common.hpp"
+#include "sea_kd_pix.hpp"             // kd_pix, kd_first, KD_MAX_TM, KD_MAX_T
 #include "../../include/sea_hip_train.h"
 
 namespace sea {
 
-constexpr int KD_MAX_TM = 512;
-constexpr int KD_MAX_T = 16384;
 constexpr int KD_FIRST_SLOTS = KD_MAX_TM + 8;     // first key of pixels 0 .. T_M (one past the last), padded to 16 bytes
-
-// pixel of key s in a row of `len` = t + 1 keys: ops/resize_dense.py, fp32 with IEEE operations (rank = s + 1, no padding)
-__device__ inline int kd_pix(int s, float len, float tm, int T_M) {
-  const float v = __fsub_rn(__fmul_rn(__fdiv_rn(__fsub_rn((float)(s + 1), 0.5f), len), tm), 1e-4f);
-  const int p = (int)floorf(v);
-  return p < 0 ? 0 : (p > T_M ? T_M : p);
-}
-// first key of pixel b: the least s in 0 .. t + 1 with s == t + 1 or pix(s) >= b.  pix is non-decreasing in s (every operation
-// in it is), so pixel b holds the keys first(b) .. first(b + 1) - 1.  The guess inverts the formula in real numbers; the two
-// loops settle it against the fp32 formula itself (a step or two).
-__device__ inline int kd_first(int b, int t, float len, float tm, int T_M) {
-  if (b >= T_M) return t + 1;
-  const float g = ceilf(((float)b + 1e-4f) * len / tm - 0.5f);
-  int s = g < 0.f ? 0 : (g > len ? t + 1 : (int)g);
-  while (s > 0 && kd_pix(s - 1, len, tm, T_M) >= b) --s;
-  while (s <= t && kd_pix(s, len, tm, T_M) < b) ++s;
-  return s;
-}
 
 // LDS slot of key s, in elements of the teacher's own type (the row is kept as it was loaded: 16-bit scores take half the
 // LDS of an fp32 copy, and the LDS a row takes is what bounds the waves per CU): one pad dword per 32 dwords.  In the pixel

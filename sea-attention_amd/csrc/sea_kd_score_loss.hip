@@ -14,7 +14,16 @@
 // global memory in 16-byte chunks, already in the accumulator's lane map, and never pass through LDS.  The same sixteen values
 // are, eight at a time, the B operand of the gradient's MFMA (k = 8 (l >> 4) + j stands for swept index 16 (l >> 4) + 8 u + j in
 // k-step u; the A operand is read from a transposed LDS image with the same numbering), so dS never leaves registers either.
+//
+// The teacher may come factored (t5 - t7: `KsQK` in place of the type of the score tensor): its q and k of the student's
+// type and head size.  Then the teacher's tile is staged in a second row image beside the student's, the teacher's own
+// fragments are loaded like the student's, and x is a second score tile in the same lane map -- same indexing, same
+// instructions, so a teacher that holds the student's bits gives the student's scores bit for bit.  Nothing T x T is read.
+// The estimator's term (t5, `kdq_fwd_kernel` below) runs on the same tile body with the teacher's tile alone.
+#include <type_traits>
+
 #include "sea_common.hpp"
+#include "sea_kd_pix.hpp"
 #include "../../include/sea_hip_train.h"
 
 namespace sea {
@@ -63,6 +72,16 @@ __device__ inline float ks_xor32_max(float v) {
 __device__ inline float ks_own_max(float v) { return ks_xor32_max(ks_xor16_max(v)); }
 __device__ inline float ks_own_sum(float v) { return xor32_sum(xor16_sum(v)); }
 
+// in place of the score tensor's element type: the teacher is q_t, k_t (KsParams::tq, tk), of the student's type T
+struct KsQK {};
+template <typename TX> constexpr bool ks_is_qk = std::is_same<TX, KsQK>::value;
+
+// a * b rounded to fp32, never fused into a following addition (the build contracts by default and honours this pragma)
+__device__ inline float ks_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 struct KsParams {
   const void* q;
   const void* k;
@@ -76,6 +95,9 @@ struct KsParams {
   const float* grad_loss;
   void* d_q;
   void* d_k;
+  const void* tq;                                  // the factored teacher (KsQK): truth is null.  (Last: the fields above keep
+  const void* tk;                                  // their places in the kernel arguments)
+  int64_t tqsn, tqsh, tqst, tksn, tksh, tkst;
 };
 
 // Rows i0 .. i0 + 63 of `src` (stride `st` elements) into LDS: the row image and, for the gradient's A operand, the transposed
@@ -160,7 +182,7 @@ __device__ inline void ks_truth_keys(const TX* xrow, int t, int Tn, int s0, floa
 // block -> (index of the 64-block of own indices, (n, h)).  All (n, h) of one block index are neighbours in the grid, and the
 // grid starts with the longest sweeps (the causal triangle: block b of the queries sweeps b + 1 key tiles, block b of the keys
 // sweeps NB - b query tiles), so the launch ends on the short ones.
-template <bool COL> __device__ inline void ks_block(const KsParams& p, int& ob, int& n, int& h) {
+template <bool COL, typename P> __device__ inline void ks_block(const P& p, int& ob, int& n, int& h) {
   const int NH = p.N * p.H, NB = (p.T + KS_TILE - 1) / KS_TILE;
   const int i = blockIdx.x / NH, nh = blockIdx.x - i * NH;
   ob = COL ? i : NB - 1 - i;
@@ -172,7 +194,9 @@ template <bool COL> __device__ inline void ks_block(const KsParams& p, int& ob, 
 template <typename T, typename TX, int D>
 __global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
   using G = KsGeo<D>;
+  constexpr bool QK = ks_is_qk<TX>;
   __shared__ __align__(16) unsigned short s_row[KS_TILE * G::RST];
+  __shared__ __align__(16) unsigned short s_xrow[QK ? KS_TILE * G::RST : 8];   // the teacher's k tile (KsQK only)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   int rb, n, h;
   ks_block<false>(p, rb, n, h);
@@ -181,9 +205,16 @@ __global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
   const int t = rb * KS_TILE + 16 * w + li;
   const bool own_ok = t < p.T;
   const int tv = own_ok ? t : -1;                  // no key is <= -1: a query past T reads and adds nothing
-  const TX* xrow = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh + (int64_t)(own_ok ? t : 0) * p.xst;
-  uint4 own[G::KK];
+  const TX* xrow = nullptr;
+  const T* tk = nullptr;
+  uint4 own[G::KK], xown[G::KK];
   ks_own_frags<T, D>(q, p.qst, t, p.T, lane, own);
+  if constexpr (QK) {
+    tk = reinterpret_cast<const T*>(p.tk) + n * p.tksn + h * p.tksh;
+    ks_own_frags<T, D>(reinterpret_cast<const T*>(p.tq) + n * p.tqsn + h * p.tqsh, p.tqst, t, p.T, lane, xown);
+  } else {
+    xrow = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh + (int64_t)(own_ok ? t : 0) * p.xst;
+  }
 
   // sweep 1: running maximum and sum of both softmaxes, per lane over its keys
   float ms = -INFINITY, ls = 0.f, mx = -INFINITY, lx = 0.f;
@@ -191,10 +222,12 @@ __global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
     const int s0 = tile * KS_TILE + 16 * g;
     __syncthreads();
     ks_stage<T, D, false>(k, p.kst, tile * KS_TILE, p.T, s_row, nullptr);
+    if constexpr (QK) ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_xrow, nullptr);
     float xv[16], sv[16];
-    ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
+    if constexpr (!QK) ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
     __syncthreads();
     ks_scores<T, D>(s_row, own, lane, sv);
+    if constexpr (QK) ks_scores<T, D>(s_xrow, xown, lane, xv);
     float ts = -INFINITY, tx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -229,15 +262,23 @@ __global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
     const int s0 = tile * KS_TILE + 16 * g;
     __syncthreads();
     ks_stage<T, D, false>(k, p.kst, tile * KS_TILE, p.T, s_row, nullptr);
+    if constexpr (QK) ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_xrow, nullptr);
     float xv[16], sv[16];
-    ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
+    if constexpr (!QK) ks_truth_keys<TX>(xrow, tv, p.T, s0, xv);
     __syncthreads();
     ks_scores<T, D>(s_row, own, lane, sv);
+    if constexpr (QK) ks_scores<T, D>(s_xrow, xown, lane, xv);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       if (s0 + e <= tv) {
         const float ds = sv[e] - M, dx = xv[e] - MX;
-        const float pe = expf(ds) * inv_l, tg = expf(dx) * inv_lx;
+        float pe = expf(ds) * inv_l, tg = expf(dx) * inv_lx;
+        if constexpr (QK) {
+          // both products rounded on their own: left to contraction, pe - tg becomes fma(a, b, -(c d)), which is the rounding
+          // error of c d and not 0 for a teacher row that equals the student's bit for bit
+          pe = ks_mul_rn(expf(ds), inv_l);
+          tg = ks_mul_rn(expf(dx), inv_lx);
+        }
         kl += tg > 0.f ? tg * ((dx - log_lx) - (ds - log_l)) : 0.f;
         const float df = pe - tg;
         mse += df * df;
@@ -266,19 +307,30 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
   using G = KsGeo<D>;
   using X = KsX<T>;
   __shared__ __align__(16) unsigned short s_row[KS_TILE * G::RST];
+  constexpr bool QK = ks_is_qk<TX>;
   __shared__ __align__(16) unsigned short s_tr[D * G::TST];
+  __shared__ __align__(16) unsigned short s_xrow[QK ? KS_TILE * G::RST : 8];   // the teacher's swept tile (KsQK only): no transposed image
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
   int ob, n, h;
   ks_block<COL>(p, ob, n, h);
   const int NB = (p.T + KS_TILE - 1) / KS_TILE;
   const T* q = reinterpret_cast<const T*>(p.q) + n * p.qsn + h * p.qsh;
   const T* k = reinterpret_cast<const T*>(p.k) + n * p.ksn + h * p.ksh;
-  const TX* x = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh;
+  const TX* x = nullptr;
+  const T* tq = nullptr;
+  const T* tk = nullptr;
+  if constexpr (QK) {
+    tq = reinterpret_cast<const T*>(p.tq) + n * p.tqsn + h * p.tqsh;
+    tk = reinterpret_cast<const T*>(p.tk) + n * p.tksn + h * p.tksh;
+  } else {
+    x = reinterpret_cast<const TX*>(p.truth) + n * p.xsn + h * p.xsh;
+  }
   const int64_t r0 = ((int64_t)n * p.H + h) * p.T;
   const int o = ob * KS_TILE + 16 * w + li;        // the lane's own index
   const bool own_ok = o < p.T;
-  uint4 own[G::KK];
+  uint4 own[G::KK], xown[G::KK];
   ks_own_frags<T, D>(COL ? k : q, COL ? p.kst : p.qst, o, p.T, lane, own);
+  if constexpr (QK) ks_own_frags<T, D>(COL ? tk : tq, COL ? p.tkst : p.tqst, o, p.T, lane, xown);
   const float k_kl = 0.1f * X::DS_SCALE, k_mse = 2.0f / (float)p.T * X::DS_SCALE;
 
   float4 st_own = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -287,7 +339,8 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
     st_own = *reinterpret_cast<const float4*>(p.row_stats + 4 * (r0 + o));
     rq_own = p.row_q[r0 + o];
   }
-  const TX* xrow = x + (int64_t)(own_ok ? o : 0) * p.xst;     // row pass only
+  const TX* xrow = nullptr;                                   // row pass, score tensor only
+  if constexpr (!QK) xrow = x + (int64_t)(own_ok ? o : 0) * p.xst;
 
   ks_f4 out[G::DT];
 #pragma unroll
@@ -298,10 +351,11 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
     const int i0 = tile * KS_TILE + 16 * g;        // the lane's first swept index
     __syncthreads();
     ks_stage<T, D, true>(COL ? q : k, COL ? p.qst : p.kst, tile * KS_TILE, p.T, s_row, s_tr);
+    if constexpr (QK) ks_stage<T, D, false>(COL ? tq : tk, COL ? p.tqst : p.tkst, tile * KS_TILE, p.T, s_xrow, nullptr);
     float xv[16], sv[16], u[16];
     bool ok[16];
     if constexpr (!COL) {
-      ks_truth_keys<TX>(xrow, own_ok ? o : -1, p.T, i0, xv);
+      if constexpr (!QK) ks_truth_keys<TX>(xrow, own_ok ? o : -1, p.T, i0, xv);
 #pragma unroll
       for (int e = 0; e < 16; ++e) ok[e] = own_ok && i0 + e <= o;
     } else {
@@ -309,11 +363,12 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
       for (int e = 0; e < 16; ++e) {
         const int t = i0 + e;
         ok[e] = t < p.T && o <= t;                 // (o <= t < T: the key is inside too)
-        xv[e] = ok[e] ? Elem<TX>::to_f(x[(int64_t)t * p.xst + o]) : 0.f;
+        if constexpr (!QK) xv[e] = ok[e] ? Elem<TX>::to_f(x[(int64_t)t * p.xst + o]) : 0.f;
       }
     }
     __syncthreads();
     ks_scores<T, D>(s_row, own, lane, sv);
+    if constexpr (QK) ks_scores<T, D>(s_xrow, xown, lane, xv);   // either pass: (swept x own) of the teacher, the student's lane map
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       float4 st = st_own;
@@ -370,6 +425,211 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
   }
 }
 
+// ---- the estimator's term on the tile body (t5) ---------------------------------------------------------------------------------
+// Same outputs as sea_kd_loss.hip's forward (t1: row_kl, row_mse, pix_tgt, row_stats = {m_e, log S}; t2 then runs unchanged), the
+// teacher's scores recomputed from q_t, k_t instead of read.  A workgroup owns 64 queries and sweeps the key tiles 0 .. rb twice.
+//   before the sweeps  every wave takes its 16 queries one at a time, 64 lanes over the T_M pixels: c_b from kd_first, m_e and S
+//                      in kd_row's own order (so row_stats carries t1's bits), left on the lanes of the query
+//   sweep 1            the teacher's row maximum and log sum exp, as the score forward takes them
+//   sweep 2            x again, tgt_s, pix(t, s) by kd_pix itself (the fp32 IEEE formula, evaluated per key), row_kl and row_mse
+//                      key by key, and G_b
+// G_b without a table and without atomics: a pixel's keys are contiguous, so a lane's 16 keys fall into segments of equal
+// pixel.  A segment with a neighbour on both sides inside the lane is a whole pixel and is stored as it is.  The lane's first
+// and last segment may go on in the neighbouring lane or tile: they are handed down the four lanes of the query in key order
+// (shuffles; all four lanes do the same arithmetic on the same values) into a carry (pixel, sum) that every lane keeps and
+// that crosses to the next tile in registers; the carry is stored when the pixel changes and after the last tile.  Every held
+// pixel is stored exactly once, in one summation order (the keys of a lane ascending, then the lanes and tiles ascending); the
+// host zeroes pix_tgt on the stream first, which is what leaves the empty pixels exactly 0.
+struct KdqParams {
+  const void* est;
+  const void* tq;
+  const void* tk;
+  int64_t esn, esh, est_t, tqsn, tqsh, tqst, tksn, tksh, tkst;
+  int N, H, T, T_M;
+  float* row_kl;
+  float* row_mse;
+  float* pix_tgt;
+  float* row_stats;
+};
+
+template <typename TE, typename T, int D>
+__global__ __launch_bounds__(KS_THREADS) void kdq_fwd_kernel(KdqParams p) {
+  using G = KsGeo<D>;
+  __shared__ __align__(16) unsigned short s_row[KS_TILE * G::RST];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, g = lane >> 4;
+  int rb, n, h;
+  ks_block<false>(p, rb, n, h);
+  const T* tq = reinterpret_cast<const T*>(p.tq) + n * p.tqsn + h * p.tqsh;
+  const T* tk = reinterpret_cast<const T*>(p.tk) + n * p.tksn + h * p.tksh;
+  const TE* est = reinterpret_cast<const TE*>(p.est) + n * p.esn + h * p.esh;
+  const int T_M = p.T_M;
+  const float tm = (float)T_M;
+  const int t = rb * KS_TILE + 16 * w + li;
+  const bool own_ok = t < p.T;
+  const int tv = own_ok ? t : -1;                  // no key is <= -1: a query past T reads and adds nothing
+  const int64_t r = ((int64_t)n * p.H + h) * p.T + (own_ok ? t : 0);
+  uint4 own[G::KK];
+  ks_own_frags<T, D>(tq, p.tqst, t, p.T, lane, own);
+
+  // the estimator's softmax over the keys, from the pixels (at most 8 per lane): kd_row's order, one query at a time
+  float me_own = 0.f, inv_s_own = 0.f, log_s_own = 0.f;
+  for (int qi = 0; qi < 16; ++qi) {
+    const int tt = rb * KS_TILE + 16 * w + qi;
+    if (tt >= p.T) break;                          // (the same for the whole wave)
+    const float len = (float)(tt + 1);
+    const TE* e = est + (int64_t)tt * p.est_t;
+    float ev[8], cn[8];
+    float me = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int b = j * 64 + lane;
+      ev[j] = cn[j] = 0.f;
+      if (b < T_M) {
+        const int c = kd_first(b + 1, tt, len, tm, T_M) - kd_first(b, tt, len, tm, T_M);
+        if (c > 0) {
+          cn[j] = (float)c;
+          ev[j] = Elem<TE>::to_f(e[b]);
+          me = fmaxf(me, ev[j]);
+        }
+      }
+    }
+    me = wave_max(me);
+    float S = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (cn[j] > 0.f) S += cn[j] * expf(ev[j] - me);
+    S = wave_sum(S);
+    if (li == qi) {
+      me_own = me;
+      inv_s_own = 1.0f / S;
+      log_s_own = logf(S);
+    }
+  }
+
+  // sweep 1: running maximum and sum of the teacher's softmax, per lane over its keys
+  float mx = -INFINITY, lx = 0.f;
+  for (int tile = 0; tile <= rb; ++tile) {
+    const int s0 = tile * KS_TILE + 16 * g;
+    __syncthreads();
+    ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_row, nullptr);
+    __syncthreads();
+    float xv[16];
+    ks_scores<T, D>(s_row, own, lane, xv);
+    float tx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      xv[e] = s0 + e <= tv ? xv[e] : -INFINITY;
+      tx = fmaxf(tx, xv[e]);
+    }
+    const float nx = fmaxf(mx, tx);
+    if (nx > -INFINITY) {
+      float b = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) b += expf(xv[e] - nx);
+      lx = lx * expf(mx - nx) + b;
+      mx = nx;
+    }
+  }
+  const float MX = ks_own_max(mx);
+  const float LX = ks_own_sum(mx > -INFINITY ? lx * expf(mx - MX) : 0.f);
+  const float inv_lx = 1.0f / LX, log_lx = logf(LX);
+
+  // sweep 2
+  const float len = (float)(t + 1);
+  const TE* erow = est + (int64_t)(own_ok ? t : 0) * p.est_t;
+  float* g_out = p.pix_tgt + r * T_M;
+  float kl = 0.f, mse = 0.f;
+  int cb = -1;                                     // the carry: pixel and the sum of its keys so far (the same on the four lanes)
+  float cv = 0.f;
+  for (int tile = 0; tile <= rb; ++tile) {
+    const int s0 = tile * KS_TILE + 16 * g;
+    __syncthreads();
+    ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_row, nullptr);
+    __syncthreads();
+    float xv[16], ee[16];
+    int px[16];
+    ks_scores<T, D>(s_row, own, lane, xv);
+    // the pixels of the lane's keys (< T_M for a key <= t; held below it for the addresses' sake) and, where the pixel changes,
+    // its estimator score: all loads issued before the first is used
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int b = kd_pix(s0 + e, len, tm, T_M);
+      px[e] = b < T_M ? b : T_M - 1;
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const bool fresh = s0 + e <= tv && (e == 0 || px[e] != px[e - 1]);
+      ee[e] = fresh ? Elem<TE>::to_f(erow[px[e]]) : 0.f;
+    }
+    int fb = -1, lb = -1, sb = -1;                 // pixel of the lane's first, last and current segment
+    float fv = 0.f, lv = 0.f, sv = 0.f, pb = 0.f, lp = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      if (s0 + e <= tv) {
+        if (px[e] != sb) {
+          if (sb >= 0) {
+            if (fb < 0) {
+              fb = sb;
+              fv = sv;
+            } else {
+              g_out[sb] = sv;                      // a whole pixel
+            }
+          }
+          sb = px[e];
+          sv = 0.f;
+          const float de = ee[e] - me_own;
+          pb = expf(de) * inv_s_own;
+          lp = de - log_s_own;
+        }
+        const float dx = xv[e] - MX;
+        const float tg = expf(dx) * inv_lx;
+        sv += tg;
+        kl += tg > 0.f ? tg * ((dx - log_lx) - lp) : 0.f;
+        const float df = pb - tg;
+        mse += df * df;
+      }
+    }
+    if (sb >= 0) {
+      if (fb < 0) {
+        fb = sb;
+        fv = sv;
+      } else {
+        lb = sb;
+        lv = sv;
+      }
+    }
+    // down the four lanes of the query, in key order
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int src = li + 16 * rr;
+      const int ofb = __shfl(fb, src), olb = __shfl(lb, src);
+      const float ofv = __shfl(fv, src), olv = __shfl(lv, src);
+      if (ofb >= 0) {
+        if (ofb == cb) {
+          cv += ofv;
+        } else {
+          if (cb >= 0 && g == 0) g_out[cb] = cv;
+          cb = ofb;
+          cv = ofv;
+        }
+        if (olb >= 0) {
+          if (g == 0) g_out[cb] = cv;
+          cb = olb;
+          cv = olv;
+        }
+      }
+    }
+  }
+  if (cb >= 0 && g == 0) g_out[cb] = cv;
+  kl = ks_own_sum(kl);
+  mse = ks_own_sum(mse);
+  if (own_ok && g == 0) {
+    p.row_kl[r] = kl;
+    p.row_mse[r] = mse;
+    *reinterpret_cast<float2*>(p.row_stats + 2 * r) = make_float2(me_own, log_s_own);
+  }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 static int ks_check(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
                     const void* truth, int truth_dtype, const int64_t* truth_strides, int64_t N, int64_t H, int64_t T, int64_t D) {
@@ -397,6 +657,52 @@ static int ks_check(const char* nm, const void* q, const void* k, int qk_dtype, 
                 "%s: %s rows must be 16-byte aligned (base pointer and every stride)", nm, t.name);
   }
   return SEA_OK;
+}
+
+// t5 - t7: the factored teacher.  Null pointers, bad strides and misalignment are SEA_EINVAL, everything the kernels have no
+// form for is SEA_EUNSUPPORTED; `student_dtype` < 0: no student to agree with (t5)
+struct KsRows { const char* name; const void* ptr; const int64_t* s; int64_t row; int vec; };
+static int ks_check_rows(const char* nm, const KsRows* a, int count) {
+  for (int i = 0; i < count; ++i) {
+    const KsRows& t = a[i];
+    SEA_REQUIRE(t.s[0] >= 0 && t.s[1] >= 0 && t.s[2] >= t.row, SEA_EINVAL, "%s: bad %s strides {%lld, %lld, %lld} for rows of %lld",
+                nm, t.name, (long long)t.s[0], (long long)t.s[1], (long long)t.s[2], (long long)t.row);
+    SEA_REQUIRE(((uintptr_t)t.ptr & 15) == 0 && t.s[0] % t.vec == 0 && t.s[1] % t.vec == 0 && t.s[2] % t.vec == 0, SEA_EINVAL,
+                "%s: %s rows must be 16-byte aligned (base pointer and every stride)", nm, t.name);
+  }
+  return SEA_OK;
+}
+static int ks_check_teacher(const char* nm, const void* tq, const void* tk, int teacher_dtype, const int64_t* tq_strides,
+                            const int64_t* tk_strides, int student_dtype, int64_t N, int64_t H, int64_t T, int64_t D) {
+  SEA_REQUIRE(tq, SEA_EINVAL, "%s: teacher_q is null", nm);
+  SEA_REQUIRE(tk, SEA_EINVAL, "%s: teacher_k is null", nm);
+  SEA_REQUIRE(tq_strides, SEA_EINVAL, "%s: teacher_q_strides is null", nm);
+  SEA_REQUIRE(tk_strides, SEA_EINVAL, "%s: teacher_k_strides is null", nm);
+  SEA_REQUIRE(teacher_dtype != SEA_F32, SEA_EUNSUPPORTED,
+              "%s: fp32 teacher q / k (teacher_dtype) is outside the kernels: 16-bit data only", nm);
+  SEA_REQUIRE(teacher_dtype == SEA_F16 || teacher_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown teacher_dtype %d", nm,
+              teacher_dtype);
+  SEA_REQUIRE(student_dtype < 0 || teacher_dtype == student_dtype, SEA_EUNSUPPORTED,
+              "%s: teacher_dtype %d is not qk_dtype %d (the teacher's q / k must have the student's type)", nm, teacher_dtype,
+              student_dtype);
+  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0, SEA_EINVAL, "%s: bad shape N=%lld H=%lld T=%lld D=%lld", nm, (long long)N,
+              (long long)H, (long long)T, (long long)D);
+  SEA_REQUIRE(D == 64 || D == 80 || D == 128, SEA_EUNSUPPORTED, "%s: D=%lld (needs D in {64, 80, 128})", nm, (long long)D);
+  SEA_REQUIRE(T <= KS_MAX_T, SEA_EUNSUPPORTED, "%s: T=%lld (needs T <= %d)", nm, (long long)T, KS_MAX_T);
+  SEA_REQUIRE(N * H * ((T + KS_TILE - 1) / KS_TILE) < (1ll << 31), SEA_EUNSUPPORTED, "%s: grid too large", nm);
+  const KsRows a[2] = {{"teacher_q", tq, tq_strides, D, 8}, {"teacher_k", tk, tk_strides, D, 8}};
+  return ks_check_rows(nm, a, 2);
+}
+static int ks_check_student(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides,
+                            const int64_t* k_strides, int64_t D) {
+  SEA_REQUIRE(q, SEA_EINVAL, "%s: q is null", nm);
+  SEA_REQUIRE(k, SEA_EINVAL, "%s: k is null", nm);
+  SEA_REQUIRE(q_strides, SEA_EINVAL, "%s: q_strides is null", nm);
+  SEA_REQUIRE(k_strides, SEA_EINVAL, "%s: k_strides is null", nm);
+  SEA_REQUIRE(qk_dtype != SEA_F32, SEA_EUNSUPPORTED, "%s: fp32 q / k (qk_dtype) is outside the kernels: 16-bit data only", nm);
+  SEA_REQUIRE(qk_dtype == SEA_F16 || qk_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown qk_dtype %d", nm, qk_dtype);
+  const KsRows a[2] = {{"q", q, q_strides, D, 8}, {"k", k, k_strides, D, 8}};
+  return ks_check_rows(nm, a, 2);
 }
 
 static KsParams ks_params(const void* q, const void* k, const int64_t* qs, const int64_t* ks, const void* truth, const int64_t* xs,
@@ -429,6 +735,9 @@ template <typename T, typename TX> static int ks_launch_d(const char* nm, bool b
   if (D == 80) return ks_launch<T, TX, 80>(nm, bwd, p, s);
   return ks_launch<T, TX, 128>(nm, bwd, p, s);
 }
+template <typename T> static int ks_launch_qk(const char* nm, bool bwd, int64_t D, const KsParams& p, hipStream_t s) {
+  return ks_launch_d<T, KsQK>(nm, bwd, D, p, s);
+}
 template <typename T> static int ks_launch_x(const char* nm, bool bwd, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
   if (truth_dtype == SEA_F32) return ks_launch_d<T, float>(nm, bwd, D, p, s);
   if (truth_dtype == SEA_F16) return ks_launch_d<T, __half>(nm, bwd, D, p, s);
@@ -437,6 +746,29 @@ template <typename T> static int ks_launch_x(const char* nm, bool bwd, int truth
 static int ks_dispatch(const char* nm, bool bwd, int qk_dtype, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
   if (qk_dtype == SEA_F16) return ks_launch_x<__half>(nm, bwd, truth_dtype, D, p, s);
   return ks_launch_x<__hip_bfloat16>(nm, bwd, truth_dtype, D, p, s);
+}
+
+template <typename TE, typename T> static int kdq_launch_d(const char* nm, int64_t D, const KdqParams& p, hipStream_t s) {
+  const dim3 grid((unsigned)((int64_t)p.N * p.H * ((p.T + KS_TILE - 1) / KS_TILE)));
+  if (D == 64) hipLaunchKernelGGL((kdq_fwd_kernel<TE, T, 64>), grid, dim3(KS_THREADS), 0, s, p);
+  else if (D == 80) hipLaunchKernelGGL((kdq_fwd_kernel<TE, T, 80>), grid, dim3(KS_THREADS), 0, s, p);
+  else hipLaunchKernelGGL((kdq_fwd_kernel<TE, T, 128>), grid, dim3(KS_THREADS), 0, s, p);
+  SEA_CHECK_LAUNCH(nm);
+  return SEA_OK;
+}
+template <typename TE> static int kdq_launch(const char* nm, int teacher_dtype, int64_t D, const KdqParams& p, hipStream_t s) {
+  if (teacher_dtype == SEA_F16) return kdq_launch_d<TE, __half>(nm, D, p, s);
+  return kdq_launch_d<TE, __hip_bfloat16>(nm, D, p, s);
+}
+
+static KsParams ks_params_qk(const void* q, const void* k, const int64_t* qs, const int64_t* ks, const void* tq, const void* tk,
+                             const int64_t* tqs, const int64_t* tks, int64_t N, int64_t H, int64_t T) {
+  const int64_t none[3] = {0, 0, 0};
+  KsParams p = ks_params(q, k, qs, ks, nullptr, none, N, H, T);
+  p.tq = tq; p.tk = tk;
+  p.tqsn = tqs[0]; p.tqsh = tqs[1]; p.tqst = tqs[2];
+  p.tksn = tks[0]; p.tksh = tks[1]; p.tkst = tks[2];
+  return p;
 }
 
 }  // namespace sea
@@ -477,4 +809,93 @@ extern "C" int sea_kd_score_loss_bwd(const void* q, const void* k, int qk_dtype,
   p.row_q = const_cast<float*>(row_q); p.row_stats = const_cast<float*>(row_stats);
   p.grad_loss = grad_loss; p.d_q = d_q; p.d_k = d_k;
   return ks_dispatch(nm, true, qk_dtype, truth_dtype, D, p, (hipStream_t)stream);
+}
+
+extern "C" int sea_kd_score_loss_qk(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                                    const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                                    const int64_t* teacher_q_strides, const int64_t* teacher_k_strides, int64_t N, int64_t H,
+                                    int64_t T, int64_t D, float* row_kl, float* row_mse, float* row_q, float* row_stats,
+                                    sea_stream_t stream) {
+  const char* nm = "sea_kd_score_loss_qk";
+  SEA_REQUIRE(q && k && q_strides && k_strides, SEA_EINVAL, "%s: %s is null", nm,
+              !q ? "q" : !k ? "k" : !q_strides ? "q_strides" : "k_strides");
+  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides,
+                            qk_dtype == SEA_F16 || qk_dtype == SEA_BF16 ? qk_dtype : -1, N, H, T, D);
+  if (rc != SEA_OK) return rc;
+  rc = ks_check_student(nm, q, k, qk_dtype, q_strides, k_strides, D);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
+  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
+  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
+  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
+  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0, SEA_EINVAL, "%s: row_stats must be 16-byte aligned", nm);
+  KsParams p = ks_params_qk(q, k, q_strides, k_strides, teacher_q, teacher_k, teacher_q_strides, teacher_k_strides, N, H, T);
+  p.row_kl = row_kl; p.row_mse = row_mse; p.row_q = row_q; p.row_stats = row_stats;
+  if (qk_dtype == SEA_F16) return ks_launch_qk<__half>(nm, false, D, p, (hipStream_t)stream);
+  return ks_launch_qk<__hip_bfloat16>(nm, false, D, p, (hipStream_t)stream);
+}
+
+extern "C" int sea_kd_score_loss_qk_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides,
+                                        const int64_t* k_strides, const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                                        const int64_t* teacher_q_strides, const int64_t* teacher_k_strides, const float* row_q,
+                                        const float* row_stats, const float* grad_loss, int64_t N, int64_t H, int64_t T, int64_t D,
+                                        void* d_q, void* d_k, sea_stream_t stream) {
+  const char* nm = "sea_kd_score_loss_qk_bwd";
+  SEA_REQUIRE(q && k && q_strides && k_strides, SEA_EINVAL, "%s: %s is null", nm,
+              !q ? "q" : !k ? "k" : !q_strides ? "q_strides" : "k_strides");
+  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides,
+                            qk_dtype == SEA_F16 || qk_dtype == SEA_BF16 ? qk_dtype : -1, N, H, T, D);
+  if (rc != SEA_OK) return rc;
+  rc = ks_check_student(nm, q, k, qk_dtype, q_strides, k_strides, D);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
+  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
+  SEA_REQUIRE(grad_loss, SEA_EINVAL, "%s: grad_loss is null", nm);
+  SEA_REQUIRE(d_q, SEA_EINVAL, "%s: d_q is null", nm);
+  SEA_REQUIRE(d_k, SEA_EINVAL, "%s: d_k is null", nm);
+  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0 && ((uintptr_t)d_q & 7) == 0 && ((uintptr_t)d_k & 7) == 0, SEA_EINVAL,
+              "%s: row_stats must be 16-byte aligned, d_q and d_k 8-byte aligned", nm);
+  KsParams p = ks_params_qk(q, k, q_strides, k_strides, teacher_q, teacher_k, teacher_q_strides, teacher_k_strides, N, H, T);
+  p.row_q = const_cast<float*>(row_q); p.row_stats = const_cast<float*>(row_stats);
+  p.grad_loss = grad_loss; p.d_q = d_q; p.d_k = d_k;
+  if (qk_dtype == SEA_F16) return ks_launch_qk<__half>(nm, true, D, p, (hipStream_t)stream);
+  return ks_launch_qk<__hip_bfloat16>(nm, true, D, p, (hipStream_t)stream);
+}
+
+extern "C" int sea_kd_estimator_loss_qk(const void* est, int est_dtype, const int64_t* est_strides, const void* teacher_q,
+                                        const void* teacher_k, int teacher_dtype, const int64_t* teacher_q_strides,
+                                        const int64_t* teacher_k_strides, int64_t N, int64_t H, int64_t T, int64_t T_m, int64_t D,
+                                        float* row_kl, float* row_mse, float* pix_tgt, float* row_stats, sea_stream_t stream) {
+  const char* nm = "sea_kd_estimator_loss_qk";
+  SEA_REQUIRE(est, SEA_EINVAL, "%s: est is null", nm);
+  SEA_REQUIRE(est_strides, SEA_EINVAL, "%s: est_strides is null", nm);
+  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides, -1, N, H, T, D);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(est_dtype == SEA_F32 || est_dtype == SEA_F16 || est_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown est_dtype %d",
+              nm, est_dtype);
+  SEA_REQUIRE(T_m > 0, SEA_EINVAL, "%s: bad shape T_m=%lld", nm, (long long)T_m);
+  SEA_REQUIRE(T_m % 4 == 0 && T_m <= KD_MAX_TM, SEA_EUNSUPPORTED, "%s: T_m=%lld (needs T_m %% 4 == 0 and T_m <= %d)", nm,
+              (long long)T_m, KD_MAX_TM);
+  const KsRows a[1] = {{"est", est, est_strides, T_m, est_dtype == SEA_F32 ? 4 : 8}};
+  rc = ks_check_rows(nm, a, 1);
+  if (rc != SEA_OK) return rc;
+  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
+  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
+  SEA_REQUIRE(pix_tgt, SEA_EINVAL, "%s: pix_tgt is null", nm);
+  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
+  SEA_REQUIRE(((uintptr_t)row_stats & 7) == 0, SEA_EINVAL, "%s: row_stats must be 8-byte aligned", nm);
+  KdqParams p = {};
+  p.est = est; p.tq = teacher_q; p.tk = teacher_k;
+  p.esn = est_strides[0]; p.esh = est_strides[1]; p.est_t = est_strides[2];
+  p.tqsn = teacher_q_strides[0]; p.tqsh = teacher_q_strides[1]; p.tqst = teacher_q_strides[2];
+  p.tksn = teacher_k_strides[0]; p.tksh = teacher_k_strides[1]; p.tkst = teacher_k_strides[2];
+  p.N = (int)N; p.H = (int)H; p.T = (int)T; p.T_M = (int)T_m;
+  p.row_kl = row_kl; p.row_mse = row_mse; p.pix_tgt = pix_tgt; p.row_stats = row_stats;
+  hipStream_t s = (hipStream_t)stream;
+  // the empty pixels' zeros: the kernel stores the held pixels only, each exactly once
+  const hipError_t e = hipMemsetAsync(pix_tgt, 0, (size_t)(N * H * T * T_m) * sizeof(float), s);
+  SEA_REQUIRE(e == hipSuccess, SEA_ELAUNCH, "%s: clearing pix_tgt failed: %s", nm, hipGetErrorString(e));
+  if (est_dtype == SEA_F32) return kdq_launch<float>(nm, teacher_dtype, D, p, s);
+  if (est_dtype == SEA_F16) return kdq_launch<__half>(nm, teacher_dtype, D, p, s);
+  return kdq_launch<__hip_bfloat16>(nm, teacher_dtype, D, p, s);
 }

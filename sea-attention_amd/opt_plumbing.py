@@ -134,6 +134,8 @@ class SeaOPTAttention(nn.Module):
         self.perlin_self_attention = PerlinSelfAttention(
             SimpleNamespace(hidden_size=embed_dim, num_attention_heads=num_heads,
                             max_position_embeddings=max_position_embeddings), perlin_config=pconfig)
+        # the teacher's (N,H,T,T) scores, or an `ops.TeacherScores` (`teacher_scores(teacher_attn, hidden_states)` below): its q
+        # and k in place of their product, for the fused distillation terms
         self.teacher_attention_scores = None
         self.teacher_context_layer = None
         self.last_loss = None
@@ -314,6 +316,19 @@ class SeaOPTDecoderLayer(nn.Module):
         if use_cache:
             out += (present,)
         return out
+
+
+def teacher_scores(attn: nn.Module, hidden_states: torch.Tensor):
+    """The teacher attention module's scores for `hidden_states` (N, T, E) in factored form: an `ops.TeacherScores` of
+    q = heads(q_proj(h) * scaling) and k = heads(k_proj(h)), in `SeaOPTAttention._heads`' layout, under no_grad.  Put it into
+    `SeaOPTAttention.teacher_attention_scores` instead of the (N,H,T,T) tensor q k^T; nothing T x T is formed."""
+    from .perlin_attention.ops import TeacherScores
+    with torch.no_grad():
+        n, t, _ = hidden_states.shape
+        q = attn.q_proj(hidden_states) * attn.scaling
+        k = attn.k_proj(hidden_states)
+        heads = lambda x: x.view(n, t, attn.num_heads, -1).transpose(1, 2).contiguous()
+        return TeacherScores(heads(q), heads(k))
 
 
 def causal_additive_mask(N: int, T_dst: int, T_src: int, dtype, device) -> torch.Tensor:

@@ -26,7 +26,9 @@ student-score term needs q k^T over ALL keys, which sparse mode exists to avoid:
 unless `fused_kd_score_loss` is set: then both modes take it from `ops.kd_score_loss` (csrc/sea_kd_score_loss.hip: q k^T
 recomputed tile by tile against the truth, no T x T tensor, scores kept in fp32; unpadded 16-bit batches inside
 `ops.kd_score_loss_supported`), and sparse mode adds it and the context MSE.  With both switches on, sparse mode's loss
-has every term of dense mode's.
+has every term of dense mode's.  `attention_scores_truth` may be an `ops.TeacherScores` (the teacher's q and k instead of their
+product): the fused terms then recompute the teacher's tile beside their own and no T x T tensor exists in the step, neither here
+nor in the caller; every other path takes `.dense()` once and runs as it does for the tensor.
 
 Scope of this round: the causal configuration (`pconfig.causal=True`, `k_flatten_dim='causal_batch'`,
 the only one the OPT/LLaMA path constructs -- perlin_opt.py:224-239) without kv-cache.
@@ -665,6 +667,24 @@ class PerlinAttention(nn.Module):
 
         self._kd_wants_scores = bool(self.fused_kd_loss and attention_scores_truth is not None and not_padded)
 
+        # `attention_scores_truth` may be an `ops.TeacherScores` (the teacher's q and k in place of their (N,H,T,T) product): the
+        # fused terms below take it as it is; every other consumer gets `.dense()`, formed at most once
+        truth_dense_cache = []
+
+        def truth_dense():
+            if not isinstance(attention_scores_truth, ops.TeacherScores):
+                return attention_scores_truth
+            if not truth_dense_cache:
+                with torch.no_grad():
+                    truth_dense_cache.append(attention_scores_truth.dense())
+            return truth_dense_cache[0]
+
+        def truth_for(supported, *tensors):
+            """the factored truth where the kernels behind `supported` take it, the dense tensor everywhere else"""
+            if isinstance(attention_scores_truth, ops.TeacherScores) and not supported(*tensors, attention_scores_truth):
+                return truth_dense()
+            return attention_scores_truth
+
         with timer("perlin"):
             N, H, T, HID = q.shape
             v, t_attention_predictor, estimated_attention_score, estimated_attention_probs = self._estimate(
@@ -685,10 +705,12 @@ class PerlinAttention(nn.Module):
             # sparse mode this term and the context term are the whole loss: the student-score term (`_kl_and_mse` of q k^T
             # over ALL keys against the truth, `_forward_dense`) needs the dense scores sparse mode exists to avoid and stays out
             # (`fused_kd_score_loss`, below, brings it in without them)
-            fused_kd = (self._kd_wants_scores and estimated_attention_score is not None
-                        and ops.kd_estimator_loss_supported(estimated_attention_score, attention_scores_truth))
+            fused_kd = self._kd_wants_scores and estimated_attention_score is not None
             if fused_kd:
-                loss = loss + ops.kd_estimator_loss(estimated_attention_score, attention_scores_truth)
+                est_truth = truth_for(ops.kd_estimator_loss_supported, estimated_attention_score)
+                fused_kd = ops.kd_estimator_loss_supported(estimated_attention_score, est_truth)
+            if fused_kd:
+                loss = loss + ops.kd_estimator_loss(estimated_attention_score, est_truth)
                 if not self.benchmarking and not head_chunk:          # the unchunked dense form returns the stretched estimate
                     estimated_attention_probs_resized = resize_dense(estimated_attention_probs, 0, False)
                     bench.register_temp_buffer('estimated_attention_probs_resized', estimated_attention_probs_resized)
@@ -699,13 +721,13 @@ class PerlinAttention(nn.Module):
                     for h0 in range(0, H, int(head_chunk)):
                         h1 = min(H, h0 + int(head_chunk))
                         sc = resize_dense(estimated_attention_score[:, h0:h1], FP_MIN, False).float()
-                        loss = loss + _kl_and_mse(sc, attention_scores_truth[:, h0:h1], causal_attention_mask, FP_MIN) \
+                        loss = loss + _kl_and_mse(sc, truth_dense()[:, h0:h1], causal_attention_mask, FP_MIN) \
                             * ((h1 - h0) / H)
                         del sc
                 else:
                     estimated_attention_probs_resized = resize_dense(estimated_attention_probs, 0, False)
                     estimated_attention_score_resized = resize_dense(estimated_attention_score, FP_MIN, False).float()
-                    loss = loss + _kl_and_mse(estimated_attention_score_resized, attention_scores_truth,
+                    loss = loss + _kl_and_mse(estimated_attention_score_resized, truth_dense(),
                                               causal_attention_mask, FP_MIN)
                     bench.register_temp_buffer('estimated_attention_probs_resized', estimated_attention_probs_resized)
                     bench.register_temp_buffer('estimated_attention_score_resized', estimated_attention_score_resized)
@@ -713,10 +735,12 @@ class PerlinAttention(nn.Module):
             # `fused_kd_score_loss`: the student-score term (`_kl_and_mse` of q k^T against the truth) on the HIP kernels, no
             # (N,H,T,T) score tensor for it.  Dense mode takes the term from here instead of `_forward_dense` (which is handed no
             # truth: it uses it for nothing else); sparse mode gains the term, and the context term with it
-            fused_score = bool(self.fused_kd_score_loss and attention_scores_truth is not None and not_padded
-                               and ops.kd_score_loss_supported(q_for_score, k_for_score, attention_scores_truth))
+            fused_score = bool(self.fused_kd_score_loss and attention_scores_truth is not None and not_padded)
             if fused_score:
-                loss = loss + ops.kd_score_loss(q_for_score, k_for_score, attention_scores_truth)
+                score_truth = truth_for(ops.kd_score_loss_supported, q_for_score, k_for_score)
+                fused_score = ops.kd_score_loss_supported(q_for_score, k_for_score, score_truth)
+            if fused_score:
+                loss = loss + ops.kd_score_loss(q_for_score, k_for_score, score_truth)
 
             if not not_padded:
                 estimated_attention_probs = estimated_attention_probs * (dst_attention_mask > -1)
@@ -730,7 +754,7 @@ class PerlinAttention(nn.Module):
             else:
                 out = self._forward_dense(q, v, q_for_score, k_for_score, t_attention_predictor,
                                           estimated_attention_probs, causal_attention_mask, dst_attention_mask,
-                                          None if fused_score else attention_scores_truth, FP_MIN, T_SRC, T_M, resize_dense,
+                                          None if fused_score else truth_dense(), FP_MIN, T_SRC, T_M, resize_dense,
                                           head_chunk=head_chunk)
                 partial_context_layer, partial_attention_probs, partial_attention_mask, attention_probs_dense, l2 = out
                 loss = loss + l2

@@ -21,3 +21,4 @@ from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value
 # training-side entry points (include/sea_hip_train.h)
 from .kd_loss import kd_estimator_loss, kd_estimator_loss_supported, kd_estimator_loss_parts
 from .kd_score_loss import kd_score_loss, kd_score_loss_supported, kd_score_loss_parts
+from .teacher_scores import TeacherScores
