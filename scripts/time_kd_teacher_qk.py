@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Forward + backward of the two KD terms with the teacher factored (`ops.TeacherScores(q_t, k_t)`: include/sea_hip_train.h
-t5 - t7) against the same ops on the teacher's (N,H,T,T) score tensor.  Per term three variants, alternating in one process:
+"the teacher") against the same ops on the teacher's (N,H,T,T) score tensor.  Per term three variants, alternating in one process:
 
     factored      the op on TeacherScores(q_t, k_t)
     tensor        the op on a pre-made score tensor

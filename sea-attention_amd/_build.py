@@ -16,7 +16,7 @@ SOURCES = ["sea_topk.hip", "sea_attn.hip", "sea_attn_tile.hip", "sea_attn_keyran
            "sea_predictor.hip", "sea_performer.hip", "sea_conv.hip", "sea_mlp.hip", "sea_decode.hip", "sea_kd_loss.hip",
            "sea_kd_score_loss.hip"]
 HEADERS = [os.path.join(CSRC, "sea_common.hpp"), os.path.join(CSRC, "sea_attn.hpp"), os.path.join(CSRC, "sea_tail.hpp"),
-           os.path.join(CSRC, "sea_convfrag.hpp"), os.path.join(CSRC, "sea_performer16.hpp"), os.path.join(CSRC, "sea_kd_pix.hpp"),
+           os.path.join(CSRC, "sea_convfrag.hpp"), os.path.join(CSRC, "sea_performer16.hpp"), os.path.join(CSRC, "sea_kd.hpp"),
            os.path.join(CSRC, "sea_tail_select_row.inc"),
            os.path.join(CSRC, "sea_tail_select_row_gen.inc"),
            os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip.h"),

@@ -81,22 +81,14 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # include/sea_hip_train.h: the training-side entries, additive beside the inference ABI above and versioned on their own
-TRAIN_ABI_VERSION = 1      # SEA_TRAIN_ABI_VERSION
+TRAIN_ABI_VERSION = 2      # SEA_TRAIN_ABI_VERSION
+_TEACHER = [ptr, c_int, _i64p, ptr, ptr, c_int, _i64p, _i64p]      # truth, its dtype and strides; teacher_q, teacher_k, theirs
 _TRAIN_SIGNATURES = {
     "sea_train_version": ([], c_int),
-    "sea_kd_estimator_loss": ([ptr, c_int, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
+    "sea_kd_estimator_loss": ([ptr, c_int, _i64p, *_TEACHER, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
     "sea_kd_estimator_loss_bwd": ([ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr], c_int),
-    # (added without a bump of the version above: include/sea_hip_train.h says why)
-    "sea_kd_score_loss": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
-    "sea_kd_score_loss_bwd": ([ptr, ptr, c_int, _i64p, _i64p, ptr, c_int, _i64p, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr, ptr],
-                              c_int),
-    # t5 - t7, the same entries with the teacher as q_t, k_t instead of the score tensor (also without a bump)
-    "sea_kd_estimator_loss_qk": ([ptr, c_int, _i64p, ptr, ptr, c_int, _i64p, _i64p, i64, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr],
-                                 c_int),
-    "sea_kd_score_loss_qk": ([ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, c_int, _i64p, _i64p, i64, i64, i64, i64, ptr, ptr, ptr, ptr,
-                              ptr], c_int),
-    "sea_kd_score_loss_qk_bwd": ([ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, c_int, _i64p, _i64p, ptr, ptr, ptr, i64, i64, i64, i64,
-                                  ptr, ptr, ptr], c_int),
+    "sea_kd_score_loss": ([ptr, ptr, c_int, _i64p, _i64p, *_TEACHER, i64, i64, i64, i64, ptr, ptr, ptr, ptr, ptr], c_int),
+    "sea_kd_score_loss_bwd": ([ptr, ptr, c_int, _i64p, _i64p, *_TEACHER, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr, ptr], c_int),
 }
 
 

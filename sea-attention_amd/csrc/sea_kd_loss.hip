@@ -9,7 +9,7 @@
 // needs the key counts c_b, the teacher's probability mass per pixel G_b and a few scalars: the forward reads the causal half
 // of the teacher's scores once, the backward is T_M wide.
 #include "sea_common.hpp"
-#include "sea_kd_pix.hpp"             // kd_pix, kd_first, KD_MAX_TM, KD_MAX_T
+#include "sea_kd.hpp"                 // kd_pix, kd_first, KD_MAX_TM, KD_MAX_T, the host checks
 #include "../../include/sea_hip_train.h"
 
 namespace sea {
@@ -224,23 +224,15 @@ __global__ __launch_bounds__(256) void kd_loss_bwd_kernel(const TE* est, int64_t
   }
 }
 
-static int kd_check_common(const char* nm, int est_dtype, const int64_t* est_strides, const void* est, int64_t N, int64_t H,
-                           int64_t T, int64_t T_m) {
-  SEA_REQUIRE(est_dtype == SEA_F32 || est_dtype == SEA_F16 || est_dtype == SEA_BF16, SEA_EINVAL, "%s: bad est dtype %d", nm,
-              est_dtype);
-  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && T_m > 0, SEA_EINVAL, "%s: bad shape N=%lld H=%lld T=%lld T_m=%lld", nm, (long long)N,
-              (long long)H, (long long)T, (long long)T_m);
-  SEA_REQUIRE(T_m % 4 == 0 && T_m <= KD_MAX_TM, SEA_EUNSUPPORTED, "%s: T_m=%lld (needs T_m %% 4 == 0 and T_m <= %d)", nm,
-              (long long)T_m, KD_MAX_TM);
-  SEA_REQUIRE(T <= KD_MAX_T, SEA_EUNSUPPORTED, "%s: T=%lld (needs T <= %d)", nm, (long long)T, KD_MAX_T);
-  SEA_REQUIRE(N * H * ((T + 1) / 2) < (1ll << 31), SEA_EUNSUPPORTED, "%s: grid too large", nm);
-  SEA_REQUIRE(est_strides[0] >= 0 && est_strides[1] >= 0 && est_strides[2] >= T_m, SEA_EINVAL,
-              "%s: bad est strides {%lld, %lld, %lld} for rows of %lld", nm, (long long)est_strides[0], (long long)est_strides[1],
-              (long long)est_strides[2], (long long)T_m);
-  const int ev = est_dtype == SEA_F32 ? 4 : 8;
-  SEA_REQUIRE(((uintptr_t)est & 15) == 0 && est_strides[0] % ev == 0 && est_strides[1] % ev == 0 && est_strides[2] % ev == 0,
-              SEA_EUNSUPPORTED, "%s: est rows must be 16-byte aligned", nm);
-  return SEA_OK;
+// What t1 and t2 check alike: est, the shape and the limits.  `block_rows`: rows per workgroup of the kernel that will run
+static int kd_check_est(const char* nm, const void* est, int est_dtype, const int64_t* est_strides, int64_t N, int64_t H,
+                        int64_t T, int64_t T_m, int block_rows) {
+  int rc = kd_check_nulls(nm, {KdArg{"est", est}, {"est_strides", est_strides}});
+  if (rc == SEA_OK) rc = kd_check_dtype(nm, "est_dtype", "est", est_dtype, true);
+  if (rc == SEA_OK) rc = kd_check_shape(nm, N, H, T, block_rows);
+  if (rc == SEA_OK) rc = kd_check_tm(nm, T_m);
+  if (rc == SEA_OK) rc = kd_check_rows(nm, {KdRows{"est", est, est_strides, T_m, est_dtype}});
+  return rc;
 }
 
 template <typename TE, typename TX> static int kd_launch_fwd(const char* nm, const KdParams& p, hipStream_t s) {
@@ -279,21 +271,26 @@ using namespace sea;
 extern "C" int sea_train_version(void) { return SEA_TRAIN_ABI_VERSION; }
 
 extern "C" int sea_kd_estimator_loss(const void* est, int est_dtype, const int64_t* est_strides, const void* truth, int truth_dtype,
-                                     const int64_t* truth_strides, int64_t N, int64_t H, int64_t T, int64_t T_m, float* row_kl,
-                                     float* row_mse, float* pix_tgt, float* row_stats, sea_stream_t stream) {
+                                     const int64_t* truth_strides, const void* teacher_q, const void* teacher_k, int teacher_dtype,
+                                     const int64_t* teacher_q_strides, const int64_t* teacher_k_strides, int64_t N, int64_t H,
+                                     int64_t T, int64_t T_m, int64_t D, float* row_kl, float* row_mse, float* pix_tgt,
+                                     float* row_stats, sea_stream_t stream) {
   const char* nm = "sea_kd_estimator_loss";
-  SEA_REQUIRE(est && est_strides && truth && truth_strides && row_kl && row_mse && pix_tgt && row_stats, SEA_EINVAL,
-              "%s: null pointer", nm);
-  SEA_REQUIRE(truth_dtype == SEA_F32 || truth_dtype == SEA_F16 || truth_dtype == SEA_BF16, SEA_EINVAL, "%s: bad truth dtype %d",
-              nm, truth_dtype);
-  const int rc = kd_check_common(nm, est_dtype, est_strides, est, N, H, T, T_m);
+  const bool factored = !truth;                    // then the tile kernel runs, and D is the teacher's head size
+  int rc = kd_check_est(nm, est, est_dtype, est_strides, N, H, T, T_m, factored ? KS_TILE : 2);
+  if (rc == SEA_OK && factored) rc = kd_check_head(nm, D);
+  if (rc == SEA_OK)
+    rc = kd_check_teacher(nm, truth, truth_dtype, truth_strides, teacher_q, teacher_k, teacher_dtype, teacher_q_strides,
+                          teacher_k_strides, -1, T, D);
+  if (rc == SEA_OK)
+    rc = kd_check_nulls(nm, {KdArg{"row_kl", row_kl}, {"row_mse", row_mse}, {"pix_tgt", pix_tgt}, {"row_stats", row_stats}});
   if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(truth_strides[0] >= 0 && truth_strides[1] >= 0 && truth_strides[2] >= T, SEA_EINVAL,
-              "%s: bad truth strides {%lld, %lld, %lld} for rows of %lld", nm, (long long)truth_strides[0],
-              (long long)truth_strides[1], (long long)truth_strides[2], (long long)T);
-  const int xv = truth_dtype == SEA_F32 ? 4 : 8;
-  SEA_REQUIRE(((uintptr_t)truth & 15) == 0 && truth_strides[0] % xv == 0 && truth_strides[1] % xv == 0 && truth_strides[2] % xv == 0,
-              SEA_EUNSUPPORTED, "%s: truth rows must be 16-byte aligned", nm);
+  hipStream_t s = (hipStream_t)stream;
+  if (factored) {
+    SEA_REQUIRE(((uintptr_t)row_stats & 7) == 0, SEA_EINVAL, "%s: row_stats must be 8-byte aligned", nm);
+    return kdq_launch_fwd(nm, est, est_dtype, est_strides, teacher_q, teacher_k, teacher_dtype, teacher_q_strides,
+                          teacher_k_strides, N, H, T, T_m, D, row_kl, row_mse, pix_tgt, row_stats, s);
+  }
   KdParams p;
   p.est = est;
   p.truth = truth;
@@ -301,7 +298,6 @@ extern "C" int sea_kd_estimator_loss(const void* est, int est_dtype, const int64
   p.xsn = truth_strides[0]; p.xsh = truth_strides[1]; p.xst = truth_strides[2];
   p.N = (int)N; p.H = (int)H; p.T = (int)T; p.T_M = (int)T_m;
   p.row_kl = row_kl; p.row_mse = row_mse; p.pix_tgt = pix_tgt; p.row_stats = row_stats;
-  hipStream_t s = (hipStream_t)stream;
   if (est_dtype == SEA_F32) return kd_launch_fwd_x<float>(nm, truth_dtype, p, s);
   if (est_dtype == SEA_F16) return kd_launch_fwd_x<__half>(nm, truth_dtype, p, s);
   return kd_launch_fwd_x<__hip_bfloat16>(nm, truth_dtype, p, s);
@@ -311,8 +307,9 @@ extern "C" int sea_kd_estimator_loss_bwd(const void* est, int est_dtype, const i
                                          const float* row_stats, const float* grad_loss, int64_t N, int64_t H, int64_t T,
                                          int64_t T_m, void* d_est, sea_stream_t stream) {
   const char* nm = "sea_kd_estimator_loss_bwd";
-  SEA_REQUIRE(est && est_strides && pix_tgt && row_stats && grad_loss && d_est, SEA_EINVAL, "%s: null pointer", nm);
-  const int rc = kd_check_common(nm, est_dtype, est_strides, est, N, H, T, T_m);
+  int rc = kd_check_est(nm, est, est_dtype, est_strides, N, H, T, T_m, 2);
+  if (rc == SEA_OK)
+    rc = kd_check_nulls(nm, {KdArg{"pix_tgt", pix_tgt}, {"row_stats", row_stats}, {"grad_loss", grad_loss}, {"d_est", d_est}});
   if (rc != SEA_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (est_dtype == SEA_F32) return kd_launch_bwd<float>(nm, est, est_strides, pix_tgt, row_stats, grad_loss, N, H, T, T_m, d_est, s);

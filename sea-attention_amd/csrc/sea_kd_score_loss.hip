@@ -15,21 +15,20 @@
 // are, eight at a time, the B operand of the gradient's MFMA (k = 8 (l >> 4) + j stands for swept index 16 (l >> 4) + 8 u + j in
 // k-step u; the A operand is read from a transposed LDS image with the same numbering), so dS never leaves registers either.
 //
-// The teacher may come factored (t5 - t7: `KsQK` in place of the type of the score tensor): its q and k of the student's
+// The teacher may come factored (truth == NULL: `KsQK` in place of the type of the score tensor): its q and k of the student's
 // type and head size.  Then the teacher's tile is staged in a second row image beside the student's, the teacher's own
 // fragments are loaded like the student's, and x is a second score tile in the same lane map -- same indexing, same
 // instructions, so a teacher that holds the student's bits gives the student's scores bit for bit.  Nothing T x T is read.
-// The estimator's term (t5, `kdq_fwd_kernel` below) runs on the same tile body with the teacher's tile alone.
+// The estimator's term with the factored teacher (t1, `kdq_fwd_kernel` below) runs on the same tile body with the teacher's tile
+// alone.
 #include <type_traits>
 
 #include "sea_common.hpp"
-#include "sea_kd_pix.hpp"
+#include "sea_kd.hpp"                 // kd_pix, kd_first, KS_TILE, the host checks
 #include "../../include/sea_hip_train.h"
 
 namespace sea {
 
-constexpr int KS_MAX_T = 16384;
-constexpr int KS_TILE = 64;                        // swept indices per tile; also own indices per workgroup (4 waves x 16)
 constexpr int KS_THREADS = 256;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 ks_bf8;
@@ -179,6 +178,23 @@ __device__ inline void ks_truth_keys(const TX* xrow, int t, int Tn, int s0, floa
   }
 }
 
+// The per-tile prologue of a sweep that stages one swept tile and reads nothing else: barrier, tile `i0 / 64` of `src` into
+// `s_row`, barrier, the score tile.  (The score kernels keep their own lines: they stage a second tile or a transposed image,
+// and issue the loads of truth between staging and the second barrier, so that they are in flight during it.)
+template <typename T, int D>
+__device__ inline void ks_sweep_tile(const T* src, int64_t st, int i0, int Tn, unsigned short* s_row,
+                                     const uint4 (&own)[KsGeo<D>::KK], int lane, float (&s)[16]) {
+  __syncthreads();
+  ks_stage<T, D, false>(src, st, i0, Tn, s_row, nullptr);
+  __syncthreads();
+  ks_scores<T, D>(s_row, own, lane, s);
+}
+
+// The finish of sweep 1 across the four lanes of an own index: from a lane's running maximum m and its sum l of exp(score - m)
+// over its keys, and the row's maximum M = ks_own_max(m), the row's sum of exp(score - M).  A lane that met no key <= t adds 0.
+// (The update inside the sweep stays written out where it is: folded into a helper it moved the forward's register allocation.)
+__device__ inline float ks_online_sum(float m, float l, float M) { return ks_own_sum(m > -INFINITY ? l * expf(m - M) : 0.f); }
+
 // block -> (index of the 64-block of own indices, (n, h)).  All (n, h) of one block index are neighbours in the grid, and the
 // grid starts with the longest sweeps (the causal triangle: block b of the queries sweeps b + 1 key tiles, block b of the keys
 // sweeps NB - b query tiles), so the launch ends on the short ones.
@@ -252,8 +268,7 @@ __global__ __launch_bounds__(KS_THREADS) void ks_fwd_kernel(KsParams p) {
     }
   }
   const float M = ks_own_max(ms), MX = ks_own_max(mx);
-  const float L = ks_own_sum(ms > -INFINITY ? ls * expf(ms - M) : 0.f);
-  const float LX = ks_own_sum(mx > -INFINITY ? lx * expf(mx - MX) : 0.f);
+  const float L = ks_online_sum(ms, ls, M), LX = ks_online_sum(mx, lx, MX);
   const float inv_l = 1.0f / L, log_l = logf(L), inv_lx = 1.0f / LX, log_lx = logf(LX);
 
   // sweep 2: the scores again, both probabilities, the three row sums key by key
@@ -425,7 +440,7 @@ __global__ __launch_bounds__(KS_THREADS) void ks_bwd_kernel(KsParams p) {
   }
 }
 
-// ---- the estimator's term on the tile body (t5) ---------------------------------------------------------------------------------
+// ---- the estimator's term on the tile body (t1 with the factored teacher) ---------------------------------------------------
 // Same outputs as sea_kd_loss.hip's forward (t1: row_kl, row_mse, pix_tgt, row_stats = {m_e, log S}; t2 then runs unchanged), the
 // teacher's scores recomputed from q_t, k_t instead of read.  A workgroup owns 64 queries and sweeps the key tiles 0 .. rb twice.
 //   before the sweeps  every wave takes its 16 queries one at a time, 64 lanes over the T_M pixels: c_b from kd_first, m_e and S
@@ -510,11 +525,8 @@ __global__ __launch_bounds__(KS_THREADS) void kdq_fwd_kernel(KdqParams p) {
   float mx = -INFINITY, lx = 0.f;
   for (int tile = 0; tile <= rb; ++tile) {
     const int s0 = tile * KS_TILE + 16 * g;
-    __syncthreads();
-    ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_row, nullptr);
-    __syncthreads();
     float xv[16];
-    ks_scores<T, D>(s_row, own, lane, xv);
+    ks_sweep_tile<T, D>(tk, p.tkst, tile * KS_TILE, p.T, s_row, own, lane, xv);
     float tx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -531,7 +543,7 @@ __global__ __launch_bounds__(KS_THREADS) void kdq_fwd_kernel(KdqParams p) {
     }
   }
   const float MX = ks_own_max(mx);
-  const float LX = ks_own_sum(mx > -INFINITY ? lx * expf(mx - MX) : 0.f);
+  const float LX = ks_online_sum(mx, lx, MX);
   const float inv_lx = 1.0f / LX, log_lx = logf(LX);
 
   // sweep 2
@@ -543,12 +555,9 @@ __global__ __launch_bounds__(KS_THREADS) void kdq_fwd_kernel(KdqParams p) {
   float cv = 0.f;
   for (int tile = 0; tile <= rb; ++tile) {
     const int s0 = tile * KS_TILE + 16 * g;
-    __syncthreads();
-    ks_stage<T, D, false>(tk, p.tkst, tile * KS_TILE, p.T, s_row, nullptr);
-    __syncthreads();
     float xv[16], ee[16];
     int px[16];
-    ks_scores<T, D>(s_row, own, lane, xv);
+    ks_sweep_tile<T, D>(tk, p.tkst, tile * KS_TILE, p.T, s_row, own, lane, xv);
     // the pixels of the lane's keys (< T_M for a key <= t; held below it for the addresses' sake) and, where the pixel changes,
     // its estimator score: all loads issued before the first is used
 #pragma unroll
@@ -630,102 +639,17 @@ __global__ __launch_bounds__(KS_THREADS) void kdq_fwd_kernel(KdqParams p) {
   }
 }
 
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-static int ks_check(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
-                    const void* truth, int truth_dtype, const int64_t* truth_strides, int64_t N, int64_t H, int64_t T, int64_t D) {
-  SEA_REQUIRE(q, SEA_EINVAL, "%s: q is null", nm);
-  SEA_REQUIRE(k, SEA_EINVAL, "%s: k is null", nm);
-  SEA_REQUIRE(q_strides, SEA_EINVAL, "%s: q_strides is null", nm);
-  SEA_REQUIRE(k_strides, SEA_EINVAL, "%s: k_strides is null", nm);
-  SEA_REQUIRE(truth, SEA_EINVAL, "%s: truth is null", nm);
-  SEA_REQUIRE(truth_strides, SEA_EINVAL, "%s: truth_strides is null", nm);
-  SEA_REQUIRE(qk_dtype != SEA_F32, SEA_EUNSUPPORTED, "%s: fp32 q / k (qk_dtype) is outside the kernels: 16-bit data only", nm);
-  SEA_REQUIRE(qk_dtype == SEA_F16 || qk_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown qk_dtype %d", nm, qk_dtype);
-  SEA_REQUIRE(truth_dtype == SEA_F32 || truth_dtype == SEA_F16 || truth_dtype == SEA_BF16, SEA_EUNSUPPORTED,
-              "%s: unknown truth_dtype %d", nm, truth_dtype);
-  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0, SEA_EINVAL, "%s: bad shape N=%lld H=%lld T=%lld D=%lld", nm, (long long)N,
-              (long long)H, (long long)T, (long long)D);
-  SEA_REQUIRE(D == 64 || D == 80 || D == 128, SEA_EUNSUPPORTED, "%s: D=%lld (needs D in {64, 80, 128})", nm, (long long)D);
-  SEA_REQUIRE(T <= KS_MAX_T, SEA_EUNSUPPORTED, "%s: T=%lld (needs T <= %d)", nm, (long long)T, KS_MAX_T);
-  SEA_REQUIRE(N * H * ((T + KS_TILE - 1) / KS_TILE) < (1ll << 31), SEA_EUNSUPPORTED, "%s: grid too large", nm);
-  const struct { const char* name; const void* ptr; const int64_t* s; int64_t row; int vec; } a[3] = {
-      {"q", q, q_strides, D, 8}, {"k", k, k_strides, D, 8}, {"truth", truth, truth_strides, T, truth_dtype == SEA_F32 ? 4 : 8}};
-  for (const auto& t : a) {
-    SEA_REQUIRE(t.s[0] >= 0 && t.s[1] >= 0 && t.s[2] >= t.row, SEA_EINVAL, "%s: bad %s strides {%lld, %lld, %lld} for rows of %lld",
-                nm, t.name, (long long)t.s[0], (long long)t.s[1], (long long)t.s[2], (long long)t.row);
-    SEA_REQUIRE(((uintptr_t)t.ptr & 15) == 0 && t.s[0] % t.vec == 0 && t.s[1] % t.vec == 0 && t.s[2] % t.vec == 0, SEA_EINVAL,
-                "%s: %s rows must be 16-byte aligned (base pointer and every stride)", nm, t.name);
-  }
-  return SEA_OK;
-}
-
-// t5 - t7: the factored teacher.  Null pointers, bad strides and misalignment are SEA_EINVAL, everything the kernels have no
-// form for is SEA_EUNSUPPORTED; `student_dtype` < 0: no student to agree with (t5)
-struct KsRows { const char* name; const void* ptr; const int64_t* s; int64_t row; int vec; };
-static int ks_check_rows(const char* nm, const KsRows* a, int count) {
-  for (int i = 0; i < count; ++i) {
-    const KsRows& t = a[i];
-    SEA_REQUIRE(t.s[0] >= 0 && t.s[1] >= 0 && t.s[2] >= t.row, SEA_EINVAL, "%s: bad %s strides {%lld, %lld, %lld} for rows of %lld",
-                nm, t.name, (long long)t.s[0], (long long)t.s[1], (long long)t.s[2], (long long)t.row);
-    SEA_REQUIRE(((uintptr_t)t.ptr & 15) == 0 && t.s[0] % t.vec == 0 && t.s[1] % t.vec == 0 && t.s[2] % t.vec == 0, SEA_EINVAL,
-                "%s: %s rows must be 16-byte aligned (base pointer and every stride)", nm, t.name);
-  }
-  return SEA_OK;
-}
-static int ks_check_teacher(const char* nm, const void* tq, const void* tk, int teacher_dtype, const int64_t* tq_strides,
-                            const int64_t* tk_strides, int student_dtype, int64_t N, int64_t H, int64_t T, int64_t D) {
-  SEA_REQUIRE(tq, SEA_EINVAL, "%s: teacher_q is null", nm);
-  SEA_REQUIRE(tk, SEA_EINVAL, "%s: teacher_k is null", nm);
-  SEA_REQUIRE(tq_strides, SEA_EINVAL, "%s: teacher_q_strides is null", nm);
-  SEA_REQUIRE(tk_strides, SEA_EINVAL, "%s: teacher_k_strides is null", nm);
-  SEA_REQUIRE(teacher_dtype != SEA_F32, SEA_EUNSUPPORTED,
-              "%s: fp32 teacher q / k (teacher_dtype) is outside the kernels: 16-bit data only", nm);
-  SEA_REQUIRE(teacher_dtype == SEA_F16 || teacher_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown teacher_dtype %d", nm,
-              teacher_dtype);
-  SEA_REQUIRE(student_dtype < 0 || teacher_dtype == student_dtype, SEA_EUNSUPPORTED,
-              "%s: teacher_dtype %d is not qk_dtype %d (the teacher's q / k must have the student's type)", nm, teacher_dtype,
-              student_dtype);
-  SEA_REQUIRE(N > 0 && H > 0 && T > 0 && D > 0, SEA_EINVAL, "%s: bad shape N=%lld H=%lld T=%lld D=%lld", nm, (long long)N,
-              (long long)H, (long long)T, (long long)D);
-  SEA_REQUIRE(D == 64 || D == 80 || D == 128, SEA_EUNSUPPORTED, "%s: D=%lld (needs D in {64, 80, 128})", nm, (long long)D);
-  SEA_REQUIRE(T <= KS_MAX_T, SEA_EUNSUPPORTED, "%s: T=%lld (needs T <= %d)", nm, (long long)T, KS_MAX_T);
-  SEA_REQUIRE(N * H * ((T + KS_TILE - 1) / KS_TILE) < (1ll << 31), SEA_EUNSUPPORTED, "%s: grid too large", nm);
-  const KsRows a[2] = {{"teacher_q", tq, tq_strides, D, 8}, {"teacher_k", tk, tk_strides, D, 8}};
-  return ks_check_rows(nm, a, 2);
-}
-static int ks_check_student(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides,
-                            const int64_t* k_strides, int64_t D) {
-  SEA_REQUIRE(q, SEA_EINVAL, "%s: q is null", nm);
-  SEA_REQUIRE(k, SEA_EINVAL, "%s: k is null", nm);
-  SEA_REQUIRE(q_strides, SEA_EINVAL, "%s: q_strides is null", nm);
-  SEA_REQUIRE(k_strides, SEA_EINVAL, "%s: k_strides is null", nm);
-  SEA_REQUIRE(qk_dtype != SEA_F32, SEA_EUNSUPPORTED, "%s: fp32 q / k (qk_dtype) is outside the kernels: 16-bit data only", nm);
-  SEA_REQUIRE(qk_dtype == SEA_F16 || qk_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown qk_dtype %d", nm, qk_dtype);
-  const KsRows a[2] = {{"q", q, q_strides, D, 8}, {"k", k, k_strides, D, 8}};
-  return ks_check_rows(nm, a, 2);
-}
-
-static KsParams ks_params(const void* q, const void* k, const int64_t* qs, const int64_t* ks, const void* truth, const int64_t* xs,
-                          int64_t N, int64_t H, int64_t T) {
-  KsParams p = {};
-  p.q = q; p.k = k; p.truth = truth;
-  p.qsn = qs[0]; p.qsh = qs[1]; p.qst = qs[2];
-  p.ksn = ks[0]; p.ksh = ks[1]; p.kst = ks[2];
-  p.xsn = xs[0]; p.xsh = xs[1]; p.xst = xs[2];
-  p.N = (int)N; p.H = (int)H; p.T = (int)T;
-  return p;
-}
-
-static inline unsigned ks_grid(const KsParams& p) { return (unsigned)((int64_t)p.N * p.H * ((p.T + KS_TILE - 1) / KS_TILE)); }
-
 template <typename T, typename TX, int D> static int ks_launch(const char* nm, bool bwd, const KsParams& p, hipStream_t s) {
+  const dim3 grid((unsigned)((int64_t)p.N * p.H * ((p.T + KS_TILE - 1) / KS_TILE)));
   if (!bwd) {
-    hipLaunchKernelGGL((ks_fwd_kernel<T, TX, D>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    hipLaunchKernelGGL((ks_fwd_kernel<T, TX, D>), grid, dim3(KS_THREADS), 0, s, p);
     SEA_CHECK_LAUNCH(nm);
   } else {
-    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, false>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, false>), grid, dim3(KS_THREADS), 0, s, p);
     SEA_CHECK_LAUNCH(nm);
-    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, true>), dim3(ks_grid(p)), dim3(KS_THREADS), 0, s, p);
+    hipLaunchKernelGGL((ks_bwd_kernel<T, TX, D, true>), grid, dim3(KS_THREADS), 0, s, p);
     SEA_CHECK_LAUNCH(nm);
   }
   return SEA_OK;
@@ -735,17 +659,48 @@ template <typename T, typename TX> static int ks_launch_d(const char* nm, bool b
   if (D == 80) return ks_launch<T, TX, 80>(nm, bwd, p, s);
   return ks_launch<T, TX, 128>(nm, bwd, p, s);
 }
-template <typename T> static int ks_launch_qk(const char* nm, bool bwd, int64_t D, const KsParams& p, hipStream_t s) {
-  return ks_launch_d<T, KsQK>(nm, bwd, D, p, s);
-}
-template <typename T> static int ks_launch_x(const char* nm, bool bwd, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
+template <typename T>
+static int ks_launch_x(const char* nm, bool bwd, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
   if (truth_dtype == SEA_F32) return ks_launch_d<T, float>(nm, bwd, D, p, s);
   if (truth_dtype == SEA_F16) return ks_launch_d<T, __half>(nm, bwd, D, p, s);
   return ks_launch_d<T, __hip_bfloat16>(nm, bwd, D, p, s);
 }
 static int ks_dispatch(const char* nm, bool bwd, int qk_dtype, int truth_dtype, int64_t D, const KsParams& p, hipStream_t s) {
-  if (qk_dtype == SEA_F16) return ks_launch_x<__half>(nm, bwd, truth_dtype, D, p, s);
-  return ks_launch_x<__hip_bfloat16>(nm, bwd, truth_dtype, D, p, s);
+  if (p.truth) {
+    if (qk_dtype == SEA_F16) return ks_launch_x<__half>(nm, bwd, truth_dtype, D, p, s);
+    return ks_launch_x<__hip_bfloat16>(nm, bwd, truth_dtype, D, p, s);
+  }
+  if (qk_dtype == SEA_F16) return ks_launch_d<__half, KsQK>(nm, bwd, D, p, s);         // the factored teacher: the student's type
+  return ks_launch_d<__hip_bfloat16, KsQK>(nm, bwd, D, p, s);
+}
+
+// What t3 and t4 share: every check of the inputs and the kernel arguments made of them.  The entry adds its own outputs to `p`
+static int ks_inputs(const char* nm, const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
+                     const void* truth, int truth_dtype, const int64_t* truth_strides, const void* tq, const void* tk,
+                     int teacher_dtype, const int64_t* tq_strides, const int64_t* tk_strides, int64_t N, int64_t H, int64_t T,
+                     int64_t D, KsParams& p) {
+  int rc = kd_check_nulls(nm, {KdArg{"q", q}, {"k", k}, {"q_strides", q_strides}, {"k_strides", k_strides}});
+  if (rc == SEA_OK) rc = kd_check_dtype(nm, "qk_dtype", "q / k", qk_dtype, false);
+  if (rc == SEA_OK) rc = kd_check_shape(nm, N, H, T, KS_TILE);
+  if (rc == SEA_OK) rc = kd_check_head(nm, D);
+  if (rc == SEA_OK)
+    rc = kd_check_teacher(nm, truth, truth_dtype, truth_strides, tq, tk, teacher_dtype, tq_strides, tk_strides, qk_dtype, T, D);
+  if (rc == SEA_OK) rc = kd_check_rows(nm, {KdRows{"q", q, q_strides, D, qk_dtype}, {"k", k, k_strides, D, qk_dtype}});
+  if (rc != SEA_OK) return rc;
+  p = {};
+  p.q = q; p.k = k;
+  p.qsn = q_strides[0]; p.qsh = q_strides[1]; p.qst = q_strides[2];
+  p.ksn = k_strides[0]; p.ksh = k_strides[1]; p.kst = k_strides[2];
+  if (truth) {
+    p.truth = truth;
+    p.xsn = truth_strides[0]; p.xsh = truth_strides[1]; p.xst = truth_strides[2];
+  } else {                                         // (truth stays null: what ks_dispatch picks the KsQK kernels by)
+    p.tq = tq; p.tk = tk;
+    p.tqsn = tq_strides[0]; p.tqsh = tq_strides[1]; p.tqst = tq_strides[2];
+    p.tksn = tk_strides[0]; p.tksh = tk_strides[1]; p.tkst = tk_strides[2];
+  }
+  p.N = (int)N; p.H = (int)H; p.T = (int)T;
+  return SEA_OK;
 }
 
 template <typename TE, typename T> static int kdq_launch_d(const char* nm, int64_t D, const KdqParams& p, hipStream_t s) {
@@ -761,14 +716,22 @@ template <typename TE> static int kdq_launch(const char* nm, int teacher_dtype, 
   return kdq_launch_d<TE, __hip_bfloat16>(nm, D, p, s);
 }
 
-static KsParams ks_params_qk(const void* q, const void* k, const int64_t* qs, const int64_t* ks, const void* tq, const void* tk,
-                             const int64_t* tqs, const int64_t* tks, int64_t N, int64_t H, int64_t T) {
-  const int64_t none[3] = {0, 0, 0};
-  KsParams p = ks_params(q, k, qs, ks, nullptr, none, N, H, T);
-  p.tq = tq; p.tk = tk;
-  p.tqsn = tqs[0]; p.tqsh = tqs[1]; p.tqst = tqs[2];
-  p.tksn = tks[0]; p.tksh = tks[1]; p.tkst = tks[2];
-  return p;
+int kdq_launch_fwd(const char* nm, const void* est, int est_dtype, const int64_t* est_strides, const void* tq, const void* tk,
+                   int teacher_dtype, const int64_t* tq_strides, const int64_t* tk_strides, int64_t N, int64_t H, int64_t T,
+                   int64_t T_m, int64_t D, float* row_kl, float* row_mse, float* pix_tgt, float* row_stats, hipStream_t s) {
+  KdqParams p = {};
+  p.est = est; p.tq = tq; p.tk = tk;
+  p.esn = est_strides[0]; p.esh = est_strides[1]; p.est_t = est_strides[2];
+  p.tqsn = tq_strides[0]; p.tqsh = tq_strides[1]; p.tqst = tq_strides[2];
+  p.tksn = tk_strides[0]; p.tksh = tk_strides[1]; p.tkst = tk_strides[2];
+  p.N = (int)N; p.H = (int)H; p.T = (int)T; p.T_M = (int)T_m;
+  p.row_kl = row_kl; p.row_mse = row_mse; p.pix_tgt = pix_tgt; p.row_stats = row_stats;
+  // the empty pixels' zeros: the kernel stores the held pixels only, each exactly once
+  const hipError_t e = hipMemsetAsync(pix_tgt, 0, (size_t)(N * H * T * T_m) * sizeof(float), s);
+  SEA_REQUIRE(e == hipSuccess, SEA_ELAUNCH, "%s: clearing pix_tgt failed: %s", nm, hipGetErrorString(e));
+  if (est_dtype == SEA_F32) return kdq_launch<float>(nm, teacher_dtype, D, p, s);
+  if (est_dtype == SEA_F16) return kdq_launch<__half>(nm, teacher_dtype, D, p, s);
+  return kdq_launch<__hip_bfloat16>(nm, teacher_dtype, D, p, s);
 }
 
 }  // namespace sea
@@ -776,126 +739,39 @@ static KsParams ks_params_qk(const void* q, const void* k, const int64_t* qs, co
 using namespace sea;
 
 extern "C" int sea_kd_score_loss(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
-                                 const void* truth, int truth_dtype, const int64_t* truth_strides, int64_t N, int64_t H, int64_t T,
-                                 int64_t D, float* row_kl, float* row_mse, float* row_q, float* row_stats, sea_stream_t stream) {
+                                 const void* truth, int truth_dtype, const int64_t* truth_strides, const void* teacher_q,
+                                 const void* teacher_k, int teacher_dtype, const int64_t* teacher_q_strides,
+                                 const int64_t* teacher_k_strides, int64_t N, int64_t H, int64_t T, int64_t D, float* row_kl,
+                                 float* row_mse, float* row_q, float* row_stats, sea_stream_t stream) {
   const char* nm = "sea_kd_score_loss";
-  const int rc = ks_check(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, N, H, T, D);
+  KsParams p;
+  int rc = ks_inputs(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, teacher_q, teacher_k,
+                     teacher_dtype, teacher_q_strides, teacher_k_strides, N, H, T, D, p);
+  if (rc == SEA_OK)
+    rc = kd_check_nulls(nm, {KdArg{"row_kl", row_kl}, {"row_mse", row_mse}, {"row_q", row_q}, {"row_stats", row_stats}});
   if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
-  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
-  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
-  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
   SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0, SEA_EINVAL, "%s: row_stats must be 16-byte aligned", nm);
-  KsParams p = ks_params(q, k, q_strides, k_strides, truth, truth_strides, N, H, T);
   p.row_kl = row_kl; p.row_mse = row_mse; p.row_q = row_q; p.row_stats = row_stats;
   return ks_dispatch(nm, false, qk_dtype, truth_dtype, D, p, (hipStream_t)stream);
 }
 
 extern "C" int sea_kd_score_loss_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
-                                     const void* truth, int truth_dtype, const int64_t* truth_strides, const float* row_q,
-                                     const float* row_stats, const float* grad_loss, int64_t N, int64_t H, int64_t T, int64_t D,
-                                     void* d_q, void* d_k, sea_stream_t stream) {
+                                     const void* truth, int truth_dtype, const int64_t* truth_strides, const void* teacher_q,
+                                     const void* teacher_k, int teacher_dtype, const int64_t* teacher_q_strides,
+                                     const int64_t* teacher_k_strides, const float* row_q, const float* row_stats,
+                                     const float* grad_loss, int64_t N, int64_t H, int64_t T, int64_t D, void* d_q, void* d_k,
+                                     sea_stream_t stream) {
   const char* nm = "sea_kd_score_loss_bwd";
-  const int rc = ks_check(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, N, H, T, D);
+  KsParams p;
+  int rc = ks_inputs(nm, q, k, qk_dtype, q_strides, k_strides, truth, truth_dtype, truth_strides, teacher_q, teacher_k,
+                     teacher_dtype, teacher_q_strides, teacher_k_strides, N, H, T, D, p);
+  if (rc == SEA_OK)
+    rc = kd_check_nulls(nm,
+                        {KdArg{"row_q", row_q}, {"row_stats", row_stats}, {"grad_loss", grad_loss}, {"d_q", d_q}, {"d_k", d_k}});
   if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
-  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
-  SEA_REQUIRE(grad_loss, SEA_EINVAL, "%s: grad_loss is null", nm);
-  SEA_REQUIRE(d_q, SEA_EINVAL, "%s: d_q is null", nm);
-  SEA_REQUIRE(d_k, SEA_EINVAL, "%s: d_k is null", nm);
   SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0 && ((uintptr_t)d_q & 7) == 0 && ((uintptr_t)d_k & 7) == 0, SEA_EINVAL,
               "%s: row_stats must be 16-byte aligned, d_q and d_k 8-byte aligned", nm);
-  KsParams p = ks_params(q, k, q_strides, k_strides, truth, truth_strides, N, H, T);
   p.row_q = const_cast<float*>(row_q); p.row_stats = const_cast<float*>(row_stats);
   p.grad_loss = grad_loss; p.d_q = d_q; p.d_k = d_k;
   return ks_dispatch(nm, true, qk_dtype, truth_dtype, D, p, (hipStream_t)stream);
-}
-
-extern "C" int sea_kd_score_loss_qk(const void* q, const void* k, int qk_dtype, const int64_t* q_strides, const int64_t* k_strides,
-                                    const void* teacher_q, const void* teacher_k, int teacher_dtype,
-                                    const int64_t* teacher_q_strides, const int64_t* teacher_k_strides, int64_t N, int64_t H,
-                                    int64_t T, int64_t D, float* row_kl, float* row_mse, float* row_q, float* row_stats,
-                                    sea_stream_t stream) {
-  const char* nm = "sea_kd_score_loss_qk";
-  SEA_REQUIRE(q && k && q_strides && k_strides, SEA_EINVAL, "%s: %s is null", nm,
-              !q ? "q" : !k ? "k" : !q_strides ? "q_strides" : "k_strides");
-  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides,
-                            qk_dtype == SEA_F16 || qk_dtype == SEA_BF16 ? qk_dtype : -1, N, H, T, D);
-  if (rc != SEA_OK) return rc;
-  rc = ks_check_student(nm, q, k, qk_dtype, q_strides, k_strides, D);
-  if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
-  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
-  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
-  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
-  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0, SEA_EINVAL, "%s: row_stats must be 16-byte aligned", nm);
-  KsParams p = ks_params_qk(q, k, q_strides, k_strides, teacher_q, teacher_k, teacher_q_strides, teacher_k_strides, N, H, T);
-  p.row_kl = row_kl; p.row_mse = row_mse; p.row_q = row_q; p.row_stats = row_stats;
-  if (qk_dtype == SEA_F16) return ks_launch_qk<__half>(nm, false, D, p, (hipStream_t)stream);
-  return ks_launch_qk<__hip_bfloat16>(nm, false, D, p, (hipStream_t)stream);
-}
-
-extern "C" int sea_kd_score_loss_qk_bwd(const void* q, const void* k, int qk_dtype, const int64_t* q_strides,
-                                        const int64_t* k_strides, const void* teacher_q, const void* teacher_k, int teacher_dtype,
-                                        const int64_t* teacher_q_strides, const int64_t* teacher_k_strides, const float* row_q,
-                                        const float* row_stats, const float* grad_loss, int64_t N, int64_t H, int64_t T, int64_t D,
-                                        void* d_q, void* d_k, sea_stream_t stream) {
-  const char* nm = "sea_kd_score_loss_qk_bwd";
-  SEA_REQUIRE(q && k && q_strides && k_strides, SEA_EINVAL, "%s: %s is null", nm,
-              !q ? "q" : !k ? "k" : !q_strides ? "q_strides" : "k_strides");
-  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides,
-                            qk_dtype == SEA_F16 || qk_dtype == SEA_BF16 ? qk_dtype : -1, N, H, T, D);
-  if (rc != SEA_OK) return rc;
-  rc = ks_check_student(nm, q, k, qk_dtype, q_strides, k_strides, D);
-  if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(row_q, SEA_EINVAL, "%s: row_q is null", nm);
-  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
-  SEA_REQUIRE(grad_loss, SEA_EINVAL, "%s: grad_loss is null", nm);
-  SEA_REQUIRE(d_q, SEA_EINVAL, "%s: d_q is null", nm);
-  SEA_REQUIRE(d_k, SEA_EINVAL, "%s: d_k is null", nm);
-  SEA_REQUIRE(((uintptr_t)row_stats & 15) == 0 && ((uintptr_t)d_q & 7) == 0 && ((uintptr_t)d_k & 7) == 0, SEA_EINVAL,
-              "%s: row_stats must be 16-byte aligned, d_q and d_k 8-byte aligned", nm);
-  KsParams p = ks_params_qk(q, k, q_strides, k_strides, teacher_q, teacher_k, teacher_q_strides, teacher_k_strides, N, H, T);
-  p.row_q = const_cast<float*>(row_q); p.row_stats = const_cast<float*>(row_stats);
-  p.grad_loss = grad_loss; p.d_q = d_q; p.d_k = d_k;
-  if (qk_dtype == SEA_F16) return ks_launch_qk<__half>(nm, true, D, p, (hipStream_t)stream);
-  return ks_launch_qk<__hip_bfloat16>(nm, true, D, p, (hipStream_t)stream);
-}
-
-extern "C" int sea_kd_estimator_loss_qk(const void* est, int est_dtype, const int64_t* est_strides, const void* teacher_q,
-                                        const void* teacher_k, int teacher_dtype, const int64_t* teacher_q_strides,
-                                        const int64_t* teacher_k_strides, int64_t N, int64_t H, int64_t T, int64_t T_m, int64_t D,
-                                        float* row_kl, float* row_mse, float* pix_tgt, float* row_stats, sea_stream_t stream) {
-  const char* nm = "sea_kd_estimator_loss_qk";
-  SEA_REQUIRE(est, SEA_EINVAL, "%s: est is null", nm);
-  SEA_REQUIRE(est_strides, SEA_EINVAL, "%s: est_strides is null", nm);
-  int rc = ks_check_teacher(nm, teacher_q, teacher_k, teacher_dtype, teacher_q_strides, teacher_k_strides, -1, N, H, T, D);
-  if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(est_dtype == SEA_F32 || est_dtype == SEA_F16 || est_dtype == SEA_BF16, SEA_EUNSUPPORTED, "%s: unknown est_dtype %d",
-              nm, est_dtype);
-  SEA_REQUIRE(T_m > 0, SEA_EINVAL, "%s: bad shape T_m=%lld", nm, (long long)T_m);
-  SEA_REQUIRE(T_m % 4 == 0 && T_m <= KD_MAX_TM, SEA_EUNSUPPORTED, "%s: T_m=%lld (needs T_m %% 4 == 0 and T_m <= %d)", nm,
-              (long long)T_m, KD_MAX_TM);
-  const KsRows a[1] = {{"est", est, est_strides, T_m, est_dtype == SEA_F32 ? 4 : 8}};
-  rc = ks_check_rows(nm, a, 1);
-  if (rc != SEA_OK) return rc;
-  SEA_REQUIRE(row_kl, SEA_EINVAL, "%s: row_kl is null", nm);
-  SEA_REQUIRE(row_mse, SEA_EINVAL, "%s: row_mse is null", nm);
-  SEA_REQUIRE(pix_tgt, SEA_EINVAL, "%s: pix_tgt is null", nm);
-  SEA_REQUIRE(row_stats, SEA_EINVAL, "%s: row_stats is null", nm);
-  SEA_REQUIRE(((uintptr_t)row_stats & 7) == 0, SEA_EINVAL, "%s: row_stats must be 8-byte aligned", nm);
-  KdqParams p = {};
-  p.est = est; p.tq = teacher_q; p.tk = teacher_k;
-  p.esn = est_strides[0]; p.esh = est_strides[1]; p.est_t = est_strides[2];
-  p.tqsn = teacher_q_strides[0]; p.tqsh = teacher_q_strides[1]; p.tqst = teacher_q_strides[2];
-  p.tksn = teacher_k_strides[0]; p.tksh = teacher_k_strides[1]; p.tkst = teacher_k_strides[2];
-  p.N = (int)N; p.H = (int)H; p.T = (int)T; p.T_M = (int)T_m;
-  p.row_kl = row_kl; p.row_mse = row_mse; p.pix_tgt = pix_tgt; p.row_stats = row_stats;
-  hipStream_t s = (hipStream_t)stream;
-  // the empty pixels' zeros: the kernel stores the held pixels only, each exactly once
-  const hipError_t e = hipMemsetAsync(pix_tgt, 0, (size_t)(N * H * T * T_m) * sizeof(float), s);
-  SEA_REQUIRE(e == hipSuccess, SEA_ELAUNCH, "%s: clearing pix_tgt failed: %s", nm, hipGetErrorString(e));
-  if (est_dtype == SEA_F32) return kdq_launch<float>(nm, teacher_dtype, D, p, s);
-  if (est_dtype == SEA_F16) return kdq_launch<__half>(nm, teacher_dtype, D, p, s);
-  return kdq_launch<__hip_bfloat16>(nm, teacher_dtype, D, p, s);
 }

@@ -1,9 +1,17 @@
 """The teacher's attention scores in factored form: `TeacherScores(q, k)` stands for the (N,H,T,T) tensor q k^T without holding it.
 
 `ops.kd_estimator_loss` and `ops.kd_score_loss` (and their `_parts` / `_supported`) take it wherever they take the score tensor
-and then recompute the teacher's product tile by tile on the matrix cores (include/sea_hip_train.h t5 - t7); `PerlinAttention`
-takes it as `attention_scores_truth` and calls `.dense()` once on every path the factored kernels do not serve."""
+and then recompute the teacher's product tile by tile on the matrix cores (include/sea_hip_train.h, "the teacher");
+`PerlinAttention` takes it as `attention_scores_truth` and calls `.dense()` once on every path the factored kernels do not serve.
+
+The module is also the one place that knows both forms of the teacher: what either is to the `*_supported` predicates
+(`teacher_supported`), to the C entries (`teacher_args`) and to an error message (`teacher_tensors`)."""
 import torch
+
+from ... import _lib
+from .flat_csr import _p
+
+_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 
 
 class TeacherScores:
@@ -46,15 +54,45 @@ class TeacherScores:
         return f"TeacherScores(shape={tuple(self.shape)}, dtype={self.dtype}, device={self.device})"
 
 
-def qk_supported(ts, N, H, T, head_sizes, max_t, dtype=None):
-    """A device `TeacherScores` the factored kernels take for a student of (N,H,T): 16-bit (`dtype` if given), D in
-    `head_sizes`, rows 16-byte aligned"""
-    from .kd_loss import _rows_aligned
-    q, k = ts.q, ts.k
-    if not (q.is_cuda and k.is_cuda and q.device == k.device):
+def _rows_aligned(t):
+    vec = 4 if t.dtype == torch.float32 else 8
+    return (t.stride(-1) == 1 and t.stride(2) >= t.shape[-1] and all(s >= 0 and s % vec == 0 for s in t.stride()[:3])
+            and t.data_ptr() % 16 == 0)
+
+
+def teacher_supported(truth, device, N, H, T, head_sizes, max_t, dtype=None):
+    """The teacher's half of the `*_supported` predicates, for a student of (N,H,T) on `device`: the score tensor (N,H,T,T) of
+    fp32 / fp16 / bf16, or a `TeacherScores` whose q / k are 16-bit (`dtype` if given) with D in `head_sizes`; either way on
+    the device, with an innermost stride of 1 and 16-byte-aligned rows."""
+    factored = isinstance(truth, TeacherScores)
+    tensors = (truth.q, truth.k) if factored else (truth,)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dim() == 4 for t in tensors):
         return False
-    if tuple(q.shape[:3]) != (N, H, T) or q.shape[-1] not in head_sizes or T > max_t or min(N, H, T) < 1:
+    if T > max_t or min(N, H, T) < 1:
         return False
-    if q.dtype not in (torch.float16, torch.bfloat16) or (dtype is not None and q.dtype != dtype):
+    if factored:
+        q = truth.q
+        if tuple(q.shape[:3]) != (N, H, T) or q.shape[-1] not in head_sizes:
+            return False
+        if q.dtype not in (torch.float16, torch.bfloat16) or (dtype is not None and q.dtype != dtype):
+            return False
+    elif tuple(truth.shape) != (N, H, T, T) or truth.dtype not in _DTYPES:
         return False
-    return _rows_aligned(q) and _rows_aligned(k)
+    return all(_rows_aligned(t) for t in tensors)
+
+
+def teacher_tensors(truth):
+    """(the device tensors of either form, how an error message shows them)"""
+    if isinstance(truth, TeacherScores):
+        q, k = truth.q, truth.k
+        return (q, k), f"teacher q {tuple(q.shape)} {q.dtype} strides {q.stride()}, k strides {k.stride()}"
+    return (truth,), f"truth {tuple(truth.shape)} {truth.dtype} strides {truth.stride()}"
+
+
+def teacher_args(truth):
+    """The eight teacher arguments of the C entries: truth, its dtype and strides, teacher_q, teacher_k, their dtype and strides,
+    None / 0 for the form that is not given."""
+    if isinstance(truth, TeacherScores):
+        q, k = truth.q, truth.k
+        return None, 0, None, _p(q), _p(k), _lib.dtype_code(q.dtype), _lib.strides3(q), _lib.strides3(k)
+    return _p(truth), _lib.dtype_code(truth.dtype), _lib.strides3(truth), None, None, 0, None, None

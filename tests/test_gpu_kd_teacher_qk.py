@@ -1,5 +1,5 @@
 """-m gpu: the distillation losses with the teacher factored -- `ops.kd_score_loss` / `ops.kd_estimator_loss` handed an
-`ops.TeacherScores(q_t, k_t)` (include/sea_hip_train.h t5 - t7, csrc/sea_kd_score_loss.hip) -- against the fp64 closed forms of
+`ops.TeacherScores(q_t, k_t)` (include/sea_hip_train.h "the teacher", csrc/sea_kd_score_loss.hip) -- against the fp64 closed forms of
 the two existing suites on the fp64 teacher product.
 
 Kernel tier.  References: `KdScoreReference(q, k, q_t k_t^T)` and `KdReference(est, q_t k_t^T)`, the product in fp64 from the

@@ -5,17 +5,11 @@
 G_b and per-row scalars.  It is held here to fp64 `torch.autograd` through `_kl_and_mse` over `resize_from_m_to_t(...,
 oversampled=1.0)`, so that the GPU test's reference (tests/test_gpu_kd_loss.py imports this class and the yardstick below) does
 not rest on the comments of the file under test.  Also here: pix is non-decreasing along every row, the comparison the GPU test
-makes can fail (a witness with one key dropped per pixel), and the two new C entries refuse bad arguments before any launch
-while the 38-entry inference ABI stays what it was."""
-import ctypes
-import os
-import re
-
+makes can fail (a witness with one key dropped per pixel).  The C entries themselves: tests/test_kd_abi.py."""
 import pytest
 import torch
 import torch.nn.functional as F
 
-from sea_attention_amd import _lib
 from sea_attention_amd.perlin_attention import ops
 from sea_attention_amd.perlin_attention.attention import _kl_and_mse
 
@@ -173,90 +167,6 @@ def test_dropping_one_key_per_pixel_is_seen():
     rows = dropped.amax(-1) >= 1e-3
     assert rows.sum().item() > 100
     assert (moved[rows] > 10 * bar).double().mean().item() >= 0.9, (bar, moved[rows].min().item())
-
-
-# ---- the C ABI: two additive entries with a version of their own; the inference ABI untouched ---------------------------
-EINVAL, EUNSUPPORTED = -1, -2
-A = ctypes.c_void_p(1 << 20)                     # 16-byte aligned, never dereferenced (the entries refuse first)
-B = ctypes.c_void_p((1 << 20) + 4096)
-ODD = ctypes.c_void_p((1 << 20) + 8)
-
-
-def _s(*v):
-    return (ctypes.c_int64 * len(v))(*v)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.sea_last_error().decode()
-
-
-def test_train_entries_are_declared_bound_and_apart_from_the_inference_abi(lib):
-    root = os.path.join(os.path.dirname(__file__), "..")
-    train = open(os.path.join(root, "include", "sea_hip_train.h")).read()
-    main = open(os.path.join(root, "include", "sea_hip.h")).read()
-    assert re.search(r"#define\s+SEA_TRAIN_ABI_VERSION\s+1\b", train) and re.search(r"#define\s+SEA_ABI_VERSION\s+6\b", main)
-    assert lib.sea_train_version() == 1 == _lib.TRAIN_ABI_VERSION
-    assert lib.sea_version() == 6 == _lib.ABI_VERSION
-    for name in ("sea_train_version", "sea_kd_estimator_loss", "sea_kd_estimator_loss_bwd"):
-        assert re.search(r"^int %s\(" % name, train, re.M), name
-        assert name in _lib._TRAIN_SIGNATURES and hasattr(lib, name)
-        assert getattr(lib, name).argtypes == _lib._TRAIN_SIGNATURES[name][0]
-        assert name not in _lib.EXPORTED_SYMBOLS and name not in main
-    declared = sorted(set(re.findall(r"\b(sea_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S))))
-    assert len(declared) == 38 and sorted(_lib.EXPORTED_SYMBOLS) == declared
-    from sea_attention_amd import _build
-    assert any(h.endswith("sea_hip_train.h") for h in _build.HEADERS) and "sea_kd_loss.hip" in _build.SOURCES
-
-
-def test_kd_estimator_loss_refusals(lib):
-    nm = "sea_kd_estimator_loss"
-    N, H, T, T_M = 1, 2, 64, 32
-
-    def call(est=A, truth=B, es=None, xs=None, ed=_lib.SEA_BF16, xd=_lib.SEA_BF16, T=T, T_M=T_M, row_kl=A, row_mse=A, pix_tgt=A,
-             row_stats=A, no_es=False, no_xs=False):
-        es = None if no_es else (es or _s(H * T * T_M, T * T_M, T_M))
-        xs = None if no_xs else (xs or _s(H * T * T, T * T, T))
-        return lib.sea_kd_estimator_loss(est, ed, es, truth, xd, xs, N, H, T, T_M, row_kl, row_mse, pix_tgt, row_stats, None)
-    for name in ("est", "truth", "row_kl", "row_mse", "pix_tgt", "row_stats"):
-        assert call(**{name: None}) == EINVAL and f"{nm}: null pointer" in _err(lib), name
-    assert call(no_es=True) == EINVAL and f"{nm}: null pointer" in _err(lib)
-    assert call(no_xs=True) == EINVAL and f"{nm}: null pointer" in _err(lib)
-    assert call(ed=7) == EINVAL and f"{nm}: bad est dtype 7" in _err(lib)
-    assert call(xd=-1) == EINVAL and f"{nm}: bad truth dtype -1" in _err(lib)
-    assert call(T=0) == EINVAL and f"{nm}: bad shape" in _err(lib)
-    assert call(es=_s(H * T * T_M, T * T_M, T_M - 8)) == EINVAL and f"{nm}: bad est strides" in _err(lib)      # rows overlap
-    assert call(xs=_s(H * T * T, T * T, T - 8)) == EINVAL and f"{nm}: bad truth strides" in _err(lib)
-    assert call(xs=_s(-8, T * T, T)) == EINVAL and f"{nm}: bad truth strides" in _err(lib)
-    assert call(T_M=30) == EUNSUPPORTED and f"{nm}: T_m=30" in _err(lib)
-    assert call(T_M=516) == EUNSUPPORTED and f"{nm}: T_m=516" in _err(lib)
-    assert call(T=16385) == EUNSUPPORTED and f"{nm}: T=16385" in _err(lib)
-    assert call(est=ODD) == EUNSUPPORTED and f"{nm}: est rows must be 16-byte aligned" in _err(lib)
-    assert call(truth=ODD) == EUNSUPPORTED and f"{nm}: truth rows must be 16-byte aligned" in _err(lib)
-    assert call(xs=_s(H * T * T, T * T, T + 4)) == EUNSUPPORTED and "truth rows must be 16-byte aligned" in _err(lib)   # bf16: 8 bytes
-
-
-def test_kd_estimator_loss_bwd_refusals(lib):
-    nm = "sea_kd_estimator_loss_bwd"
-    N, H, T, T_M = 1, 2, 64, 32
-
-    def call(est=A, es=None, ed=_lib.SEA_F16, pix_tgt=B, row_stats=B, grad=B, d_est=B, T=T, T_M=T_M, no_es=False):
-        es = None if no_es else (es or _s(H * T * T_M, T * T_M, T_M))
-        return lib.sea_kd_estimator_loss_bwd(est, ed, es, pix_tgt, row_stats, grad, N, H, T, T_M, d_est, None)
-    for name in ("est", "pix_tgt", "row_stats", "grad", "d_est"):
-        assert call(**{name: None}) == EINVAL and f"{nm}: null pointer" in _err(lib), name
-    assert call(no_es=True) == EINVAL and f"{nm}: null pointer" in _err(lib)
-    assert call(ed=3) == EINVAL and f"{nm}: bad est dtype 3" in _err(lib)
-    assert call(es=_s(H * T * T_M, T * T_M, 8)) == EINVAL and f"{nm}: bad est strides" in _err(lib)
-    assert call(T_M=30) == EUNSUPPORTED and f"{nm}: T_m=30" in _err(lib)
-    assert call(T_M=516) == EUNSUPPORTED and f"{nm}: T_m=516" in _err(lib)
-    assert call(T=16385) == EUNSUPPORTED and f"{nm}: T=16385" in _err(lib)
-    assert call(est=ODD) == EUNSUPPORTED and f"{nm}: est rows must be 16-byte aligned" in _err(lib)
-    assert call(es=_s(H * T * T_M, T * T_M, T_M + 4)) == EUNSUPPORTED and "16-byte aligned" in _err(lib)
 
 
 def test_ops_are_exported_and_refuse_what_the_kernels_do_not_take():

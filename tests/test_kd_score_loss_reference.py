@@ -5,18 +5,13 @@
 the header states.  It is held here to fp64 `torch.autograd` through `_kl_and_mse(q @ k^T, truth, mask)`, so that the GPU test's
 reference (tests/test_gpu_kd_score_loss.py imports this class and the yardstick below) does not rest on the comments of the
 file under test.  Also here: the comparison the GPU test makes can fail (two witnesses: a row that loses its diagonal key, and
-the padded k-step of head size 80 forgotten), and the two new C entries refuse bad arguments before any launch while the
-38-entry inference ABI and both version numbers stay what they were."""
-import ctypes
+the padded k-step of head size 80 forgotten).  The C entries themselves: tests/test_kd_abi.py."""
 import inspect
-import os
-import re
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from sea_attention_amd import _lib
 from sea_attention_amd.perlin_attention import PerlinAttention, ops
 from sea_attention_amd.perlin_attention.attention import _kl_and_mse
 from test_kd_loss_reference import FP_MIN16, FP_MIN32, bar_of, causal_rows_mask
@@ -156,92 +151,6 @@ def test_the_comparison_can_fail(shape, dtype):
             frac = (moved > 10 * bars[nm]).double().mean().item()
             print(f"[kd-score-witness] {shape} {nm} columns 64 .. 79 dropped: {frac:.3f} of the rows t >= 8")
             assert frac == 1.0, (nm, frac, bars[nm], moved.min().item())
-
-
-# ---- the C ABI: two more additive entries; both version numbers and the inference ABI untouched --------------------------
-EINVAL, EUNSUPPORTED = -1, -2
-A = ctypes.c_void_p(1 << 20)                     # 16-byte aligned, never dereferenced (the entries refuse first)
-B = ctypes.c_void_p((1 << 20) + 4096)
-ODD = ctypes.c_void_p((1 << 20) + 8)
-NAMES = ("sea_kd_score_loss", "sea_kd_score_loss_bwd")
-
-
-def _s(*v):
-    return (ctypes.c_int64 * len(v))(*v)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.sea_last_error().decode()
-
-
-def test_score_entries_are_declared_bound_and_apart_from_the_inference_abi(lib):
-    root = os.path.join(os.path.dirname(__file__), "..")
-    train = open(os.path.join(root, "include", "sea_hip_train.h")).read()
-    main = open(os.path.join(root, "include", "sea_hip.h")).read()
-    assert re.search(r"#define\s+SEA_TRAIN_ABI_VERSION\s+1\b", train) and re.search(r"#define\s+SEA_ABI_VERSION\s+6\b", main)
-    assert lib.sea_train_version() == 1 == _lib.TRAIN_ABI_VERSION and lib.sea_version() == 6 == _lib.ABI_VERSION
-    assert "WITHOUT a bump" in train
-    for name in NAMES:
-        decl = re.search(r"^int %s\((.*?)\);" % name, train, re.M | re.S)
-        assert decl, name
-        assert name in _lib._TRAIN_SIGNATURES and hasattr(lib, name)
-        argtypes, restype = _lib._TRAIN_SIGNATURES[name]
-        assert getattr(lib, name).argtypes == argtypes and restype is ctypes.c_int
-        # the binding matches the declaration argument by argument
-        want = []
-        for arg in decl.group(1).replace("\n", " ").split(","):
-            arg = arg.strip()
-            want.append(_lib._i64p if arg.startswith("const int64_t*") else ctypes.c_void_p if "*" in arg or arg.startswith("sea_stream_t")
-                        else ctypes.c_int64 if arg.startswith("int64_t") else ctypes.c_int)
-        assert list(argtypes) == want, name
-        assert name not in _lib.EXPORTED_SYMBOLS and name not in main
-    declared = sorted(set(re.findall(r"\b(sea_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S))))
-    assert len(declared) == 38 and sorted(_lib.EXPORTED_SYMBOLS) == declared
-    from sea_attention_amd import _build
-    assert "sea_kd_score_loss.hip" in _build.SOURCES
-
-
-def _call(lib, name, N=1, H=2, T=64, D=64, qd=_lib.SEA_BF16, xd=_lib.SEA_BF16, **kw):
-    """`name` with good arguments (never-dereferenced pointers) except for what `kw` replaces"""
-    a = dict(q=A, k=B, qs=_s(H * T * D, T * D, D), ks=_s(H * T * D, T * D, D), truth=A, xs=_s(H * T * T, T * T, T),
-             row_kl=A, row_mse=A, row_q=A, row_stats=A, grad_loss=A, d_q=A, d_k=B)
-    a.update(kw)
-    head = (a["q"], a["k"], qd, a["qs"], a["ks"], a["truth"], xd, a["xs"])
-    if name == "sea_kd_score_loss":
-        return lib.sea_kd_score_loss(*head, N, H, T, D, a["row_kl"], a["row_mse"], a["row_q"], a["row_stats"], None)
-    return lib.sea_kd_score_loss_bwd(*head, a["row_q"], a["row_stats"], a["grad_loss"], N, H, T, D, a["d_q"], a["d_k"], None)
-
-
-@pytest.mark.parametrize("name", NAMES)
-def test_kd_score_loss_refusals(lib, name):
-    H, T, D = 2, 64, 64
-    own = ("row_kl", "row_mse", "row_q", "row_stats") if name == "sea_kd_score_loss" else ("row_q", "row_stats", "grad_loss", "d_q", "d_k")
-    for arg, shown in [("q", "q"), ("k", "k"), ("qs", "q_strides"), ("ks", "k_strides"), ("truth", "truth"), ("xs", "truth_strides"),
-                       *[(o, o) for o in own]]:
-        assert _call(lib, name, **{arg: None}) == EINVAL and f"{name}: {shown} is null" in _err(lib), arg
-    for arg in ("q", "k", "truth"):                                            # a misaligned base
-        assert _call(lib, name, **{arg: ODD}) == EINVAL and f"{name}: {arg} rows must be 16-byte aligned" in _err(lib), arg
-    for arg, shown, row in (("qs", "q", D), ("ks", "k", D), ("xs", "truth", T)):
-        # a stride that breaks 16-byte rows (bf16: 4 elements are 8 bytes)
-        assert _call(lib, name, **{arg: _s(H * T * row, T * row, row + 4)}) == EINVAL and f"{shown} rows must be 16-byte aligned" in _err(lib)
-        assert _call(lib, name, **{arg: _s(H * T * row + 4, T * row, row)}) == EINVAL and f"{shown} rows must be 16-byte aligned" in _err(lib)
-        # the entries take no innermost stride: it is 1, so rows of `row` elements cannot be closer than that (a view with an
-        # innermost stride of 2 would need it), nor may a stride be negative
-        assert _call(lib, name, **{arg: _s(H * T * row, T * row, row - 8)}) == EINVAL and f"{name}: bad {shown} strides" in _err(lib)
-        assert _call(lib, name, **{arg: _s(-8, T * row, row)}) == EINVAL and f"{name}: bad {shown} strides" in _err(lib)
-    assert _call(lib, name, T=0) == EINVAL and f"{name}: bad shape" in _err(lib)
-    assert _call(lib, name, D=72, qs=_s(H * T * 72, T * 72, 72), ks=_s(H * T * 72, T * 72, 72)) == EUNSUPPORTED and f"{name}: D=72" in _err(lib)
-    T2 = 16385
-    assert _call(lib, name, T=T2, qs=_s(H * T2 * D, T2 * D, D), ks=_s(H * T2 * D, T2 * D, D), xs=_s(H * T2 * 16392, T2 * 16392, 16392)) \
-        == EUNSUPPORTED and f"{name}: T=16385" in _err(lib)
-    assert _call(lib, name, qd=_lib.SEA_F32) == EUNSUPPORTED and "fp32 q / k" in _err(lib) and "qk_dtype" in _err(lib)
-    assert _call(lib, name, qd=7) == EUNSUPPORTED and f"{name}: unknown qk_dtype 7" in _err(lib)
-    assert _call(lib, name, xd=-1) == EUNSUPPORTED and f"{name}: unknown truth_dtype -1" in _err(lib)
 
 
 def test_ops_are_exported_and_refuse_what_the_kernels_do_not_take():

@@ -1,21 +1,17 @@
 """The distillation losses with the teacher FACTORED (`ops.TeacherScores(q_t, k_t)` in place of the (N,H,T,T) score tensor;
-include/sea_hip_train.h t5 - t7): what can be held without a GPU.
+include/sea_hip_train.h, "the teacher"): what can be held without a GPU.
 
 `TeacherScores` and `opt_plumbing.teacher_scores`; the layer on the CPU, where every path is a fallback and must return, bit for
 bit, what it returns for the tensor q_t k_t^T; the references of the two existing suites (`KdReference`, `KdScoreReference`) on the
 fp64 teacher product against the fp32 yardsticks on the fp32 product -- the kernels keep the product's fp32 accumulator, they do
 NOT round it to the data type, and the printed rate says why; two witnesses that the GPU comparison can fail (the teacher's key
-tile taken from the student, the padded k-step of head size 80 forgotten for the teacher); and the three C entries: declared,
-bound, both version numbers where they were, bad arguments refused before any launch."""
-import ctypes
-import os
-import re
-
+tile taken from the student, the padded k-step of head size 80 forgotten for the teacher).  The C entries themselves:
+tests/test_kd_abi.py."""
 import pytest
 import torch
 
 import sea_attention_amd as S
-from sea_attention_amd import _lib, opt_plumbing
+from sea_attention_amd import opt_plumbing
 from sea_attention_amd.perlin_attention import PerlinAttentionConfig, PerlinSelfAttention, ops
 from test_kd_loss_reference import FP_MIN16, KdReference, bar_of, torch_rows
 from test_kd_score_loss_reference import KdScoreReference, torch_score_rows
@@ -184,7 +180,7 @@ def test_the_comparison_can_fail(shape, dtype):
     """(a) The teacher's key tile taken from the STUDENT's k misses row_kl and row_mse of both terms, and pix_tgt, by more than 10
     bars in every row t >= 8.  (b) At D = 80, columns 64 .. 79 of the teacher's product dropped miss them by more than 10 bars in
     every row t >= 8.  Printed, not asserted: the rate for a product rounded to the 16-bit type -- why the kernels' semantics
-    (the fp32 accumulator, t5 - t7 of the header) is a stated deviation from handing over the teacher's own bmm result."""
+    (the fp32 accumulator, "the teacher" in the header) is a stated deviation from handing over the teacher's own bmm result."""
     N, H, T, D = shape
     q, k, qt, kt, est = _witness_inputs(shape, dtype)
     x64 = _dd(qt, kt)
@@ -212,102 +208,3 @@ def test_the_comparison_can_fail(shape, dtype):
     if D == 80:
         rates("teacher columns 64 .. 79 dropped", _dd(qt[..., :64], kt[..., :64]), True)
     rates(f"teacher product rounded to {str(dtype)[6:]}", torch.matmul(qt.float(), kt.float().transpose(-1, -2)).to(dtype).double(), False)
-
-
-# ---- the C ABI: three more additive entries; both version numbers and the inference ABI untouched --------------------------
-EINVAL, EUNSUPPORTED = -1, -2
-A = ctypes.c_void_p(1 << 20)                     # 16-byte aligned, never dereferenced (the entries refuse first)
-B = ctypes.c_void_p((1 << 20) + 4096)
-ODD = ctypes.c_void_p((1 << 20) + 8)
-NAMES = ("sea_kd_estimator_loss_qk", "sea_kd_score_loss_qk", "sea_kd_score_loss_qk_bwd")
-
-
-def _s(*v):
-    return (ctypes.c_int64 * len(v))(*v)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.sea_last_error().decode()
-
-
-def test_qk_entries_are_declared_bound_and_apart_from_the_inference_abi(lib):
-    root = os.path.join(os.path.dirname(__file__), "..")
-    train = open(os.path.join(root, "include", "sea_hip_train.h")).read()
-    main = open(os.path.join(root, "include", "sea_hip.h")).read()
-    assert re.search(r"#define\s+SEA_TRAIN_ABI_VERSION\s+1\b", train) and re.search(r"#define\s+SEA_ABI_VERSION\s+6\b", main)
-    assert lib.sea_train_version() == 1 == _lib.TRAIN_ABI_VERSION and lib.sea_version() == 6 == _lib.ABI_VERSION
-    assert "WITHOUT a bump" in train
-    for name in NAMES:
-        decl = re.search(r"^int %s\((.*?)\);" % name, train, re.M | re.S)
-        assert decl, name
-        assert name in _lib._TRAIN_SIGNATURES and hasattr(lib, name)
-        argtypes, restype = _lib._TRAIN_SIGNATURES[name]
-        assert getattr(lib, name).argtypes == argtypes and restype is ctypes.c_int
-        want = []                                                              # the binding matches the declaration argument by argument
-        for arg in decl.group(1).replace("\n", " ").split(","):
-            arg = arg.strip()
-            want.append(_lib._i64p if arg.startswith("const int64_t*") else ctypes.c_void_p if "*" in arg or arg.startswith("sea_stream_t")
-                        else ctypes.c_int64 if arg.startswith("int64_t") else ctypes.c_int)
-        assert list(argtypes) == want, name
-        assert "truth" not in decl.group(1) and "teacher_q" in decl.group(1) and "teacher_k_strides" in decl.group(1)
-        assert name not in _lib.EXPORTED_SYMBOLS and name not in main
-    for old in ("sea_kd_estimator_loss", "sea_kd_estimator_loss_bwd", "sea_kd_score_loss", "sea_kd_score_loss_bwd"):
-        assert re.search(r"^int %s\(" % old, train, re.M) and old in _lib._TRAIN_SIGNATURES           # the existing entries stay
-    declared = sorted(set(re.findall(r"\b(sea_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S))))
-    assert len(declared) == 38 and sorted(_lib.EXPORTED_SYMBOLS) == declared
-
-
-def _call(lib, name, N=1, H=2, T=64, D=64, T_M=32, qd=_lib.SEA_BF16, td=_lib.SEA_BF16, ed=_lib.SEA_BF16, **kw):
-    """`name` with good arguments (never-dereferenced pointers) except for what `kw` replaces"""
-    rows = _s(H * T * D, T * D, D)
-    a = dict(q=A, k=B, qs=rows, ks=rows, tq=A, tk=B, tqs=rows, tks=rows, est=A, es=_s(H * T * T_M, T * T_M, T_M),
-             row_kl=A, row_mse=A, row_q=A, row_stats=A, pix_tgt=A, grad_loss=A, d_q=A, d_k=B)
-    a.update(kw)
-    teacher = (a["tq"], a["tk"], td, a["tqs"], a["tks"])
-    if name == "sea_kd_estimator_loss_qk":
-        return lib.sea_kd_estimator_loss_qk(a["est"], ed, a["es"], *teacher, N, H, T, T_M, D, a["row_kl"], a["row_mse"], a["pix_tgt"],
-                                            a["row_stats"], None)
-    head = (a["q"], a["k"], qd, a["qs"], a["ks"], *teacher)
-    if name == "sea_kd_score_loss_qk":
-        return lib.sea_kd_score_loss_qk(*head, N, H, T, D, a["row_kl"], a["row_mse"], a["row_q"], a["row_stats"], None)
-    return lib.sea_kd_score_loss_qk_bwd(*head, a["row_q"], a["row_stats"], a["grad_loss"], N, H, T, D, a["d_q"], a["d_k"], None)
-
-
-@pytest.mark.parametrize("name", NAMES)
-def test_qk_entries_refuse_before_any_launch(lib, name):
-    H, T, D = 2, 64, 64
-    score = name != "sea_kd_estimator_loss_qk"
-    own = {"sea_kd_estimator_loss_qk": ("est", "row_kl", "row_mse", "pix_tgt", "row_stats"),
-           "sea_kd_score_loss_qk": ("q", "k", "row_kl", "row_mse", "row_q", "row_stats"),
-           "sea_kd_score_loss_qk_bwd": ("q", "k", "row_q", "row_stats", "grad_loss", "d_q", "d_k")}[name]
-    for arg, shown in [("tq", "teacher_q"), ("tk", "teacher_k"), ("tqs", "teacher_q_strides"), ("tks", "teacher_k_strides"),
-                       *[(o, o) for o in own]]:
-        assert _call(lib, name, **{arg: None}) == EINVAL and f"{name}: {shown} is null" in _err(lib), arg
-    for arg, shown in (("tq", "teacher_q"), ("tk", "teacher_k")):              # a misaligned base, a stride that breaks 16-byte rows
-        assert _call(lib, name, **{arg: ODD}) == EINVAL and f"{name}: {shown} rows must be 16-byte aligned" in _err(lib), arg
-        assert _call(lib, name, **{arg + "s": _s(H * T * D, T * D, D + 4)}) == EINVAL and f"{shown} rows must be 16-byte aligned" in _err(lib)
-        assert _call(lib, name, **{arg + "s": _s(H * T * D, T * D, D - 8)}) == EINVAL and f"{name}: bad {shown} strides" in _err(lib)
-    if score:
-        assert _call(lib, name, q=ODD) == EINVAL and f"{name}: q rows must be 16-byte aligned" in _err(lib)
-    else:
-        assert _call(lib, name, est=ODD) == EINVAL and f"{name}: est rows must be 16-byte aligned" in _err(lib)
-    r72 = _s(H * T * 72, T * 72, 72)
-    assert _call(lib, name, D=72, qs=r72, ks=r72, tqs=r72, tks=r72) == EUNSUPPORTED and f"{name}: D=72" in _err(lib)
-    assert _call(lib, name, td=_lib.SEA_F32) == EUNSUPPORTED and "fp32 teacher q / k" in _err(lib) and "teacher_dtype" in _err(lib)
-    assert _call(lib, name, td=7) == EUNSUPPORTED and f"{name}: unknown teacher_dtype 7" in _err(lib)
-    T2 = 16385
-    r2 = _s(H * T2 * D, T2 * D, D)
-    assert _call(lib, name, T=T2, qs=r2, ks=r2, tqs=r2, tks=r2) == EUNSUPPORTED and f"{name}: T=16385" in _err(lib)
-    assert _call(lib, name, T=0) == EINVAL and f"{name}: bad shape" in _err(lib)
-    if score:                                                                  # the teacher must have the student's type
-        assert _call(lib, name, qd=_lib.SEA_BF16, td=_lib.SEA_F16) == EUNSUPPORTED and "is not qk_dtype" in _err(lib)
-        assert _call(lib, name, qd=_lib.SEA_F32, td=_lib.SEA_BF16) == EUNSUPPORTED and "fp32 q / k" in _err(lib)
-    else:
-        assert _call(lib, name, T_M=516, es=_s(H * T * 516, T * 516, 516)) == EUNSUPPORTED and f"{name}: T_m=516" in _err(lib)
-        assert _call(lib, name, T_M=30, es=_s(H * T * 32, T * 32, 32)) == EUNSUPPORTED and f"{name}: T_m=30" in _err(lib)
-        assert _call(lib, name, ed=5) == EUNSUPPORTED and f"{name}: unknown est_dtype 5" in _err(lib)
