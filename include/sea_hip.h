@@ -49,8 +49,12 @@ extern "C" {
  *      sea_decode_cnn_tail_select and the sliced entry sea_cumavg_sliced, added beside ABI 5, are gone; sea_decode_stage takes
  *      `rows` (and [n, h, t] strides), sea_decode_cnn_tail_select takes `y1_scratch` and `rows` (NULL, 1 = the one-row form),
  *      sea_cumavg takes `n_slices, workspace, workspace_bytes` (1, NULL, 0 = one pass)
+ *   7  one entry point per operator, the last one: sea_sparse_attention_bwd_gather is gone; sea_sparse_attention_bwd takes
+ *      `workspace, workspace_bytes, form` (NULL, 0 where the atomic form runs) and no longer wants dk / dv zeroed, and
+ *      sea_sparse_attention_bwd_workspace_bytes takes `dtype`, `D` and `form` too.  One alignment rule for both forms (q, k, v,
+ *      dout, dq, dk, dv): the atomic form used to accept misaligned fp32 dout / dq / dk / dv
  *      */
-#define SEA_ABI_VERSION 6
+#define SEA_ABI_VERSION 7
 
 enum sea_dtype { SEA_F32 = 0, SEA_F16 = 1, SEA_BF16 = 2 };
 
@@ -347,33 +351,39 @@ int sea_sparse_attention(const void* q, const void* k, const void* v, int dtype,
 int64_t sea_attention_few_rows(void);
 
 /* Backward of the fused operator WITHOUT its epilogue (o = sum_e softmax_e(q.k_e) v_e; the caller applies row scale and mix
- * in its autograd framework): dQ, dK, dV from dO.  Reference shape: masked_mm.py:169-267 + the dense branch's autograd
- * (attention.py:1061-1133).  probs = the forward's probs_out with row_scale = NULL; out / dout / dq fp32 (N,H,T_dst,D)
- * contiguous; dk / dv fp32 (N,H,T_src,D) contiguous, ZEROED by the caller (rows are accumulated with fp32 atomics). */
+ * in its autograd framework): dQ, dK, dV from dO.  Reference shape: masked_mm.py:169-267 (gradients flow through the kept
+ * entries only) + the dense branch's autograd (attention.py:1061-1133).  probs = the forward's probs_out with row_scale = NULL;
+ * out / dout / dq fp32 (N,H,T_dst,D) contiguous; dk / dv fp32 (N,H,T_src,D) contiguous: every row is WRITTEN, in both forms --
+ * the caller does not zero them.  dQ is a plain store per row and the same from run to run; dK / dV sum a key's entries in the
+ * order the launch reached them and agree between runs to fp32 rounding, in both forms.
+ * form:
+ *   SEA_ATTN_BWD_GATHER  (round 3) no float atomics: dK / dV are gathered over the transposed pattern.  The library counts the
+ *                        entries of every (n, head, key) column (int32 atomics), scans them into list starts, lets the row pass
+ *                        (dQ) drop a 16-byte record {row, p, ds} into its key's list, and a column pass (one lane group per
+ *                        key) sums dK = sum ds q_row, dV = sum p dO_row with plain stores.  Rows of up to 16 lanes (D <= 64
+ *                        fp32, D <= 128 16-bit); wider rows: SEA_EUNSUPPORTED.  Needs `workspace`;
+ *   SEA_ATTN_BWD_ATOMIC  the first form: dK / dV rows accumulated with fp32 atomics, cleared first by a hipMemsetAsync on
+ *                        `stream` (graph-capturable).  Rows of up to 64 lanes.  workspace / workspace_bytes are not read
+ *                        (NULL, 0);
+ *   SEA_ATTN_BWD_AUTO    the gather form where it has kernels (rows of up to 16 lanes), the atomic form for wider rows: what a
+ *                        caller passes; the library decides from dtype and D.  Another value: SEA_EINVAL.
+ * workspace: caller-owned scratch of sea_sparse_attention_bwd_workspace_bytes(dtype, N, H, T_src, D, col_stride_n, form) bytes,
+ * contents undefined before and after.  The query returns 0 where the atomic form runs and for arguments the entry refuses;
+ * else 2 * 4 * ceil4(N * (H * T_src + 1)) bytes of list starts and cursors (ceil4: up to a multiple of 4) + max(16 * N *
+ * col_stride_n, 128 * N) bytes of records.  Where the gather form runs, NULL or fewer bytes is SEA_EINVAL.
+ * q, k, v, dout, dq, dk, dv -- and workspace where it is read -- are 16-byte aligned (SEA_EUNSUPPORTED).  Null pointers, a bad
+ * dtype, shape or form: SEA_EINVAL; D, strides (multiples of the 16-byte fragment), alignment, a pinned form without kernels:
+ * SEA_EUNSUPPORTED.  Every refusal comes before anything is launched or cleared. */
+enum sea_attn_bwd_form { SEA_ATTN_BWD_AUTO = 0, SEA_ATTN_BWD_GATHER = 1, SEA_ATTN_BWD_ATOMIC = 2 };
+int64_t sea_sparse_attention_bwd_workspace_bytes(int dtype, int64_t N, int64_t H, int64_t T_src, int64_t D,
+                                                 int64_t col_stride_n, int form);
 int sea_sparse_attention_bwd(const void* q, const void* k, const void* v, int dtype,
                              int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                              const int32_t* crow, const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
                              const float* probs, int64_t probs_stride_n, const float* out, const float* dout,
-                             float* dq, float* dk, float* dv, sea_stream_t stream);
-
-/* The same backward WITHOUT float atomics (round 3): dK / dV are gathered over the transposed pattern.  The library counts
- * the entries of every (n, head, key) column (int32 atomics), scans them into list starts, lets the row pass (dQ, plain
- * stores) drop a 16-byte record {row, p, ds} into its key's list, and a column pass (one lane group per key) sums
- * dK = sum ds q_row, dV = sum p dO_row with plain stores -- every dk / dv row is written, the caller does NOT zero them.
- * Same arguments as sea_sparse_attention_bwd plus a caller-owned scratch buffer of
- * sea_sparse_attention_bwd_workspace_bytes(N, H, T_src, col_stride_n) bytes (16-byte aligned; contents undefined afterwards).
- * Rows wider than 16 lanes (fp32 with D > 64) are SEA_EUNSUPPORTED here and take the atomic form.  The records of a key are
- * in the order the row pass reached them: sums agree between runs to fp32 rounding, like the atomic form.
- * Reference shape: masked_mm.py:169-267 (gradients flow through the kept entries only). */
-int64_t sea_sparse_attention_bwd_workspace_bytes(int64_t N, int64_t H, int64_t T_src, int64_t col_stride_n);
-int sea_sparse_attention_bwd_gather(const void* q, const void* k, const void* v, int dtype,
-                                    int64_t N, int64_t H, int64_t T_dst, int64_t T_src, int64_t D,
-                                    const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                    const int32_t* crow, const int32_t* col, int64_t col_stride_n, const int32_t* head_off,
-                                    const float* probs, int64_t probs_stride_n, const float* out, const float* dout,
-                                    float* dq, float* dk, float* dv, void* workspace, int64_t workspace_bytes,
-                                    sea_stream_t stream);
+                             float* dq, float* dk, float* dv, void* workspace, int64_t workspace_bytes, int form,
+                             sea_stream_t stream);
 
 /* Kernel-choice plan for SEA_ATTN_AUTO, made on the device (no host round trip, graph-capturable).  One byte per (n, h,
  * 16-row block): 1 where the block's entries per staged 16-key tile favour the MFMA tile kernel -- estimated from the

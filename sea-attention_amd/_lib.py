@@ -9,7 +9,7 @@ import torch
 from . import _build
 
 SEA_F32, SEA_F16, SEA_BF16 = 0, 1, 2
-ABI_VERSION = 6            # include/sea_hip.h: SEA_ABI_VERSION
+ABI_VERSION = 7            # include/sea_hip.h: SEA_ABI_VERSION
 _DTYPES = {torch.float32: SEA_F32, torch.float16: SEA_F16, torch.bfloat16: SEA_BF16}
 
 _lib = None
@@ -35,11 +35,9 @@ _SIGNATURES = {
     "sea_sparse_attention": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p,
                               ptr, ptr, i64, ptr, ptr, ptr, _i64p, ptr, ptr, c_int, _i64p, ptr, i64, ptr, c_int,
                               ptr, i64, c_int, c_int, c_int, ptr, i64, ptr, i64, i64, ptr], c_int),
+    "sea_sparse_attention_bwd_workspace_bytes": ([c_int, i64, i64, i64, i64, i64, c_int], i64),
     "sea_sparse_attention_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
-                                  ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr], c_int),
-    "sea_sparse_attention_bwd_workspace_bytes": ([i64, i64, i64, i64], i64),
-    "sea_sparse_attention_bwd_gather": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, ptr, ptr, i64, ptr,
-                                         ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+                                  ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, i64, c_int, ptr], c_int),
     "sea_attention_plan": ([ptr, i64, i64, i64, i64, i64, c_int, ctypes.c_float, ptr, ptr], c_int),
     "sea_sparse_attention_bytes": ([i64, i64, i64, i64, i64, c_int], i64),
     "sea_split_layernorm": ([ptr, c_int, i64, i64, i64, i64, i64, ptr, ptr, ctypes.c_float, c_int, ptr, ptr], c_int),
@@ -97,6 +95,7 @@ def library_path():
 
 
 SEA_ATTN_AUTO, SEA_ATTN_GATHER, SEA_ATTN_TILE, SEA_ATTN_KEYRANGE = 0, 1, 2, 3
+SEA_ATTN_BWD_AUTO, SEA_ATTN_BWD_GATHER, SEA_ATTN_BWD_ATOMIC = 0, 1, 2      # `form` of sea_sparse_attention_bwd
 SEA_ATTN_ROW_POOL_SHIFT = 4                     # flags bits 4..7: log2 of the fused gather form's row pool (0 = none)
 # flags bits 16..17 / 18..19 (every path but the key-range form, whose range_keys sit there): the order the attention grid's
 # workgroups take their row blocks in (0 = ascending) and log2 of the pairs the grouped order interleaves

@@ -863,16 +863,6 @@ __global__ __launch_bounds__(256) void csr_spmm_kernel(SpmmParams p) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-static int lanes_per_row(int D, int vec) {
-  const int need = (D + vec - 1) / vec;
-  int l = 1;
-  while (l < need) l *= 2;
-  return l < 4 ? 4 : l;
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool strides_ok(const int64_t* s, int vec) { return s[0] % vec == 0 && s[1] % vec == 0 && s[2] % vec == 0; }
-
 // A decoding step (T_dst of a few rows per (n, h)): the fused form has nothing to win there (one row per workgroup), and the
 // plain lane-group kernel warms the row's K / V lines with its idle lane groups first (below).  sea_attention_few_rows().
 constexpr int64_t SEA_ATTN_FEW_ROWS = 2048;

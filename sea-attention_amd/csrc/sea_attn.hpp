@@ -370,6 +370,17 @@ __device__ inline int rows_by_length(int len, int gi, int sub, bool* rowok) {
   return slot;
 }
 
+// ---- host side, forward and backward ---------------------------------------------------------------------------------
+// lanes of a row's group: 16-byte fragments of `vec` elements, a power of two, at least 4
+inline int lanes_per_row(int D, int vec) {
+  const int need = (D + vec - 1) / vec;
+  int l = 1;
+  while (l < need) l *= 2;
+  return l < 4 ? 4 : l;
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool strides_ok(const int64_t* s, int vec) { return s[0] % vec == 0 && s[1] % vec == 0 && s[2] % vec == 0; }
+
 // the tile-block counter sits behind the plan's bytes, 4-byte aligned
 __host__ __device__ inline int64_t plan_count_offset(int64_t N, int64_t H, int64_t TB16) { return (N * H * TB16 + 3) & ~(int64_t)3; }
 

@@ -46,7 +46,7 @@ def call(lib, bits=A, ws=WS, stride=None, range_keys=RANGE, block_path=None, t_s
 
 
 def test_keyrange_path_is_declared(lib):
-    assert _lib.SEA_ATTN_KEYRANGE == 3 and lib.sea_version() == 6 == _lib.ABI_VERSION
+    assert _lib.SEA_ATTN_KEYRANGE == 3 and lib.sea_version() == 7 == _lib.ABI_VERSION
     assert "sea_sparse_attention" in _lib.EXPORTED_SYMBOLS
 
 

@@ -39,7 +39,7 @@ def test_decode_entries_are_declared_and_bound(lib):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
     for name in REMOVED:                         # ABI 5 and 6: the suffixed forms are arguments of their operator
         assert name not in _lib.EXPORTED_SYMBOLS and not hasattr(lib, name)
-    assert lib.sea_version() == 6
+    assert lib.sea_version() == 7
 
 
 def test_rows_entries_are_declared_and_bound(lib):
@@ -49,7 +49,7 @@ def test_rows_entries_are_declared_and_bound(lib):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
         assert len(_lib._SIGNATURES[name][0]) == nargs and getattr(lib, name).argtypes == _lib._SIGNATURES[name][0]
         assert name + "_rows" not in _lib.EXPORTED_SYMBOLS and not hasattr(lib, name + "_rows")
-    assert lib.sea_version() == 6 == _lib.ABI_VERSION
+    assert lib.sea_version() == 7 == _lib.ABI_VERSION
 
 
 def test_decode_stage_refusals(lib):

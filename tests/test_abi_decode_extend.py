@@ -37,8 +37,8 @@ def test_extend_entries_are_declared_bound_and_exported(lib):
         assert re.search(r"^int %s\(" % name, header, re.M), name
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
         assert getattr(lib, name).argtypes == _lib._SIGNATURES[name][0]
-    assert lib.sea_version() == 6 == _lib.ABI_VERSION
-    assert re.search(r"#define\s+SEA_ABI_VERSION\s+6\b", header)
+    assert lib.sea_version() == 7 == _lib.ABI_VERSION
+    assert re.search(r"#define\s+SEA_ABI_VERSION\s+7\b", header)
 
 
 def test_decode_gather_rows_refusals(lib):

@@ -25,7 +25,7 @@ def _err(lib):
 
 def test_fork_entry_is_declared_and_bound_at_abi_6(lib):
     assert "sea_decode_fork" in _lib.EXPORTED_SYMBOLS and hasattr(lib, "sea_decode_fork")
-    assert lib.sea_version() == 6 == _lib.ABI_VERSION
+    assert lib.sea_version() == 7 == _lib.ABI_VERSION
 
 
 def _staging_slot(lib, H=8, D=64, nb=64, dtype=_lib.SEA_BF16, x=4096, y1=1024, cap=1000, page_rows=64):

@@ -10,7 +10,8 @@ twice counts twice, as in the kernels):
 `test_closed_forms_match_autograd` (no GPU) holds these forms to torch.autograd in fp64 through
 softmax(q . k[keys]) @ v[keys] per list, so they do not rest on the header comment of the file under test.
 
-Tier A: `sea_sparse_attention_bwd_gather` and `sea_sparse_attention_bwd` through the C ABI.  The test supplies `probs` and
+Tier A: `sea_sparse_attention_bwd` through the C ABI, its `form` pinned to the gather and to the atomic form (and left to the
+library on one case per side of its lane rule).  The test supplies `probs` and
 `out` itself: the reference's p and o rounded to fp32 on the device CSR's slots (the device `col` is the oracle's, asserted;
 slots past an item's end hold NaN).  What is measured is then the backward's own rounding, and the bar is DERIVED
 (`BwdReference`; u = 2^-24, D the head size, L the list's length, R the key's record count; a sum of n products formed in
@@ -25,8 +26,8 @@ lane-group sum, the row's and the key's chains and any order of the atomics):
     bar dV  = R u sum_r p_r |dO_r|  +  sum_r e_p_r |dO_r|  +  u |dV|
 each times 1 + 1e-3 for the terms of second order.  Nothing in them is measured.  Exact, asserted outright: dQ of a row that
 keeps nothing is 0, dK / dV of a key without a record are 0, everything is finite although every K / V row no kept key
-names is NaN; the gather form gets a workspace of 0xFF bytes and NaN-filled dq / dk / dv.  In the strided cases K / V are views
-of a fused projection and q has a wider row pitch of its own with NaN around its rows (`run_abi`).
+names is NaN; both forms get NaN-filled dq / dk / dv, the gather form a workspace of 0xFF bytes, the atomic form NULL.  In the
+strided cases K / V are views of a fused projection and q has a wider row pitch of its own with NaN around its rows (`run_abi`).
 
 Tier B: `ops.sparse_attention_autograd` on the same poisoned inputs, both `backward_form`s: gradients in the input type
 within 1 ulp of the reference rounded to that type, plus the Tier A bar with the forward's error carried through the same
@@ -55,7 +56,7 @@ DEV = "cuda:0"
 U = 2.0 ** -24
 
 # name: (form, dtype, d, N, H, T_dst, T_src, T_m, max_k, causal, strided, one_entry) -- `Case`'s spec; form "gather": both
-# entry points run the case, "atomic": sea_sparse_attention_bwd only (rows wider than 16 lanes).  Every query row's pixels
+# forms run the case, "atomic": the atomic form only (rows wider than 16 lanes).  Every query row's pixels
 # are two keys wide or more (causal: T_src - T_dst + 1 >= 2 T_m) and max_k >= 2, so no list has one entry: there p = 1 and
 # ds = dp - delta = 0 identically, and a lost entry cannot show in dQ or dK (asserted in check_case)
 SPECS = {
@@ -275,7 +276,8 @@ def forward_on_slots(c: Case, stride):
 
 
 def run_abi(c: Case, r: BwdReference, form):
-    """One backward launch the way _SparseAttentionFn.backward makes it; fp32 (dq, dk, dv)."""
+    """One backward launch the way _SparseAttentionFn.backward makes it, `form` pinned ("gather" / "atomic") or left to the
+    library ("auto"); fp32 (dq, dk, dv)."""
     lib = _lib.load()
     dv_, p_ = c.dev, flat_csr._p
     q, kk, vv, csr = dv_["q"], dv_["kk"], dv_["vv"], dv_["csr"]
@@ -294,16 +296,14 @@ def run_abi(c: Case, r: BwdReference, form):
     common = (p_(q), p_(kk), p_(vv), _lib.dtype_code(c.dtype), N, H, T_dst, T_src, D, _lib.strides3(q), _lib.strides3(kk),
               _lib.strides3(vv), p_(csr.crow), p_(csr.col), csr.col.stride(0), p_(csr.head_off), p_(probs), probs.stride(0),
               p_(out), p_(dout), p_(dq))
+    dk, dv = nan(N, H, T_src, D), nan(N, H, T_src, D)                       # both forms write every row: neither gets zeros
+    code = {"gather": _lib.SEA_ATTN_BWD_GATHER, "atomic": _lib.SEA_ATTN_BWD_ATOMIC, "auto": _lib.SEA_ATTN_BWD_AUTO}[form]
     with torch.cuda.device(q.device):
-        if form == "gather":
-            dk, dv = nan(N, H, T_src, D), nan(N, H, T_src, D)
-            nb = int(lib.sea_sparse_attention_bwd_workspace_bytes(N, H, T_src, csr.col.stride(0)))
-            ws = torch.full((nb,), 0xFF, dtype=torch.uint8, device=DEV)
-            _lib.check(lib.sea_sparse_attention_bwd_gather(*common, p_(dk), p_(dv), p_(ws), nb, _lib.stream_ptr()),
-                       "sea_sparse_attention_bwd_gather")
-        else:
-            dk, dv = torch.zeros_like(nan(N, H, T_src, D)), torch.zeros_like(nan(N, H, T_src, D))
-            _lib.check(lib.sea_sparse_attention_bwd(*common, p_(dk), p_(dv), _lib.stream_ptr()), "sea_sparse_attention_bwd")
+        nb = int(lib.sea_sparse_attention_bwd_workspace_bytes(_lib.dtype_code(c.dtype), N, H, T_src, D, csr.col.stride(0), code))
+        assert (nb > 0) == (form == "gather" or (form == "auto" and lanes_per_row(c.dtype, c.d) <= 16))
+        ws = torch.full((nb,), 0xFF, dtype=torch.uint8, device=DEV) if nb else None         # the atomic form: NULL, 0
+        _lib.check(lib.sea_sparse_attention_bwd(*common, p_(dk), p_(dv), p_(ws), nb, code, _lib.stream_ptr()),
+                   "sea_sparse_attention_bwd")
         torch.cuda.synchronize()
     return {"dq": dq.cpu(), "dk": dk.cpu(), "dv": dv.cpu()}
 
@@ -344,6 +344,16 @@ def test_atomic_form_matches_fp64(name):
     c, r = case(name), reference(name)
     check_selection(c)
     check_gradients(c, r, "atomic", run_abi(c, r, "atomic"), r.bar)
+
+
+@gpu
+@pytest.mark.parametrize("name", ["g8_bf16_d64", "a32_f32_d128"])
+def test_auto_form_matches_fp64(name):
+    """SEA_ATTN_BWD_AUTO on either side of the lane rule: the gather form with its workspace at 8 lanes, the atomic form with
+    NULL, 0 at 32 (`run_abi` asserts which the workspace query announces)."""
+    c, r = case(name), reference(name)
+    check_selection(c)
+    check_gradients(c, r, "auto", run_abi(c, r, "auto"), r.bar)
 
 
 @gpu
