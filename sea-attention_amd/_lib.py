@@ -89,6 +89,16 @@ _TRAIN_SIGNATURES = {
     "sea_kd_score_loss_bwd": ([ptr, ptr, c_int, _i64p, _i64p, *_TEACHER, ptr, ptr, ptr, i64, i64, i64, i64, ptr, ptr, ptr], c_int),
 }
 
+# include/sea_hip_estimator_grad.h: gradients of the estimator's kernels, additive and versioned on their own as well
+ESTIMATOR_GRAD_ABI_VERSION = 1      # SEA_ESTIMATOR_GRAD_ABI_VERSION
+_ESTIMATOR_GRAD_SIGNATURES = {
+    "sea_estimator_grad_version": ([], c_int),
+    "sea_performer_causal_bwd_supported": ([i64, i64, c_int], c_int),
+    "sea_performer_causal_bwd_workspace_bytes": ([i64, i64, i64, i64, i64, c_int], i64),
+    "sea_performer_causal_bwd": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
+                                  ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -136,6 +146,13 @@ def load(build_if_missing=True):
     if lib.sea_train_version() != TRAIN_ABI_VERSION:
         raise RuntimeError(f"{path}: training entries of version {lib.sea_train_version()}, this binding speaks "
                            f"{TRAIN_ABI_VERSION} (include/sea_hip_train.h) -- rebuild the library from this tree's csrc/")
+    for name, (argtypes, restype) in _ESTIMATOR_GRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_estimator_grad_version() != ESTIMATOR_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: estimator-gradient entries of version {lib.sea_estimator_grad_version()}, this binding speaks "
+                           f"{ESTIMATOR_GRAD_ABI_VERSION} (include/sea_hip_estimator_grad.h) -- rebuild the library from this tree's csrc/")
     _lib = lib
     return lib
 

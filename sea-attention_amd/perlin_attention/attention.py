@@ -215,6 +215,12 @@ class PerlinAttention(nn.Module):
         # term dense mode's has.  Stated deviation under this opt-in: the kernels keep q k^T in its fp32 accumulator, the torch
         # form rounds it to the data type before the softmaxes
         self.fused_kd_score_loss = False
+        # training: True = the Performer step of the estimator runs on the HIP kernels UNDER AUTOGRAD
+        # (`ops.performer_value_autograd`: the forward launch of inference, the backward of csrc/sea_performer_bwd.hip, nothing
+        # saved but q, k, v, the value embedding and the projection) wherever the batch is unpadded, the estimator's q / k / v
+        # share a dtype and a length and `ops.performer_value_grad_supported` holds; elsewhere, and with False, `self.performer`
+        # runs as before.  The MLP, the CNN and the tail stay torch modules under autograd either way
+        self.fused_performer_grad = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -333,10 +339,11 @@ class PerlinAttention(nn.Module):
             self._keep_cache[key] = hit
         return hit
 
-    def _hip_estimator_ok(self, x):
+    def _hip_estimator_ok(self, x, autograd_too=False):
         """HIP kernels for ChannelSplit+LN1 / predictor tail apply when: device tensor, autograd off, the standard
-        causal predictor layout, and shapes inside the kernels' limits.  Otherwise the torch modules run."""
-        if self.force_torch_estimator or not x.is_cuda or torch.is_grad_enabled() or not self.pconfig.causal:
+        causal predictor layout, and shapes inside the kernels' limits.  Otherwise the torch modules run.
+        `autograd_too`: the same conditions without the autograd one (the Performer step has a backward: `fused_performer_grad`)."""
+        if self.force_torch_estimator or not x.is_cuda or (torch.is_grad_enabled() and not autograd_too) or not self.pconfig.causal:
             return False
         T_M = self.pconfig.attention_predictor_length
         body = list(self.attention_predictor_cnn[1].module.net.children())
@@ -451,7 +458,26 @@ class PerlinAttention(nn.Module):
         hip_perf = (self._hip_estimator_ok(q) and not_padded and q_for_atten.shape == v_for_atten.shape
                     and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
                     and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype)
-        if hip_perf:
+        hip_perf_grad = False
+        if self.fused_performer_grad and torch.is_grad_enabled() and not hip_perf:
+            pos = self.v_eye_learned_causal[0, 0, :T_SRC, :]
+            hip_perf_grad = (self._hip_estimator_ok(q, autograd_too=True) and not_padded and q_for_atten.shape == v_for_atten.shape
+                             and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
+                             and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype
+                             and ops.performer_value_grad_supported(q_for_atten, k_for_atten, v_for_atten, pos,
+                                                                    self.performer.projection_matrix))
+        if hip_perf_grad:
+            # training: the same launch as below with a backward on the kernels; the gradients reach the value embedding and
+            # the estimator's q / k / v branches through it
+            with timer("performer"):
+                performer_value = ops.performer_value_autograd(q_for_atten, k_for_atten, v_for_atten, pos,
+                                                               self.performer.projection_matrix,
+                                                               n_segments=self.performer_segments)
+                if v_for_atten is not v:           # a separate estimator branch for v: the last third is the LAYER's v, as below
+                    performer_value = torch.cat([performer_value[..., :2 * q.shape[-1]], v], dim=-1)
+                bench.register_temp_buffer('performer_context_layer', performer_value[..., :2 * q.shape[-1]])
+                bench.register_temp_buffer('performer_value', performer_value)
+        elif hip_perf:
             # value augmentation + Performer + concat with v: one launch (two with segments) of the kernel form
             # csrc/sea_performer.hip picks for the dtype and shape
             with timer("performer"):

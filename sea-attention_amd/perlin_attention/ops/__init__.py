@@ -22,3 +22,5 @@ from .predictor import (split_layernorm, predictor_tail, cumavg, performer_value
 from .kd_loss import kd_estimator_loss, kd_estimator_loss_supported, kd_estimator_loss_parts
 from .kd_score_loss import kd_score_loss, kd_score_loss_supported, kd_score_loss_parts
 from .teacher_scores import TeacherScores
+# gradients of the estimator's kernels (include/sea_hip_estimator_grad.h)
+from .performer_grad import performer_value_autograd, performer_value_grad_supported
