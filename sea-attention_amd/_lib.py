@@ -99,6 +99,16 @@ _ESTIMATOR_GRAD_SIGNATURES = {
                                   ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_predictor_grad.h: gradients of the predictor's kernels, additive and versioned on their own as well
+PREDICTOR_GRAD_ABI_VERSION = 1      # SEA_PREDICTOR_GRAD_ABI_VERSION
+_PREDICTOR_GRAD_SIGNATURES = {
+    "sea_predictor_grad_version": ([], c_int),
+    "sea_predictor_tail_bwd_supported": ([i64, i64, i64, i64, i64, c_int], c_int),
+    "sea_predictor_tail_bwd_workspace_bytes": ([i64, i64, i64, i64, i64, i64, i64, c_int], i64),
+    "sea_predictor_tail_bwd": ([ptr, c_int, i64, i64, i64, i64, i64, i64, i64, _i64p, ptr, ptr, ptr, ctypes.c_float,
+                                ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -153,6 +163,13 @@ def load(build_if_missing=True):
     if lib.sea_estimator_grad_version() != ESTIMATOR_GRAD_ABI_VERSION:
         raise RuntimeError(f"{path}: estimator-gradient entries of version {lib.sea_estimator_grad_version()}, this binding speaks "
                            f"{ESTIMATOR_GRAD_ABI_VERSION} (include/sea_hip_estimator_grad.h) -- rebuild the library from this tree's csrc/")
+    for name, (argtypes, restype) in _PREDICTOR_GRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_predictor_grad_version() != PREDICTOR_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: predictor-gradient entries of version {lib.sea_predictor_grad_version()}, this binding speaks "
+                           f"{PREDICTOR_GRAD_ABI_VERSION} (include/sea_hip_predictor_grad.h) -- rebuild the library from this tree's csrc/")
     _lib = lib
     return lib
 

@@ -42,6 +42,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import _lib
 from ..utils import get_bench
 from .config import PerlinAttentionConfig, get_default_config
 from .modules import CausalConv2d, KeepRes, UpsampleFP32
@@ -219,8 +220,17 @@ class PerlinAttention(nn.Module):
         # (`ops.performer_value_autograd`: the forward launch of inference, the backward of csrc/sea_performer_bwd.hip, nothing
         # saved but q, k, v, the value embedding and the projection) wherever the batch is unpadded, the estimator's q / k / v
         # share a dtype and a length and `ops.performer_value_grad_supported` holds; elsewhere, and with False, `self.performer`
-        # runs as before.  The MLP, the CNN and the tail stay torch modules under autograd either way
+        # runs as before.  The MLP and the CNN stay torch modules under autograd either way; the tail has its own switch below
         self.fused_performer_grad = False
+        # training: True = the predictor's tail (cnn.keepres.upsam, cnn.keepres.conv4, the KeepRes area resize, cnn.lnorm2 and
+        # the softmax over T_M) runs as ONE op on the HIP kernels UNDER AUTOGRAD (`ops.predictor_tail_autograd`: the forward
+        # launch of inference, the backward of csrc/sea_tail_bwd.hip, nothing saved but the tail's input and its parameters --
+        # autograd keeps about 14 times the (N,H,T,T_M) map for the five framework ops) wherever the predictor has the standard
+        # causal layout and `ops.predictor_tail_grad_supported` holds (x4 upsample, T_M a multiple of 32 up to 256); padded
+        # batches included.  Elsewhere, and with False, the torch modules run as before.  Stated deviation under this opt-in: the
+        # kernels keep z, the resize and the LayerNorm in fp32 where the 16-bit torch chain rounds between ops.  cnn.lnorm1, the
+        # (conv, ReLU) pairs and the MLP stay torch modules under autograd either way
+        self.fused_tail_grad = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -353,6 +363,20 @@ class PerlinAttention(nn.Module):
                 and conv4.kernel_size == 1 and conv4.padding == (0, 1) and conv4.causal
                 and T_M % 4 == 0 and T_M <= 512 and (T_M // 4) % vec == 0
                 and ((T_M // 4 + 63) // 64) * ((self.num_attention_heads + 7) // 8) <= 16)
+
+    def _tail_grad_ok(self, x):
+        """`fused_tail_grad` applies to the row decoder's output x (N, C, T, T_M / 4): the switch and autograd are on, the
+        predictor has the standard causal layout (`_hip_estimator_ok` without its autograd condition: its body ends in
+        UpsampleFP32((1, 4)) + a 1x1 CausalConv2d) and the backward kernel has a form for the shapes.  Padded batches qualify:
+        the tail is row-local."""
+        if not (self.fused_tail_grad and torch.is_grad_enabled() and self._hip_estimator_ok(x, autograd_too=True)):
+            return False
+        if x.dim() != 4 or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            return False
+        T_M = self.pconfig.attention_predictor_length
+        conv4 = list(self.attention_predictor_cnn[1].module.net.children())[-1].module
+        return bool(_lib.load().sea_predictor_tail_bwd_supported(conv4.in_channels, conv4.out_channels, T_M // 4, 4, T_M,
+                                                                 _lib.dtype_code(x.dtype)))
 
     def _fused_mlp_ok(self, x):
         """One-launch predictor MLP (csrc/sea_mlp.hip): inference on 16-bit data with the standard
@@ -553,6 +577,7 @@ class PerlinAttention(nn.Module):
             bench.register_temp_buffer('estimated_attention_score', estimated_attention_score)
             bench.register_temp_buffer('estimated_attention_probs', estimated_attention_probs)
             return v, t_attention_predictor, estimated_attention_score, estimated_attention_probs
+        tail_grad = False
         with timer("predictor"):
             query_skips = int(os.environ.get('QUERY_SKIPS', '1'))
             with timer("predictor.enc"):
@@ -618,12 +643,33 @@ class PerlinAttention(nn.Module):
                     estimated_attention_score = self.attention_predictor_dec_row(t_attention_predictor)
                     bench.register_temp_buffer('estimated_attention_score_dec_row', estimated_attention_score)
                 with timer("predictor.cnn"):
-                    estimated_attention_score = self.attention_predictor_cnn(estimated_attention_score)
+                    tail_grad = self._tail_grad_ok(estimated_attention_score)
+                    if tail_grad:
+                        # training: lnorm1 and the (conv, ReLU) pairs as the torch modules they are, then the tail -- upsample,
+                        # 1x1 conv, area resize, lnorm2, softmax -- as ONE op whose backward recomputes all of it from y
+                        cnn = self.attention_predictor_cnn
+                        keepres, ln2 = cnn[1].module, cnn[2].module
+                        body = list(keepres.net.children())
+                        y = cnn[0](estimated_attention_score)
+                        for layer in body[:-2]:
+                            y = layer(y)
+                        conv4 = body[-1].module
+                        w4 = conv4.weight[:, :, 0, 0]          # a view: the gradient reaches the parameter
+                        T_M_ = self.pconfig.attention_predictor_length
+                        if not ops.predictor_tail_grad_supported(y, w4, conv4.bias, ln2.weight, ln2.bias, 4, T_M_):
+                            y = y.contiguous()                 # (a layout the kernels do not read; the op raises on anything else)
+                        with timer("cnn.tail"):
+                            estimated_attention_probs, estimated_attention_score = ops.predictor_tail_autograd(
+                                y, w4, conv4.bias, ln2.weight, ln2.bias, 4, T_M_, ln2.eps)
+                        if query_skips > 1:
+                            estimated_attention_probs = estimated_attention_probs.repeat_interleave(query_skips, dim=-2)
+                    else:
+                        estimated_attention_score = self.attention_predictor_cnn(estimated_attention_score)
                     if query_skips > 1:
                         estimated_attention_score = estimated_attention_score.repeat_interleave(query_skips, dim=-2)
                         t_attention_predictor = t_attention_predictor.repeat_interleave(query_skips, dim=-2)
                 bench.register_temp_buffer('t_attention_predictor', t_attention_predictor)
-        if not use_hip:
+        if not use_hip and not tail_grad:
             with timer("mask_softmax"):
                 estimated_attention_probs = torch.softmax(estimated_attention_score.float(), dim=-1) \
                     .to(estimated_attention_score.dtype)

@@ -24,3 +24,5 @@ from .kd_score_loss import kd_score_loss, kd_score_loss_supported, kd_score_loss
 from .teacher_scores import TeacherScores
 # gradients of the estimator's kernels (include/sea_hip_estimator_grad.h)
 from .performer_grad import performer_value_autograd, performer_value_grad_supported
+# gradients of the predictor's kernels (include/sea_hip_predictor_grad.h)
+from .predictor_tail_grad import predictor_tail_autograd, predictor_tail_grad_supported
