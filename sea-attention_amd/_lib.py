@@ -109,6 +109,15 @@ _PREDICTOR_GRAD_SIGNATURES = {
                                 ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_predictor_cnn_grad.h: gradients of the predictor CNN's (convolution, ReLU) pairs, additive and versioned on their own
+PREDICTOR_CNN_GRAD_ABI_VERSION = 1      # SEA_PREDICTOR_CNN_GRAD_ABI_VERSION
+_PREDICTOR_CNN_GRAD_SIGNATURES = {
+    "sea_predictor_cnn_grad_version": ([], c_int),
+    "sea_causal_conv_relu_bwd_supported": ([i64, i64, c_int, c_int, c_int, c_int], c_int),
+    "sea_causal_conv_relu_bwd_workspace_bytes": ([i64, i64, i64, i64, c_int, c_int], i64),
+    "sea_causal_conv_relu_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, ptr, i64, c_int, c_int, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -170,6 +179,14 @@ def load(build_if_missing=True):
     if lib.sea_predictor_grad_version() != PREDICTOR_GRAD_ABI_VERSION:
         raise RuntimeError(f"{path}: predictor-gradient entries of version {lib.sea_predictor_grad_version()}, this binding speaks "
                            f"{PREDICTOR_GRAD_ABI_VERSION} (include/sea_hip_predictor_grad.h) -- rebuild the library from this tree's csrc/")
+    for name, (argtypes, restype) in _PREDICTOR_CNN_GRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_predictor_cnn_grad_version() != PREDICTOR_CNN_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: predictor-CNN-gradient entries of version {lib.sea_predictor_cnn_grad_version()}, this binding "
+                           f"speaks {PREDICTOR_CNN_GRAD_ABI_VERSION} (include/sea_hip_predictor_cnn_grad.h) -- rebuild the library from "
+                           "this tree's csrc/")
     _lib = lib
     return lib
 

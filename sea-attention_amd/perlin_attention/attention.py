@@ -231,6 +231,14 @@ class PerlinAttention(nn.Module):
         # kernels keep z, the resize and the LayerNorm in fp32 where the 16-bit torch chain rounds between ops.  cnn.lnorm1, the
         # (conv, ReLU) pairs and the MLP stay torch modules under autograd either way
         self.fused_tail_grad = False
+        # training: True = inside the branch `fused_tail_grad` opens, the (conv, ReLU) pairs of cnn.keepres run on the HIP kernels
+        # UNDER AUTOGRAD as well (`ops.causal_conv_relu_autograd`: the forward launch of inference on C8 activations, the backward
+        # of csrc/sea_conv_bwd.hip, nothing saved but each pair's input, output and parameters) wherever
+        # `ops.causal_conv_relu_grad_supported` holds for every pair (16-bit data, 3 x 3, dilation 1 or 2, C <= 80, W <= 64); the
+        # two re-layouts to and from C8 are torch copies.  Elsewhere, and with False, the torch modules run as before.  Stated
+        # deviation under this opt-in: the weight gradient is an fp32 sum cast once; the torch chain's passes through the 16-bit
+        # copy of the weight.  cnn.lnorm1 and the MLP stay torch modules under autograd either way
+        self.fused_cnn_grad = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -377,6 +385,21 @@ class PerlinAttention(nn.Module):
         conv4 = list(self.attention_predictor_cnn[1].module.net.children())[-1].module
         return bool(_lib.load().sea_predictor_tail_bwd_supported(conv4.in_channels, conv4.out_channels, T_M // 4, 4, T_M,
                                                                  _lib.dtype_code(x.dtype)))
+
+    def _cnn_grad_pairs(self, body, x):
+        """`fused_cnn_grad`: the (CausalConv2d, ReLU) pairs in front of the tail, when the switch is on and the backward kernels
+        take every one of them on the lnorm1 output x (N, C, T, W); None otherwise."""
+        if not self.fused_cnn_grad or x.dtype not in (torch.float16, torch.bfloat16) or len(body) % 2 or not body:
+            return None
+        convs = [getattr(m, 'module', m) for m in body[0::2]]
+        lib, code = _lib.load(), _lib.dtype_code(x.dtype)
+        for cv, act in zip(convs, body[1::2]):
+            if not (isinstance(cv, CausalConv2d) and isinstance(act, nn.ReLU) and cv.causal and cv.stride in (1, (1, 1))
+                    and isinstance(cv.dilation, int) and cv.in_channels == cv.out_channels == x.shape[1]
+                    and lib.sea_causal_conv_relu_bwd_supported(cv.in_channels, x.shape[-1], cv.kernel_size, cv.dilation,
+                                                               cv.padding[1], code)):
+                return None
+        return convs
 
     def _fused_mlp_ok(self, x):
         """One-launch predictor MLP (csrc/sea_mlp.hip): inference on 16-bit data with the standard
@@ -651,8 +674,16 @@ class PerlinAttention(nn.Module):
                         keepres, ln2 = cnn[1].module, cnn[2].module
                         body = list(keepres.net.children())
                         y = cnn[0](estimated_attention_score)
-                        for layer in body[:-2]:
-                            y = layer(y)
+                        convs = self._cnn_grad_pairs(body[:-2], y)
+                        if convs is not None:
+                            # the pairs on the C8 kernels under autograd too; the re-layouts around them are torch copies
+                            y = ops.to_c8(y)
+                            for cv in convs:
+                                y = ops.causal_conv_relu_autograd(y, cv.weight, cv.bias, cv.kernel_size, cv.dilation, cv.padding[1])
+                            y = ops.from_c8(y)
+                        else:
+                            for layer in body[:-2]:
+                                y = layer(y)
                         conv4 = body[-1].module
                         w4 = conv4.weight[:, :, 0, 0]          # a view: the gradient reaches the parameter
                         T_M_ = self.pconfig.attention_predictor_length

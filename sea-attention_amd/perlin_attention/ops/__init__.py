@@ -26,3 +26,5 @@ from .teacher_scores import TeacherScores
 from .performer_grad import performer_value_autograd, performer_value_grad_supported
 # gradients of the predictor's kernels (include/sea_hip_predictor_grad.h)
 from .predictor_tail_grad import predictor_tail_autograd, predictor_tail_grad_supported
+# gradients of the predictor CNN's (convolution, ReLU) pairs (include/sea_hip_predictor_cnn_grad.h)
+from .predictor_cnn_grad import causal_conv_relu_autograd, causal_conv_relu_grad_supported
