@@ -118,6 +118,17 @@ _PREDICTOR_CNN_GRAD_SIGNATURES = {
     "sea_causal_conv_relu_bwd": ([ptr, ptr, ptr, c_int, i64, i64, i64, i64, ptr, i64, c_int, c_int, ptr, ptr, ptr, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_predictor_mlp_grad.h: the gradient of the predictor MLP, additive and versioned on its own
+PREDICTOR_MLP_GRAD_ABI_VERSION = 1      # SEA_PREDICTOR_MLP_GRAD_ABI_VERSION
+_f32 = ctypes.c_float
+_PREDICTOR_MLP_GRAD_SIGNATURES = {
+    "sea_predictor_mlp_grad_version": ([], c_int),
+    "sea_predictor_mlp_bwd_supported": ([i64, i64, i64, i64, c_int], c_int),
+    "sea_predictor_mlp_bwd_workspace_bytes": ([i64, i64, i64, i64, i64, i64, c_int], i64),
+    "sea_predictor_mlp_bwd": ([ptr, _i64p, ptr, ptr, c_int, i64, i64, i64, i64, i64, i64, ptr, ptr, ptr, _f32, _f32, ptr, ptr, ptr, ptr,
+                               ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -186,6 +197,14 @@ def load(build_if_missing=True):
     if lib.sea_predictor_cnn_grad_version() != PREDICTOR_CNN_GRAD_ABI_VERSION:
         raise RuntimeError(f"{path}: predictor-CNN-gradient entries of version {lib.sea_predictor_cnn_grad_version()}, this binding "
                            f"speaks {PREDICTOR_CNN_GRAD_ABI_VERSION} (include/sea_hip_predictor_cnn_grad.h) -- rebuild the library from "
+                           "this tree's csrc/")
+    for name, (argtypes, restype) in _PREDICTOR_MLP_GRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_predictor_mlp_grad_version() != PREDICTOR_MLP_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: predictor-MLP-gradient entries of version {lib.sea_predictor_mlp_grad_version()}, this binding "
+                           f"speaks {PREDICTOR_MLP_GRAD_ABI_VERSION} (include/sea_hip_predictor_mlp_grad.h) -- rebuild the library from "
                            "this tree's csrc/")
     _lib = lib
     return lib

@@ -239,6 +239,14 @@ class PerlinAttention(nn.Module):
         # deviation under this opt-in: the weight gradient is an fp32 sum cast once; the torch chain's passes through the 16-bit
         # copy of the weight.  cnn.lnorm1 and the MLP stay torch modules under autograd either way
         self.fused_cnn_grad = False
+        # training: True = where the `fused_tail_grad` branch opens, `fused_cnn_grad` takes every (conv, ReLU) pair and the modules
+        # have the one-launch MLP's structure (`_fused_mlp_ok` without its autograd condition: QUERY_SKIPS = 1, no enc_per_layer),
+        # attention_predictor_enc, the row decoder's Linear + ChannelSplit(2) and cnn.lnorm1 run as ONE op on the HIP kernels UNDER
+        # AUTOGRAD too (`ops.predictor_mlp_autograd`: the forward launch of inference, the recomputing backward of
+        # csrc/sea_mlp_bwd.hip, nothing saved but the MLP's input and its parameters) wherever `ops.predictor_mlp_grad_supported`
+        # holds (16-bit data, d = 64, T_M <= 256, H % 4 == 0).  Its C8 output goes straight into the conv op: the `to_c8` copy is
+        # gone.  The gates stay the torch Linear on t_attention_predictor.  Elsewhere, and with False, nothing changes
+        self.fused_mlp_grad = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -401,12 +409,13 @@ class PerlinAttention(nn.Module):
                 return None
         return convs
 
-    def _fused_mlp_ok(self, x):
+    def _fused_mlp_ok(self, x, autograd_too=False):
         """One-launch predictor MLP (csrc/sea_mlp.hip): inference on 16-bit data with the standard
         enc = Linear+LayerNorm+GELU / dec_row = Linear+ChannelSplit(2) / 2-way gate modules, C8 CNN available.
         Dense and sparse mode share it (so both see the same probability map); dense mode also asks for the
-        encoder output, which its gate / probing code reads."""
-        if not (self._hip_estimator_ok(x) and x.dtype in (torch.float16, torch.bfloat16)):
+        encoder output, which its gate / probing code reads.  `autograd_too`: the same conditions without the autograd one
+        (`_mlp_grad_ok`)."""
+        if not (self._hip_estimator_ok(x, autograd_too) and x.dtype in (torch.float16, torch.bfloat16)):
             return False
         if self.pconfig.attention_predictor_enc_per_layer or int(os.environ.get('QUERY_SKIPS', '1')) != 1:
             return False
@@ -424,6 +433,23 @@ class PerlinAttention(nn.Module):
                 and tuple(ln1.normalized_shape) == (dec[0].out_features // 2,)
                 and ops.predictor_mlp_supported(enc[0].out_features, dec[0].out_features, x.shape[1], x.shape[-1])
                 and self._c8_cnn_ok(x, body))
+
+    def _mlp_grad_ok(self, x):
+        """`fused_mlp_grad` applies to the MLP's input x (N, H, T, 3d): the switch and autograd are on, the `fused_tail_grad` branch
+        opens and `fused_cnn_grad` takes every pair on the row decoder's output (both asked with an empty tensor of its shape), the
+        modules have the one-launch MLP's structure and the backward kernels have a form for the shapes.  Returns the pairs'
+        convolutions, or None."""
+        if not (self.fused_mlp_grad and torch.is_grad_enabled() and x.dim() == 4 and self._fused_mlp_ok(x, autograd_too=True)):
+            return None
+        N, H, _T, _ = x.shape
+        dec = torch.empty((N, 2 * H, 0, self.attention_predictor_dec_row[0].out_features // 2), dtype=x.dtype, device=x.device)
+        body = list(self.attention_predictor_cnn[1].module.net.children())
+        convs = self._cnn_grad_pairs(body[:-2], dec) if self._tail_grad_ok(dec) else None
+        if convs is None or not ops.predictor_mlp_grad_supported(
+                x, self.attention_predictor_enc[0], self.attention_predictor_enc[1], self.attention_predictor_dec_row[0],
+                self.attention_predictor_cnn[0].module, self.attention_predictor_dec_scaler[0]):
+            return None
+        return convs
 
     def _c8_cnn_ok(self, x, body):
         """Channel-blocked (C8) MFMA conv pipeline: body = (CausalConv2d k x k, ReLU)* + upsample + 1x1 conv.  16-bit data on the
@@ -596,6 +622,32 @@ class PerlinAttention(nn.Module):
                     estimated_attention_probs, estimated_attention_score = self._c8_cnn_and_tail(
                         x, list(keepres.net.children()), ln2, want_scores,
                         self.benchmarking and not_padded and not get_bench().activate_temp_buffers, q, T_SRC)
+                bench.register_temp_buffer('t_attention_predictor', t_attention_predictor)
+            bench.register_temp_buffer('estimated_attention_score', estimated_attention_score)
+            bench.register_temp_buffer('estimated_attention_probs', estimated_attention_probs)
+            return v, t_attention_predictor, estimated_attention_score, estimated_attention_probs
+        mlp_grad_convs = self._mlp_grad_ok(performer_value)
+        if mlp_grad_convs is not None:
+            # training: the MLP as one op under autograd, its C8 output straight into the (conv, ReLU) ops, then the tail op
+            with timer("predictor"):
+                cnn = self.attention_predictor_cnn
+                keepres, ln2 = cnn[1].module, cnn[2].module
+                body = list(keepres.net.children())
+                with timer("predictor.mlp"):
+                    y, t_attention_predictor = ops.predictor_mlp_autograd(
+                        performer_value, self.attention_predictor_enc[0], self.attention_predictor_enc[1],
+                        self.attention_predictor_dec_row[0], cnn[0].module, self.attention_predictor_dec_scaler[0], want_tpred=True)
+                    bench.register_temp_buffer('estimated_attention_score_dec_row', None,
+                                               lazy=lambda: self.attention_predictor_dec_row(t_attention_predictor))
+                with timer("predictor.cnn"):
+                    for cv in mlp_grad_convs:
+                        y = ops.causal_conv_relu_autograd(y, cv.weight, cv.bias, cv.kernel_size, cv.dilation, cv.padding[1])
+                    y = ops.from_c8(y)
+                    conv4 = body[-1].module
+                    with timer("cnn.tail"):
+                        estimated_attention_probs, estimated_attention_score = ops.predictor_tail_autograd(
+                            y, conv4.weight[:, :, 0, 0], conv4.bias, ln2.weight, ln2.bias, 4, self.pconfig.attention_predictor_length,
+                            ln2.eps)
                 bench.register_temp_buffer('t_attention_predictor', t_attention_predictor)
             bench.register_temp_buffer('estimated_attention_score', estimated_attention_score)
             bench.register_temp_buffer('estimated_attention_probs', estimated_attention_probs)

@@ -28,3 +28,5 @@ from .performer_grad import performer_value_autograd, performer_value_grad_suppo
 from .predictor_tail_grad import predictor_tail_autograd, predictor_tail_grad_supported
 # gradients of the predictor CNN's (convolution, ReLU) pairs (include/sea_hip_predictor_cnn_grad.h)
 from .predictor_cnn_grad import causal_conv_relu_autograd, causal_conv_relu_grad_supported
+# the gradient of the predictor MLP (include/sea_hip_predictor_mlp_grad.h)
+from .predictor_mlp_grad import predictor_mlp_autograd, predictor_mlp_grad_supported

@@ -524,6 +524,36 @@ def _pack_a_fragments(w: torch.Tensor, kperm=None) -> torch.Tensor:
     return w[(16 * tile + li).expand(K // 32, M // 16, 4, 16, 8), k.expand(K // 32, M // 16, 4, 16, 8)].contiguous()
 
 
+def mlp_images(dt, device, enc_lin, enc_ln, dec_lin, ln1, scaler_lin):
+    """(w1_packed, w2_packed, vectors) of csrc/sea_mlp.hip for these modules in `dt`, cached per parameter set (`_cached`): the
+    forward and the backward (ops.predictor_mlp_autograd) take the same entry."""
+    Din, D1, Wd = enc_lin.in_features, enc_lin.out_features, dec_lin.out_features // 2
+
+    def build():
+        KP = (Din + 31) // 32 * 32
+        w1 = torch.zeros((D1, KP), dtype=dt, device=device)
+        w1[:, :Din] = enc_lin.weight.to(dt)
+        # each half (split) of the decoder owns ceil(Wd / 16) whole 16-row tiles; rows past Wd are zero (T_M = 96: Wd = 24)
+        WdP = (Wd + 15) // 16 * 16
+        w2 = torch.zeros((2 * WdP + 16, D1), dtype=dt, device=device)
+        w2[:Wd] = dec_lin.weight[:Wd].to(dt)
+        w2[WdP:WdP + Wd] = dec_lin.weight[Wd:].to(dt)
+        w2[2 * WdP:2 * WdP + 2] = scaler_lin.weight.to(dt)
+        w1p = _pack_a_fragments(w1)
+        w2p = _pack_a_fragments(w2, kperm=lambda ks, g, j: 16 * (2 * ks + j // 4) + 4 * g + j % 4)
+        f = lambda t: t.to(dt).float().reshape(-1)
+
+        def padded(t, parts):                                     # `parts` runs of Wd values, each zero-padded to WdP
+            o = torch.zeros((parts, WdP), dtype=torch.float32, device=device)
+            o[:, :Wd] = f(t).view(parts, Wd)
+            return o.reshape(-1)
+        vec = torch.cat([f(enc_lin.bias), f(enc_ln.weight), f(enc_ln.bias), padded(dec_lin.bias, 2), padded(ln1.weight, 1),
+                         padded(ln1.bias, 1), f(scaler_lin.bias)]).contiguous()
+        return w1p, w2p, vec
+    return _cached("mlp", (enc_lin.weight, enc_lin.bias, enc_ln.weight, enc_ln.bias, dec_lin.weight, dec_lin.bias,
+                           ln1.weight, ln1.bias, scaler_lin.weight, scaler_lin.bias), dt, build)
+
+
 @_lib.device_guarded
 def predictor_mlp(x: torch.Tensor, enc_lin, enc_ln, dec_lin, ln1, scaler_lin, want_tpred: bool = False,
                   x_c8_out: Optional[torch.Tensor] = None):
@@ -541,30 +571,7 @@ def predictor_mlp(x: torch.Tensor, enc_lin, enc_ln, dec_lin, ln1, scaler_lin, wa
     assert predictor_mlp_supported(D1, D2, H, Din) and tuple(ln1.normalized_shape) == (Wd,)
     if x.stride(-1) != 1:
         x = x.contiguous()
-
-    def build():
-        KP = (Din + 31) // 32 * 32
-        w1 = torch.zeros((D1, KP), dtype=dt, device=x.device)
-        w1[:, :Din] = enc_lin.weight.to(dt)
-        # each half (split) of the decoder owns ceil(Wd / 16) whole 16-row tiles; rows past Wd are zero (T_M = 96: Wd = 24)
-        WdP = (Wd + 15) // 16 * 16
-        w2 = torch.zeros((2 * WdP + 16, D1), dtype=dt, device=x.device)
-        w2[:Wd] = dec_lin.weight[:Wd].to(dt)
-        w2[WdP:WdP + Wd] = dec_lin.weight[Wd:].to(dt)
-        w2[2 * WdP:2 * WdP + 2] = scaler_lin.weight.to(dt)
-        w1p = _pack_a_fragments(w1)
-        w2p = _pack_a_fragments(w2, kperm=lambda ks, g, j: 16 * (2 * ks + j // 4) + 4 * g + j % 4)
-        f = lambda t: t.to(dt).float().reshape(-1)
-
-        def padded(t, parts):                                     # `parts` runs of Wd values, each zero-padded to WdP
-            o = torch.zeros((parts, WdP), dtype=torch.float32, device=x.device)
-            o[:, :Wd] = f(t).view(parts, Wd)
-            return o.reshape(-1)
-        vec = torch.cat([f(enc_lin.bias), f(enc_ln.weight), f(enc_ln.bias), padded(dec_lin.bias, 2), padded(ln1.weight, 1),
-                         padded(ln1.bias, 1), f(scaler_lin.bias)]).contiguous()
-        return w1p, w2p, vec
-    w1p, w2p, vec = _cached("mlp", (enc_lin.weight, enc_lin.bias, enc_ln.weight, enc_ln.bias, dec_lin.weight, dec_lin.bias,
-                                    ln1.weight, ln1.bias, scaler_lin.weight, scaler_lin.bias), dt, build)
+    w1p, w2p, vec = mlp_images(dt, x.device, enc_lin, enc_ln, dec_lin, ln1, scaler_lin)
     if x_c8_out is None:
         x_c8, xs_n = torch.empty((N, T, H * 2 // 8, Wd, 8), dtype=dt, device=x.device), 0
     else:
