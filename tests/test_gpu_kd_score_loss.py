@@ -296,14 +296,19 @@ def test_sparse_mode_gains_the_term(layers_and_inputs, monkeypatch):
     assert torch.equal(on.context_layer, off.context_layer)                   # the switch does not touch the attention itself
 
 
+def padded_mask(causal, rows, items=slice(None)):
+    """the additive causal mask (N,1,T,T) with the last `rows` query rows of the batch items `items` padded"""
+    padded = causal.clone()
+    padded[items, :, causal.shape[-2] - rows:, :] = torch.finfo(torch.float16).min / 2
+    return padded
+
+
 @pytest.mark.parametrize("what", ["padded", "fp32"])
 def test_fallbacks_change_nothing(layers_and_inputs, monkeypatch, what):
     _layers, _x, causal, _st, _ct = layers_and_inputs
     kw = {}
     if what == "padded":
-        padded = causal.clone()
-        padded[:, :, T_ - 8:, :] = torch.finfo(torch.float16).min / 2          # the last 8 query rows are padding
-        kw = dict(mask=padded)
+        kw = dict(mask=padded_mask(causal, 8))                                 # the last 8 query rows are padding
     else:
         kw = dict(dtype=F32)
     calls = []

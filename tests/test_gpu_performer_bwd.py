@@ -164,6 +164,34 @@ def test_saves_the_five_inputs_returns_none_where_no_gradient_is_wanted_and_take
 
 
 @pytest.mark.gpu
+def test_fp32_value_embedding_under_bf16_data():
+    """fp32 master weights: pos is an fp32 leaf whose values bf16 cannot hold -- every value (1 + 2^-10) times a bf16 number, which
+    rounds back to that number.  The forward is bitwise the forward on the rounded pos, dpos comes back fp32, and every gradient is
+    held to the case's own fp64 reference (evaluated on the rounded pos: the case's pos itself) under the case's own bars."""
+    idx = 0
+    N, H, T, D, nb, dt, _seed = CASES[idx]
+    inp, ref, _yard, amb, bars = _case(idx)
+    pos32 = inp[3].float() * (1 + 2.0 ** -10)
+    assert dt == BF and torch.equal(pos32.to(BF), inp[3]) and (pos32 != inp[3].float()).float().mean().item() > 0.99
+    out16, _grads16 = _kernel_grads(inp)
+    qd, kd, vd, _pd, Wd, gd = _device_inputs(inp)
+    pd = pos32.to(DEV).requires_grad_(True)
+    out = ops.performer_value_autograd(qd, kd, vd, pd, Wd)
+    got = torch.autograd.grad(out, [qd, kd, vd, pd], grad_outputs=gd)
+    torch.cuda.synchronize()
+    assert torch.equal(out, out16)
+    assert [g.dtype for g in got] == [BF, BF, BF, F32] and got[3].shape == pos32.shape and (got[3][T:] == 0).all()
+    failures = []
+    for i, name in enumerate(NAMES):
+        x = got[i].cpu()
+        err = (_kept(x, i, amb) - _kept(ref[i], i, amb)).abs().max().item()
+        print(f"[perf-bwd] {_id(CASES[idx])} fp32 pos {name}: max err {err:.3e} bar {bars[i]:.3e} ratio {err / bars[i]:.3f}")
+        if not (torch.isfinite(x).all() and err <= bars[i]):
+            failures.append((name, err, bars[i]))
+    assert not failures, failures
+
+
+@pytest.mark.gpu
 def test_one_row():
     """T = 1: ctx = V_0 whatever q and k are (up to the 1e-6 of the denominator), so dv = g[D:2D] + g[2D:], dpos = sum over the heads
     of g[:D], both to the rounding of the output type, and dq = dk = 0: fp32 cancellation of O(|g|) terms leaves about 1e-7 |g|, a

@@ -99,6 +99,39 @@ def test_kernels_against_fp64_reference(idx):
 
 
 @pytest.mark.gpu
+def test_fp32_parameters_under_bf16_data():
+    """fp32 master weights: weight and bias are fp32 leaves whose values bf16 cannot hold -- every live value (1 + 2^-10) times a bf16
+    number, which rounds back to that number.  The forward is bitwise the forward on the rounded parameters, both gradients come back
+    fp32, and every gradient is held to this file's fp64 reference on the rounded weight under this file's bar."""
+    idx = 0
+    N, C, _T, W, d, dt = CASES[idx]
+    x, w, _b, g = _inputs(idx)
+    b = (0.1 * torch.randn(C, generator=torch.Generator().manual_seed(58))).to(dt)          # (the case's own bias is zero)
+    w32, b32 = (t.float() * (1 + 2.0 ** -10) for t in (w, b))
+    assert dt == BF and torch.equal(w32.to(BF), w) and torch.equal(b32.to(BF), b)
+    assert (w32[:, :, :3] != w[:, :, :3].float()).float().mean().item() > 0.99 and (b32 != b.float()).all() and (w32[:, :, 3:] == 0).all()
+    x8 = ops.to_c8(x.to(DEV)).requires_grad_(True)
+    wd, bd = w32.to(DEV).requires_grad_(True), b32.to(DEV).requires_grad_(True)
+    y = ops.causal_conv_relu_autograd(x8, wd, bd, 3, d, d)
+    dx, dW, db = torch.autograd.grad(y, [x8, wd, bd], grad_outputs=ops.to_c8(g.to(DEV)))
+    torch.cuda.synchronize()
+    assert torch.equal(y, ops.causal_conv_c8(x8.detach(), w.to(DEV), b.to(DEV), 3, d, d, relu=True))
+    assert (dx.dtype, dW.dtype, db.dtype) == (BF, torch.float32, torch.float32) and dW.shape == (C, C, 5, 3) and (dW[:, :, 3:] == 0).all()
+    y4 = ops.from_c8(y.detach()).cpu()
+    assert 0.25 <= (y4 == 0).float().mean().item() <= 0.75
+    dp = g.double() * (y4 > 0)
+    ref = _grads(x.double(), w[:, :, :3].double(), dp, d)
+    yard = [t.to(dt) for t in _grads(x.float(), w[:, :, :3].float(), dp.float(), d)]
+    failures = []
+    for name, v, r, yd in zip(("dx", "dW", "db"), (ops.from_c8(dx), dW[:, :, :3], db), ref, yard):
+        bar, err = bar_of(yd, r), (v.double().cpu() - r).abs().max().item()
+        print(f"[cnn-bwd] {tuple(x.shape)} d={d} fp32 parameters {name}: max err {err:.3e} bar {bar:.3e} ratio {err / bar:.3f}")
+        if not (torch.isfinite(v).all() and err <= bar):
+            failures.append((name, err, bar))
+    assert not failures, failures
+
+
+@pytest.mark.gpu
 def test_outside_the_predicate_the_op_raises():
     x8 = torch.zeros((1, 2, 1, 8, 8), device=DEV)                                          # fp32 data: the layer keeps its torch path
     w, b = torch.zeros((8, 8, 5, 3), device=DEV), torch.zeros(8, device=DEV)

@@ -121,6 +121,43 @@ def test_kernels_against_fp64_reference(idx):
 
 
 @pytest.mark.gpu
+def test_fp32_parameters_under_bf16_data():
+    """fp32 master weights: the modules stay fp32 and their values are such as bf16 cannot hold -- every value (1 + 2^-10) times a
+    bf16 number, which rounds back to that number.  The forward is bitwise the forward of the rounded modules, the eight parameter
+    gradients come back fp32, and every gradient is held to this file's fp64 reference on the rounded parameters under this file's
+    bar (the yardstick: the rounded modules' chain in the data type)."""
+    idx = 0
+    dt = CASES[idx][5]
+    x, p, g_y, g_tp = _inputs(idx)
+    mods16 = _modules(p, dt)
+    mods = _modules([t.float() * (1 + 2.0 ** -10) for t in p], torch.float32)
+    params16 = [q for m in mods16[:4] for q in (m.weight, m.bias)]
+    params = [q for m in mods[:4] for q in (m.weight, m.bias)]
+    with torch.no_grad():
+        for m, m16 in zip(mods[4:], mods16[4:]):                                           # (the gates' Linear: the same values)
+            m.weight.copy_(m16.weight), m.bias.copy_(m16.bias)
+    for q, q16 in zip(params, params16):
+        assert dt == BF and q.dtype == torch.float32 and torch.equal(q.detach().to(BF), q16.detach())
+        assert (q.detach() != q16.detach().float()).float().mean().item() > 0.99
+    xd = x.contiguous().to(DEV).requires_grad_(True)
+    y8, tpred = ops.predictor_mlp_autograd(xd, *mods)
+    want8, want_tp = ops.predictor_mlp(xd.detach(), *mods16, want_tpred=True)[:2]
+    assert torch.equal(y8, want8) and torch.equal(tpred, want_tp)
+    got = torch.autograd.grad([y8, tpred], [xd, *params], grad_outputs=[ops.to_c8(g_y.to(DEV)), g_tp.to(DEV)])
+    torch.cuda.synchronize()
+    assert [v.dtype for v in got] == [BF] + [torch.float32] * 8
+    ref = _chain_grads(x.double(), [t.double() for t in p], g_y.double(), g_tp.double())
+    yard = _chain_grads(xd, params16, g_y.to(DEV), g_tp.to(DEV))
+    failures = []
+    for name, v, r, yd in zip(NAMES, got, ref, yard):
+        bar, err = bar_of(yd.cpu(), r), (v.double().cpu() - r).abs().max().item()
+        print(f"[mlp-bwd] {tuple(x.shape)} D2={CASES[idx][4]} fp32 parameters {name}: max err {err:.3e} bar {bar:.3e} ratio {err / bar:.3f}")
+        if not (v.shape == r.shape and torch.isfinite(v).all() and err <= bar):
+            failures.append((name, err, bar))
+    assert not failures, failures
+
+
+@pytest.mark.gpu
 def test_outside_the_predicate_the_op_raises():
     mods = _modules(_inputs(4)[1], BF)
     x = torch.zeros((1, 4, 2, 64), device=DEV)                                             # fp32 data: the layer keeps its torch path

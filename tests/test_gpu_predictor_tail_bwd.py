@@ -136,6 +136,34 @@ def test_either_incoming_gradient_may_be_absent(mode):
 
 
 @pytest.mark.gpu
+def test_fp32_parameters_under_bf16_data():
+    """fp32 master weights: the four parameters are fp32 leaves whose values bf16 cannot hold -- every value (1 + 2^-10) times a bf16
+    number, which rounds back to that number.  The forward is bitwise the forward on the rounded parameters, their gradients come
+    back fp32, and every gradient is held to the case's own fp64 reference (on the rounded parameters: the case's own) and bars."""
+    idx = 0
+    T_m, dt = CASES[idx][3], CASES[idx][4]
+    inp, ref, bars = _case(idx)
+    (probs16, scores16), _g16, _in16 = _kernel(idx)
+    yd, params16, g_s, g_p = _device_inputs(idx)
+    params = [(t.detach().float() * (1 + 2.0 ** -10)).requires_grad_(True) for t in params16]
+    for t, t16 in zip(params, params16):
+        assert dt == BF and torch.equal(t.detach().to(BF), t16.detach()) and (t.detach() != t16.detach().float()).float().mean().item() > 0.99
+    probs, scores = ops.predictor_tail_autograd(yd, *params, 4, T_m, EPS)
+    got = torch.autograd.grad([scores, probs], [yd, *params], grad_outputs=[g_s, g_p])
+    torch.cuda.synchronize()
+    assert torch.equal(probs, probs16) and torch.equal(scores, scores16)
+    dy, dW, db, dga, dbe = got
+    assert [g.dtype for g in got] == [BF, F32, F32, F32, F32] and (db == 0).all()
+    failures = []
+    for name, x, r, bar in zip(NAMES, (dy, dW, dga, dbe), ref, bars):
+        err = (x.double().cpu() - r).abs().max().item()
+        print(f"[tail-bwd] {_id(CASES[idx])} fp32 parameters {name}: max err {err:.3e} bar {bar:.3e} ratio {err / bar:.3f}")
+        if not (x.shape == r.shape and torch.isfinite(x).all() and err <= bar):
+            failures.append((name, err, bar))
+    assert not failures, failures
+
+
+@pytest.mark.gpu
 def test_saves_y_and_the_parameters_only_and_returns_none_where_no_gradient_is_wanted():
     idx = 1                                                                    # (2,32,37,256) bf16: a map of 1.2 MB
     N, H, T, T_m, dt, _layout, _seed = CASES[idx]
