@@ -3,7 +3,11 @@
 csrc/sea_performer.hip, the backward of csrc/sea_performer_bwd.hip) against the torch path the layer runs without
 `fused_performer_grad` -- `FastAttention` (perlin_attention/performer.py) plus the two concatenations.  bf16 data, nb = 33.  Both
 variants run alternately in one process; per variant the script prints min / median / max of the rounds, the peak device memory
-above the inputs, and how far the two sets of gradients are apart."""
+above the inputs, and how far the two sets of gradients are apart.
+
+    --grad-segments N|auto   a third variant in the same rounds: the backward cut into row segments (`grad_segments` of the op)
+    --shapes N,H,T,D ...     other shapes than the two of DESIGN 5.10"""
+import argparse
 import json
 import os
 import statistics
@@ -13,7 +17,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from sea_attention_amd import _lib                                                   # noqa: E402
 from sea_attention_amd.perlin_attention import ops                                  # noqa: E402
+from sea_attention_amd.perlin_attention.ops import performer_grad                    # noqa: E402
 from sea_attention_amd.perlin_attention.performer import FastAttention               # noqa: E402
 
 DEV = "cuda:0"
@@ -24,6 +30,10 @@ WARMUP, ROUNDS = 3, 10
 
 def hip_step(fa, q, k, v, pos):
     return ops.performer_value_autograd(q, k, v, pos, fa.projection_matrix)
+
+
+def hip_seg_step(grad_segments):
+    return lambda fa, q, k, v, pos: ops.performer_value_autograd(q, k, v, pos, fa.projection_matrix, grad_segments=grad_segments)
 
 
 def torch_step(fa, q, k, v, pos):
@@ -39,8 +49,14 @@ def step(fn, fa, leaves, g):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grad-segments", default=None)
+    ap.add_argument("--shapes", nargs="*", default=None)
+    args = ap.parse_args()
+    seg = args.grad_segments if args.grad_segments in (None, "auto") else int(args.grad_segments)
+    shapes = SHAPES if not args.shapes else [tuple(int(x) for x in s.split(",")) for s in args.shapes]
     assert torch.cuda.is_available(), "needs the MI355X"
-    for N, H, T, D in SHAPES:
+    for N, H, T, D in shapes:
         gen = torch.Generator(device=DEV).manual_seed(0)
         rnd = lambda *s: torch.randn(s, generator=gen, device=DEV)
         torch.manual_seed(0)
@@ -49,6 +65,8 @@ def main():
         leaves.append(rnd(T, D).bfloat16().requires_grad_(True))
         g = rnd(N, H, T, 3 * D).bfloat16()
         variants = {"hip": hip_step, "torch": torch_step}
+        if seg is not None:
+            variants["hip_seg"] = hip_seg_step(seg)
         res = {k: {"ms": []} for k in variants}
         for name, fn in variants.items():
             for _ in range(WARMUP):
@@ -80,6 +98,12 @@ def main():
             out[name] = {"ms_min": round(min(ms), 3), "ms_median": round(statistics.median(ms), 3), "ms_max": round(max(ms), 3),
                          "held_mb_after_forward": res[name]["held_mb_after_forward"],
                          "peak_mb_above_inputs": res[name]["peak_mb_above_inputs"]}
+        if seg is not None:
+            requested = performer_grad.grad_segments_for(leaves[0], seg)
+            out["grad_segments"] = {"requested": requested, "effective": _lib.load().sea_performer_causal_bwd_seg_count(T, requested)}
+            out["seg_speedup_median"] = round(statistics.median(res["hip"]["ms"]) / statistics.median(res["hip_seg"]["ms"]), 2)
+            out["seg_max_abs_grad_difference"] = {n: (a - b).abs().max().item() for n, a, b in
+                                                  zip(("dq", "dk", "dv", "dpos"), res["hip_seg"]["grads"], res["torch"]["grads"])}
         out["speedup_median"] = round(statistics.median(res["torch"]["ms"]) / statistics.median(res["hip"]["ms"]), 2)
         out["max_abs_grad_difference"] = {n: (a - b).abs().max().item() for n, a, b in
                                           zip(("dq", "dk", "dv", "dpos"), res["hip"]["grads"], res["torch"]["grads"])}

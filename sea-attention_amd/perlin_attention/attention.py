@@ -222,6 +222,9 @@ class PerlinAttention(nn.Module):
         # share a dtype and a length and `ops.performer_value_grad_supported` holds; elsewhere, and with False, `self.performer`
         # runs as before.  The MLP and the CNN stay torch modules under autograd either way; the tail has its own switch below
         self.fused_performer_grad = False
+        # with `fused_performer_grad`: the row segments that backward is cut into per (n, h) (`grad_segments` of the op: None = one
+        # workgroup per (n, h) and sweep as before, an int >= 1, or "auto" = enough for every CU -- for one sequence per GPU)
+        self.fused_performer_grad_segments = None
         # training: True = the predictor's tail (cnn.keepres.upsam, cnn.keepres.conv4, the KeepRes area resize, cnn.lnorm2 and
         # the softmax over T_M) runs as ONE op on the HIP kernels UNDER AUTOGRAD (`ops.predictor_tail_autograd`: the forward
         # launch of inference, the backward of csrc/sea_tail_bwd.hip, nothing saved but the tail's input and its parameters --
@@ -543,9 +546,10 @@ class PerlinAttention(nn.Module):
             # training: the same launch as below with a backward on the kernels; the gradients reach the value embedding and
             # the estimator's q / k / v branches through it
             with timer("performer"):
+                seg = {} if self.fused_performer_grad_segments is None else {"grad_segments": self.fused_performer_grad_segments}
                 performer_value = ops.performer_value_autograd(q_for_atten, k_for_atten, v_for_atten, pos,
                                                                self.performer.projection_matrix,
-                                                               n_segments=self.performer_segments)
+                                                               n_segments=self.performer_segments, **seg)
                 if v_for_atten is not v:           # a separate estimator branch for v: the last third is the LAYER's v, as below
                     performer_value = torch.cat([performer_value[..., :2 * q.shape[-1]], v], dim=-1)
                 bench.register_temp_buffer('performer_context_layer', performer_value[..., :2 * q.shape[-1]])

@@ -37,53 +37,95 @@ def performer_value_grad_supported(q, k, v, pos, projection) -> bool:
     return all(_aligned(t) for t in (q, k, v)) and (pos.dtype != q.dtype or _aligned(pos))
 
 
+def _forward(ctx, q, k, v, pos, projection, n_segments):
+    with torch.no_grad():
+        q_d, k_d, v_d, pos_d = q.detach(), k.detach(), v.detach(), pos.detach()
+        out = performer_value(q_d, k_d, v_d, pos_d, projection, n_segments=n_segments)
+        # the very tensor the forward launch read (ops.predictor's cache): the projection rounded to the data type, as fp32
+        proj = _cached("proj", (projection,), q.dtype, lambda: projection.to(q.dtype).float().contiguous())
+    ctx.save_for_backward(q_d, k_d, v_d, pos_d, proj)
+    return out
+
+
+@_lib.device_guarded
+def _backward(grad_out, saved, need, segments=None):
+    """(dq, dk, dv, dpos), None where `need` is False.  `segments` None: `sea_performer_causal_bwd`; an int: that many row
+    segments requested of `sea_performer_causal_bwd_seg`."""
+    q, k, v, pos, proj = saved
+    if not any(need[:4]):
+        return None, None, None, None
+    lib = _lib.load()
+    N, H, T, D = q.shape
+    nb = proj.shape[0]
+    code = _lib.dtype_code(q.dtype)
+    g = grad_out if grad_out.dtype == q.dtype else grad_out.to(q.dtype)
+    g = g.contiguous()
+    pos_in = pos if pos.dtype == q.dtype else pos.to(q.dtype)
+    pos_in = pos_in if pos_in.stride(-1) == 1 else pos_in.contiguous()
+    d_q, d_k, d_v = (torch.empty((N, H, T, D), dtype=q.dtype, device=q.device) for _ in range(3))
+    d_pos = torch.empty((T, D), dtype=torch.float32, device=q.device)
+    if segments is None:
+        name, seg = "sea_performer_causal_bwd", ()
+        ws_bytes = lib.sea_performer_causal_bwd_workspace_bytes(N, H, T, D, nb, code)
+    else:
+        name, seg = "sea_performer_causal_bwd_seg", (segments,)
+        ws_bytes = lib.sea_performer_causal_bwd_seg_workspace_bytes(N, H, T, D, nb, code, segments)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
+    _lib.check(getattr(lib, name)(
+        _p(q), _p(k), _p(v), _p(pos_in), code, _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
+        pos_in.stride(0), _p(g), _p(d_q), _p(d_k), _p(d_v), _p(d_pos), *seg, _p(ws), ws_bytes, _lib.stream_ptr()), name)
+    g_pos = None
+    if need[3]:
+        g_pos = torch.zeros(pos.shape, dtype=pos.dtype, device=pos.device)
+        g_pos[:T] = d_pos
+    return d_q if need[0] else None, d_k if need[1] else None, d_v if need[2] else None, g_pos
+
+
 class _PerformerValueFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, pos, projection, n_segments):
-        with torch.no_grad():
-            q_d, k_d, v_d, pos_d = q.detach(), k.detach(), v.detach(), pos.detach()
-            out = performer_value(q_d, k_d, v_d, pos_d, projection, n_segments=n_segments)
-            # the very tensor the forward launch read (ops.predictor's cache): the projection rounded to the data type, as fp32
-            proj = _cached("proj", (projection,), q.dtype, lambda: projection.to(q.dtype).float().contiguous())
-        ctx.save_for_backward(q_d, k_d, v_d, pos_d, proj)
-        return out
+        return _forward(ctx, q, k, v, pos, projection, n_segments)
 
     @staticmethod
     @once_differentiable
-    @_lib.device_guarded
     def backward(ctx, grad_out):
-        q, k, v, pos, proj = ctx.saved_tensors
-        if not any(ctx.needs_input_grad[:4]):
-            return None, None, None, None, None, None
-        lib = _lib.load()
-        N, H, T, D = q.shape
-        nb = proj.shape[0]
-        code = _lib.dtype_code(q.dtype)
-        g = grad_out if grad_out.dtype == q.dtype else grad_out.to(q.dtype)
-        g = g.contiguous()
-        pos_in = pos if pos.dtype == q.dtype else pos.to(q.dtype)
-        pos_in = pos_in if pos_in.stride(-1) == 1 else pos_in.contiguous()
-        d_q, d_k, d_v = (torch.empty((N, H, T, D), dtype=q.dtype, device=q.device) for _ in range(3))
-        d_pos = torch.empty((T, D), dtype=torch.float32, device=q.device)
-        ws_bytes = lib.sea_performer_causal_bwd_workspace_bytes(N, H, T, D, nb, code)
-        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
-        _lib.check(lib.sea_performer_causal_bwd(
-            _p(q), _p(k), _p(v), _p(pos_in), code, _p(proj), N, H, T, D, nb, _lib.strides3(q), _lib.strides3(k), _lib.strides3(v),
-            pos_in.stride(0), _p(g), _p(d_q), _p(d_k), _p(d_v), _p(d_pos), _p(ws), ws_bytes, _lib.stream_ptr()),
-            "sea_performer_causal_bwd")
-        need = ctx.needs_input_grad
-        g_pos = None
-        if need[3]:
-            g_pos = torch.zeros(pos.shape, dtype=pos.dtype, device=pos.device)
-            g_pos[:T] = d_pos
-        return (d_q if need[0] else None, d_k if need[1] else None, d_v if need[2] else None, g_pos, None, None)
+        return (*_backward(grad_out, ctx.saved_tensors, ctx.needs_input_grad), None, None)
 
 
-def performer_value_autograd(q, k, v, pos, projection, n_segments=None):
+class _PerformerValueSegFn(torch.autograd.Function):
+    """The same op with the backward cut into row segments (`grad_segments`, an int >= 1)"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pos, projection, n_segments, grad_segments):
+        ctx.grad_segments = grad_segments
+        return _forward(ctx, q, k, v, pos, projection, n_segments)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return (*_backward(grad_out, ctx.saved_tensors, ctx.needs_input_grad, ctx.grad_segments), None, None, None)
+
+
+def grad_segments_for(q, grad_segments):
+    """The count `performer_value_autograd` requests for `grad_segments`: an int >= 1 as it is, "auto" one segment per
+    ceil(CUs / (N H)) -- enough workgroups per sweep to give every CU of q's device one."""
+    if grad_segments == "auto":
+        cus = torch.cuda.get_device_properties(q.device).multi_processor_count
+        return -(-cus // (q.shape[0] * q.shape[1]))
+    if isinstance(grad_segments, bool) or not isinstance(grad_segments, int) or grad_segments < 1:
+        raise ValueError(f"grad_segments must be None, an int >= 1 or 'auto', got {grad_segments!r}")
+    return grad_segments
+
+
+def performer_value_autograd(q, k, v, pos, projection, n_segments=None, grad_segments=None):
     """`ops.performer_value(q, k, v, pos, projection)` (no cumulative average), differentiable with respect to q, k, v and pos.
-    Raises where `performer_value_grad_supported` does not hold: there is no other path behind this name."""
+    `grad_segments`: None runs the backward as one workgroup per (n, h) and sweep; an int >= 1 or "auto" asks for that many row
+    segments per (n, h) (`sea_performer_causal_bwd_seg`: one sequence per GPU leaves most CUs idle otherwise; 1 gives the bits
+    of None).  Raises where `performer_value_grad_supported` does not hold: there is no other path behind this name."""
     if not performer_value_grad_supported(q, k, v, pos, projection):
         raise RuntimeError(f"performer_value_autograd: q {tuple(q.shape)} {q.dtype} strides {q.stride()}, nb={projection.shape[0]} "
                            "is outside the backward kernels (ops.performer_value_grad_supported)")
-    return _PerformerValueFn.apply(q, k, v, pos, projection, n_segments)
+    if grad_segments is None:
+        return _PerformerValueFn.apply(q, k, v, pos, projection, n_segments)
+    return _PerformerValueSegFn.apply(q, k, v, pos, projection, n_segments, grad_segments_for(q, grad_segments))
