@@ -139,6 +139,17 @@ _PREDICTOR_MLP_GRAD_SIGNATURES = {
                                ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_context_grad.h: the sparse context branch (scale, mix, cumulative average) under autograd, versioned on its own
+CONTEXT_GRAD_ABI_VERSION = 1      # SEA_CONTEXT_GRAD_ABI_VERSION
+_CONTEXT_GRAD_SIGNATURES = {
+    "sea_context_grad_version": ([], c_int),
+    "sea_context_grad_supported": ([i64, i64, i64, c_int, c_int], c_int),
+    "sea_context_grad_workspace_bytes": ([i64, i64, i64, i64, c_int], i64),
+    "sea_context_mix_fwd": ([ptr, _i64p, ptr, ptr, ptr, c_int, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr], c_int),
+    "sea_context_mix_bwd": ([ptr, _i64p, ptr, ptr, ptr, ptr, c_int, c_int, i64, i64, i64, i64, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+    "sea_context_dv_finish": ([ptr, ptr, ptr, c_int, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -224,6 +235,13 @@ def load(build_if_missing=True):
         raise RuntimeError(f"{path}: predictor-MLP-gradient entries of version {lib.sea_predictor_mlp_grad_version()}, this binding "
                            f"speaks {PREDICTOR_MLP_GRAD_ABI_VERSION} (include/sea_hip_predictor_mlp_grad.h) -- rebuild the library from "
                            "this tree's csrc/")
+    for name, (argtypes, restype) in _CONTEXT_GRAD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_context_grad_version() != CONTEXT_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: context-gradient entries of version {lib.sea_context_grad_version()}, this binding speaks "
+                           f"{CONTEXT_GRAD_ABI_VERSION} (include/sea_hip_context_grad.h) -- rebuild the library from this tree's csrc/")
     _lib = lib
     return lib
 

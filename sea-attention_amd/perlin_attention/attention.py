@@ -250,6 +250,13 @@ class PerlinAttention(nn.Module):
         # holds (16-bit data, d = 64, T_M <= 256, H % 4 == 0).  Its C8 output goes straight into the conv op: the `to_c8` copy is
         # gone.  The gates stay the torch Linear on t_attention_predictor.  Elsewhere, and with False, nothing changes
         self.fused_mlp_grad = False
+        # training: True = the training branch of `_forward_sparse` runs from q, k, v to the (N, T, H d) context as ONE op on the HIP
+        # kernels UNDER AUTOGRAD (`ops.sparse_context_autograd`: the attention launch and backward of `sparse_attention_autograd`
+        # with the cumulative average of v, its rounding, the row scale, the mix, the permute and the cast in the kernels of
+        # csrc/sea_context_grad.hip on both sides; saved: q, k, v, the gates, the per-entry probabilities and the fp32 product --
+        # not the average, the scaled or mixed product or the permuted copy) wherever the batch is unpadded, T == T_SRC and
+        # `ops.sparse_context_grad_supported` holds.  Elsewhere (padded batches, probing), and with False, nothing changes
+        self.fused_context_grad = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -1206,8 +1213,14 @@ class PerlinAttention(nn.Module):
                     sig = torch.sigmoid(estimated_scales.float())
                     row_scale = sig[..., 0].contiguous() if self.pconfig.partial_attention_scaler else None
                     average_scale = sig[..., 1].contiguous()
+            # `fused_context_grad`: under autograd the average is formed, mixed in and differentiated inside the one op below
+            context_op = (self.fused_context_grad and torch.is_grad_enabled() and not_padded and not probing and T == T_SRC
+                          and self._avg_ahead is None and self._fused_context_ok(q_for_score, k_for_score, v, csr, row_scale,
+                                                                                 average_scale))
             with timer("attention.avg_pool"):
-                if self._avg_ahead is not None and not_padded:         # came out of the Performer launch
+                if context_op:
+                    average_context_layer = None
+                elif self._avg_ahead is not None and not_padded:       # came out of the Performer launch
                     average_context_layer, self._avg_ahead = self._avg_ahead, None
                 else:
                     avg_v = v if not_padded else v * (dst_attention_mask > -1)
@@ -1224,7 +1237,7 @@ class PerlinAttention(nn.Module):
                 ks = ks.to(qs.dtype)
             if vs.dtype != qs.dtype:
                 vs = vs.to(qs.dtype)
-            if average_context_layer.dtype != qs.dtype:
+            if average_context_layer is not None and average_context_layer.dtype != qs.dtype:
                 average_context_layer = average_context_layer.to(qs.dtype)
             want_probs = self.return_attention_probs or probing
             probs_csr = None
@@ -1241,6 +1254,9 @@ class PerlinAttention(nn.Module):
                     bench.register_temp_buffer('partial_context_layer_2', p2)
                     with timer("context_permute"):
                         ctx = p2.permute(0, 2, 1, 3).contiguous().view(N, T, H * HID).to(out_dtype)
+                elif context_op:
+                    # the same branch as one op: scale, mix, average, permute and cast in the kernels, forwards and backwards
+                    ctx = ops.sparse_context_autograd(qs, ks, v, csr, row_scale, average_scale, out_dtype)
                 elif torch.is_grad_enabled() and any(t_.requires_grad for t_ in (qs, ks, vs, average_scale, average_context_layer)
                                                     + ((row_scale,) if row_scale is not None else ())):
                     # training through the sparse branch: HIP forward + backward for the sparse product
@@ -1284,6 +1300,15 @@ class PerlinAttention(nn.Module):
         if self.materialize_csr:
             return ctx, (probs_csr.to_sparse_csr() if probs_csr is not None else None), csr.to_sparse_csr()
         return ctx, probs_csr, csr
+
+    def _fused_context_ok(self, q, k, v, csr, row_scale, mix):
+        """`fused_context_grad` applies: something wants a gradient (the arm `_forward_sparse` takes today under autograd), q, k, v
+        share a dtype (the op takes v itself, strides and all) and the op's predicate holds on what the branch would hand it."""
+        gates = (mix,) + ((row_scale,) if row_scale is not None else ())
+        if not any(t.requires_grad for t in (q, k, v) + gates) or not (q.dtype == k.dtype == v.dtype):
+            return False
+        qs, ks = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k))
+        return ops.sparse_context_grad_supported(qs, ks, v, csr, row_scale, mix, self.context_layer_dtype or torch.float32)
 
     # ------------------------------------------------------------------------------------------------
     def _forward_dense(self, q, v, q_for_score, k_for_score, t_attention_predictor, probs, causal_attention_mask,
