@@ -150,6 +150,14 @@ _CONTEXT_GRAD_SIGNATURES = {
     "sea_context_dv_finish": ([ptr, ptr, ptr, c_int, c_int, i64, i64, i64, i64, ptr, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_predictor_mlp_f32.h: the one-launch predictor MLP for fp32 data, additive and versioned on its own
+PREDICTOR_MLP_F32_ABI_VERSION = 1      # SEA_PREDICTOR_MLP_F32_ABI_VERSION
+_PREDICTOR_MLP_F32_SIGNATURES = {
+    "sea_predictor_mlp_f32_version": ([], c_int),
+    "sea_predictor_mlp_f32_supported": ([i64, i64, i64, i64], c_int),
+    "sea_predictor_mlp_f32": ([ptr, i64, i64, i64, i64, _i64p, i64, i64, ptr, ptr, ptr, _f32, _f32, ptr, i64, ptr, ptr, ptr, ptr], c_int),
+}
+
 
 def library_path():
     return _build.LIB_PATH
@@ -242,6 +250,13 @@ def load(build_if_missing=True):
     if lib.sea_context_grad_version() != CONTEXT_GRAD_ABI_VERSION:
         raise RuntimeError(f"{path}: context-gradient entries of version {lib.sea_context_grad_version()}, this binding speaks "
                            f"{CONTEXT_GRAD_ABI_VERSION} (include/sea_hip_context_grad.h) -- rebuild the library from this tree's csrc/")
+    for name, (argtypes, restype) in _PREDICTOR_MLP_F32_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_predictor_mlp_f32_version() != PREDICTOR_MLP_F32_ABI_VERSION:
+        raise RuntimeError(f"{path}: fp32 predictor-MLP entries of version {lib.sea_predictor_mlp_f32_version()}, this binding speaks "
+                           f"{PREDICTOR_MLP_F32_ABI_VERSION} (include/sea_hip_predictor_mlp_f32.h) -- rebuild the library from this tree's csrc/")
     _lib = lib
     return lib
 

@@ -257,6 +257,12 @@ class PerlinAttention(nn.Module):
         # not the average, the scaled or mixed product or the permuted copy) wherever the batch is unpadded, T == T_SRC and
         # `ops.sparse_context_grad_supported` holds.  Elsewhere (padded batches, probing), and with False, nothing changes
         self.fused_context_grad = False
+        # inference on fp32 data: True = attention_predictor_enc, the row decoder's Linear + ChannelSplit(2), cnn.lnorm1 and the two
+        # gates run as ONE launch on the fp32 matrix instruction (`ops.predictor_mlp_f32`, csrc/sea_mlp_f32.hip) wherever the modules
+        # have the one-launch MLP's structure, `ops.predictor_mlp_f32_supported` holds (d = 64, T_M in {32, 64, 96, 128, 256}, H % 4 == 0)
+        # and the C8 convolutions take fp32; its C8 output goes straight into them.  Dense and sparse mode both take it.  With False
+        # (the default), under autograd and elsewhere: two library GEMMs, two LayerNorm launches, a re-layout copy, a third GEMM
+        self.fused_mlp_fp32 = False
         self._kd_wants_scores = False       # this call's estimator must hand out its scores (sparse mode drops them otherwise)
         self._fused_gates = None           # (row_scale, average_scale) when the fused predictor MLP produced them
         self._fused_selection = None        # (bits, row_nnz, head_off) when the tail kernel also ran the top-k selection
@@ -419,13 +425,14 @@ class PerlinAttention(nn.Module):
                 return None
         return convs
 
-    def _fused_mlp_ok(self, x, autograd_too=False):
+    def _fused_mlp_ok(self, x, autograd_too=False, fp32=False):
         """One-launch predictor MLP (csrc/sea_mlp.hip): inference on 16-bit data with the standard
         enc = Linear+LayerNorm+GELU / dec_row = Linear+ChannelSplit(2) / 2-way gate modules, C8 CNN available.
         Dense and sparse mode share it (so both see the same probability map); dense mode also asks for the
         encoder output, which its gate / probing code reads.  `autograd_too`: the same conditions without the autograd one
-        (`_mlp_grad_ok`)."""
-        if not (self._hip_estimator_ok(x, autograd_too) and x.dtype in (torch.float16, torch.bfloat16)):
+        (`_mlp_grad_ok`).  `fp32`: the same conditions for fp32 data and csrc/sea_mlp_f32.hip (`fused_mlp_fp32`): the dtype and
+        shape conditions are `ops.predictor_mlp_f32_supported`."""
+        if not (self._hip_estimator_ok(x, autograd_too) and x.dtype in ((torch.float32,) if fp32 else (torch.float16, torch.bfloat16))):
             return False
         if self.pconfig.attention_predictor_enc_per_layer or int(os.environ.get('QUERY_SKIPS', '1')) != 1:
             return False
@@ -441,7 +448,8 @@ class PerlinAttention(nn.Module):
         body = list(self.attention_predictor_cnn[1].module.net.children())
         return (isinstance(ln1, nn.LayerNorm) and ln1.elementwise_affine
                 and tuple(ln1.normalized_shape) == (dec[0].out_features // 2,)
-                and ops.predictor_mlp_supported(enc[0].out_features, dec[0].out_features, x.shape[1], x.shape[-1])
+                and (ops.predictor_mlp_f32_supported(x, enc[0], enc[1], dec[0], ln1, sc[0]) if fp32 else
+                     ops.predictor_mlp_supported(enc[0].out_features, dec[0].out_features, x.shape[1], x.shape[-1]))
                 and self._c8_cnn_ok(x, body))
 
     def _mlp_grad_ok(self, x):
@@ -618,11 +626,12 @@ class PerlinAttention(nn.Module):
             bench.register_temp_buffer('estimated_attention_probs', estimated_attention_probs)
             return v, t_attention_predictor, estimated_attention_score, estimated_attention_probs
         fused_mlp = self._fused_mlp_ok(performer_value)
-        if fused_mlp:
+        mlp_fp32 = not fused_mlp and self.fused_mlp_fp32 and self._fused_mlp_ok(performer_value, fp32=True)
+        if fused_mlp or mlp_fp32:
             with timer("predictor"):
                 want_scores = get_bench().activate_temp_buffers or (not self.benchmarking) or self._kd_wants_scores
                 with timer("predictor.mlp"):   # enc + dec_row + lnorm1 (+ the two gates) in one launch
-                    x, t_attention_predictor, row_scale, avg_scale = ops.predictor_mlp(
+                    x, t_attention_predictor, row_scale, avg_scale = (ops.predictor_mlp_f32 if mlp_fp32 else ops.predictor_mlp)(
                         performer_value, self.attention_predictor_enc[0], self.attention_predictor_enc[1],
                         self.attention_predictor_dec_row[0], self.attention_predictor_cnn[0].module,
                         self.attention_predictor_dec_scaler[0], want_tpred=want_scores)

@@ -30,5 +30,7 @@ from .predictor_tail_grad import predictor_tail_autograd, predictor_tail_grad_su
 from .predictor_cnn_grad import causal_conv_relu_autograd, causal_conv_relu_grad_supported
 # the gradient of the predictor MLP (include/sea_hip_predictor_mlp_grad.h)
 from .predictor_mlp_grad import predictor_mlp_autograd, predictor_mlp_grad_supported
+# the one-launch predictor MLP for fp32 data (include/sea_hip_predictor_mlp_f32.h)
+from .predictor_mlp_f32 import predictor_mlp_f32, predictor_mlp_f32_supported
 # the sparse context branch -- scale, mix and cumulative average around the sparse product (include/sea_hip_context_grad.h)
 from .context_grad import sparse_context_autograd, sparse_context_grad_supported
