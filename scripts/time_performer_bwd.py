@@ -6,7 +6,9 @@ variants run alternately in one process; per variant the script prints min / med
 above the inputs, and how far the two sets of gradients are apart.
 
     --grad-segments N|auto   a third variant in the same rounds: the backward cut into row segments (`grad_segments` of the op)
-    --shapes N,H,T,D ...     other shapes than the two of DESIGN 5.10"""
+    --shapes N,H,T,D ...     other shapes than the two of DESIGN 5.10
+    --head-size 80|128       the shapes and feature counts of DESIGN 5.10b; "hip" is then `ops.performer_value_autograd_wide`
+    --nb F                   the feature count (default 33; 43 / 77 with --head-size 80 / 128)"""
 import argparse
 import json
 import os
@@ -24,11 +26,14 @@ from sea_attention_amd.perlin_attention.performer import FastAttention          
 
 DEV = "cuda:0"
 SHAPES = [(8, 32, 4096, 64), (1, 32, 4096, 64)]
+WIDE_SHAPES = {80: ([(8, 32, 4096, 80)], 43), 128: ([(8, 40, 4096, 128), (1, 40, 4096, 128)], 77)}     # OPT-2.7B, LLaMA-13B
 NB = 33
 WARMUP, ROUNDS = 3, 10
 
 
 def hip_step(fa, q, k, v, pos):
+    if q.shape[-1] != 64:
+        return ops.performer_value_autograd_wide(q, k, v, pos, fa.projection_matrix)
     return ops.performer_value_autograd(q, k, v, pos, fa.projection_matrix)
 
 
@@ -52,15 +57,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grad-segments", default=None)
     ap.add_argument("--shapes", nargs="*", default=None)
+    ap.add_argument("--head-size", type=int, choices=sorted(WIDE_SHAPES), default=None)
+    ap.add_argument("--nb", type=int, default=None)
     args = ap.parse_args()
     seg = args.grad_segments if args.grad_segments in (None, "auto") else int(args.grad_segments)
-    shapes = SHAPES if not args.shapes else [tuple(int(x) for x in s.split(",")) for s in args.shapes]
+    default_shapes, default_nb = WIDE_SHAPES[args.head_size] if args.head_size else (SHAPES, NB)
+    shapes = default_shapes if not args.shapes else [tuple(int(x) for x in s.split(",")) for s in args.shapes]
+    nb = args.nb or default_nb
     assert torch.cuda.is_available(), "needs the MI355X"
     for N, H, T, D in shapes:
         gen = torch.Generator(device=DEV).manual_seed(0)
         rnd = lambda *s: torch.randn(s, generator=gen, device=DEV)
         torch.manual_seed(0)
-        fa = FastAttention(dim_heads=D, nb_features=NB, causal=True, generalized_attention=True).to(DEV).to(torch.bfloat16)
+        fa = FastAttention(dim_heads=D, nb_features=nb, causal=True, generalized_attention=True).to(DEV).to(torch.bfloat16)
         leaves = [(rnd(N, H, T, D) * s).bfloat16().requires_grad_(True) for s in (D ** -0.5, 1.0, 1.0)]
         leaves.append(rnd(T, D).bfloat16().requires_grad_(True))
         g = rnd(N, H, T, 3 * D).bfloat16()
@@ -92,7 +101,7 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 res[name]["ms"].append(e0.elapsed_time(e1))
-        out = {"shape": [N, H, T, D], "nb": NB, "dtype": "bf16", "rounds": ROUNDS}
+        out = {"shape": [N, H, T, D], "nb": nb, "dtype": "bf16", "rounds": ROUNDS}
         for name in variants:
             ms = res[name]["ms"]
             out[name] = {"ms_min": round(min(ms), 3), "ms_median": round(statistics.median(ms), 3), "ms_max": round(max(ms), 3),

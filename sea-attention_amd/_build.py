@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libsea_hip.so")
 SOURCES = ["sea_topk.hip", "sea_attn.hip", "sea_attn_tile.hip", "sea_attn_keyrange.hip", "sea_attn_bwd.hip", "sea_csr_ops.hip",
            "sea_predictor.hip", "sea_performer.hip", "sea_conv.hip", "sea_mlp.hip", "sea_decode.hip", "sea_kd_loss.hip",
            "sea_kd_score_loss.hip", "sea_performer_bwd.hip", "sea_tail_bwd.hip", "sea_conv_bwd.hip", "sea_mlp_bwd.hip",
-           "sea_performer_bwd_seg.hip", "sea_context_grad.hip", "sea_mlp_f32.hip"]
+           "sea_performer_bwd_seg.hip", "sea_context_grad.hip", "sea_mlp_f32.hip", "sea_performer_bwd_wide.hip"]
 HEADERS = [os.path.join(CSRC, "sea_common.hpp"), os.path.join(CSRC, "sea_attn.hpp"), os.path.join(CSRC, "sea_tail.hpp"),
            os.path.join(CSRC, "sea_convfrag.hpp"), os.path.join(CSRC, "sea_performer16.hpp"), os.path.join(CSRC, "sea_kd.hpp"),
            os.path.join(CSRC, "sea_performer_bwd.hpp"), os.path.join(CSRC, "sea_tail_select_row.inc"),
@@ -28,7 +28,8 @@ HEADERS = [os.path.join(CSRC, "sea_common.hpp"), os.path.join(CSRC, "sea_attn.hp
            os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_predictor_cnn_grad.h"),
            os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_predictor_mlp_grad.h"),
            os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_context_grad.h"),
-           os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_predictor_mlp_f32.h")]
+           os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_predictor_mlp_f32.h"),
+           os.path.join(os.path.dirname(PKG_DIR), "include", "sea_hip_estimator_grad_wide.h")]
 # -fno-slp-vectorize: the SLP pass packs adjacent scalar f32 adds/muls into v_pk_* pairs plus the v_mov traffic
 # to form the register pairs; on gfx950 that is a net loss in these VALU-issue-bound kernels (A/B: -1.5 % step)
 COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
@@ -40,6 +41,7 @@ FILE_FLAGS = {"sea_attn_tile.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               # no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the recomputing backward: it must reproduce the forward's bits
               # nor in the row-segmented Performer backward (new code is built without them; sea_performer_bwd.hip keeps its build)
               "sea_performer_bwd_seg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "sea_performer_bwd_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "sea_mlp_bwd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the context branch's forward and backward recompute one average: the same scalar fp32 ops in both
               "sea_context_grad.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}

@@ -109,8 +109,18 @@ _ESTIMATOR_GRAD_SEG_SIGNATURES = {
                                       ptr, ptr, ptr, ptr, ptr, i64, ptr, i64, ptr], c_int),
 }
 
+# include/sea_hip_estimator_grad_wide.h: the Performer's backward for the head sizes 80 and 128, additive and versioned on its own
+ESTIMATOR_GRAD_WIDE_ABI_VERSION = 1      # SEA_ESTIMATOR_GRAD_WIDE_ABI_VERSION
+_ESTIMATOR_GRAD_WIDE_SIGNATURES = {
+    "sea_estimator_grad_wide_version": ([], c_int),
+    "sea_performer_causal_bwd_wide_supported": ([i64, i64, c_int], c_int),
+    "sea_performer_causal_bwd_wide_workspace_bytes": ([i64, i64, i64, i64, i64, c_int], i64),
+    "sea_performer_causal_bwd_wide": ([ptr, ptr, ptr, ptr, c_int, ptr, i64, i64, i64, i64, i64, _i64p, _i64p, _i64p, i64,
+                                       ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr], c_int),
+}
+
 # include/sea_hip_predictor_grad.h: gradients of the predictor's kernels, additive and versioned on their own as well
-PREDICTOR_GRAD_ABI_VERSION = 1     # SEA_PREDICTOR_GRAD_ABI_VERSION
+PREDICTOR_GRAD_ABI_VERSION = 1    # SEA_PREDICTOR_GRAD_ABI_VERSION
 _PREDICTOR_GRAD_SIGNATURES = {
     "sea_predictor_grad_version": ([], c_int),
     "sea_predictor_tail_bwd_supported": ([i64, i64, i64, i64, i64, c_int], c_int),
@@ -219,6 +229,14 @@ def load(build_if_missing=True):
     if lib.sea_estimator_grad_seg_version() != ESTIMATOR_GRAD_SEG_ABI_VERSION:
         raise RuntimeError(f"{path}: segmented estimator-gradient entries of version {lib.sea_estimator_grad_seg_version()}, this "
                            f"binding speaks {ESTIMATOR_GRAD_SEG_ABI_VERSION} (include/sea_hip_estimator_grad_seg.h) -- rebuild the "
+                           "library from this tree's csrc/")
+    for name, (argtypes, restype) in _ESTIMATOR_GRAD_WIDE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
+    if lib.sea_estimator_grad_wide_version() != ESTIMATOR_GRAD_WIDE_ABI_VERSION:
+        raise RuntimeError(f"{path}: wide-head estimator-gradient entries of version {lib.sea_estimator_grad_wide_version()}, this "
+                           f"binding speaks {ESTIMATOR_GRAD_WIDE_ABI_VERSION} (include/sea_hip_estimator_grad_wide.h) -- rebuild the "
                            "library from this tree's csrc/")
     for name, (argtypes, restype) in _PREDICTOR_GRAD_SIGNATURES.items():
         fn = getattr(lib, name)

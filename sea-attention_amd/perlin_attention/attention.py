@@ -219,11 +219,14 @@ class PerlinAttention(nn.Module):
         # training: True = the Performer step of the estimator runs on the HIP kernels UNDER AUTOGRAD
         # (`ops.performer_value_autograd`: the forward launch of inference, the backward of csrc/sea_performer_bwd.hip, nothing
         # saved but q, k, v, the value embedding and the projection) wherever the batch is unpadded, the estimator's q / k / v
-        # share a dtype and a length and `ops.performer_value_grad_supported` holds; elsewhere, and with False, `self.performer`
-        # runs as before.  The MLP and the CNN stay torch modules under autograd either way; the tail has its own switch below
+        # share a dtype and a length and `ops.performer_value_grad_supported` holds (head size 64) or, failing that,
+        # `ops.performer_value_grad_wide_supported` (head sizes 80 / 128: `ops.performer_value_autograd_wide`,
+        # csrc/sea_performer_bwd_wide.hip); elsewhere, and with False, `self.performer` runs as before.  The MLP and the CNN stay
+        # torch modules under autograd either way; the tail has its own switch below
         self.fused_performer_grad = False
         # with `fused_performer_grad`: the row segments that backward is cut into per (n, h) (`grad_segments` of the op: None = one
-        # workgroup per (n, h) and sweep as before, an int >= 1, or "auto" = enough for every CU -- for one sequence per GPU)
+        # workgroup per (n, h) and sweep as before, an int >= 1, or "auto" = enough for every CU -- for one sequence per GPU).
+        # Ignored at the head sizes 80 / 128, where `ops.performer_value_autograd_wide` runs: it has no row segments
         self.fused_performer_grad_segments = None
         # training: True = the predictor's tail (cnn.keepres.upsam, cnn.keepres.conv4, the KeepRes area resize, cnn.lnorm2 and
         # the softmax over T_M) runs as ONE op on the HIP kernels UNDER AUTOGRAD (`ops.predictor_tail_autograd`: the forward
@@ -549,22 +552,28 @@ class PerlinAttention(nn.Module):
         hip_perf = (self._hip_estimator_ok(q) and not_padded and q_for_atten.shape == v_for_atten.shape
                     and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
                     and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype)
-        hip_perf_grad = False
+        hip_perf_grad = hip_perf_grad_wide = False
         if self.fused_performer_grad and torch.is_grad_enabled() and not hip_perf:
             pos = self.v_eye_learned_causal[0, 0, :T_SRC, :]
-            hip_perf_grad = (self._hip_estimator_ok(q, autograd_too=True) and not_padded and q_for_atten.shape == v_for_atten.shape
-                             and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
-                             and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype
-                             and ops.performer_value_grad_supported(q_for_atten, k_for_atten, v_for_atten, pos,
-                                                                    self.performer.projection_matrix))
+            grad_args = (q_for_atten, k_for_atten, v_for_atten, pos, self.performer.projection_matrix)
+            may = (self._hip_estimator_ok(q, autograd_too=True) and not_padded and q_for_atten.shape == v_for_atten.shape
+                   and ops.performer_supported(q.shape[-1], self.performer_nb_features, q_for_atten.dtype)
+                   and T_SRC == q.shape[-2] and q_for_atten.dtype == k_for_atten.dtype == v_for_atten.dtype)
+            hip_perf_grad = may and ops.performer_value_grad_supported(*grad_args)
+            # head sizes 80 / 128: the same conditions, the wide-head op (csrc/sea_performer_bwd_wide.hip)
+            hip_perf_grad_wide = may and not hip_perf_grad and ops.performer_value_grad_wide_supported(*grad_args)
+            hip_perf_grad = hip_perf_grad or hip_perf_grad_wide
         if hip_perf_grad:
             # training: the same launch as below with a backward on the kernels; the gradients reach the value embedding and
             # the estimator's q / k / v branches through it
             with timer("performer"):
-                seg = {} if self.fused_performer_grad_segments is None else {"grad_segments": self.fused_performer_grad_segments}
-                performer_value = ops.performer_value_autograd(q_for_atten, k_for_atten, v_for_atten, pos,
-                                                               self.performer.projection_matrix,
-                                                               n_segments=self.performer_segments, **seg)
+                if hip_perf_grad_wide:
+                    performer_value = ops.performer_value_autograd_wide(*grad_args, n_segments=self.performer_segments)
+                else:
+                    seg = {} if self.fused_performer_grad_segments is None else {"grad_segments": self.fused_performer_grad_segments}
+                    performer_value = ops.performer_value_autograd(q_for_atten, k_for_atten, v_for_atten, pos,
+                                                                   self.performer.projection_matrix,
+                                                                   n_segments=self.performer_segments, **seg)
                 if v_for_atten is not v:           # a separate estimator branch for v: the last third is the LAYER's v, as below
                     performer_value = torch.cat([performer_value[..., :2 * q.shape[-1]], v], dim=-1)
                 bench.register_temp_buffer('performer_context_layer', performer_value[..., :2 * q.shape[-1]])

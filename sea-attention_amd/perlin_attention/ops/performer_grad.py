@@ -48,9 +48,10 @@ def _forward(ctx, q, k, v, pos, projection, n_segments):
 
 
 @_lib.device_guarded
-def _backward(grad_out, saved, need, segments=None):
-    """(dq, dk, dv, dpos), None where `need` is False.  `segments` None: `sea_performer_causal_bwd`; an int: that many row
-    segments requested of `sea_performer_causal_bwd_seg`."""
+def _backward(grad_out, saved, need, segments=None, entry="sea_performer_causal_bwd"):
+    """(dq, dk, dv, dpos), None where `need` is False.  `segments` None: `entry` (`sea_performer_causal_bwd`, or
+    `sea_performer_causal_bwd_wide` with the same argument list); an int: that many row segments requested of
+    `sea_performer_causal_bwd_seg`."""
     q, k, v, pos, proj = saved
     if not any(need[:4]):
         return None, None, None, None
@@ -65,8 +66,8 @@ def _backward(grad_out, saved, need, segments=None):
     d_q, d_k, d_v = (torch.empty((N, H, T, D), dtype=q.dtype, device=q.device) for _ in range(3))
     d_pos = torch.empty((T, D), dtype=torch.float32, device=q.device)
     if segments is None:
-        name, seg = "sea_performer_causal_bwd", ()
-        ws_bytes = lib.sea_performer_causal_bwd_workspace_bytes(N, H, T, D, nb, code)
+        name, seg = entry, ()
+        ws_bytes = getattr(lib, entry + "_workspace_bytes")(N, H, T, D, nb, code)
     else:
         name, seg = "sea_performer_causal_bwd_seg", (segments,)
         ws_bytes = lib.sea_performer_causal_bwd_seg_workspace_bytes(N, H, T, D, nb, code, segments)
@@ -107,6 +108,19 @@ class _PerformerValueSegFn(torch.autograd.Function):
         return (*_backward(grad_out, ctx.saved_tensors, ctx.needs_input_grad, ctx.grad_segments), None, None, None)
 
 
+class _PerformerValueWideFn(torch.autograd.Function):
+    """The same op for the head sizes 80 and 128: the backward of csrc/sea_performer_bwd_wide.hip"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pos, projection, n_segments):
+        return _forward(ctx, q, k, v, pos, projection, n_segments)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return (*_backward(grad_out, ctx.saved_tensors, ctx.needs_input_grad, entry="sea_performer_causal_bwd_wide"), None, None)
+
+
 def grad_segments_for(q, grad_segments):
     """The count `performer_value_autograd` requests for `grad_segments`: an int >= 1 as it is, "auto" one segment per
     ceil(CUs / (N H)) -- enough workgroups per sweep to give every CU of q's device one."""
@@ -129,3 +143,30 @@ def performer_value_autograd(q, k, v, pos, projection, n_segments=None, grad_seg
     if grad_segments is None:
         return _PerformerValueFn.apply(q, k, v, pos, projection, n_segments)
     return _PerformerValueSegFn.apply(q, k, v, pos, projection, n_segments, grad_segments_for(q, grad_segments))
+
+
+def performer_value_grad_wide_supported(q, k, v, pos, projection) -> bool:
+    """`performer_value_grad_supported` for the head sizes it refuses (`sea_performer_causal_bwd_wide_supported`: D = 80 / 128, up
+    to 80 features): the same conditions on the tensors, the other predicate of the library.  False at D = 64."""
+    ts = (q, k, v, pos, projection)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts) or q.dim() != 4 or pos.dim() != 2 or projection.dim() != 2:
+        return False
+    N, H, T, D = q.shape
+    if q.dtype not in _DTYPES or not (k.dtype == v.dtype == q.dtype) or k.shape != q.shape or v.shape != q.shape:
+        return False
+    if min(N, H, T) < 1 or pos.shape[0] < T or pos.shape[1] != D or projection.shape[1] != D or T >= 1 << 24:
+        return False
+    if not _lib.load().sea_performer_causal_bwd_wide_supported(D, projection.shape[0], _lib.dtype_code(q.dtype)):
+        return False
+    return all(_aligned(t) for t in (q, k, v)) and (pos.dtype != q.dtype or _aligned(pos))
+
+
+def performer_value_autograd_wide(q, k, v, pos, projection, n_segments=None):
+    """`performer_value_autograd` for the head sizes 80 and 128 (`sea_performer_causal_bwd_wide`: the value columns split over two
+    workgroups per (n, h); no row segments).  The forward is `ops.performer_value`; saved are q, k, v, pos and the rounded
+    projection.  Raises where `performer_value_grad_wide_supported` does not hold: there is no other path behind this name."""
+    if not performer_value_grad_wide_supported(q, k, v, pos, projection):
+        raise RuntimeError(f"performer_value_autograd_wide: q {tuple(q.shape)} {q.dtype} strides {q.stride()}, "
+                           f"nb={projection.shape[0]} is outside the wide-head backward kernels "
+                           "(ops.performer_value_grad_wide_supported)")
+    return _PerformerValueWideFn.apply(q, k, v, pos, projection, n_segments)
